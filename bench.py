@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — training patches/s of the dual-modal fusion hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,panms}]     (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,panms}] [--dump-outputs DIR] [--full]
+                                                                                  (N > 1: launched by torch.distributed.run)
 
 Workloads (`--config`, BASELINE.json `configs` by index; default 1, the configuration the metric is quoted on):
   1      synthetic 145x145 scene, 200-band HSI + 1-band SAR, 11x11 patches, 17 logits, batch 256 per GPU, fp32   (configs[1])
@@ -14,10 +15,21 @@ forward + loss + backward + ADAM on one batch; inputs (padded scenes, the shuffl
 in HBM before the timed region.
 
 One JSON line on rank 0.  `value` = N*B*K / (max-over-ranks wall time of exactly K steps, barrier + synchronize on both
-sides).  `roofline` is for the dominant kernel: algorithmic bytes (or matrix-core flops) per launch / its mean duration,
-measured here with HIP events on the launch stream in an instrumented pass of the same steps.  `kappa` comes from training
-continued to `--kappa-steps` steps (independent of --steps); `cpu_baseline` = the CPU oracle's restatement of the reference
-train loop (oracle/solver_ref.py) on the same batches, timed on this host (first chunk excluded as warm-up).
+sides); `ms_per_step` = that wall time / K.  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, after the timed region, as float32
+DIR/<name>.npy (rank 0; the inputs are seeded, so the same arguments give the same inputs in every run):
+  logits       [B, K] (config 4: [4*bs, K])   logits of the last timed step's batch
+  loss         [B]    (config 4: [1])         its per-patch cross-entropy (config 4: its qua_loss)
+  params              the flat weights after the last step's optimiser update
+  adam_m, adam_v      ADAM's moment estimates after it
+  step_losses  [K]                            the mean loss of every timed step
+
+`--full` adds what takes runs of its own.  `roofline` is for the dominant kernel: algorithmic bytes (or matrix-core flops)
+per launch / its mean duration, measured here with HIP events on the launch stream in an instrumented pass of the same
+steps.  `kappa` comes from training continued to `--kappa-steps` steps (independent of --steps); `cpu_baseline` = the CPU
+oracle's restatement of the reference train loop (oracle/solver_ref.py) on the same batches, timed on this host (first
+chunk excluded as warm-up).
 """
 import argparse
 import json
@@ -178,6 +190,28 @@ def issue_roofline(cfgname, kernel_key, kern_ms):
                      '2.4 GHz / 3.15 cycles per instruction (profiles/r2_valu_rate.txt)'}
 
 
+DUMP_MAX_ELEMS = 2 << 20            # per array (8 MB of float32): six arrays stay under 64 MB
+
+
+def snapshot_outputs(eng, losses, K_steps):
+    """The arrays a caller of the timed path holds after its last step, copied to the host (before anything else runs)."""
+    out = {'logits': eng.logits, 'loss': eng.loss, 'params': eng.theta, 'adam_m': eng.m, 'adam_v': eng.v,
+           'step_losses': losses[-K_steps:]}
+    return {k: v.detach().cpu().clone() for k, v in out.items()}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array; an array larger than DUMP_MAX_ELEMS is replaced by a fixed,
+    seeded sample of its flattened elements (sorted indices, the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a.numpy(), dtype=np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script under torch.distributed.run as a CHILD
     process (this process has not initialised the GPU and never will), pass its output through, return its exit code."""
@@ -216,10 +250,15 @@ def main():
     ap.add_argument('--steps-per-graph', type=int, default=None,
                     help='steps per captured hipGraph; 0 = eager launches from Python; -1 = one C loop of launches (dmf_train_plan_steps). '
                          'Default: -1 where that exists (one GPU, late-fusion net, no loss scaler: 15.75 against 15.97 us per step from graphs of 50), else 50')
-    ap.add_argument('--kappa-steps', type=int, default=2200, help='train to this many steps (from the initial weights) before kappa')
-    ap.add_argument('--cpu-seconds', type=float, default=90.0, help='CPU oracle budget (rank 0, N=1 only)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-cpu-spread', action='store_true', help='skip the second CPU oracle training (kappa noise floor)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as float32 DIR/<name>.npy (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the figures that take runs of their own: the instrumented kernel pass (roofline), kappa after '
+                         '--kappa-steps, the CPU oracle baseline')
+    ap.add_argument('--kappa-steps', type=int, default=2200, help='--full: train to this many steps (from the initial weights) before kappa')
+    ap.add_argument('--cpu-seconds', type=float, default=90.0, help='--full: CPU oracle budget (rank 0, N=1 only)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU oracle')
+    ap.add_argument('--no-cpu-spread', action='store_true', help='--full: skip the second CPU oracle training (kappa noise floor)')
     args = ap.parse_args()
     for k, v in CONFIGS[args.config].items():
         if k != 'name' and getattr(args, k) is None:
@@ -282,7 +321,7 @@ def main():
     eng = TrainEngine(net, scene, B, lr=1e-3, process_group=pg, comm=comm, scaler=scaler())
 
     total = W_steps + K_steps
-    plan_steps = max(total, args.kappa_steps)
+    plan_steps = max(total, args.kappa_steps) if args.full else total      # (the same batches either way: a prefix)
     plan_idx = make_plan(train, plan_steps, B * world, seed=1)                 # global batches of world*B
     mine = plan_idx.reshape(plan_steps, world, B)[:, rank, :].reshape(-1)      # this rank's contiguous shard per step
     eng.load_plan(xy_tab[mine], lab_tab[mine])
@@ -368,12 +407,14 @@ def main():
         dist.all_reduce(one)
         n_ranks_seen = int(one.item())
     value = world * B * K_steps / dt
+    if args.dump_outputs and rank == 0:                  # before anything below reuses the engine's buffers
+        dump_outputs(args.dump_outputs, snapshot_outputs(eng, eng.mean_losses(), K_steps))
 
-    # ---- instrumented pass: mean duration of the dominant kernel, HIP events on the launch stream
+    # ---- instrumented pass (--full): mean duration of the dominant kernel, HIP events on the launch stream
     n_inst = min(max(K_steps, 100), 200)                 # (at least 100 launches, however short the timed region was: batches repeat)
     alg_patch = 2 * ((2 if args.half else 4) * P * P * C + 4 * (S * P) * (S * P) * C2)     # --half: the primary bands are 2 bytes
     kern_ms = None
-    if rank == 0 or world > 1:
+    if args.full and (rank == 0 or world > 1):
         inst_idx = np.concatenate([mine[(i % plan_steps) * B:(i % plan_steps + 1) * B] for i in range(n_inst)])
         inst_plan_xy = torch.from_numpy(xy_tab[inst_idx]).to(dev)
         inst_lab = torch.from_numpy(lab_tab[inst_idx]).to(dev)
@@ -411,15 +452,16 @@ def main():
         kern_ms = float(np.mean([a_.elapsed_time(b_) / GROUP for a_, b_ in ev]))
     losses = eng.mean_losses().numpy() if world == 1 else np.zeros(0)
 
-    # ---- kappa: training continues to --kappa-steps (a fixed budget, not --steps), then the held-out split is classified on
-    # the device; with N ranks every rank classifies its shard of the pixels and the K x K matrices are all-reduced
+    # ---- kappa (--full): training continues to --kappa-steps (a fixed budget, not --steps), then the held-out split is
+    # classified on the device; with N ranks every rank classifies its shard of the pixels and the K x K matrices are all-reduced
     done = total
-    if plan_steps > done:
-        eng.run_plan(plan_steps - done, spg if (n_replays or spg < 0) else 0)
-        done = plan_steps
-    n_test = min(len(test), 8192)
-    ev_eng = EvalEngine(net, scene, 2048)
-    m_test = ev_eng.confusion(xy_tab[test[:n_test]], lab_tab[test[:n_test]], process_group=pg).cpu().numpy().astype(np.float64)
+    if args.full:
+        if plan_steps > done:
+            eng.run_plan(plan_steps - done, spg if (n_replays or spg < 0) else 0)
+            done = plan_steps
+        n_test = min(len(test), 8192)
+        ev_eng = EvalEngine(net, scene, 2048)
+        m_test = ev_eng.confusion(xy_tab[test[:n_test]], lab_tab[test[:n_test]], process_group=pg).cpu().numpy().astype(np.float64)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -436,7 +478,10 @@ def main():
         except Exception:
             traffic = None
     v2 = bool(lib.patch_v2_used(eng.shape)) if hasattr(lib, 'patch_v2_used') else False
-    if args.attention:
+    roof = None
+    if kern_ms is None:
+        pass                                             # (a plain run: no instrumented pass)
+    elif args.attention:
         # matrix-core work per patch (padded shapes, tools/attn_bench.py): forward 3 projections + QK^T + PV + out-proj, the
         # backward's recompute of it, and the backward products fed as hi/lo bf16 pairs
         fwd = 2.0 * (3 * 128 * 64 * 96 + 2 * 3 * 128 * 128 * 32 + 128 * 96 * 48)
@@ -470,8 +515,10 @@ def main():
         'roofline': roof,
         'step_frac_of_hbm_roof': value / world * (alg_patch + 28.0 * eng.theta.numel() / B) / HBM_PEAK,
     }
+    if roof is None:
+        del out['roofline']
     default_shape = all(getattr(args, k) == v for k, v in CONFIGS[args.config].items() if k != 'name')
-    if not args.attention and not args.half and default_shape:
+    if args.full and not args.attention and not args.half and default_shape:
         ir = issue_roofline(args.config if args.config != '3' else '', ', 1, 1, false>', kern_ms)
         if ir is not None:
             out['issue_roofline'] = ir
@@ -479,6 +526,12 @@ def main():
         out['config']['allreduce_note'] = exchange_note
     if losses.size:
         out['loss_first_last'] = [float(losses[0]), float(losses[min(len(losses), total) - 1])]
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
 
     from indicators.kappa import aa_oa_quiet
     aa, oa, kp = aa_oa_quiet(m_test)
@@ -635,6 +688,8 @@ def main_stage2(args, dev, pg=None, rank=0, world=1, backend='nccl'):
         dist.all_reduce(one)
         n_seen = int(one.item())
     losses = eng.losses().numpy()
+    if args.dump_outputs and rank == 0:                  # before the instrumented pass reuses the engine's buffers
+        dump_outputs(args.dump_outputs, snapshot_outputs(eng, torch.from_numpy(losses), K_steps))
     if rank != 0:
         if world > 1:
             import torch.distributed as dist
@@ -643,17 +698,19 @@ def main_stage2(args, dev, pg=None, rank=0, world=1, backend='nccl'):
         return
     P = args.patch
     alg_patch = 2 * ((2 if args.half else 4) * P * P * 4 + 4 * P * P * 1)
-    # dominant kernel: the forward(+unit-gradient) patch kernel over the 4*bs stacked patches, HIP events on the launch stream
-    n_inst = min(K_steps, 100)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_inst)]
-    inp = lib.input_gather(eng.shape, scene.A, scene.B, eng.plan_xy[:4 * bs])
-    torch.cuda.synchronize()
-    for i in range(n_inst):
-        ev[i][0].record()
-        eng.time_dominant(inp)
-        ev[i][1].record()
-    torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev[n_inst // 10:]]))
+    # dominant kernel (--full): the forward(+unit-gradient) patch kernel over the 4*bs stacked patches, HIP events on the launch stream
+    kern_ms = None
+    if args.full:
+        n_inst = min(K_steps, 100)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_inst)]
+        inp = lib.input_gather(eng.shape, scene.A, scene.B, eng.plan_xy[:4 * bs])
+        torch.cuda.synchronize()
+        for i in range(n_inst):
+            ev[i][0].record()
+            eng.time_dominant(inp)
+            ev[i][1].record()
+        torch.cuda.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev[n_inst // 10:]]))
     out = {
         'metric': 'training patches/sec + kappa, 11x11x200 HSI + 11x11x1 SAR, 1/2/4/8 MI355X',
         'value': world * 4 * bs * K_steps / dt, 'unit': 'patches/s', 'n_gpus': world, 'steps': K_steps, 'warmup': W_steps,
@@ -667,16 +724,19 @@ def main_stage2(args, dev, pg=None, rank=0, world=1, backend='nccl'):
                    'n_ranks_seen': n_seen},
         'roofline': {'bound': 'hbm', 'achieved': 4 * bs * alg_patch / (kern_ms * 1e-3) / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s',
                      'frac': 4 * bs * alg_patch / (kern_ms * 1e-3) / HBM_PEAK, 'traffic': None,
-                     'kernel': eng.dominant_name(), 'kernel_ms': kern_ms, 'algorithmic_bytes_per_launch': 4 * bs * alg_patch},
+                     'kernel': eng.dominant_name(), 'kernel_ms': kern_ms, 'algorithmic_bytes_per_launch': 4 * bs * alg_patch}
+                    if kern_ms is not None else None,
         'loss_first_last': [float(losses[0]), float(losses[-1])] if losses.size else None,
     }
-    if world == 1 and all(getattr(args, k) == v for k, v in CONFIGS['4'].items() if k != 'name') and eng.unit:
+    if kern_ms is None:
+        del out['roofline']
+    if args.full and world == 1 and all(getattr(args, k) == v for k, v in CONFIGS['4'].items() if k != 'name') and eng.unit:
         ir = issue_roofline('4', ', 5, 1, %s>' % ('true' if args.half else 'false'), kern_ms)
         if ir is not None:
             out['issue_roofline'] = ir
     if sc is not None:
         out['loss_scaler'] = {'scale': sc.get_scale(), 'skipped_steps': sc.skipped_steps()}
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle.gmfnet_ref import Net as RefNet
         from oracle import solver_ref
         torch.set_num_threads(min(len(os.sched_getaffinity(0)), 16))

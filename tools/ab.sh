@@ -3,7 +3,7 @@
 A=$1; B=$2; shift 2
 for rep in 1 2; do
   for L in $A $B; do
-    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --no-cpu --steps 400 --warmup 40 "$@" 2>/dev/null | python3 -c "
+    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --full --no-cpu --steps 400 --warmup 40 "$@" 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

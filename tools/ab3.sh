@@ -3,7 +3,7 @@
 LIBS=$1
 for args in "--config 1" "--batch 1024 --steps 300" "--config 4 --half 0" "--config 3"; do
   for L in $LIBS; do
-    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --no-cpu --kappa-steps 0 --steps 600 --warmup 60 $args 2>/dev/null | python3 -c "
+    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --full --no-cpu --kappa-steps 0 --steps 600 --warmup 60 $args 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -3,7 +3,7 @@
 LIBS=$1; shift
 for rep in 1 2 3; do
   for L in $LIBS; do
-    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --no-cpu --steps 2000 --warmup 200 --kappa-steps 0 "$@" 2>/dev/null | python3 -c "
+    DMF_LIB=$PWD/dual-modal-fusion_amd/dmf/$L python3 bench.py --full --no-cpu --steps 2000 --warmup 200 --kappa-steps 0 "$@" 2>/dev/null | python3 -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -1,11 +1,11 @@
-"""Turn the rocprofv3 outputs a GPU run left under gpurun_out/ into the small summaries committed in profiles/.
+"""Turn the rocprofv3 outputs a GPU run left under profile_out/ into the small summaries committed in profiles/.
 
     python tools/summarize_profiles.py <round-tag>       e.g.  r1
 
 Inputs (produced on the GPU box, see profiles/README.md for the exact commands):
-  gpurun_out/prof_<tag>/**/_kernel_stats.csv        rocprofv3 --kernel-trace --stats      -- python3 bench.py ...
-  gpurun_out/pmc_fetch/**/_counter_collection.csv   rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py ...
-  gpurun_out/pmc_write/**/_counter_collection.csv   rocprofv3 --pmc WRITE_SIZE --kernel-trace -- python3 bench.py ...
+  profile_out/prof_<tag>/**/_kernel_stats.csv        rocprofv3 --kernel-trace --stats      -- python3 bench.py ...
+  profile_out/pmc_fetch/**/_counter_collection.csv   rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py ...
+  profile_out/pmc_write/**/_counter_collection.csv   rocprofv3 --pmc WRITE_SIZE --kernel-trace -- python3 bench.py ...
 HBM bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE / WRITE_SIZE are in KiB and, on gfx950,
 FETCH_SIZE reports exactly half the bytes of a 16-B-per-lane coalesced read stream (MI355X_MICROARCH.md §HBM),
 which is what the patch kernel's window loads are.
@@ -30,14 +30,14 @@ def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else 'r1'
     out = os.path.join(ROOT, 'profiles')
     os.makedirs(out, exist_ok=True)
-    stats = newest(glob.glob(os.path.join(ROOT, 'gpurun_out', 'prof_' + tag, '**', '*_kernel_stats.csv'), recursive=True))
+    stats = newest(glob.glob(os.path.join(ROOT, 'profile_out', 'prof_' + tag, '**', '*_kernel_stats.csv'), recursive=True))
     if stats:
         rows = list(csv.reader(open(stats[0])))
         with open(os.path.join(out, tag + '_kernel_stats.csv'), 'w', newline='') as f:
             csv.writer(f).writerows(rows[:12])
     pmc = {}
     for name, ctr in (('pmc_fetch', 'FETCH_SIZE'), ('pmc_write', 'WRITE_SIZE')):
-        files = newest(glob.glob(os.path.join(ROOT, 'gpurun_out', name, '**', '*_counter_collection.csv'), recursive=True))
+        files = newest(glob.glob(os.path.join(ROOT, 'profile_out', name, '**', '*_counter_collection.csv'), recursive=True))
         if not files:
             continue
         d = collections.defaultdict(list)
@@ -59,12 +59,12 @@ def main():
     json.dump(summary, open(os.path.join(out, tag + '_pmc_traffic.json'), 'w'), indent=1)
     print(json.dumps(summary, indent=1)[:1500])
     # ---- attention network: kernel stats of a train step + matrix-core counters of the attention kernels
-    stats = newest(glob.glob(os.path.join(ROOT, 'gpurun_out', 'prof_' + tag + 'attn', '**', '*_kernel_stats.csv'), recursive=True))
+    stats = newest(glob.glob(os.path.join(ROOT, 'profile_out', 'prof_' + tag + 'attn', '**', '*_kernel_stats.csv'), recursive=True))
     if stats:
         rows = list(csv.reader(open(stats[0])))
         with open(os.path.join(out, tag + '_attn_kernel_stats.csv'), 'w', newline='') as f:
             csv.writer(f).writerows(rows[:10])
-    files = newest(glob.glob(os.path.join(ROOT, 'gpurun_out', 'pmc_attn', '**', '*_counter_collection.csv'), recursive=True))
+    files = newest(glob.glob(os.path.join(ROOT, 'profile_out', 'pmc_attn', '**', '*_counter_collection.csv'), recursive=True))
     if files:
         d = collections.defaultdict(lambda: collections.defaultdict(list))
         dur = collections.defaultdict(list)
@@ -98,12 +98,12 @@ def main():
 
 
 def issue_counts(tag):
-    """gpurun_out/pmc_valu{1,4,pan}: SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVES of every dmf kernel (rocprofv3 --pmc ... on
+    """profile_out/pmc_valu{1,4,pan}: SQ_INSTS_VALU / SQ_INSTS_SALU / SQ_WAVES of every dmf kernel (rocprofv3 --pmc ... on
     bench.py --config 1 / 4 / panms, eager launches) -> profiles/<tag>_issue_counts.json + profiles/issue_counts.json (bench.py
     reads the latter for its `issue_roofline`).  The counters are per launch, summed over all waves of the grid."""
     res = {'round': tag, 'counters': 'rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES --kernel-trace', 'configs': {}}
     for name, cfgname in (('pmc_valu1', '1'), ('pmc_valu4', '4'), ('pmc_valupan', 'panms')):
-        files = newest(glob.glob(os.path.join(ROOT, 'gpurun_out', name, '**', '*_counter_collection.csv'), recursive=True))
+        files = newest(glob.glob(os.path.join(ROOT, 'profile_out', name, '**', '*_counter_collection.csv'), recursive=True))
         if not files:
             continue
         d = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -124,8 +124,8 @@ def issue_counts(tag):
 
 
 def configs_md(tag):
-    """gpurun_out/<tag>_config_lines.jsonl (tools/collect_r2.sh: a '# command' line, then bench.py's JSON line) -> profiles/<tag>_configs.md"""
-    src = os.path.join(ROOT, 'gpurun_out', tag + '_config_lines.jsonl')
+    """profile_out/<tag>_config_lines.jsonl (tools/collect_r2.sh: a '# command' line, then bench.py's JSON line) -> profiles/<tag>_configs.md"""
+    src = os.path.join(ROOT, 'profile_out', tag + '_config_lines.jsonl')
     if not os.path.exists(src):
         return
     rows, cmd = [], None

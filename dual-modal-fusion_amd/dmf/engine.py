@@ -15,6 +15,9 @@ Data parallel (world_size > 1), two forms with identical updates on every rank:
     reduce + Adam launch (one-shot over xGMI, rank-ordered sum), still two launches per step and graph-replayable;
   * without: `dmf_grad_reduce` -> all-reduce(sum) of ONE flat fp32 gradient over RCCL -> `dmf_adam_step(1/world)`.
 """
+import contextlib
+import sys
+
 import numpy as np
 import torch
 
@@ -80,32 +83,173 @@ class LossScaler:
         return (self.growth_factor, self.backoff_factor, self.growth_interval)
 
 
-class TrainEngine:
-    def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
-                 optimizer='ADAM', momentum=0.0, alpha=0.99):
-        """optimizer: 'ADAM' (fused into the reduce launch), or the reference's other two (utils/utils.py:13-16) — 'SGD'
-        (`momentum`) and 'RMSprop' (`alpha`, eps 1e-8) — as a third launch on the flat gradient."""
+class _PlanEngine:
+    """What both train engines share: parameters and optimiser state, the epoch plan on the device, and the hipGraph that
+    replays steps of it.  A subclass says how one step is launched (`_plan_launch`) and what differs around a capture."""
+
+    def __init__(self, net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha):
         if optimizer not in ('ADAM', 'SGD', 'RMSprop'):
             raise lib.DmfError('optimizer %r is not one of ADAM, SGD, RMSprop' % (optimizer,))
         self.optim, self.momentum, self.alpha = optimizer, float(momentum), float(alpha)
-        self.net, self.scene, self.B = net, scene, int(batch)
+        self.lr, self.b1, self.b2, self.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        self.net, self.scene, self.scaler = net, scene, scaler
         self.shape = net.shape
         lib.shape_supported(self.shape)
         if getattr(scene, 'half', False):
             lib.require_half(self.shape)
-        self.scaler = scaler
+        self.pg, self.world, self.rank = process_group, 1, 0
+        if process_group is not None:
+            import torch.distributed as dist
+            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        dev = scene.device
+        self.theta = net.flat_parameters()
+        self.m = torch.zeros_like(self.theta)
+        self.v = torch.zeros_like(self.theta)
+        self.grad = torch.zeros_like(self.theta)
+        # device-side bookkeeping for graph replay
+        self.dev_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.dev_cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step_count = self.host_cursor = self.plan_steps = 0
+        self.plan_xy = self.plan_labels = self.loss_hist = None
+        self.graph, self.graph_steps, self.graph_hparams = None, 0, None
+
+    def _hparams(self):
+        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha) + (self.scaler.hparams() if self.scaler is not None else ())
+
+    def _check_labels(self, lab):
+        K = self.net.arch['K']
+        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
+            raise lib.DmfError('label outside [0, %d)' % K)
+
+    def _optimizer_step(self, grad_scale, dev_step, cursor):
+        """SGD / RMSprop on the flat gradient (utils/utils.py:13-16); m holds the optimiser's one state vector (SGD: momentum
+        buffer, RMSprop: running mean of squares)."""
+        if self.optim == 'SGD':
+            lib.sgd_step(self.theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=grad_scale,
+                         step_dev=dev_step, cursor_dev=cursor)
+        else:
+            lib.rmsprop_step(self.theta, self.grad, self.m, self.lr, self.alpha, grad_scale=grad_scale, cursor_dev=cursor)
+
+    # ------------------------------------------------------------------ epoch plan + hipGraph replay
+    def _install_plan(self, n, **plan):
+        """Make `plan` (attribute name -> device tensor) the loaded plan of n steps and rewind to its first step.  A plan of
+        the same shape is copied into the tensors already there: a captured graph keeps reading valid addresses."""
+        if self.plan_xy is not None and self.plan_xy.shape == plan['plan_xy'].shape:
+            for name, t in plan.items():
+                getattr(self, name).copy_(t)
+        else:
+            for name, t in plan.items():
+                setattr(self, name, t)
+            self.loss_hist = torch.empty(max(n, 1), device=self.scene.device)
+            self.graph = None
+        self.loss_hist.zero_()
+        self.dev_cursor.zero_()
+        self.host_cursor, self.plan_steps = 0, n
+
+    def _plan_step(self):
+        if self.host_cursor >= self.plan_steps:          # the kernel reads plan[cursor] unchecked: never step past the plan
+            raise lib.DmfError('the loaded plan has %d steps, all of them are done' % self.plan_steps)
+        self._plan_launch()
+        self.host_cursor += 1
+
+    def _steps_to_run(self, steps):
+        steps = self.plan_steps - self.host_cursor if steps is None else steps
+        if self.plan_xy is None or steps < 0 or self.host_cursor + steps > self.plan_steps:
+            raise lib.DmfError('run_plan(%d): the loaded plan has %d steps, %d of them done' % (
+                steps, self.plan_steps, self.host_cursor))
+        return steps
+
+    def run_plan(self, steps=None, steps_per_graph=0):
+        """Run `steps` steps of the loaded plan (default: all).  steps_per_graph > 0 replays a captured hipGraph of that
+        many steps while whole graphs fit (where `_graphable()`), the rest is launched eagerly.  No host synchronisation."""
+        steps = self._steps_to_run(steps)
+        done = 0
+        if steps_per_graph > 0 and self._graphable():
+            # lr, betas and eps are launch arguments baked into the captured graph (reference: `scheduler.step()` changes
+            # the optimiser's lr every epoch, mainsolver.py:60): a change invalidates the graph
+            if self.graph is None or self.graph_steps != steps_per_graph or self.graph_hparams != self._hparams():
+                self._capture_for_replay(steps_per_graph)
+            while self.graph is not None and steps - done >= steps_per_graph:
+                self._before_replay(steps_per_graph)
+                self.graph.replay()
+                self.step_count += steps_per_graph
+                self.host_cursor += steps_per_graph
+                done += steps_per_graph
+        for _ in range(steps - done):
+            self._plan_step()
+        return steps
+
+    @contextlib.contextmanager
+    def _state_kept(self):
+        """Save everything a step changes (weights, optimiser and scaler state, device step count and cursor, loss history,
+        host step count and cursor) and put it back on leaving, also when the body raises.  Yields the restore function
+        for a body that needs the state back early."""
+        tensors = [t for t in (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist) if t is not None]
+        if self.scaler is not None:
+            tensors.append(self.scaler.state)
+        saved = [t.clone() for t in tensors]
+        counts = (self.step_count, self.host_cursor)
+
+        def restore():
+            for t, s in zip(tensors, saved):
+                t.copy_(s)
+            self.step_count, self.host_cursor = counts
+        try:
+            yield restore
+        finally:
+            restore()
+
+    def _capture(self, n):
+        """Capture n steps of the plan in a hipGraph.  Consumes no steps: the engine ends where it began, also when the
+        capture fails."""
+        self.graph = None
+        with self._state_kept() as restore:
+            # hipFuncSetAttribute is not capturable, so every kernel must have been launched once before the capture:
+            # run one step eagerly, then put back the exact pre-step state (capture itself executes nothing)
+            self._plan_step()
+            torch.cuda.synchronize()
+            restore()
+            self._prepare_capture(n)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for k in range(n):
+                    self._graph_step(k)
+        self.graph, self.graph_steps, self.graph_hparams = g, n, self._hparams()
+        _upload_graph(g)
+
+    # hooks around the capture and replay; by default the graph's steps read plan[cursor] like eager plan steps
+    def _capture_for_replay(self, n):
+        self._capture(n)
+
+    def _prepare_capture(self, n):
+        pass
+
+    def _graph_step(self, k):
+        self._plan_launch()
+
+    def _before_replay(self, n):
+        pass
+
+    def losses(self):
+        """Per-step mean loss of the plan steps run so far (one D2H copy)."""
+        return self.loss_hist[:int(self.dev_cursor.item())].cpu()
+
+
+class TrainEngine(_PlanEngine):
+    def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
+                 optimizer='ADAM', momentum=0.0, alpha=0.99):
+        """optimizer: 'ADAM' (fused into the reduce launch), or the reference's other two (utils/utils.py:13-16) — 'SGD'
+        (`momentum`) and 'RMSprop' (`alpha`, eps 1e-8) — as a third launch on the flat gradient."""
+        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
         if optimizer != 'ADAM' and (comm is not None or scaler is not None):
             raise lib.DmfError('%s: single GPU or RCCL data parallel, no loss scaler (the fused exchange and the scaler step are ADAM)' % optimizer)
-        self.lr, self.b1, self.b2, self.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         dev = scene.device
-        self.theta = net.flat_parameters()
         if self.theta.device != dev:
             raise lib.DmfError('net and scene must be on the same device')
-        self.m = torch.zeros_like(self.theta)
-        self.v = torch.zeros_like(self.theta)
-        self.grad = torch.zeros_like(self.theta)
+        self.B = int(batch)
         K = net.arch['K']
         self.logits = torch.empty(self.B, K, device=dev)
         self.loss = torch.zeros(self.B, device=dev)
@@ -113,23 +257,12 @@ class TrainEngine:
         self.attn_ws = None
         if self.shape.attention:                      # token maps + dense gradient maps of the attention block
             self.attn_ws = torch.empty(lib.attn_train_workspace_bytes(self.shape, self.B), dtype=torch.uint8, device=dev)
-        self.step_count = 0
-        self.pg = process_group
-        self.world = 1
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world = dist.get_world_size(process_group)
         self.comm = comm if self.world > 1 else None
         if self.comm is not None and (self.comm.world != self.world or self.comm.capacity < self.theta.numel()):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
-        # device-side bookkeeping for graph replay
-        self.dev_step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.dev_cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.plan_xy = self.plan_labels = self.plan_pack = self.loss_hist = None
-        self.host_cursor = 0
-        self.graph = None
-        self.graph_steps = 0
-        self.graph_hparams = None
+        self.plan_pack = self.win = None
+        self._rccl_graph = True          # False once RCCL refused to be captured (run_plan), or set by a caller
+        self._force_collective = False   # tests only: see _single()
 
     # ------------------------------------------------------------------ eager step (host-side step count)
     def step(self, xy, labels, check=True):
@@ -138,8 +271,7 @@ class TrainEngine:
             raise lib.DmfError('engine was built for batches of at most %d, got %d' % (self.B, xy.shape[0]))
         if check:     # one D2H copy per call; load_plan() validates a whole epoch at once and run_plan() skips this
             lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.cpu().numpy())
-            if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= self.net.arch['K']):
-                raise lib.DmfError('label outside [0, %d)' % self.net.arch['K'])
+            self._check_labels(labels)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         self._launch(inp, labels, None, None)
 
@@ -150,76 +282,51 @@ class TrainEngine:
 
     def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
         self.step_count += 1
-        theta = self.theta
-        nB = inp.B
-        if (self.comm is not None or self.scaler is not None) and dev_step is None:
-            dev_step = self.dev_step                     # the exchange numbers its rounds by the device step count; with a
-                                                         # loss scaler skipped steps make the device count the only true one
-        if self.optim != 'ADAM':
-            # forward + loss + backward, flat gradient [all-reduce], then the optimiser's own launch; m holds its one state
-            # vector (SGD: momentum buffer, RMSprop: running mean of squares)
-            if dev_step is None:
-                dev_step = self.dev_step                 # (SGD's first step is told by the device count: the patch kernel advances it)
-            if self.shape.attention:
-                lib.train_attn_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits, self.loss,
-                                       self.ws, self.attn_ws, adam_step_dev=dev_step)
-            else:
-                lib.train_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
-                                  adam_step_dev=dev_step)
-            lib.grad_reduce(self.shape, nB, self.ws, self.grad)
-            if not self._single():
-                import torch.distributed as dist
-                dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
-            if loss_hist is not None:
-                loss_hist.scatter_(0, dev_cursor.long(), self.loss[:nB].mean().reshape(1))
-            if self.optim == 'SGD':
-                lib.sgd_step(theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=1.0 / self.world,
-                             step_dev=dev_step, cursor_dev=dev_cursor)
-            else:
-                lib.rmsprop_step(theta, self.grad, self.m, self.lr, self.alpha, grad_scale=1.0 / self.world, cursor_dev=dev_cursor)
-            return
-        if self.scaler is not None:
-            # scaler.scale(loss).backward() -> [all-reduce] -> scaler.unscale_ + scaler.step(opt) + scaler.update()
-            sc = self.scaler
-            lib.train_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
-                              adam_step_dev=dev_step, scaler_state=sc.state)
-            if self._single():                          # three launches: patch kernel, reduce (+ unscale + check), Adam-or-skip
-                lib.grad_reduce_scaled(self.shape, nB, self.ws, self.grad, sc.state, cursor_dev=dev_cursor,
-                                       loss=self.loss if loss_hist is not None else None, loss_hist=loss_hist)
-                lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                                 sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
-                return
-            import torch.distributed as dist
-            lib.grad_reduce(self.shape, nB, self.ws, self.grad)
-            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)     # the check must see the SUM: after it
-            if loss_hist is not None:
-                loss_hist.scatter_(0, dev_cursor.long(), self.loss[:nB].mean().reshape(1))
-            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step,
-                             grad_scale=1.0 / self.world, cursor_dev=dev_cursor)
-            return
+        theta, sc, nB = self.theta, self.scaler, inp.B
+        if dev_step is None and (self.comm is not None or sc is not None or self.optim != 'ADAM'):
+            dev_step = self.dev_step      # the exchange numbers its rounds by the device step count; with a loss scaler skipped
+                                          # steps make the device count the only true one; SGD's first step is told by it
         if self.shape.attention:
             lib.train_attn_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits, self.loss,
                                    self.ws, self.attn_ws, adam_step_dev=dev_step)
         else:
             lib.train_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
-                              adam_step_dev=dev_step)
-        if self._single():
+                              adam_step_dev=dev_step, scaler_state=sc.state if sc is not None else None)
+        loss = self.loss if loss_hist is not None else None
+        if self.optim != 'ADAM':          # flat gradient [all-reduce], then the optimiser's own launch
+            self._reduce_gradient(nB, dev_cursor, loss_hist)
+            self._optimizer_step(1.0 / self.world, dev_step, dev_cursor)
+        elif sc is not None and self._single():
+            # scaler.scale(loss).backward() -> scaler.unscale_ + scaler.step(opt) + scaler.update(): reduce (+ unscale + check),
+            # then Adam-or-skip
+            lib.grad_reduce_scaled(self.shape, nB, self.ws, self.grad, sc.state, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
+            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
+                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
+        elif sc is not None:              # the check must see the SUM: after the all-reduce
+            self._reduce_gradient(nB, dev_cursor, loss_hist)
+            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
+                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step,
+                             grad_scale=1.0 / self.world, cursor_dev=dev_cursor)
+        elif self._single():
             lib.grad_reduce_adam(self.shape, nB, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
-                                 self.step_count, adam_step_dev=dev_step, cursor_dev=dev_cursor,
-                                 loss=self.loss if loss_hist is not None else None, loss_hist=loss_hist)
+                                 self.step_count, adam_step_dev=dev_step, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
         elif self.comm is not None:
             lib.grad_reduce_xgmi_adam(self.shape, nB, self.ws, theta, self.m, self.v, self.comm.c, self.lr, self.b1,
-                                      self.b2, self.eps, 1.0 / self.world, dev_step, cursor_dev=dev_cursor,
-                                      loss=self.loss if loss_hist is not None else None, loss_hist=loss_hist)
+                                      self.b2, self.eps, 1.0 / self.world, dev_step, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
         else:
-            import torch.distributed as dist
-            lib.grad_reduce(self.shape, nB, self.ws, self.grad)
-            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
-            if loss_hist is not None:                    # (this rank's mean loss of the step, as the fused forms record it)
-                loss_hist.scatter_(0, dev_cursor.long(), self.loss[:nB].mean().reshape(1))
+            self._reduce_gradient(nB, dev_cursor, loss_hist)
             lib.adam_step(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count,
                           grad_scale=1.0 / self.world, adam_step_dev=dev_step, cursor_dev=dev_cursor)
+
+    def _reduce_gradient(self, nB, dev_cursor, loss_hist):
+        """The unfused forms: the slab rows into the flat gradient, its all-reduce (sum) over the group where the step has a
+        collective, and the step's mean loss (this rank's, as the fused forms record it) at dev_cursor."""
+        lib.grad_reduce(self.shape, nB, self.ws, self.grad)
+        if not self._single():
+            import torch.distributed as dist
+            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
+        if loss_hist is not None:
+            loss_hist.scatter_(0, dev_cursor.long(), self.loss[:nB].mean().reshape(1))
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def load_plan(self, xy_all, labels_all):
@@ -229,87 +336,46 @@ class TrainEngine:
         lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
         if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
             raise lib.DmfError('plan length must be a multiple of the batch size')
-        xy_host = xy.cpu().numpy()
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)
-        K = self.net.arch['K']
-        if int(lab.min()) < 0 or int(lab.max()) >= K:
-            raise lib.DmfError('label outside [0, %d)' % K)
+        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.cpu().numpy())
+        self._check_labels(lab)
         n = xy.shape[0] // self.B
-        same = self.plan_xy is not None and self.plan_xy.shape == xy.shape
         # the same stream once more, step by step [n][2B coordinates | B labels]: the window of a captured graph is refilled
         # from it with ONE device copy per replay
         pack = torch.cat([xy.view(n, 2 * self.B), lab.view(n, self.B)], 1).contiguous()
-        if same:                                   # keep addresses stable for an already captured graph
-            self.plan_xy.copy_(xy); self.plan_labels.copy_(lab); self.plan_pack.copy_(pack)
-        else:
-            self.plan_xy, self.plan_labels, self.plan_pack = xy, lab, pack
-            self.loss_hist = torch.zeros(n, device=dev)
-            self.graph = None
-        self.dev_cursor.zero_()
-        self.host_cursor = 0
+        self._install_plan(n, plan_xy=xy, plan_labels=lab, plan_pack=pack)
         if self.scaler is None and self.optim == 'ADAM':   # (with a scaler the device count is authoritative: skipped steps;
             self.dev_step.fill_(self.step_count)           #  the other optimisers always step by the device count)
-        self.plan_steps = n
         return n
 
-    def _plan_step(self):
-        if self.host_cursor >= self.plan_steps:          # the kernel reads plan[cursor] unchecked: never step past the plan
-            raise lib.DmfError('the loaded plan has %d steps, all of them are done' % self.plan_steps)
+    def _plan_launch(self):
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=self.B, cursor=self.dev_cursor)
         self._launch(inp, self.plan_labels, self.dev_step, self.dev_cursor, self.loss_hist)
-        self.host_cursor += 1
 
     def _fill_window(self, n):
         """Copy the next n steps of the plan into the fixed window the captured graph reads (one small async copy)."""
         self.win.copy_(self.plan_pack[self.host_cursor:self.host_cursor + n])
 
     def run_plan(self, steps=None, steps_per_graph=0):
-        """Run `steps` steps of the loaded plan (default: all).  steps_per_graph > 0 replays a captured hipGraph
-        (single GPU, or data parallel over the xgmi communicator); 0 launches eagerly.  No host synchronisation."""
-        steps = self.plan_steps - self.host_cursor if steps is None else steps
-        if self.plan_xy is None or steps < 0 or self.host_cursor + steps > self.plan_steps:
-            raise lib.DmfError('run_plan(%d): the loaded plan has %d steps, %d of them done' % (
-                steps, getattr(self, 'plan_steps', 0), self.host_cursor))
-        done = 0
-        if steps_per_graph < 0 and self._native_loop_ok():
-            # the library's own loop: 2 launches per step enqueued from C, the batches read straight from the plan (no window,
-            # no graph): for a short run the fixed cost is one kernel launch instead of a window copy + a graph launch
-            k0 = self.host_cursor
-            inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy[k0 * self.B:(k0 + steps) * self.B], B=self.B)
-            lib.train_plan_steps(self.shape, inp, self.theta, self.net.pool_w, self.plan_labels[k0 * self.B:(k0 + steps) * self.B],
-                                 1.0 / self.B, self.logits, self.loss, self.ws, self.m, self.v, self.lr, self.b1, self.b2, self.eps,
-                                 self.dev_step, self.dev_cursor, self.loss_hist, steps)
-            self.step_count += steps
-            self.host_cursor += steps
-            return steps
-        if steps_per_graph > 0 and self._graphable():
-            # lr, betas and eps are launch arguments baked into the captured graph (reference: `scheduler.step()` changes
-            # the optimiser's lr every epoch, mainsolver.py:60): a change invalidates the graph
-            if self.graph is None or self.graph_steps != steps_per_graph or self.graph_hparams != self._hparams():
-                try:
-                    self._capture(steps_per_graph)
-                except RuntimeError:
-                    if self._single() or self.comm is not None:
-                        raise
-                    # RCCL's all-reduce refused to be captured (every rank runs the same software, so every rank lands
-                    # here): stay on eager launches for the rest of this engine's life
-                    self._rccl_graph = False
-                    self.graph = None
-                    torch.cuda.synchronize()
-            while self.graph is not None and steps - done >= steps_per_graph:
-                self._fill_window(steps_per_graph)
-                self.graph.replay()
-                self.step_count += steps_per_graph
-                self.host_cursor += steps_per_graph
-                done += steps_per_graph
-        for _ in range(steps - done):
-            self._plan_step()
+        """As _PlanEngine.run_plan (graph replay on one GPU or over the xgmi communicator; RCCL: see _graphable); and
+        steps_per_graph < 0 hands the steps to the library's own launch loop where `_native_loop_ok()`."""
+        if steps_per_graph >= 0 or not self._native_loop_ok():
+            return super().run_plan(steps, steps_per_graph)
+        steps = self._steps_to_run(steps)
+        # the library's own loop: 2 launches per step enqueued from C, the batches read straight from the plan (no window,
+        # no graph): for a short run the fixed cost is one kernel launch instead of a window copy + a graph launch
+        k0 = self.host_cursor
+        inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy[k0 * self.B:(k0 + steps) * self.B], B=self.B)
+        lib.train_plan_steps(self.shape, inp, self.theta, self.net.pool_w, self.plan_labels[k0 * self.B:(k0 + steps) * self.B],
+                             1.0 / self.B, self.logits, self.loss, self.ws, self.m, self.v, self.lr, self.b1, self.b2, self.eps,
+                             self.dev_step, self.dev_cursor, self.loss_hist, steps)
+        self.step_count += steps
+        self.host_cursor += steps
         return steps
 
     def _single(self):
         """One rank and no collective in the step.  `_force_collective` (tests only) keeps the group's all-reduce in the step of
         a ONE-rank group, so that the RCCL form of the step — eager and captured in a hipGraph — runs on a one-GPU box."""
-        return self.world == 1 and not getattr(self, '_force_collective', False)
+        return self.world == 1 and not self._force_collective
 
     def _native_loop_ok(self):
         """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler."""
@@ -321,47 +387,44 @@ class TrainEngine:
         all_reduce of 32 KB per ~16-us step would otherwise bound the step by the host (DMF_RCCL_GRAPH=0 switches this off)."""
         if self._single() or self.comm is not None:
             return True
-        if self.scaler is not None or self.optim != 'ADAM' or not getattr(self, '_rccl_graph', True):
+        if self.scaler is not None or self.optim != 'ADAM' or not self._rccl_graph:
             return False
         import os
         import torch.distributed as dist
         return dist.get_backend(self.pg) == 'nccl' and os.environ.get('DMF_RCCL_GRAPH', '1') != '0'
 
-    def _capture(self, n):
-        # hipFuncSetAttribute is not capturable, so every kernel must have been launched once before the capture:
-        # run one step eagerly, then put back the exact pre-step state (capture itself executes nothing).
-        state = (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist)
-        if self.scaler is not None:
-            state = state + (self.scaler.state,)
-        count0 = self.step_count
-        saved = [t.clone() for t in state]
-        self._plan_step()
-        torch.cuda.synchronize()
-        for t, s in zip(state, saved):
-            t.copy_(s)
-        self.step_count = count0
+    def _capture_for_replay(self, n):
+        try:
+            self._capture(n)
+        except RuntimeError as e:         # (a DmfError too: RCCL can invalidate the capture under the library's next launch)
+            if self._single() or self.comm is not None:
+                raise
+            # RCCL's all-reduce refused to be captured (every rank runs the same software, so every rank lands here): stay
+            # on eager launches for the rest of this engine's life; the capture has put the engine's state back
+            print('dmf: the step with the RCCL all-reduce could not be captured in a hipGraph (%s); eager launches from '
+                  'here on' % e, file=sys.stderr, flush=True)
+            self._rccl_graph = False
+            torch.cuda.synchronize()
+
+    def _prepare_capture(self, n):
         if self.comm is not None:                  # the eager step used up an exchange sequence number; the bias is
             self.comm.rewind(1)                    # a launch argument, so it has to move BEFORE the capture
-        self.host_cursor -= 1                      # (the eager step above advanced it)
         # Inside the graph step k reads its coordinates and labels from slot k of a FIXED window (plain pointers baked
         # into the launch) instead of plan[cursor]: every kernel starts cold after the previous kernel's cache
         # write-back / invalidate, and `kernarg -> cursor -> coordinates -> gather` is one dependent miss longer than
         # `kernarg -> coordinates -> gather`.  The window is refilled from the plan before every replay.
-        dev = self.scene.device
-        self.win = torch.empty(n, 3 * self.B, dtype=torch.int32, device=dev)      # per step: 2B coordinates, B labels
+        self.win = torch.empty(n, 3 * self.B, dtype=torch.int32, device=self.scene.device)   # per step: 2B coordinates, B labels
         if self.host_cursor + n <= self.plan_steps:
             self._fill_window(n)
         else:
             self.win.zero_()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for k in range(n):
-                inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.win[k, :2 * self.B].view(self.B, 2))
-                self._launch(inp, self.win[k, 2 * self.B:], self.dev_step, self.dev_cursor, self.loss_hist)
-        self.step_count = count0
-        self.graph, self.graph_steps, self.graph_hparams = g, n, self._hparams()
-        _upload_graph(g)
+
+    def _graph_step(self, k):
+        inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.win[k, :2 * self.B].view(self.B, 2))
+        self._launch(inp, self.win[k, 2 * self.B:], self.dev_step, self.dev_cursor, self.loss_hist)
+
+    def _before_replay(self, n):
+        self._fill_window(n)
 
     def warm_graph(self):
         """One replay of the captured graph that leaves no trace (weights, optimiser state, cursors and loss history are put
@@ -370,24 +433,14 @@ class TrainEngine:
         xGMI exchange a replay also advances the sequence numbers in the peers' inboxes, which cannot be put back."""
         if self.graph is None or not self._single() or self.host_cursor + self.graph_steps > self.plan_steps:
             return False
-        state = (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist)
-        if self.scaler is not None:
-            state = state + (self.scaler.state,)
-        saved = [t.clone() for t in state]
-        self._fill_window(self.graph_steps)
-        self.graph.replay()
-        torch.cuda.synchronize()
-        for t, s_ in zip(state, saved):
-            t.copy_(s_)
+        with self._state_kept():
+            self._fill_window(self.graph_steps)
+            self.graph.replay()
+            torch.cuda.synchronize()
         torch.cuda.synchronize()
         return True
 
-    def _hparams(self):
-        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha) + (self.scaler.hparams() if self.scaler is not None else ())
-
-    def mean_losses(self):
-        """Per-step mean CE of the plan steps run so far (one D2H copy)."""
-        return self.loss_hist[:int(self.dev_cursor.item())].cpu()
+    mean_losses = _PlanEngine.losses
 
 
 class EvalEngine:
@@ -404,6 +457,8 @@ class EvalEngine:
         self.attn_ws = None
         if self.shape.attention:
             self.attn_ws = torch.empty(lib.attn_workspace_bytes(self.shape, self.B), dtype=torch.uint8, device=dev)
+        self.ce = torch.zeros(self.B, device=dev)
+        self._no_ce = False
 
     def predict(self, xy):
         """xy [n,2] int32 device -> (logits [n,K], pred [n]) views valid until the next call."""
@@ -423,10 +478,8 @@ class EvalEngine:
         n = xy.shape[0]
         if n > self.B:
             raise lib.DmfError('batch larger than the engine was built for')
-        if self.shape.attention or getattr(self, '_no_ce', False):
+        if self.shape.attention or self._no_ce:
             return None
-        if not hasattr(self, 'ce'):
-            self.ce = torch.zeros(self.B, device=self.scene.device)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         try:
             lib.forward_ce(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
@@ -435,18 +488,35 @@ class EvalEngine:
             return None
         return self.ce[:n].double().sum()
 
+    def _shard(self, process_group, *tensors):
+        """With a process group: this rank's contiguous shard of the rows of each tensor."""
+        if process_group is None:
+            return tensors
+        import torch.distributed as dist
+        from .parallel import shard_range
+        lo, hi = shard_range(tensors[0].shape[0], dist.get_rank(process_group), dist.get_world_size(process_group))
+        return tuple(t[lo:hi].contiguous() for t in tensors)
+
+    @staticmethod
+    def _all_reduce(x, process_group, allreduce_):
+        """x <- allreduce_ (dmf.parallel.allreduce_sum_ / allreduce_max_) of x over the group, if one is given."""
+        if process_group is None:
+            return
+        import torch.distributed as dist
+        if dist.get_backend(process_group) == 'nccl':
+            allreduce_(x, process_group)
+        else:                                       # gloo (CPU tests, one-GPU rehearsal): reduce on the host
+            x.copy_(allreduce_(x.cpu(), process_group))
+
     def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
         """Confusion matrix [K,K] int64 (rows = prediction) over all given pixels; one D2H at the end.
         With a process group every rank classifies its contiguous shard of the pixels and the matrices are summed."""
+        from .parallel import allreduce_sum_
         dev = self.scene.device
         K = self.net.arch['K']
         xy_all = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
         labels_all = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        if process_group is not None:
-            import torch.distributed as dist
-            from .parallel import shard_range
-            lo, hi = shard_range(xy_all.shape[0], dist.get_rank(process_group), dist.get_world_size(process_group))
-            xy_all, labels_all = xy_all[lo:hi].contiguous(), labels_all[lo:hi].contiguous()
+        xy_all, labels_all = self._shard(process_group, xy_all, labels_all)
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_all.cpu().numpy())
         if matrix is None:
             matrix = torch.zeros(K, K, dtype=torch.int64, device=dev)
@@ -454,24 +524,16 @@ class EvalEngine:
             xy = xy_all[i:i + self.B]
             _, pred = self.predict(xy)
             lib.confusion_accum(pred, labels_all[i:i + self.B], K, matrix)
-        if process_group is not None:
-            from .parallel import allreduce_sum_
-            if dist.get_backend(process_group) == 'nccl':
-                allreduce_sum_(matrix, process_group)
-            else:                                   # gloo (CPU tests, one-GPU rehearsal): reduce on the host
-                matrix.copy_(allreduce_sum_(matrix.cpu(), process_group))
+        self._all_reduce(matrix, process_group, allreduce_sum_)
         return matrix
 
     def label_map(self, xy_all, H, W, label_map=None, process_group=None):
         """Predicted class of every given pixel written at (x, y) of an [H, W] int32 map (mainsolver.py:171-183).
         With a process group the pixels are sharded and the tiles merged (every pixel is written by one rank)."""
+        from .parallel import allreduce_max_
         dev = self.scene.device
         xy_all = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
-        if process_group is not None:
-            import torch.distributed as dist
-            from .parallel import shard_range
-            lo, hi = shard_range(xy_all.shape[0], dist.get_rank(process_group), dist.get_world_size(process_group))
-            xy_all = xy_all[lo:hi].contiguous()
+        xy_all, = self._shard(process_group, xy_all)
         xy_host = xy_all.cpu().numpy()
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)
         if len(xy_host) and (int(xy_host[:, 0].max()) >= H or int(xy_host[:, 1].max()) >= W):
@@ -482,12 +544,7 @@ class EvalEngine:
             xy = xy_all[i:i + self.B]
             _, pred = self.predict(xy)
             lib.labelmap_write(pred, xy, W, label_map)
-        if process_group is not None:
-            from .parallel import allreduce_max_
-            if dist.get_backend(process_group) == 'nccl':
-                allreduce_max_(label_map, process_group)
-            else:
-                label_map.copy_(allreduce_max_(label_map.cpu(), process_group))
+        self._all_reduce(label_map, process_group, allreduce_max_)
         return label_map
 
 
@@ -522,7 +579,7 @@ class QuaScene:
         return torch.cat(out)
 
 
-class QuaTrainEngine:
+class QuaTrainEngine(_PlanEngine):
     """Stage-2 train step (tostagesolver.py:268-278) on the resident tall scene, no host sync.  The loss couples the whole
     batch, so it cannot ride inside the per-patch kernel like cross-entropy does.  Two forms:
       * unit-gradient step (shapes with a v2 kernel): `dmf_forward_unit` (forward of the 4*bs stacked patches + the conv
@@ -535,54 +592,23 @@ class QuaTrainEngine:
 
     def __init__(self, net, scene, bs, dqtl, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, scaler=None,
                  optimizer='ADAM', momentum=0.0, alpha=0.99):
-        if optimizer not in ('ADAM', 'SGD', 'RMSprop'):
-            raise lib.DmfError('optimizer %r is not one of ADAM, SGD, RMSprop' % (optimizer,))
-        if optimizer != 'ADAM' and scaler is not None:
-            raise lib.DmfError('the loss-scaler step is ADAM')
-        self.optim, self.momentum, self.alpha = optimizer, float(momentum), float(alpha)
         if not net.arch.get('single_input'):
             raise lib.DmfError('stage 2 needs the single-input net (cfg["gmf"]["single_input"] = 1)')
-        self.net, self.scene, self.bs = net, scene, int(bs)
-        self.shape = net.shape
-        lib.shape_supported(self.shape)
+        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
+        if optimizer != 'ADAM' and scaler is not None:
+            raise lib.DmfError('the loss-scaler step is ADAM')
+        self.bs = int(bs)
         self.unit = lib.unit_supported(self.shape)
-        if getattr(scene, 'half', False):
-            lib.require_half(self.shape)
-        self.scaler = scaler
         if scaler is not None and (process_group is not None or not self.unit):
             raise lib.DmfError('loss scaling in stage 2: unit-gradient step on one GPU')
         self.params = lib.qua_params(dqtl)
-        self.lr, self.b1, self.b2, self.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         dev = scene.device
-        self.theta = net.flat_parameters()
-        self.m = torch.zeros_like(self.theta)
-        self.v = torch.zeros_like(self.theta)
-        self.grad = torch.zeros_like(self.theta)
         K = net.arch['K']
-        self.pg, self.world, self.rank = process_group, 1, 0
-        if process_group is not None:
-            import torch.distributed as dist
-            self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         self.logits = torch.empty(4 * self.bs, K, device=dev)
         self.dlogits = torch.empty(4 * self.bs, K, device=dev)
         self.loss = torch.zeros(1, device=dev)
         self.ws = torch.empty(lib.workspace_bytes(self.shape, 4 * self.bs) // 4, device=dev)
-        self.dev_cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.dev_step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.step_count = 0
-        self.plan_xy = self.plan_labels = self.plan_labels_global = self.loss_hist = None
-        self.graph, self.graph_steps, self.graph_hparams = None, 0, None
-
-    def _hparams(self):
-        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha)
-
-    def _optimizer_step(self, theta, grad_scale, dev_step, cursor):
-        """SGD / RMSprop on the flat gradient (utils/utils.py:13-16); m holds the optimiser's one state vector."""
-        if self.optim == 'SGD':
-            lib.sgd_step(theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=grad_scale,
-                         step_dev=dev_step, cursor_dev=cursor)
-        else:
-            lib.rmsprop_step(theta, self.grad, self.m, self.lr, self.alpha, grad_scale=grad_scale, cursor_dev=cursor)
+        self.plan_labels_global = None
 
     def _step(self, inp, bs, labels, cursor, loss_hist, dev_step=None):
         self.step_count += 1
@@ -615,7 +641,7 @@ class QuaTrainEngine:
             lib.backward_dlogits(self.shape, inp, theta, self.net.pool_w, self.dlogits, self.ws)
         if self.world == 1 and self.optim != 'ADAM':
             lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
-            self._optimizer_step(theta, 1.0, dev_step if self.unit else None, cursor)
+            self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
         elif self.world == 1:
             lib.grad_reduce_adam(self.shape, 4 * bs, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
                                  self.step_count, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
@@ -630,7 +656,7 @@ class QuaTrainEngine:
                 self.grad.copy_(g)
             # the loss kernel already divided by the GLOBAL batch (it saw all ranks' logits): the sum over ranks is the gradient
             if self.optim != 'ADAM':
-                self._optimizer_step(theta, 1.0, None, cursor)
+                self._optimizer_step(1.0, None, cursor)
             else:
                 lib.adam_step(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count,
                               grad_scale=1.0, cursor_dev=cursor)
@@ -669,9 +695,7 @@ class QuaTrainEngine:
         xy4 = self.scene.stack_xy(torch.as_tensor(xy).cpu()).to(dev).contiguous()
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.cpu().numpy())
         lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int32).contiguous()
-        K = self.net.arch['K']
-        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
-            raise lib.DmfError('label outside [0, %d)' % K)
+        self._check_labels(lab)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy4)
         self._step(inp, bs, lab, None, None)
 
@@ -685,83 +709,31 @@ class QuaTrainEngine:
         if xy.shape[0] % (self.bs * W) or xy.shape[0] != lab.shape[0]:
             raise lib.DmfError('plan length must be a multiple of the (global) batch size')
         n = xy.shape[0] // (self.bs * W)
-        K = self.net.arch['K']
-        if n and (int(lab.min()) < 0 or int(lab.max()) >= K):
-            raise lib.DmfError('label outside [0, %d)' % K)
+        self._check_labels(lab)
         self.plan_labels_global = lab
         if W > 1:
             xy = xy.view(n, W, self.bs, 2)[:, self.rank].reshape(-1, 2)
             lab = lab.view(n, W, self.bs)[:, self.rank].reshape(-1).contiguous()
         xy4 = torch.cat([self.scene.stack_xy(xy[i * self.bs:(i + 1) * self.bs]) for i in range(n)]) if n else xy
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.numpy())
-        same = self.plan_xy is not None and self.plan_xy.shape == xy4.shape
-        if same:                                   # keep addresses stable for an already captured graph
-            self.plan_xy.copy_(xy4); self.plan_labels.copy_(lab)
-        else:
-            self.plan_xy, self.plan_labels = xy4.to(dev).contiguous(), lab
-            self.loss_hist = torch.zeros(max(n, 1), device=dev)
-            self.graph = None
-        self.loss_hist.zero_()
-        self.dev_cursor.zero_()
-        self.host_cursor = 0
+        self._install_plan(n, plan_xy=xy4.to(dev).contiguous(), plan_labels=lab)
         if self.scaler is None:
             self.dev_step.fill_(self.step_count)
-        self.plan_steps = n
         return n
 
-    def _plan_step(self):
-        if self.host_cursor >= self.plan_steps:          # the kernel reads plan[cursor] unchecked: never step past the plan
-            raise lib.DmfError('the loaded plan has %d steps, all of them are done' % self.plan_steps)
+    def _plan_launch(self):
+        # (the captured graph runs these same launches: its steps read plan[cursor])
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=4 * self.bs, cursor=self.dev_cursor)
         self._step(inp, self.bs, self.plan_labels, self.dev_cursor, self.loss_hist, self.dev_step)
-        self.host_cursor += 1
+
+    def _graphable(self):
+        return self.unit and self.world == 1
 
     def _capture(self, n):
-        """Capture n steps (unit-gradient form, one GPU).  hipFuncSetAttribute is not capturable: one eager step first,
-        then the exact pre-step state is put back (capture itself executes nothing)."""
-        if not self.unit or self.world > 1:
+        """Capture n steps (unit-gradient form, one GPU); see _PlanEngine._capture."""
+        if not self._graphable():
             raise lib.DmfError('graph replay needs the unit-gradient step on one GPU')
-        state = (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist)
-        if self.scaler is not None:
-            state = state + (self.scaler.state,)
-        count0 = self.step_count
-        saved = [t.clone() for t in state]
-        self._plan_step()
-        torch.cuda.synchronize()
-        for t, s in zip(state, saved):
-            t.copy_(s)
-        self.step_count = count0
-        self.host_cursor -= 1
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(n):
-                inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=4 * self.bs, cursor=self.dev_cursor)
-                self._step(inp, self.bs, self.plan_labels, self.dev_cursor, self.loss_hist, self.dev_step)
-        self.step_count = count0
-        self.graph, self.graph_steps, self.graph_hparams = g, n, self._hparams()
-        _upload_graph(g)
-
-    def run_plan(self, steps=None, steps_per_graph=0):
-        steps = self.plan_steps - self.host_cursor if steps is None else steps
-        if self.plan_xy is None or steps < 0 or self.host_cursor + steps > self.plan_steps:
-            raise lib.DmfError('run_plan(%d): the loaded plan has %d steps, %d of them done' % (
-                steps, getattr(self, 'plan_steps', 0), self.host_cursor))
-        done = 0
-        if steps_per_graph > 0 and self.unit and self.world == 1:
-            if self.graph is None or self.graph_steps != steps_per_graph or self.graph_hparams != self._hparams():
-                self._capture(steps_per_graph)
-            while steps - done >= steps_per_graph:
-                self.graph.replay()
-                self.step_count += steps_per_graph
-                self.host_cursor += steps_per_graph
-                done += steps_per_graph
-        for _ in range(steps - done):
-            self._plan_step()
-        return steps
-
-    def losses(self):
-        return self.loss_hist[:int(self.dev_cursor.item())].cpu()
+        super()._capture(n)
 
     # bench.py: the step's dominant launch alone (for HIP-event timing) and its name
     def time_dominant(self, inp):

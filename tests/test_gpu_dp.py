@@ -377,6 +377,59 @@ def test_rccl_form_of_the_step_on_a_one_rank_group(graph_steps):
         assert out['captured_1'], 'the all-reduce was not captured in the step graph (eager fallback taken)'
 
 
+def _train_rccl_failed_capture(rank, world, port, q):
+    import datetime
+    import torch.distributed as dist
+    MS, PAN, xy, lab = _problem(48 * 6)
+    from dmf.engine import Scene, TrainEngine
+    from model.gmfnet import Net
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    torch.cuda.set_device(0)
+    dist.init_process_group('nccl', rank=0, world_size=1, timeout=datetime.timedelta(seconds=60), device_id=torch.device('cuda', 0))
+    out = {}
+    for failing in (False, True):
+        torch.manual_seed(0)
+        net = Net(CFG).to('cuda:0')
+        eng = TrainEngine(net, Scene(MS, PAN, 'cuda:0'), 48, lr=1e-2, process_group=dist.group.WORLD)
+        eng._force_collective = True           # the RCCL form: dmf_grad_reduce -> RCCL all-reduce -> dmf_adam_step
+        eng.load_plan(xy, lab)
+        if failing:
+            launch, in_capture = eng._launch, []
+
+            def interrupted(*a, **k):           # a Python error before any launch of the graph's second step
+                if torch.cuda.is_current_stream_capturing():
+                    in_capture.append(1)
+                    if len(in_capture) == 2:
+                        raise RuntimeError('capture interrupted by the test')
+                return launch(*a, **k)
+            eng._launch = interrupted
+            eng.run_plan(1, 0)
+            eng.run_plan(4, 2)                  # the capture fails: run_plan falls back to eager steps
+            out['fell_back'] = (len(in_capture), eng.graph is None, eng._rccl_graph)
+            eng.run_plan(1, 0)
+        else:
+            eng.run_plan(6, 0)
+        torch.cuda.synchronize()
+        state = (eng.step_count, eng.host_cursor, int(eng.dev_step.item()))
+        theta, losses = eng.theta.cpu().numpy(), eng.mean_losses().numpy()
+        eng.load_plan(xy, lab)                  # the next epoch starts from the host step count
+        out[failing] = state + (int(eng.dev_step.item()), theta, losses)
+    q.put(out)
+    dist.destroy_process_group()
+
+
+def test_rccl_form_falls_back_to_eager_steps_after_a_failed_capture():
+    """A capture of the RCCL form that fails part-way (here: a Python error at the start of the graph's second step) leaves
+    the engine where it was before the capture: run_plan falls back to eager steps, and step count, cursor, device step
+    count, weights and losses equal those of an engine that ran the same steps eagerly, bit for bit."""
+    out = _run_ranks(_train_rccl_failed_capture, 1, ())
+    assert out['fell_back'] == (2, True, False), out['fell_back']
+    eager, failed = out[False], out[True]
+    assert failed[:4] == eager[:4] == (6, 6, 6, 6), (failed[:4], eager[:4])
+    assert np.array_equal(failed[4], eager[4])
+    assert np.array_equal(failed[5], eager[5]) and failed[5].shape == (6,)
+
+
 def test_xgmi_wait_is_bounded_and_sticky():
     """A peer that never arrives: the waiting lanes give up after timeout_ms, the communicator's status turns 1 and stays 1,
     and later exchanges on it return without waiting (a stuck peer must cost one time-out, not one per step) — the exit

@@ -1007,14 +1007,23 @@ int32_t dmf_rmsprop_step(float* theta, const float* grad, float* square_avg, int
   return check(hipGetLastError(), "rmsprop launch");
 }
 
+int32_t dmf_qua_loss_ranks(const float* gathered, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,
+                           const int32_t* labels_global, const int32_t* cursor, const dmf_qua_params* prm, float grad_scale,
+                           const float* scaler_state, float* loss, float* loss_hist, float* dlogits_rank, void* stream) {
+  if (gathered == nullptr || labels_global == nullptr || prm == nullptr) return fail("%s", "null argument");
+  if (ranks < 1 || rank < 0 || rank >= ranks) return fail("%s", "qua_loss: ranks must be positive and 0 <= rank < ranks");
+  if (bs_r <= 0 || K < 2 || K > KMAX) return fail("%s", "qua_loss: bs must be positive and 2 <= K <= DMF_KMAX");
+  if ((int64_t)ranks * 4 * bs_r * K > INT32_MAX) return fail("%s", "qua_loss: the gathered batch is too large");
+  QuaArgs a{gathered, ranks * bs_r, K, labels_global, cursor, prm->alpha, prm->beta, prm->gamma, prm->epsilon, prm->tao,
+            grad_scale, loss, loss_hist, dlogits_rank, scaler_state, ranks, rank, bs_r};
+  return check(launch_qua_loss(a, static_cast<hipStream_t>(stream)), "qua_loss launch");
+}
+
 int32_t dmf_qua_loss_scaled(const float* logits, int32_t bs, int32_t K, const int32_t* labels, const int32_t* cursor,
                             const dmf_qua_params* prm, float grad_scale, const float* scaler_state, float* loss,
                             float* loss_hist, float* dlogits, void* stream) {
-  if (logits == nullptr || labels == nullptr || prm == nullptr) return fail("%s", "null argument");
-  if (bs <= 0 || K < 2 || K > KMAX) return fail("%s", "qua_loss: bs must be positive and 2 <= K <= DMF_KMAX");
-  QuaArgs a{logits, bs, K, labels, cursor, prm->alpha, prm->beta, prm->gamma, prm->epsilon, prm->tao, grad_scale,
-            loss, loss_hist, dlogits, scaler_state};
-  return check(launch_qua_loss(a, static_cast<hipStream_t>(stream)), "qua_loss launch");
+  return dmf_qua_loss_ranks(logits, 1, 0, bs, K, labels, cursor, prm, grad_scale, scaler_state, loss, loss_hist, dlogits,
+                            stream);
 }
 
 int32_t dmf_qua_loss(const float* logits, int32_t bs, int32_t K, const int32_t* labels, const int32_t* cursor,

@@ -106,6 +106,10 @@ struct QuaArgs {
   float alpha, beta, gamma, eps, tao, grad_scale;
   float* loss; float* loss_hist; float* dlogits;
   const float* scaler;   // nullable: device loss-scaler state, [0] multiplies grad_scale
+  // the logits as all_gather_into_tensor leaves them, rank-major [ranks][4][bs_r][K] (bs = ranks * bs_r): global sample
+  // g = r * bs_r + i of stream st at row r * 4 * bs_r + st * bs_r + i; dlogits is rank `rank`'s block [4][bs_r][K] only.
+  // ranks = 1, rank = 0, bs_r = bs: the stream-major [4][bs][K] of one GPU.
+  int ranks, rank, bs_r;
 };
 hipError_t launch_qua_loss(const QuaArgs& a, hipStream_t st);
 hipError_t launch_pair_argmax(const float* logits, int bs, int K, int32_t* pred, hipStream_t st);

@@ -43,6 +43,12 @@ __device__ __forceinline__ void block_sum(float (&v)[N], float* red) {
   __syncthreads();
 }
 
+// row of global sample g, stream st in the (gathered) logits: rank-major [ranks][4][bs_r][K] (QuaArgs)
+__device__ __forceinline__ size_t qua_row(const QuaArgs& a, int st, int g) {
+  const int r = g / a.bs_r, i = g - r * a.bs_r;
+  return ((size_t)r * 4 + st) * a.bs_r + i;
+}
+
 __device__ __forceinline__ float xlogx(float y) { return y > 0.f ? y * logf(y) : 0.f; }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
@@ -59,6 +65,8 @@ __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f 
 // KC > 0: K <= KC, every loop over the classes is unrolled to KC (guarded by k < K) — with run-time trip counts each
 // iteration waits for its own LDS / global access, and one 1024-thread workgroup has nothing else to hide that behind.
 // KC = 0: any K, run-time loops.
+// Data parallel (a.ranks > 1): the logits are the gathered global batch, visited in global sample order (the sums are
+// those of one GPU with the whole batch); sweep 3 makes only the rows of rank a.rank, into its own dlogits block.
 #define DMF_KLOOP(k, k0) _Pragma("unroll") for (int k = k0; k < (KC ? KC : K); ++k) if (KC == 0 || k < K)
 template <int KC>
 __global__ __launch_bounds__(QT) void qua_loss_kernel(const QuaArgs a, const int TS) {
@@ -77,12 +85,13 @@ __global__ __launch_bounds__(QT) void qua_loss_kernel(const QuaArgs a, const int
   const float ll_hit = logf(l_hit), ll_miss = logf(l_miss);
   const int ntile = (bs + TS - 1) / TS;
   const bool one_tile = ntile == 1;
+  const int lo = a.rank * a.bs_r, hi = lo + a.bs_r;       // this rank's global samples (sweep 3)
 
   // softmax rows of tile `t0..t0+nt` -> sP
   auto fill = [&](int t0, int nt) {
     for (int row = tid; row < 4 * nt; row += QT) {
       const int st = row / nt, i = row - st * nt;
-      const float* x = a.logits + ((size_t)st * bs + t0 + i) * K;
+      const float* x = a.logits + qua_row(a, st, t0 + i) * K;
       float mx = x[0];
       DMF_KLOOP(k, 1) mx = fmaxf(mx, x[k]);
       float sum = 0.f;
@@ -184,9 +193,11 @@ __global__ __launch_bounds__(QT) void qua_loss_kernel(const QuaArgs a, const int
   const float cB1 = al, cB2 = al * (1.f - s2), cB3 = al * s2 + a.beta * GB;
   for (int t = 0; t < ntile; ++t) {
     const int t0 = t * TS, nt = min(TS, bs - t0);
+    if (t0 + nt <= lo || t0 >= hi) continue;               // (uniform: no row of this rank in the tile)
     if (!one_tile) { __syncthreads(); fill(t0, nt); }
     for (int w = tid; w < 4 * nt; w += QT) {
       const int st = w / nt, i = w - st * nt;
+      if (t0 + i < lo || t0 + i >= hi) continue;
       const float* p = sP + (size_t)i * K;
       const float* q = p + (size_t)TS * K;
       const float* r = q + (size_t)TS * K;
@@ -226,7 +237,7 @@ __global__ __launch_bounds__(QT) void qua_loss_kernel(const QuaArgs a, const int
         return d;
       };
       const float* y = sP + ((size_t)st * TS + i) * K;
-      float* g = a.dlogits + ((size_t)st * bs + t0 + i) * K;
+      float* g = a.dlogits + ((size_t)st * a.bs_r + (t0 + i - lo)) * K;
       float ip = 0.f;
       float dk[KC ? KC : 1];                               // the row of dProb: registers (KC > 0) or parked in its output
       DMF_KLOOP(k, 0) { const float d = dprob(k); if (KC) dk[KC ? k : 0] = d; else g[k] = d; ip += d * y[k]; }
@@ -273,7 +284,7 @@ __device__ __forceinline__ QeRows qe_rows(const QuaArgs& a) {
   const int ic = r.i < a.bs ? r.i : a.bs - 1;
 #pragma unroll
   for (int st = 0; st < 4; ++st) {
-    const float x = r.k < a.K ? a.logits[((size_t)st * a.bs + ic) * a.K + r.k] : -INFINITY;
+    const float x = r.k < a.K ? a.logits[qua_row(a, st, ic) * a.K + r.k] : -INFINITY;
     const float mx = row16_max(x);
     const float e = r.k < a.K ? expf(x - mx) : 0.f;
     const float inv = 1.f / row16_sum(e);
@@ -409,10 +420,12 @@ __global__ __launch_bounds__(256) void qua_e3_kernel(const QuaArgs a, const int 
     d[3] = -inv_n * (cA3 * pk + cB3 * qk) / (sk + a.eps);
   }
   const float gs = a.grad_scale * (a.scaler != nullptr ? a.scaler[0] : 1.f);
+  const int own = r.i - a.rank * a.bs_r;                  // this rank's rows only (data parallel: its dlogits block)
+  const bool put = r.on && own >= 0 && own < a.bs_r;
 #pragma unroll
   for (int st = 0; st < 4; ++st) {
     const float ip = row16_sum(d[st] * r.y[st]);          // (lanes beyond K, samples beyond bs: d = 0)
-    if (r.on) a.dlogits[((size_t)st * bs + r.i) * K + r.k] = gs * r.y[st] * (d[st] - ip);
+    if (put) a.dlogits[((size_t)st * a.bs_r + own) * K + r.k] = gs * r.y[st] * (d[st] - ip);
   }
 }
 

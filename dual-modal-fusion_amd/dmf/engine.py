@@ -112,6 +112,9 @@ class _PlanEngine:
         self.step_count = self.host_cursor = self.plan_steps = 0
         self.plan_xy = self.plan_labels = self.loss_hist = None
         self.graph, self.graph_steps, self.graph_hparams = None, 0, None
+        self.comm = None                 # the one-shot xgmi exchange (TrainEngine only)
+        self._rccl_graph = True          # False once RCCL refused to be captured (run_plan), or set by a caller
+        self._force_collective = False   # tests only: see _single()
 
     def _hparams(self):
         return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha) + (self.scaler.hparams() if self.scaler is not None else ())
@@ -218,9 +221,43 @@ class _PlanEngine:
         self.graph, self.graph_steps, self.graph_hparams = g, n, self._hparams()
         _upload_graph(g)
 
+    def _single(self):
+        """One rank and no collective in the step.  `_force_collective` (tests only) keeps the group's collectives in the step
+        of a ONE-rank group, so that the RCCL form of the step — eager and captured in a hipGraph — runs on a one-GPU box."""
+        return self.world == 1 and not self._force_collective
+
+    def _rccl_capturable(self):
+        """The step's collectives can be captured in a hipGraph: the group is RCCL (its collectives are capturable; gloo's run
+        on the host), no capture of them has failed yet, and DMF_RCCL_GRAPH=0 does not switch it off."""
+        if not self._rccl_graph:
+            return False
+        import os
+        import torch.distributed as dist
+        return dist.get_backend(self.pg) == 'nccl' and os.environ.get('DMF_RCCL_GRAPH', '1') != '0'
+
+    def _all_reduce_grad(self):
+        """self.grad <- its sum over the group: RCCL on the device, gloo through the host."""
+        import torch.distributed as dist
+        if dist.get_backend(self.pg) == 'nccl':
+            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
+        else:
+            g = self.grad.cpu()
+            dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.pg)
+            self.grad.copy_(g)
+
     # hooks around the capture and replay; by default the graph's steps read plan[cursor] like eager plan steps
     def _capture_for_replay(self, n):
-        self._capture(n)
+        try:
+            self._capture(n)
+        except RuntimeError as e:         # (a DmfError too: RCCL can invalidate the capture under the library's next launch)
+            if self._single() or self.comm is not None:
+                raise
+            # RCCL's collective refused to be captured (every rank runs the same software, so every rank lands here): stay
+            # on eager launches for the rest of this engine's life; the capture has put the engine's state back
+            print('dmf: the step with the RCCL collectives could not be captured in a hipGraph (%s); eager launches from '
+                  'here on' % e, file=sys.stderr, flush=True)
+            self._rccl_graph = False
+            torch.cuda.synchronize()
 
     def _prepare_capture(self, n):
         pass
@@ -261,8 +298,6 @@ class TrainEngine(_PlanEngine):
         if self.comm is not None and (self.comm.world != self.world or self.comm.capacity < self.theta.numel()):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
         self.plan_pack = self.win = None
-        self._rccl_graph = True          # False once RCCL refused to be captured (run_plan), or set by a caller
-        self._force_collective = False   # tests only: see _single()
 
     # ------------------------------------------------------------------ eager step (host-side step count)
     def step(self, xy, labels, check=True):
@@ -372,11 +407,6 @@ class TrainEngine(_PlanEngine):
         self.host_cursor += steps
         return steps
 
-    def _single(self):
-        """One rank and no collective in the step.  `_force_collective` (tests only) keeps the group's all-reduce in the step of
-        a ONE-rank group, so that the RCCL form of the step — eager and captured in a hipGraph — runs on a one-GPU box."""
-        return self.world == 1 and not self._force_collective
-
     def _native_loop_ok(self):
         """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler."""
         return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention
@@ -387,24 +417,9 @@ class TrainEngine(_PlanEngine):
         all_reduce of 32 KB per ~16-us step would otherwise bound the step by the host (DMF_RCCL_GRAPH=0 switches this off)."""
         if self._single() or self.comm is not None:
             return True
-        if self.scaler is not None or self.optim != 'ADAM' or not self._rccl_graph:
+        if self.scaler is not None or self.optim != 'ADAM':
             return False
-        import os
-        import torch.distributed as dist
-        return dist.get_backend(self.pg) == 'nccl' and os.environ.get('DMF_RCCL_GRAPH', '1') != '0'
-
-    def _capture_for_replay(self, n):
-        try:
-            self._capture(n)
-        except RuntimeError as e:         # (a DmfError too: RCCL can invalidate the capture under the library's next launch)
-            if self._single() or self.comm is not None:
-                raise
-            # RCCL's all-reduce refused to be captured (every rank runs the same software, so every rank lands here): stay
-            # on eager launches for the rest of this engine's life; the capture has put the engine's state back
-            print('dmf: the step with the RCCL all-reduce could not be captured in a hipGraph (%s); eager launches from '
-                  'here on' % e, file=sys.stderr, flush=True)
-            self._rccl_graph = False
-            torch.cuda.synchronize()
+        return self._rccl_capturable()
 
     def _prepare_capture(self, n):
         if self.comm is not None:                  # the eager step used up an exchange sequence number; the bias is
@@ -443,7 +458,32 @@ class TrainEngine(_PlanEngine):
     mean_losses = _PlanEngine.losses
 
 
-class EvalEngine:
+class _ShardedEval:
+    """What both evaluation engines share for a process group: every rank takes its contiguous shard of the pixels, and the
+    per-rank results are combined by an all-reduce."""
+
+    def _shard(self, process_group, *tensors):
+        """With a process group: this rank's contiguous shard of the rows of each tensor."""
+        if process_group is None:
+            return tensors
+        import torch.distributed as dist
+        from .parallel import shard_range
+        lo, hi = shard_range(tensors[0].shape[0], dist.get_rank(process_group), dist.get_world_size(process_group))
+        return tuple(t[lo:hi].contiguous() for t in tensors)
+
+    @staticmethod
+    def _all_reduce(x, process_group, allreduce_):
+        """x <- allreduce_ (dmf.parallel.allreduce_sum_ / allreduce_max_) of x over the group, if one is given."""
+        if process_group is None:
+            return
+        import torch.distributed as dist
+        if dist.get_backend(process_group) == 'nccl':
+            allreduce_(x, process_group)
+        else:                                       # gloo (CPU tests, one-GPU rehearsal): reduce on the host
+            x.copy_(allreduce_(x.cpu(), process_group))
+
+
+class EvalEngine(_ShardedEval):
     """Forward + argmax + on-device confusion matrix / label map (mainsolver.py:102-147,164-197)."""
 
     def __init__(self, net, scene, batch):
@@ -487,26 +527,6 @@ class EvalEngine:
             self._no_ce = True
             return None
         return self.ce[:n].double().sum()
-
-    def _shard(self, process_group, *tensors):
-        """With a process group: this rank's contiguous shard of the rows of each tensor."""
-        if process_group is None:
-            return tensors
-        import torch.distributed as dist
-        from .parallel import shard_range
-        lo, hi = shard_range(tensors[0].shape[0], dist.get_rank(process_group), dist.get_world_size(process_group))
-        return tuple(t[lo:hi].contiguous() for t in tensors)
-
-    @staticmethod
-    def _all_reduce(x, process_group, allreduce_):
-        """x <- allreduce_ (dmf.parallel.allreduce_sum_ / allreduce_max_) of x over the group, if one is given."""
-        if process_group is None:
-            return
-        import torch.distributed as dist
-        if dist.get_backend(process_group) == 'nccl':
-            allreduce_(x, process_group)
-        else:                                       # gloo (CPU tests, one-GPU rehearsal): reduce on the host
-            x.copy_(allreduce_(x.cpu(), process_group))
 
     def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
         """Confusion matrix [K,K] int64 (rows = prediction) over all given pixels; one D2H at the end.
@@ -587,8 +607,12 @@ class QuaTrainEngine(_PlanEngine):
         (dh, dz, scaled slab rows) -> `dmf_grad_reduce_adam`: the patches are visited ONCE, and the four launches replay
         from a captured hipGraph (`run_plan(steps, steps_per_graph)`);
       * otherwise `dmf_forward` -> `dmf_qua_loss` -> `dmf_backward_dlogits` (recomputes the forward) -> reduce + ADAM.
-    Data parallel (process_group): every rank takes its shard of each batch; the logits of all ranks are gathered so that
-    the batch-coupled loss is the GLOBAL batch's, the flat gradient is all-reduced (sum) and ADAM runs with 1/world."""
+    Data parallel (process_group): every rank takes its shard of each global batch; `all_gather_into_tensor` of the logits
+    into a buffer allocated once (gloo: a host gather and one H2D copy into it) -> `dmf_qua_loss_ranks` (the GLOBAL batch's
+    loss, this rank's rows of d loss / d logits) -> backward -> `dmf_grad_reduce` -> all-reduce(sum) -> the optimiser step
+    on the device step count and cursor.  With a loss scaler (unit form, ADAM) the step is `dmf_unscale_adam(unscaled = 0)`
+    after the all-reduce, so every rank sees the same sum and takes the same skip decision.  Over RCCL the whole step
+    replays from a captured hipGraph like the single-GPU one."""
 
     def __init__(self, net, scene, bs, dqtl, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, scaler=None,
                  optimizer='ADAM', momentum=0.0, alpha=0.99):
@@ -599,8 +623,8 @@ class QuaTrainEngine(_PlanEngine):
             raise lib.DmfError('the loss-scaler step is ADAM')
         self.bs = int(bs)
         self.unit = lib.unit_supported(self.shape)
-        if scaler is not None and (process_group is not None or not self.unit):
-            raise lib.DmfError('loss scaling in stage 2: unit-gradient step on one GPU')
+        if scaler is not None and not self.unit:
+            raise lib.DmfError('loss scaling in stage 2: unit-gradient step')
         self.params = lib.qua_params(dqtl)
         dev = scene.device
         K = net.arch['K']
@@ -609,99 +633,91 @@ class QuaTrainEngine(_PlanEngine):
         self.loss = torch.zeros(1, device=dev)
         self.ws = torch.empty(lib.workspace_bytes(self.shape, 4 * self.bs) // 4, device=dev)
         self.plan_labels_global = None
+        # data parallel: the logits of all ranks, rank-major [world][4][bs][K] as all_gather_into_tensor leaves them
+        self.gathered = torch.empty(self.world * 4 * self.bs, K, device=dev) if process_group is not None else None
+
+    def _gather(self, bs):
+        """This rank's logits [4*bs, K] -> the gathered [world*4*bs, K] (rank-major)."""
+        import torch.distributed as dist
+        mine, out = self.logits[:4 * bs], self.gathered[:self.world * 4 * bs]
+        if dist.get_backend(self.pg) == 'nccl':
+            dist.all_gather_into_tensor(out, mine, group=self.pg)
+        else:                                       # gloo: gather on the host, one H2D copy into the same buffer
+            parts = [torch.empty(mine.shape) for _ in range(self.world)]
+            dist.all_gather(parts, mine.cpu(), group=self.pg)
+            out.copy_(torch.cat(parts))
+        return out
 
     def _step(self, inp, bs, labels, cursor, loss_hist, dev_step=None):
+        """One step on this rank's 4*bs stacked patches; labels: the GLOBAL batch's ([world*bs] at row cursor)."""
         self.step_count += 1
-        theta = self.theta
-        if self.scaler is not None:
-            # scaler.scale(loss).backward(); scaler.step(opt); scaler.update()  (tostagesolver.py:98,119 do this for the
-            # stage-1 pair; here it wraps the stage-2 step)
-            sc = self.scaler
-            dev_step = self.dev_step if dev_step is None else dev_step
-            lib.forward_unit(self.shape, inp, theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
-            lib.qua_loss(self.logits[:4 * bs], bs, labels, self.params, loss=self.loss, dlogits=self.dlogits[:4 * bs],
-                         cursor=cursor, loss_hist=loss_hist, scaler_state=sc.state)
-            lib.backward_unit(self.shape, 4 * bs, theta, self.dlogits, self.ws)
-            lib.grad_reduce_scaled(self.shape, 4 * bs, self.ws, self.grad, sc.state, cursor_dev=cursor)
-            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
-            return
+        theta, sc = self.theta, self.scaler
+        if sc is not None and dev_step is None:
+            dev_step = self.dev_step      # with a loss scaler skipped steps make the device count the only true one
         if self.unit:
             lib.forward_unit(self.shape, inp, theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
         else:
             lib.forward(self.shape, inp, theta, self.net.pool_w, self.logits)
-        if self.world == 1:
+        scaler_state = sc.state if sc is not None else None
+        if self._single():
             lib.qua_loss(self.logits[:4 * bs], bs, labels, self.params, loss=self.loss, dlogits=self.dlogits[:4 * bs],
-                         cursor=cursor, loss_hist=loss_hist)
+                         cursor=cursor, loss_hist=loss_hist, scaler_state=scaler_state)
         else:
-            self._global_loss(bs, labels, cursor, loss_hist)
+            lib.qua_loss_ranks(self._gather(bs), self.world, self.rank, bs, labels, self.params, loss=self.loss,
+                               dlogits=self.dlogits[:4 * bs], cursor=cursor, loss_hist=loss_hist, scaler_state=scaler_state)
         if self.unit:
             lib.backward_unit(self.shape, 4 * bs, theta, self.dlogits, self.ws)
         else:
             lib.backward_dlogits(self.shape, inp, theta, self.net.pool_w, self.dlogits, self.ws)
-        if self.world == 1 and self.optim != 'ADAM':
+        if not self._single():
+            # the loss kernel already divided by the GLOBAL batch: the sum over ranks is the gradient
             lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
-            self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
-        elif self.world == 1:
-            lib.grad_reduce_adam(self.shape, 4 * bs, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
-                                 self.step_count, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
-        else:
-            import torch.distributed as dist
-            lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
-            if dist.get_backend(self.pg) == 'nccl':
-                dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
-            else:
-                g = self.grad.cpu()
-                dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.pg)
-                self.grad.copy_(g)
-            # the loss kernel already divided by the GLOBAL batch (it saw all ranks' logits): the sum over ranks is the gradient
-            if self.optim != 'ADAM':
-                self._optimizer_step(1.0, None, cursor)
+            self._all_reduce_grad()
+            if sc is not None:            # the check must see the SUM (include/dmf.h): after the all-reduce
+                lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
+                                 sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, grad_scale=1.0,
+                                 cursor_dev=cursor)
+            elif self.optim != 'ADAM':
+                self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
             else:
                 lib.adam_step(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count,
-                              grad_scale=1.0, cursor_dev=cursor)
-
-    def _global_loss(self, bs, labels, cursor, loss_hist):
-        """qua_loss couples all samples of the batch (six batch-mean KL terms): every rank evaluates it on the logits of
-        ALL ranks (4*bs*world x K floats, a few tens of KB) and keeps its own rows of d loss / d logits."""
-        import torch.distributed as dist
-        W, K = self.world, self.logits.shape[1]
-        mine = self.logits[:4 * bs].contiguous()
-        if dist.get_backend(self.pg) == 'nccl':
-            parts = [torch.empty_like(mine) for _ in range(W)]
-            dist.all_gather(parts, mine, group=self.pg)
+                              grad_scale=1.0, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
+        elif sc is not None:
+            # scaler.scale(loss).backward(); scaler.step(opt); scaler.update()  (tostagesolver.py:98,119 do this for the
+            # stage-1 pair; here it wraps the stage-2 step)
+            lib.grad_reduce_scaled(self.shape, 4 * bs, self.ws, self.grad, sc.state, cursor_dev=cursor)
+            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
+                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
+        elif self.optim != 'ADAM':
+            lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
+            self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
         else:
-            host = [torch.empty(4 * bs, K) for _ in range(W)]
-            dist.all_gather(host, mine.cpu(), group=self.pg)
-            parts = [h.to(mine.device) for h in host]
-        # rank r holds [stream][bs] rows; the global batch is [stream][rank][bs]
-        glob = torch.stack([p.view(4, bs, K) for p in parts], 1).reshape(4 * W * bs, K).contiguous()
-        step = int(self.host_cursor)
-        glab = self.plan_labels_global[step * W * bs:(step + 1) * W * bs].contiguous()
-        gdl = torch.empty_like(glob)
-        lib.qua_loss(glob, W * bs, glab, self.params, loss=self.loss, dlogits=gdl)
-        if loss_hist is not None:
-            loss_hist[step:step + 1].copy_(self.loss)
-        self.dlogits[:4 * bs].copy_(gdl.view(4, W, bs, K)[:, self.rank].reshape(4 * bs, K))
+            lib.grad_reduce_adam(self.shape, 4 * bs, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
+                                 self.step_count, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
 
     def step(self, xy, labels):
-        """One step on the bs pixels `xy` [bs, 2] (host or device ints) with `labels` [bs]."""
-        if self.world > 1:
-            raise lib.DmfError('data-parallel stage 2 runs from a plan (load_plan / run_plan)')
-        bs = int(xy.shape[0])
+        """One step on the bs pixels `xy` [bs, 2] (host or device ints) with `labels` [bs].  Data parallel: `xy` / `labels`
+        are the GLOBAL batch (the same on every rank, e.g. the solver's short last batch); every rank trains on its
+        contiguous shard of len // world pixels, and the remainder that the world size does not divide is dropped."""
+        n = int(xy.shape[0])
+        W = 1 if self._single() else self.world
+        bs = n // W
         if bs > self.bs:
             raise lib.DmfError('engine was built for batches of at most %d' % self.bs)
+        if bs == 0:
+            raise lib.DmfError('a batch of %d pixels gives the %d ranks no pixel each' % (n, W))
         dev = self.scene.device
-        xy4 = self.scene.stack_xy(torch.as_tensor(xy).cpu()).to(dev).contiguous()
+        lo = 0 if W == 1 else self.rank * bs
+        xy4 = self.scene.stack_xy(torch.as_tensor(xy).cpu()[lo:lo + bs]).to(dev).contiguous()
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.cpu().numpy())
-        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int32).contiguous()
+        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int32)[:W * bs].contiguous()
         self._check_labels(lab)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy4)
         self._step(inp, bs, lab, None, None)
 
     def load_plan(self, xy_all, labels_all):
         """An epoch of full GLOBAL batches: xy_all [n*bs*world, 2], labels_all [n*bs*world]; rank r trains on rows
-        [r*bs, (r+1)*bs) of every global batch."""
+        [r*bs, (r+1)*bs) of every global batch, and the loss reads the global batch's labels."""
         dev = self.scene.device
         W = self.world
         xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
@@ -710,13 +726,13 @@ class QuaTrainEngine(_PlanEngine):
             raise lib.DmfError('plan length must be a multiple of the (global) batch size')
         n = xy.shape[0] // (self.bs * W)
         self._check_labels(lab)
-        self.plan_labels_global = lab
         if W > 1:
             xy = xy.view(n, W, self.bs, 2)[:, self.rank].reshape(-1, 2)
-            lab = lab.view(n, W, self.bs)[:, self.rank].reshape(-1).contiguous()
         xy4 = torch.cat([self.scene.stack_xy(xy[i * self.bs:(i + 1) * self.bs]) for i in range(n)]) if n else xy
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.numpy())
-        self._install_plan(n, plan_xy=xy4.to(dev).contiguous(), plan_labels=lab)
+        # (the labels as one tensor that a captured graph keeps reading: a plan of the same shape is copied into it)
+        self._install_plan(n, plan_xy=xy4.to(dev).contiguous(), plan_labels_global=lab)
+        self.plan_labels = self.plan_labels_global
         if self.scaler is None:
             self.dev_step.fill_(self.step_count)
         return n
@@ -724,15 +740,17 @@ class QuaTrainEngine(_PlanEngine):
     def _plan_launch(self):
         # (the captured graph runs these same launches: its steps read plan[cursor])
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=4 * self.bs, cursor=self.dev_cursor)
-        self._step(inp, self.bs, self.plan_labels, self.dev_cursor, self.loss_hist, self.dev_step)
+        self._step(inp, self.bs, self.plan_labels_global, self.dev_cursor, self.loss_hist, self.dev_step)
 
     def _graphable(self):
-        return self.unit and self.world == 1
+        """The unit-gradient form on one GPU, or over an RCCL group (its all-gather and all-reduce are captured with the
+        step's launches, TrainEngine's rules: _rccl_capturable); gloo steps eagerly."""
+        return self.unit and (self._single() or self._rccl_capturable())
 
     def _capture(self, n):
-        """Capture n steps (unit-gradient form, one GPU); see _PlanEngine._capture."""
+        """Capture n steps (unit-gradient form, one GPU or RCCL); see _PlanEngine._capture."""
         if not self._graphable():
-            raise lib.DmfError('graph replay needs the unit-gradient step on one GPU')
+            raise lib.DmfError('graph replay needs the unit-gradient step on one GPU or over RCCL')
         super()._capture(n)
 
     # bench.py: the step's dominant launch alone (for HIP-event timing) and its name
@@ -750,7 +768,7 @@ class QuaTrainEngine(_PlanEngine):
         return 'dmf::patch_kernel<ShapeQua, MODE_BWD> (dmf_backward_dlogits: forward recompute + backward of the 4*bs stacked patches)'
 
 
-class QuaEvalEngine:
+class QuaEvalEngine(_ShardedEval):
     """Stage-2 prediction `(out[:bs] + out[bs:2*bs]).softmax(-1).argmax` (tostagesolver.py:337): only the ms and pan
     streams enter it, so only those two are computed."""
 
@@ -790,24 +808,32 @@ class QuaEvalEngine:
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.stack_xy(host, 2).numpy())
         return xy_all.to(dev).contiguous(), host.numpy()
 
-    def confusion(self, xy_all, labels_all, matrix=None):
+    def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
         """Confusion matrix [K,K] int64 (rows = prediction) of the pair prediction over all given pixels, in chunks of the
-        engine's size (tostagesolver.py:331-341)."""
+        engine's size (tostagesolver.py:331-341).  With a process group every rank classifies its contiguous shard of the
+        pixels and the matrices are summed (a given `matrix` is added to on every rank: pass zeros)."""
+        from .parallel import allreduce_sum_
         dev = self.scene.device
         K = self.net.arch['K']
-        xy_all, _ = self._checked_all(xy_all)
+        xy_all = torch.as_tensor(xy_all).to(torch.int32)
         labels_all = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
+        xy_all, labels_all = self._shard(process_group, xy_all, labels_all)
+        xy_all, _ = self._checked_all(xy_all)
         if matrix is None:
             matrix = torch.zeros(K, K, dtype=torch.int64, device=dev)
         for i in range(0, xy_all.shape[0], self.B):
             n = self._forward(xy_all[i:i + self.B], 2, checked=True)
             lib.pair_argmax(self.logits, n, self.pred)
             lib.confusion_accum(self.pred[:n], labels_all[i:i + n], K, matrix)
+        self._all_reduce(matrix, process_group, allreduce_sum_)
         return matrix
 
-    def label_map(self, xy_all, H, W, label_map=None):
-        """Pair prediction of every given pixel written at (x, y) of an [H, W] int32 map (tostagesolver.py:360-383)."""
+    def label_map(self, xy_all, H, W, label_map=None, process_group=None):
+        """Pair prediction of every given pixel written at (x, y) of an [H, W] int32 map (tostagesolver.py:360-383).
+        With a process group the pixels are sharded and the tiles merged (every pixel is written by one rank)."""
+        from .parallel import allreduce_max_
         dev = self.scene.device
+        xy_all, = self._shard(process_group, torch.as_tensor(xy_all).to(torch.int32))
         xy_all, host = self._checked_all(xy_all)
         if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
             raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))
@@ -818,6 +844,7 @@ class QuaEvalEngine:
             n = self._forward(xy, 2, checked=True)
             lib.pair_argmax(self.logits, n, self.pred)
             lib.labelmap_write(self.pred[:n], xy, W, label_map)
+        self._all_reduce(label_map, process_group, allreduce_max_)
         return label_map
 
     def predict(self, xy):

@@ -60,6 +60,7 @@ def _load():
         'dmf_unscale_adam': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, f32, i32, i32, vp, vp, vp]),
         'dmf_grad_reduce_scaled': (i32, [SP, i32, vp, vp, vp, vp, vp, vp, vp]),
         'dmf_qua_loss_scaled': (i32, [vp, i32, i32, vp, vp, C.POINTER(QuaParams), f32, vp, vp, vp, vp, vp]),
+        'dmf_qua_loss_ranks': (i32, [vp, i32, i32, i32, i32, vp, vp, C.POINTER(QuaParams), f32, vp, vp, vp, vp, vp]),
         'dmf_attn_train_workspace_bytes': (i64, [SP, i32]),
         'dmf_train_attn_fwd_bwd': (i32, [SP, IP, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
         'dmf_backward_dlogits': (i32, [SP, IP, vp, vp, vp, vp, vp]),
@@ -397,6 +398,26 @@ def qua_loss(logits, bs, labels, params, loss=None, dlogits=None, grad_scale=1.0
             raise DmfError('dlogits must have the shape of logits')
     check(_lib.dmf_qua_loss_scaled(_ptr(logits), bs, K, _ptr(labels), _ptr(cursor), C.byref(params), grad_scale,
                                    _ptr(scaler_state), _ptr(loss), _ptr(loss_hist), _ptr(dlogits), _stream()))
+
+
+def qua_loss_ranks(gathered, ranks, rank, bs_r, labels_global, params, loss=None, dlogits=None, grad_scale=1.0, cursor=None,
+                   loss_hist=None, scaler_state=None):
+    """qua_loss of the GLOBAL batch of `ranks` data-parallel ranks from their gathered logits [ranks*4*bs_r, K] (rank-major,
+    as all_gather_into_tensor leaves them); dlogits [4*bs_r, K]: rank `rank`'s rows.  ranks = 1 is qua_loss."""
+    _dev(gathered, torch.float32, 'gathered'); _dev(labels_global, torch.int32, 'labels_global')
+    if gathered.dim() != 2 or gathered.shape[0] != 4 * ranks * bs_r:
+        raise DmfError('qua_loss_ranks wants gathered logits [ranks*4*bs_r, K]')
+    if not 0 <= rank < ranks:
+        raise DmfError('qua_loss_ranks: rank %d of %d ranks' % (rank, ranks))
+    if cursor is None and labels_global.numel() < ranks * bs_r:
+        raise DmfError('qua_loss_ranks wants one label per sample of the global batch')
+    if dlogits is not None:
+        _dev(dlogits, torch.float32, 'dlogits')
+        if dlogits.shape != (4 * bs_r, gathered.shape[1]):
+            raise DmfError('dlogits must be [4*bs_r, K]: this rank\'s rows')
+    check(_lib.dmf_qua_loss_ranks(_ptr(gathered), ranks, rank, bs_r, gathered.shape[1], _ptr(labels_global), _ptr(cursor),
+                                  C.byref(params), grad_scale, _ptr(scaler_state), _ptr(loss), _ptr(loss_hist), _ptr(dlogits),
+                                  _stream()))
 
 
 def pair_argmax(logits, bs, pred):

@@ -59,9 +59,12 @@ class BaseSolver:
         self.records = {'Epoch': [], 'PSNR': [], 'SSIM': [], 'Loss': []}
         self.scene = None
         self.fast = bool(cfg.get('fast_path', 1)) and str(self.DEVICE).startswith('cuda')
+        # gmf.half: 1 — the fast path keeps the primary scene in fp16 and trains with the device loss scaler (the drop-in
+        # path rounds its patches to fp16 as they are staged, model/gmfnet.py)
+        self.half = bool((cfg.get('gmf') or {}).get('half', 0))
         if self.fast:
             from dmf.engine import Scene
-            self.scene = Scene(self.MS, self.PAN, self.DEVICE)
+            self.scene = Scene(self.MS, self.PAN, self.DEVICE, half=self.half)
 
     def _loader(self, subset, batch, shuffle):
         twin = Subset(self.index_dataset, indices=subset.indices)

@@ -11,6 +11,9 @@ Two execution paths, same arithmetic:
     materialisation, no per-step host sync, confusion matrix and label maps built on the device;
   * drop-in (`fast_path: 0`): the reference's own loop body (mainsolver.py:49-55) over materialised batches through
     `Net.forward` / autograd / torch ADAM.
+`gmf.half: 1` on the fast path: fp16 resident scene and the device loss scaler (dmf.engine.LossScaler with GradScaler's
+defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gives the switch; SGD / RMSprop are refused
+(the scaler step is ADAM), and the one-shot xgmi exchange is not used (it does not carry the scaler).
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -117,6 +120,16 @@ class Solver(BaseSolver):
         self.train_time = time.time() - time1
         self.epoch = 0
 
+    def _loss_scaler(self, hp):
+        """gmf.half: 1 on the fast path -> the device loss scaler with GradScaler's defaults; its step is ADAM."""
+        if not self.half:
+            return None
+        if hp['optimizer'] != 'ADAM':
+            raise ValueError('gmf.half: 1 trains with the loss scaler, whose step is ADAM; schedule.optimizer is %s'
+                             % hp['optimizer'])
+        from dmf.engine import LossScaler
+        return LossScaler(self.DEVICE)
+
     def _make_engines(self):
         from dmf.engine import EvalEngine, TrainEngine
         if self.cfg['schedule']['loss'] != 'Criterion':
@@ -124,10 +137,11 @@ class Solver(BaseSolver):
         hp = optim_hparams(self.cfg)                             # ADAM (fused), SGD or RMSprop (utils/utils.py:10-16)
         if self.cfg['batchsize'] % self.world:
             raise ValueError('batchsize %d is not divisible by the %d ranks' % (self.cfg['batchsize'], self.world))
+        scaler = self._loss_scaler(hp)
         self.engine = TrainEngine(self.cur_model, self.scene, self.cfg['batchsize'] // self.world, lr=hp['lr'], betas=hp['betas'],
                                   eps=hp['eps'], process_group=self.process_group,
-                                  comm=self.comm if hp['optimizer'] == 'ADAM' else None, optimizer=hp['optimizer'],
-                                  momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99))
+                                  comm=self.comm if hp['optimizer'] == 'ADAM' and scaler is None else None, scaler=scaler,
+                                  optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99))
         self.eval_engine = EvalEngine(self.cur_model, self.scene, self._eval_chunk())
 
     def _eval_chunk(self):

@@ -13,6 +13,11 @@ Stage 1 (:86-238) trains `model.generator` / `model.discriminator`, which the re
 is NOT built.  Run stage 2 on stage-1 outputs that already exist (`dqtl.pre_trained: 1`: `msgan.npy`, `pangan.npy`
 under cfg['expo_result'] + cfg['dqtl']['WEIGHTS'], as the reference does at :241-243).  `pan.npy` (:246) is produced
 from the PAN image with `pan2ms` (image_convert/IHS.py:14-19, on the GPU) when the file does not exist.
+`gmf.half: 1` on the fast path: fp16 tall scene and the device loss scaler around the ADAM step (as in solver.mainsolver).
+Data parallel (`test.py` with `solver: toStageSolver` under `torch.distributed.run`, fast path only): every rank iterates the
+same shuffled stream, the engine trains each rank on its contiguous shard of every global batch and evaluates the loss on
+the gathered global batch (dmf.engine.QuaTrainEngine); the short last batch is sharded the same way (a remainder that the
+world size does not divide is dropped); test / colour shard the pixels; rank 0 writes the artefacts.
 Deliberate differences: label maps are written as PNG (the reference writes .jpg here and .png in Solver); `nohup: 1`
 works (reference bug at :300); the t-SNE / feature visualisation helpers (:416-530) are out of scope.
 """
@@ -65,7 +70,7 @@ class toStageSolver(Solver):
         self.index_dataset = self.dataset.index_view()
         if self.fast:
             from dmf.engine import QuaScene
-            self.qua_scene = QuaScene(scenes, self.DEVICE)
+            self.qua_scene = QuaScene(scenes, self.DEVICE, half=self.half)
 
     # ------------------------------------------------------------------ hooks of Solver.train
     def _make_engines(self):
@@ -73,8 +78,11 @@ class toStageSolver(Solver):
         if self.cfg['schedule']['loss'] != 'qua_loss':
             raise ValueError('stage 2 trains with schedule.loss: qua_loss')
         hp = optim_hparams(self.cfg)
-        self.engine = QuaTrainEngine(self.cur_model, self.qua_scene, self.cfg['batchsize'], self.cfg['dqtl'], lr=hp['lr'],
-                                     betas=hp['betas'], eps=hp['eps'], optimizer=hp['optimizer'],
+        if self.cfg['batchsize'] % self.world:
+            raise ValueError('batchsize %d is not divisible by the %d ranks' % (self.cfg['batchsize'], self.world))
+        self.engine = QuaTrainEngine(self.cur_model, self.qua_scene, self.cfg['batchsize'] // self.world, self.cfg['dqtl'],
+                                     lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], process_group=self.process_group,
+                                     scaler=self._loss_scaler(hp), optimizer=hp['optimizer'],
                                      momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99))
         self._make_eval_engine()
 
@@ -85,7 +93,7 @@ class toStageSolver(Solver):
                                          max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], 8192), self.cfg['dqtl'])
 
     def _train_epoch_fast(self):
-        eng, B = self.engine, self.cfg['batchsize']
+        eng, B = self.engine, self.cfg['batchsize']              # (global batches: the engine takes this rank's shard)
         hp = epoch_hparams(self.cfg, self.epoch)              # lr (and, under OneCycleLR, beta1 / momentum) of this epoch
         eng.lr = float(hp['lr'])
         if 'betas' in hp:
@@ -100,7 +108,7 @@ class toStageSolver(Solver):
             eng.run_plan(len(full), int(self.cfg.get('steps_per_graph', 0)) if eng.unit else 0)
             losses = eng.losses().tolist()
         for xy, lab in batches:
-            if xy.shape[0] != B:                                             # DataLoader keeps the short last batch
+            if xy.shape[0] != B and xy.shape[0] >= self.world:               # DataLoader keeps the short last batch
                 eng.step(xy, lab)
                 losses.append(float(eng.loss.item()))
         self.step_losses += losses
@@ -170,14 +178,19 @@ class toStageSolver(Solver):
         with torch.no_grad():
             if self.fast:                                    # the whole split in the engine's own chunks
                 parts = [self._xy_labels(b) for b in self.test_index_loader]
-                matrix = self.eval_engine.confusion(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), matrix)
+                matrix = self.eval_engine.confusion(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), matrix,
+                                                    process_group=self.process_group)
             else:
                 for batch in self.test_loader:               # every batch (:331-341)
                     pred, target, _ = self._pair_pred(batch)
                     lib.confusion_accum(pred, target.contiguous(), K, matrix)
         self.test_time = time.time() - time1
         self.test_matrix = matrix.cpu().numpy().astype(np.float64)
-        self.indicator()
+        if self.rank == 0:
+            self.indicator()
+        else:
+            from indicators.kappa import aa_oa_quiet
+            self.result = list(aa_oa_quiet(self.test_matrix)) + [None]
 
     def color(self):
         from dmf import lib
@@ -193,7 +206,8 @@ class toStageSolver(Solver):
                                  (self.cfg['color']['unsupervised'], (self.color_index_loader2, self.color_loader2))):
                 m = torch.zeros(H, W, dtype=torch.int32, device=self.DEVICE)
                 if use and self.fast:
-                    m = self.eval_engine.label_map(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W, m)
+                    m = self.eval_engine.label_map(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W, m,
+                                                   process_group=self.process_group)
                 elif use:
                     for batch in loaders[1]:
                         pred, _, xy = self._pair_pred(batch)
@@ -202,7 +216,7 @@ class toStageSolver(Solver):
         label_np1 = maps[0]
         label_np2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
         self.label_maps = (label_np1, label_np2)
-        if self.cfg['color']['supervised']:
+        if self.cfg['color']['supervised'] and self.rank == 0:
             Image.fromarray(lut[label_np1]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_1.png")
             Image.fromarray(lut[label_np2]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_2.png")
 

@@ -1,7 +1,9 @@
 """Launcher (mirror of the reference test.py:7-14): seed 3407, render config.yml, Solver(cfg).run().
 
+`solver: toStageSolver` (NEW key; default `Solver`) runs stage 2 of the two-stage path (solver/tostagesolver.py) instead.
 Under `python -m torch.distributed.run --nproc-per-node N test.py config.yml` (one process per GPU) the same run is
-data parallel: every rank seeds identically, takes GPU LOCAL_RANK, and the solver shards every batch (solver/mainsolver.py).
+data parallel: every rank seeds identically, takes GPU LOCAL_RANK, and the solver shards every batch (solver/mainsolver.py,
+solver/tostagesolver.py).
 """
 import os
 import sys
@@ -10,7 +12,24 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from solver.mainsolver import Solver          # noqa: E402
+from solver.tostagesolver import toStageSolver  # noqa: E402
 from utils.config import get_render_config    # noqa: E402
+
+
+SOLVERS = {'Solver': Solver, 'toStageSolver': toStageSolver}
+
+
+def solver_class(cfg):
+    """The solver the configuration names (`solver`, default Solver)."""
+    name = cfg.get('solver') or 'Solver'
+    if name not in SOLVERS:
+        raise ValueError('solver: %r is not one of %s' % (name, ', '.join(sorted(SOLVERS))))
+    return SOLVERS[name]
+
+
+def uses_xgmi_exchange(cfg):
+    """The one-shot exchange is the single-stage solver's, without the loss scaler (gmf.half) that it does not carry."""
+    return bool(solver_class(cfg) is Solver and cfg.get('xgmi_exchange', 1) and not (cfg.get('gmf') or {}).get('half', 0))
 
 
 def attach_process_group(solver, cfg):
@@ -19,7 +38,7 @@ def attach_process_group(solver, cfg):
     from dmf import xgmi
     solver.process_group = dist.group.WORLD
     solver.rank, solver.world = dist.get_rank(), dist.get_world_size()
-    if dist.get_backend() == 'nccl' and cfg.get('xgmi_exchange', 1):
+    if dist.get_backend() == 'nccl' and uses_xgmi_exchange(cfg):
         import importlib
         net = importlib.import_module('model.' + cfg['model_name'].lower()).Net(args=cfg)
         solver.comm = xgmi.create(sum(p.numel() for p in net.parameters()), solver.process_group)
@@ -42,7 +61,8 @@ if __name__ == "__main__":
         cfg = box[0]
         cfg['device'] = 'cuda:%d' % local
         torch.manual_seed(3407)
-        attach_process_group(Solver(cfg), cfg).run()
+        attach_process_group(solver_class(cfg)(cfg), cfg).run()
         dist.destroy_process_group()
     else:
-        Solver(get_render_config(path)).run()
+        cfg = get_render_config(path)
+        solver_class(cfg)(cfg).run()

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 300   /* 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 301   /* 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -236,6 +236,16 @@ int32_t dmf_qua_loss(const float* logits, int32_t bs, int32_t K, const int32_t* 
 int32_t dmf_qua_loss_scaled(const float* logits, int32_t bs, int32_t K, const int32_t* labels, const int32_t* cursor,
                             const dmf_qua_params* params, float grad_scale, const float* scaler_state,
                             float* loss, float* loss_hist, float* dlogits, void* stream);
+/* The same loss for data-parallel stage 2, on the logits as all_gather_into_tensor leaves them: gathered
+ * [ranks][4][bs_r][K] (rank-major; global sample g = r*bs_r + i of stream s at row r*4*bs_r + s*bs_r + i).  The global batch
+ * is bs = ranks*bs_r in the order [rank][bs_r]: labels_global[(*cursor)*bs + g]; loss / loss_hist[*cursor] get the GLOBAL
+ * loss; dlogits_rank [4][bs_r][K] (may be NULL) gets rank `rank`'s rows only, multiplied by grad_scale * scaler_state[0]
+ * (scaler_state may be NULL).  Loss and rows are bit-identical to dmf_qua_loss_scaled on the same batch restacked
+ * stream-major [4][bs][K]; ranks = 1, rank = 0 is dmf_qua_loss_scaled. */
+int32_t dmf_qua_loss_ranks(const float* gathered, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,
+                           const int32_t* labels_global, const int32_t* cursor, const dmf_qua_params* params,
+                           float grad_scale, const float* scaler_state, float* loss, float* loss_hist,
+                           float* dlogits_rank, void* stream);
 /* Replaces `(output[:bs] + output[bs:2*bs]).softmax(dim=-1).data.max(1)[1]` (tostagesolver.py:337,366,378). */
 int32_t dmf_pair_argmax(const float* logits, int32_t bs, int32_t K, int32_t* pred, void* stream);
 /* Auxiliary input of the single-stream net: per-pixel mean over bands, ((x0+x1)+x2)+... then / C.

@@ -10,10 +10,9 @@ What it removes from the reference's hot loop (solver/mainsolver.py:49-58):
   * per-launch host work                                   -> an epoch plan (shuffled coordinates + labels) is
     uploaded once and a captured hipGraph of `steps_per_graph` steps is replayed; batch cursor and the
     Adam step count live in device memory.
-Data parallel (world_size > 1), two forms with identical updates on every rank:
-  * with a `dmf.xgmi.Communicator`: `dmf_grad_reduce_xgmi_adam` — the ranks exchange their flat gradient inside the
-    reduce + Adam launch (one-shot over xGMI, rank-ordered sum), still two launches per step and graph-replayable;
-  * without: `dmf_grad_reduce` -> all-reduce(sum) of ONE flat fp32 gradient over RCCL -> `dmf_adam_step(1/world)`.
+Data parallel (world_size > 1) gives identical updates on every rank, from ONE flat fp32 gradient per step: exchanged
+inside the reduce + Adam launch by a `dmf.xgmi.Communicator`, or all-reduced over the process group.  What runs after the
+backward, for every optimiser, loss-scaler and group form of both train engines: `_PlanEngine._update`.
 """
 import contextlib
 import sys
@@ -90,6 +89,8 @@ class _PlanEngine:
     def __init__(self, net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha):
         if optimizer not in ('ADAM', 'SGD', 'RMSprop'):
             raise lib.DmfError('optimizer %r is not one of ADAM, SGD, RMSprop' % (optimizer,))
+        if scaler is not None and optimizer != 'ADAM':
+            raise lib.DmfError('%s with a loss scaler: the loss-scaler step is ADAM' % optimizer)
         self.optim, self.momentum, self.alpha = optimizer, float(momentum), float(alpha)
         self.lr, self.b1, self.b2, self.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         self.net, self.scene, self.scaler = net, scene, scaler
@@ -124,14 +125,61 @@ class _PlanEngine:
         if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
             raise lib.DmfError('label outside [0, %d)' % K)
 
-    def _optimizer_step(self, grad_scale, dev_step, cursor):
-        """SGD / RMSprop on the flat gradient (utils/utils.py:13-16); m holds the optimiser's one state vector (SGD: momentum
-        buffer, RMSprop: running mean of squares)."""
-        if self.optim == 'SGD':
-            lib.sgd_step(self.theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=grad_scale,
-                         step_dev=dev_step, cursor_dev=cursor)
+    # ------------------------------------------------------------------ the optimiser update of one step
+    def _counts_on_device(self):
+        """Is the device step counter the true step count?  Then eager steps advance it too, and load_plan leaves it alone;
+        otherwise eager steps use the host count `step_count` and load_plan copies it into the counter.  With a loss
+        scaler it is: a skipped step takes its count back on the device."""
+        return self.scaler is not None
+
+    def _count_step(self, dev_step):
+        """Count one step on the host; returns the device step counter the step's launches take (None: the host count).
+        A plan step gives it; an eager step (dev_step None) takes it where `_counts_on_device()`."""
+        self.step_count += 1
+        return self.dev_step if dev_step is None and self._counts_on_device() else dev_step
+
+    def _update(self, rows, dev_step, cursor, sum_scale, loss=None, loss_hist=None):
+        """The launches after the backward, from the slab rows of `rows` patches in self.ws:
+          ADAM, no scaler, one GPU      dmf_grad_reduce_adam (reduce + ADAM in one launch)
+          ADAM, no scaler, xGMI comm    dmf_grad_reduce_xgmi_adam (the ranks' rank-ordered sum inside that launch)
+          scaler, one GPU               dmf_grad_reduce_scaled (reduce, unscale, check) -> dmf_unscale_adam(unscaled = 1):
+                                        GradScaler's unscale_, step and update (tostagesolver.py:98,119)
+          everything else               dmf_grad_reduce -> all-reduce(sum) where the step has a collective -> the mean loss
+                                        into loss_hist[cursor] -> dmf_unscale_adam (the check sees the SUM, so every rank
+                                        takes the same skip decision) / dmf_sgd_step / dmf_rmsprop_step / dmf_adam_step
+        sum_scale scales the all-reduced gradient: 1/world where the loss is a per-rank mean, 1 where the loss kernel
+        already divided by the global batch.  dev_step: the device step counter, or None for the host count.  loss /
+        loss_hist: where the step's mean loss (this rank's) is recorded; None where the loss kernel records it itself.
+        SGD and RMSprop keep their one state vector in m (momentum buffer / running mean of squares)."""
+        sc, hp = self.scaler, (self.lr, self.b1, self.b2, self.eps)
+        fused = sc is None and self.optim == 'ADAM'
+        if fused and self._single():
+            lib.grad_reduce_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count,
+                                 adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+        elif fused and self.comm is not None:
+            lib.grad_reduce_xgmi_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, self.comm.c, *hp, sum_scale,
+                                      dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+        elif sc is not None and self._single():
+            lib.grad_reduce_scaled(self.shape, rows, self.ws, self.grad, sc.state, cursor_dev=cursor, loss=loss,
+                                   loss_hist=loss_hist)
+            lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step, unscaled=True)
         else:
-            lib.rmsprop_step(self.theta, self.grad, self.m, self.lr, self.alpha, grad_scale=grad_scale, cursor_dev=cursor)
+            lib.grad_reduce(self.shape, rows, self.ws, self.grad)
+            if not self._single():
+                self._all_reduce_grad()
+            if loss_hist is not None:
+                loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
+            if sc is not None:
+                lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step,
+                                 grad_scale=sum_scale, cursor_dev=cursor)
+            elif self.optim == 'SGD':
+                lib.sgd_step(self.theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=sum_scale,
+                             step_dev=dev_step, cursor_dev=cursor)
+            elif self.optim == 'RMSprop':
+                lib.rmsprop_step(self.theta, self.grad, self.m, self.lr, self.alpha, grad_scale=sum_scale, cursor_dev=cursor)
+            else:
+                lib.adam_step(self.theta, self.grad, self.m, self.v, *hp, self.step_count, grad_scale=sum_scale,
+                              adam_step_dev=dev_step, cursor_dev=cursor)
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def _install_plan(self, n, **plan):
@@ -148,6 +196,8 @@ class _PlanEngine:
         self.loss_hist.zero_()
         self.dev_cursor.zero_()
         self.host_cursor, self.plan_steps = 0, n
+        if not self._counts_on_device():
+            self.dev_step.fill_(self.step_count)
 
     def _plan_step(self):
         if self.host_cursor >= self.plan_steps:          # the kernel reads plan[cursor] unchecked: never step past the plan
@@ -276,13 +326,13 @@ class _PlanEngine:
 class TrainEngine(_PlanEngine):
     def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
                  optimizer='ADAM', momentum=0.0, alpha=0.99):
-        """optimizer: 'ADAM' (fused into the reduce launch), or the reference's other two (utils/utils.py:13-16) — 'SGD'
-        (`momentum`) and 'RMSprop' (`alpha`, eps 1e-8) — as a third launch on the flat gradient."""
+        """optimizer: 'ADAM', or the reference's other two (utils/utils.py:13-16) — 'SGD' (`momentum`) and 'RMSprop'
+        (`alpha`, eps 1e-8).  The launches after the backward: _PlanEngine._update."""
         super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
-        if optimizer != 'ADAM' and (comm is not None or scaler is not None):
-            raise lib.DmfError('%s: single GPU or RCCL data parallel, no loss scaler (the fused exchange and the scaler step are ADAM)' % optimizer)
+        if optimizer != 'ADAM' and comm is not None:
+            raise lib.DmfError('%s: single GPU or RCCL data parallel (the fused xgmi exchange is ADAM)' % optimizer)
         dev = scene.device
         if self.theta.device != dev:
             raise lib.DmfError('net and scene must be on the same device')
@@ -315,53 +365,22 @@ class TrainEngine(_PlanEngine):
         inp = lib.input_patches(self.shape, a, b)
         self._launch(inp, labels, None, None)
 
-    def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
-        self.step_count += 1
-        theta, sc, nB = self.theta, self.scaler, inp.B
-        if dev_step is None and (self.comm is not None or sc is not None or self.optim != 'ADAM'):
-            dev_step = self.dev_step      # the exchange numbers its rounds by the device step count; with a loss scaler skipped
-                                          # steps make the device count the only true one; SGD's first step is told by it
-        if self.shape.attention:
-            lib.train_attn_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits, self.loss,
-                                   self.ws, self.attn_ws, adam_step_dev=dev_step)
-        else:
-            lib.train_fwd_bwd(self.shape, inp, theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
-                              adam_step_dev=dev_step, scaler_state=sc.state if sc is not None else None)
-        loss = self.loss if loss_hist is not None else None
-        if self.optim != 'ADAM':          # flat gradient [all-reduce], then the optimiser's own launch
-            self._reduce_gradient(nB, dev_cursor, loss_hist)
-            self._optimizer_step(1.0 / self.world, dev_step, dev_cursor)
-        elif sc is not None and self._single():
-            # scaler.scale(loss).backward() -> scaler.unscale_ + scaler.step(opt) + scaler.update(): reduce (+ unscale + check),
-            # then Adam-or-skip
-            lib.grad_reduce_scaled(self.shape, nB, self.ws, self.grad, sc.state, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
-            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
-        elif sc is not None:              # the check must see the SUM: after the all-reduce
-            self._reduce_gradient(nB, dev_cursor, loss_hist)
-            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step,
-                             grad_scale=1.0 / self.world, cursor_dev=dev_cursor)
-        elif self._single():
-            lib.grad_reduce_adam(self.shape, nB, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
-                                 self.step_count, adam_step_dev=dev_step, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
-        elif self.comm is not None:
-            lib.grad_reduce_xgmi_adam(self.shape, nB, self.ws, theta, self.m, self.v, self.comm.c, self.lr, self.b1,
-                                      self.b2, self.eps, 1.0 / self.world, dev_step, cursor_dev=dev_cursor, loss=loss, loss_hist=loss_hist)
-        else:
-            self._reduce_gradient(nB, dev_cursor, loss_hist)
-            lib.adam_step(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count,
-                          grad_scale=1.0 / self.world, adam_step_dev=dev_step, cursor_dev=dev_cursor)
+    def _counts_on_device(self):
+        """As _PlanEngine's, and: the xgmi exchange numbers its rounds by the device step count, and SGD's first step is told
+        by it."""
+        return self.comm is not None or self.scaler is not None or self.optim != 'ADAM'
 
-    def _reduce_gradient(self, nB, dev_cursor, loss_hist):
-        """The unfused forms: the slab rows into the flat gradient, its all-reduce (sum) over the group where the step has a
-        collective, and the step's mean loss (this rank's, as the fused forms record it) at dev_cursor."""
-        lib.grad_reduce(self.shape, nB, self.ws, self.grad)
-        if not self._single():
-            import torch.distributed as dist
-            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg)
-        if loss_hist is not None:
-            loss_hist.scatter_(0, dev_cursor.long(), self.loss[:nB].mean().reshape(1))
+    def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
+        dev_step = self._count_step(dev_step)
+        sc, nB = self.scaler, inp.B
+        if self.shape.attention:
+            lib.train_attn_fwd_bwd(self.shape, inp, self.theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits,
+                                   self.loss, self.ws, self.attn_ws, adam_step_dev=dev_step)
+        else:
+            lib.train_fwd_bwd(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
+                              adam_step_dev=dev_step, scaler_state=sc.state if sc is not None else None)
+        # the loss is this rank's mean: the sum over the ranks is scaled by 1/world
+        self._update(nB, dev_step, dev_cursor, 1.0 / self.world, self.loss if loss_hist is not None else None, loss_hist)
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def load_plan(self, xy_all, labels_all):
@@ -378,8 +397,6 @@ class TrainEngine(_PlanEngine):
         # from it with ONE device copy per replay
         pack = torch.cat([xy.view(n, 2 * self.B), lab.view(n, self.B)], 1).contiguous()
         self._install_plan(n, plan_xy=xy, plan_labels=lab, plan_pack=pack)
-        if self.scaler is None and self.optim == 'ADAM':   # (with a scaler the device count is authoritative: skipped steps;
-            self.dev_step.fill_(self.step_count)           #  the other optimisers always step by the device count)
         return n
 
     def _plan_launch(self):
@@ -603,24 +620,20 @@ class QuaTrainEngine(_PlanEngine):
     """Stage-2 train step (tostagesolver.py:268-278) on the resident tall scene, no host sync.  The loss couples the whole
     batch, so it cannot ride inside the per-patch kernel like cross-entropy does.  Two forms:
       * unit-gradient step (shapes with a v2 kernel): `dmf_forward_unit` (forward of the 4*bs stacked patches + the conv
-        backward for a unit gradient per pooled feature) -> `dmf_qua_loss` (value + d/dlogits) -> `dmf_backward_unit`
-        (dh, dz, scaled slab rows) -> `dmf_grad_reduce_adam`: the patches are visited ONCE, and the four launches replay
-        from a captured hipGraph (`run_plan(steps, steps_per_graph)`);
-      * otherwise `dmf_forward` -> `dmf_qua_loss` -> `dmf_backward_dlogits` (recomputes the forward) -> reduce + ADAM.
+        backward for a unit gradient per pooled feature) -> `dmf_qua_loss_ranks` (value + d/dlogits) -> `dmf_backward_unit`
+        (dh, dz, scaled slab rows) -> the update: the patches are visited ONCE, and the step replays from a captured
+        hipGraph (`run_plan(steps, steps_per_graph)`);
+      * otherwise `dmf_forward` -> `dmf_qua_loss_ranks` -> `dmf_backward_dlogits` (recomputes the forward) -> the update.
     Data parallel (process_group): every rank takes its shard of each global batch; `all_gather_into_tensor` of the logits
-    into a buffer allocated once (gloo: a host gather and one H2D copy into it) -> `dmf_qua_loss_ranks` (the GLOBAL batch's
-    loss, this rank's rows of d loss / d logits) -> backward -> `dmf_grad_reduce` -> all-reduce(sum) -> the optimiser step
-    on the device step count and cursor.  With a loss scaler (unit form, ADAM) the step is `dmf_unscale_adam(unscaled = 0)`
-    after the all-reduce, so every rank sees the same sum and takes the same skip decision.  Over RCCL the whole step
-    replays from a captured hipGraph like the single-GPU one."""
+    into a buffer allocated once (gloo: a host gather and one H2D copy into it) feeds the loss of the GLOBAL batch, which
+    writes this rank's rows of d loss / d logits.  Over RCCL the whole step replays from a captured hipGraph like the
+    single-GPU one.  The update after the backward (optimiser, loss scaler, all-reduce): _PlanEngine._update."""
 
     def __init__(self, net, scene, bs, dqtl, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, scaler=None,
                  optimizer='ADAM', momentum=0.0, alpha=0.99):
         if not net.arch.get('single_input'):
             raise lib.DmfError('stage 2 needs the single-input net (cfg["gmf"]["single_input"] = 1)')
         super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
-        if optimizer != 'ADAM' and scaler is not None:
-            raise lib.DmfError('the loss-scaler step is ADAM')
         self.bs = int(bs)
         self.unit = lib.unit_supported(self.shape)
         if scaler is not None and not self.unit:
@@ -650,50 +663,23 @@ class QuaTrainEngine(_PlanEngine):
 
     def _step(self, inp, bs, labels, cursor, loss_hist, dev_step=None):
         """One step on this rank's 4*bs stacked patches; labels: the GLOBAL batch's ([world*bs] at row cursor)."""
-        self.step_count += 1
-        theta, sc = self.theta, self.scaler
-        if sc is not None and dev_step is None:
-            dev_step = self.dev_step      # with a loss scaler skipped steps make the device count the only true one
+        dev_step = self._count_step(dev_step)
         if self.unit:
-            lib.forward_unit(self.shape, inp, theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
+            lib.forward_unit(self.shape, inp, self.theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
         else:
-            lib.forward(self.shape, inp, theta, self.net.pool_w, self.logits)
-        scaler_state = sc.state if sc is not None else None
-        if self._single():
-            lib.qua_loss(self.logits[:4 * bs], bs, labels, self.params, loss=self.loss, dlogits=self.dlogits[:4 * bs],
-                         cursor=cursor, loss_hist=loss_hist, scaler_state=scaler_state)
-        else:
-            lib.qua_loss_ranks(self._gather(bs), self.world, self.rank, bs, labels, self.params, loss=self.loss,
-                               dlogits=self.dlogits[:4 * bs], cursor=cursor, loss_hist=loss_hist, scaler_state=scaler_state)
+            lib.forward(self.shape, inp, self.theta, self.net.pool_w, self.logits)
+        # the loss of the global batch from the logits of all ranks (one GPU: its own logits, world 1, rank 0)
+        logits = self.logits[:4 * bs] if self._single() else self._gather(bs)
+        lib.qua_loss_ranks(logits, self.world, self.rank, bs, labels, self.params, loss=self.loss,
+                           dlogits=self.dlogits[:4 * bs], cursor=cursor, loss_hist=loss_hist,
+                           scaler_state=self.scaler.state if self.scaler is not None else None)
         if self.unit:
-            lib.backward_unit(self.shape, 4 * bs, theta, self.dlogits, self.ws)
+            lib.backward_unit(self.shape, 4 * bs, self.theta, self.dlogits, self.ws)
         else:
-            lib.backward_dlogits(self.shape, inp, theta, self.net.pool_w, self.dlogits, self.ws)
-        if not self._single():
-            # the loss kernel already divided by the GLOBAL batch: the sum over ranks is the gradient
-            lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
-            self._all_reduce_grad()
-            if sc is not None:            # the check must see the SUM (include/dmf.h): after the all-reduce
-                lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                                 sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, grad_scale=1.0,
-                                 cursor_dev=cursor)
-            elif self.optim != 'ADAM':
-                self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
-            else:
-                lib.adam_step(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.step_count,
-                              grad_scale=1.0, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
-        elif sc is not None:
-            # scaler.scale(loss).backward(); scaler.step(opt); scaler.update()  (tostagesolver.py:98,119 do this for the
-            # stage-1 pair; here it wraps the stage-2 step)
-            lib.grad_reduce_scaled(self.shape, 4 * bs, self.ws, self.grad, sc.state, cursor_dev=cursor)
-            lib.unscale_adam(theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, self.eps, sc.state,
-                             sc.growth_factor, sc.backoff_factor, sc.growth_interval, dev_step, unscaled=True)
-        elif self.optim != 'ADAM':
-            lib.grad_reduce(self.shape, 4 * bs, self.ws, self.grad)
-            self._optimizer_step(1.0, dev_step if self.unit else None, cursor)
-        else:
-            lib.grad_reduce_adam(self.shape, 4 * bs, self.ws, theta, self.m, self.v, None, self.lr, self.b1, self.b2, self.eps,
-                                 self.step_count, adam_step_dev=dev_step if self.unit else None, cursor_dev=cursor)
+            lib.backward_dlogits(self.shape, inp, self.theta, self.net.pool_w, self.dlogits, self.ws)
+        # the loss kernel already divided by the GLOBAL batch: the sum over the ranks is the gradient.  dmf_forward does not
+        # count steps: the non-unit form updates by the host count
+        self._update(4 * bs, dev_step if self.unit else None, cursor, 1.0)
 
     def step(self, xy, labels):
         """One step on the bs pixels `xy` [bs, 2] (host or device ints) with `labels` [bs].  Data parallel: `xy` / `labels`
@@ -733,8 +719,6 @@ class QuaTrainEngine(_PlanEngine):
         # (the labels as one tensor that a captured graph keeps reading: a plan of the same shape is copied into it)
         self._install_plan(n, plan_xy=xy4.to(dev).contiguous(), plan_labels_global=lab)
         self.plan_labels = self.plan_labels_global
-        if self.scaler is None:
-            self.dev_step.fill_(self.step_count)
         return n
 
     def _plan_launch(self):

@@ -1,0 +1,276 @@
+"""CPU: the launch sequence of one train step of both train engines, for every optimiser, loss-scaler, group and net form
+they accept — eager (`step`) and from the plan (`run_plan(1, 0)`).
+
+The library's entry points are replaced by a recorder: the host-only queries still reach the real library, every launch
+returns 0 and is recorded with its scalar arguments and its pointer arguments named by the engine attribute they point
+into.  The lib.py wrappers run their real argument marshalling (device checks and the stream are stubbed for CPU
+tensors).  The torch.distributed collectives of the step are recorded too, on a one-rank gloo group whose collectives
+are kept in the step (`_force_collective`).  `expected_update` below states the update rule after the backward."""
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+import torch
+
+DQTL = {'alpha': 0.1, 'beta': 0.05, 'gamma': 1.0, 'epsilon': 1e-8, 'tao': 0.1}
+HOST_QUERIES = ('dmf_version', 'dmf_last_error', 'dmf_shape_supported', 'dmf_patch_variant', 'dmf_param_layout',
+                'dmf_workspace_bytes', 'dmf_attn_workspace_bytes', 'dmf_attn_train_workspace_bytes', 'dmf_half_supported',
+                'dmf_unit_supported', 'dmf_xgmi_sizes')
+# pointer -> name: engine attributes first (a plan may be the caller's own tensor), then the caller's eager batch
+NAMED = ('theta', 'm', 'v', 'grad', 'ws', 'attn_ws', 'logits', 'dlogits', 'loss', 'gathered', 'plan_xy', 'plan_labels',
+         'dev_step', 'dev_cursor', 'loss_hist')
+
+
+class Ptr(int):
+    """A recorded pointer argument, named when the calls are taken."""
+
+
+class Recorder:
+    """Stand-in for lib._lib."""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    @staticmethod
+    def arg(a):
+        if isinstance(a, C.c_void_p):
+            return None if a.value is None else Ptr(a.value)
+        if isinstance(a, C.c_float):
+            return float(np.float32(a.value))
+        if isinstance(a, float):
+            return float(np.float32(a))
+        obj = getattr(a, '_obj', None)           # C.byref(...)
+        if isinstance(obj, C.Structure):
+            from dmf import lib
+            if isinstance(obj, lib.Input):
+                return ('input', obj.mode, obj.B) + tuple(None if p is None else Ptr(p) for p in (obj.sceneA, obj.sceneB, obj.xy)) + (
+                    obj.Wp, obj.WpB, None if obj.cursor is None else Ptr(obj.cursor), obj.half)
+            return {lib.Shape: 'shape', lib.QuaParams: 'params', lib.XgmiComm: 'comm'}[type(obj)]
+        return a
+
+    def __getattr__(self, entry):
+        if entry in HOST_QUERIES:
+            return getattr(self.real, entry)
+
+        def launch(*args):
+            self.calls.append((entry,) + tuple(self.arg(a) for a in args))
+            return 0
+        return launch
+
+    def collective(self, fn, entry):
+        def call(*args, **kw):
+            t = args[1] if entry == 'all_gather' else args[0]
+            self.calls.append((entry, Ptr(t.data_ptr())))
+            return fn(*args, **kw)
+        return call
+
+    def take(self, eng, **extra):
+        """The calls since the last take(), pointers named by the engine's tensor (or one of `extra`) they point into."""
+        tensors = {n: getattr(eng, n) for n in NAMED if getattr(eng, n, None) is not None}
+        tensors.update(pool_w=eng.net.pool_w, sceneA=eng.scene.A, sceneB=eng.scene.B, **extra)
+        if eng.scaler is not None:
+            tensors['scaler'] = eng.scaler.state
+
+        def name(a):
+            if isinstance(a, tuple):
+                return tuple(name(x) for x in a)
+            if not isinstance(a, Ptr):
+                return a
+            for n, t in tensors.items():
+                lo = t.data_ptr()
+                if t.numel() and lo <= a < lo + t.numel() * t.element_size():
+                    return n if a == lo else '%s+%d' % (n, a - lo)
+            return '?'
+        calls, self.calls = [name(c) for c in self.calls], []
+        # the stage-2 loss of one rank: dmf_qua_loss_scaled(l, bs, K, ...) is dmf_qua_loss_ranks(l, 1, 0, bs, K, ...)
+        return [('dmf_qua_loss_ranks', c[1], 1, 0) + c[2:] if c[0] == 'dmf_qua_loss_scaled' else c for c in calls]
+
+
+@pytest.fixture(scope='module')
+def group(tmp_path_factory):
+    import torch.distributed as dist
+    dist.init_process_group('gloo', init_method='file://%s' % tmp_path_factory.mktemp('pg').joinpath('store'),
+                            rank=0, world_size=1)
+    yield dist.group.WORLD
+    dist.destroy_process_group()
+
+
+@pytest.fixture
+def rec(monkeypatch):
+    import torch.distributed as dist
+    from dmf import lib
+    r = Recorder(lib._lib)
+    monkeypatch.setattr(lib, '_lib', r)
+    monkeypatch.setattr(lib, '_dev', lambda t, dtype, name: t)
+    monkeypatch.setattr(lib, '_stream', lambda: None)
+    for entry in ('all_reduce', 'all_gather', 'all_gather_into_tensor'):
+        monkeypatch.setattr(dist, entry, r.collective(getattr(dist, entry), entry))
+    return r
+
+
+def expected_update(e, rows, dev_step, cursor, sum_scale, loss, loss_hist, collective, xgmi):
+    """The launches (and collectives) after the backward."""
+    sc, step = e.scaler, e.step_count
+    hp = (e.lr, e.b1, e.b2, e.eps)
+    if sc is None and e.optim == 'ADAM' and not collective:
+        return [('dmf_grad_reduce_adam', 'shape', rows, 'ws', 'theta', 'm', 'v', None) + hp +
+                (step, dev_step, cursor, loss, loss_hist, None)]
+    if sc is None and e.optim == 'ADAM' and xgmi:
+        return [('dmf_grad_reduce_xgmi_adam', 'shape', rows, 'ws', 'theta', 'm', 'v', 'comm') + hp +
+                (sum_scale, dev_step, cursor, loss, loss_hist, None)]
+    n = e.theta.numel()
+    scaler = ('scaler', sc.growth_factor, sc.backoff_factor, sc.growth_interval) if sc is not None else ()
+    if sc is not None and not collective:
+        return [('dmf_grad_reduce_scaled', 'shape', rows, 'ws', 'grad', 'scaler', cursor, loss, loss_hist, None),
+                ('dmf_unscale_adam', 'theta', 'grad', 'm', 'v', n) + hp + (1.0,) + scaler + (1, dev_step, None, None)]
+    out = [('dmf_grad_reduce', 'shape', rows, 'ws', 'grad', None)]
+    if collective:
+        out.append(('all_reduce', 'grad'))
+    if sc is not None:
+        out.append(('dmf_unscale_adam', 'theta', 'grad', 'm', 'v', n) + hp + (sum_scale,) + scaler + (0, dev_step, cursor, None))
+    elif e.optim == 'SGD':
+        out.append(('dmf_sgd_step', 'theta', 'grad', 'm', n, e.lr, e.momentum, step, sum_scale, dev_step, cursor, None))
+    elif e.optim == 'RMSprop':
+        out.append(('dmf_rmsprop_step', 'theta', 'grad', 'm', n, e.lr, e.alpha, 1e-8, sum_scale, cursor, None))
+    else:
+        out.append(('dmf_adam_step', 'theta', 'grad', 'm', 'v', n) + hp + (step, sum_scale, dev_step, cursor, None))
+    return out
+
+
+def _f32(calls):
+    """Float arguments as the float32 the C ABI takes (the recorder records them so)."""
+    return [tuple(float(np.float32(a)) if isinstance(a, float) else a for a in c) for c in calls]
+
+
+def _forms():
+    for optim in ('ADAM', 'SGD', 'RMSprop'):
+        for scaler in (False, True):
+            for grp in ('single', 'collective', 'xgmi'):
+                for attention in (False, True):
+                    if scaler and (optim != 'ADAM' or attention or grp == 'xgmi'):
+                        continue
+                    if grp == 'xgmi' and optim != 'ADAM':
+                        continue
+                    yield '%s-%s-%s-%s' % (optim, 'scaler' if scaler else 'fp32', grp, 'attn' if attention else 'late')
+
+
+def _parse(form):
+    optim, scaler, grp, net = form.split('-')
+    return optim, scaler == 'scaler', grp, net
+
+
+# ------------------------------------------------------------------------------------------------ TrainEngine
+@pytest.mark.parametrize('form', list(_forms()))
+def test_train_engine_step_launches(form, rec, group):
+    from dmf import lib
+    from dmf.engine import LossScaler, Scene, TrainEngine
+    from model.gmfnet import Net
+    optim, use_scaler, grp, net_kind = _parse(form)
+    cfg = {'patch_size': 11, 'Categories_Number': 17, 'data_city': 's', 'DATA_DICT': {'s': {'size': [40, 40, 200]}},
+           'scale': 1, 'aux_bands': 1, 'gmf': {'width': 40, 'hidden': 64, 'pool_sigma': 2.5, 'attention': int(net_kind == 'attn')},
+           'trans': {'embed_dim': 96, 'num_head': 3}}
+    torch.manual_seed(0)
+    net = Net(cfg)
+    scene = Scene(np.zeros((50, 50, 200), np.float32), np.zeros((50, 50, 1), np.float32), 'cpu')
+    B = 8
+    scaler = LossScaler('cpu') if use_scaler else None
+    eng = TrainEngine(net, scene, B, lr=2e-3, process_group=None if grp == 'single' else group, scaler=scaler,
+                      optimizer=optim, momentum=0.5)
+    if grp != 'single':
+        eng._force_collective = True
+    if grp == 'xgmi':         # (the constructor keeps a communicator only for world > 1)
+        eng.comm = types.SimpleNamespace(c=lib.XgmiComm(world=1), world=1, capacity=eng.theta.numel(), rewind=lambda n: None)
+    rng = np.random.default_rng(0)
+    xy = torch.from_numpy(rng.integers(0, 30, (B, 2)).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, 17, B).astype(np.int32))
+    collective, xgmi = grp != 'single', grp == 'xgmi'
+    on_device = xgmi or use_scaler or optim != 'ADAM'
+
+    def forward(dev_step, xy_name, labels_name, cursor):
+        inp = ('input', 1, B, 'sceneA', 'sceneB', xy_name, 50, 50, cursor, 0)
+        if net_kind == 'attn':
+            return [('dmf_train_attn_fwd_bwd', 'shape', inp, 'theta', 'pool_w', labels_name, None, 1.0 / B, 'logits', 'loss',
+                     'ws', 'attn_ws', dev_step, None)]
+        if use_scaler:
+            return [('dmf_train_fwd_bwd_scaled', 'shape', inp, 'theta', 'pool_w', labels_name, 1.0 / B, 'scaler', 'logits',
+                     'loss', 'ws', dev_step, None)]
+        return [('dmf_train_fwd_bwd', 'shape', inp, 'theta', 'pool_w', labels_name, 1.0 / B, 'logits', 'loss', 'ws',
+                 dev_step, None)]
+
+    rec.take(eng)
+    eng.step(xy, labels)
+    dev = 'dev_step' if on_device else None
+    assert rec.take(eng, xy=xy, labels=labels) == _f32(forward(dev, 'xy', 'labels', None) + expected_update(
+        eng, B, dev, None, 1.0, None, None, collective, xgmi))
+
+    eng.load_plan(rng.integers(0, 30, (2 * B, 2)).astype(np.int32), rng.integers(0, 17, 2 * B).astype(np.int32))
+    rec.take(eng)
+    assert eng.run_plan(1, 0) == 1
+    assert rec.take(eng) == _f32(forward('dev_step', 'plan_xy', 'plan_labels', 'dev_cursor') + expected_update(
+        eng, B, 'dev_step', 'dev_cursor', 1.0, 'loss', 'loss_hist', collective, xgmi))
+    assert eng.step_count == 2 and eng.host_cursor == 1
+
+
+# ------------------------------------------------------------------------------------------------ QuaTrainEngine
+def _qua_forms():
+    for form in _forms():
+        optim, use_scaler, grp, net_kind = _parse(form)
+        if net_kind == 'late' and grp != 'xgmi':
+            for unit in ('unit', 'nonunit'):
+                if not (use_scaler and unit == 'nonunit'):
+                    yield '%s-%s-%s-%s' % (optim, 'scaler' if use_scaler else 'fp32', grp, unit)
+
+
+@pytest.mark.parametrize('form', list(_qua_forms()))
+def test_stage2_engine_step_launches(form, rec, group, monkeypatch):
+    from dmf import lib
+    from dmf.engine import LossScaler, QuaScene, QuaTrainEngine
+    from model.gmfnet import Net
+    optim, use_scaler, grp, unit = _parse(form)
+    unit = unit == 'unit'
+    if not unit:
+        monkeypatch.setattr(lib, 'unit_supported', lambda shape: False)
+    cfg = {'patch_size': 16, 'Categories_Number': 5, 'data_city': 's', 'DATA_DICT': {'s': {'size': [20, 20, 4]}},
+           'gmf': {'width': 40, 'single_input': 1}}
+    torch.manual_seed(0)
+    net = Net(cfg)
+    scene = QuaScene([np.zeros((36, 36, 4), np.float32)] * 4, 'cpu')
+    bs, K = 8, 5
+    scaler = LossScaler('cpu') if use_scaler else None
+    eng = QuaTrainEngine(net, scene, bs, DQTL, lr=2e-3, process_group=None if grp == 'single' else group, scaler=scaler,
+                         optimizer=optim, momentum=0.5)
+    assert eng.unit == unit
+    collective = grp != 'single'
+    if collective:
+        eng._force_collective = True
+    rng = np.random.default_rng(0)
+    xy = torch.from_numpy(rng.integers(0, 20, (bs, 2)).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, K, bs).astype(np.int32))
+
+    def launches(dev_step, xy_name, labels_name, cursor, loss_hist):
+        inp = ('input', 1, 4 * bs, 'sceneA', 'sceneB', xy_name, 36, 36, cursor, 0)
+        if unit:
+            out = [('dmf_forward_unit', 'shape', inp, 'theta', 'pool_w', 'logits', 'ws', dev_step, None)]
+        else:
+            out = [('dmf_forward', 'shape', inp, 'theta', 'pool_w', 'logits', None, None)]
+        if collective:
+            out.append(('all_gather', 'logits'))
+        out.append(('dmf_qua_loss_ranks', 'gathered' if collective else 'logits', 1, 0, bs, K, labels_name, cursor, 'params',
+                    1.0, 'scaler' if use_scaler else None, 'loss', loss_hist, 'dlogits', None))
+        if unit:
+            out.append(('dmf_backward_unit', 'shape', 4 * bs, 'theta', 'dlogits', 'ws', None))
+        else:
+            out.append(('dmf_backward_dlogits', 'shape', inp, 'theta', 'pool_w', 'dlogits', 'ws', None))
+        return out + expected_update(eng, 4 * bs, dev_step if unit else None, cursor, 1.0, None, None, collective, False)
+
+    rec.take(eng)
+    eng.step(xy, labels)
+    dev = 'dev_step' if use_scaler else None
+    assert rec.take(eng, labels=labels) == _f32(launches(dev, '?', 'labels', None, None))
+
+    eng.load_plan(rng.integers(0, 20, (2 * bs, 2)).astype(np.int32), rng.integers(0, K, 2 * bs).astype(np.int32))
+    rec.take(eng)
+    assert eng.run_plan(1, 0) == 1
+    assert rec.take(eng) == _f32(launches('dev_step', 'plan_xy', 'plan_labels', 'dev_cursor', 'loss_hist'))
+    assert eng.step_count == 2 and eng.host_cursor == 1

@@ -476,8 +476,15 @@ class TrainEngine(_PlanEngine):
 
 
 class _ShardedEval:
-    """What both evaluation engines share for a process group: every rank takes its contiguous shard of the pixels, and the
-    per-rank results are combined by an all-reduce."""
+    """The whole-set passes of both evaluation engines: confusion matrix and label map over any number of pixels, in chunks
+    of the engine's size.  With a process group every rank takes its contiguous shard of the pixels and the per-rank results
+    are combined by an all-reduce.  An engine states two hooks:
+      * `_check_bounds(xy_host)`: refuse pixels [n,2] (numpy) whose patches leave the resident scene;
+      * `_chunk_pred(xy)`: pixels [n <= B, 2] on the device, already checked -> `pred[:n]` (one forward with its argmax)."""
+
+    def _check_batch(self, n):
+        if n > self.B:
+            raise lib.DmfError('batch larger than the engine was built for')
 
     def _shard(self, process_group, *tensors):
         """With a process group: this rank's contiguous shard of the rows of each tensor."""
@@ -498,6 +505,45 @@ class _ShardedEval:
             allreduce_(x, process_group)
         else:                                       # gloo (CPU tests, one-GPU rehearsal): reduce on the host
             x.copy_(allreduce_(x.cpu(), process_group))
+
+    def _whole_set(self, process_group, xy_all, *more):
+        """(this rank's pixels on the host as numpy, the same and the rows of `more` that go with them on the device as
+        int32); the pixels' bounds are checked here, once for the whole set."""
+        dev = self.scene.device
+        rows = self._shard(process_group, *(torch.as_tensor(t).to(torch.int32) for t in (xy_all,) + more))
+        host = rows[0].cpu().numpy()
+        self._check_bounds(host)
+        return (host,) + tuple(t.to(dev).contiguous() for t in rows)
+
+    def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
+        """Confusion matrix [K,K] int64 (rows = prediction) over all given pixels (mainsolver.py:137-147, tostagesolver.py:
+        331-341).  With a process group the matrices of the ranks are summed (a given `matrix` is added to on every rank:
+        pass zeros)."""
+        from .parallel import allreduce_sum_
+        K = self.net.arch['K']
+        _, xy_all, labels_all = self._whole_set(process_group, xy_all, labels_all)
+        if matrix is None:
+            matrix = torch.zeros(K, K, dtype=torch.int64, device=self.scene.device)
+        for i in range(0, xy_all.shape[0], self.B):
+            pred = self._chunk_pred(xy_all[i:i + self.B])
+            lib.confusion_accum(pred, labels_all[i:i + self.B], K, matrix)
+        self._all_reduce(matrix, process_group, allreduce_sum_)
+        return matrix
+
+    def label_map(self, xy_all, H, W, label_map=None, process_group=None):
+        """Predicted class of every given pixel written at (x, y) of an [H, W] int32 map (mainsolver.py:171-183,
+        tostagesolver.py:360-383).  With a process group the tiles are merged (every pixel is written by one rank)."""
+        from .parallel import allreduce_max_
+        host, xy_all = self._whole_set(process_group, xy_all)
+        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
+            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))      # labelmap_kernel writes map[x * W + y]
+        if label_map is None:
+            label_map = torch.zeros(H, W, dtype=torch.int32, device=self.scene.device)
+        for i in range(0, xy_all.shape[0], self.B):
+            xy = xy_all[i:i + self.B]
+            lib.labelmap_write(self._chunk_pred(xy), xy, W, label_map)
+        self._all_reduce(label_map, process_group, allreduce_max_)
+        return label_map
 
 
 class EvalEngine(_ShardedEval):
@@ -520,8 +566,7 @@ class EvalEngine(_ShardedEval):
     def predict(self, xy):
         """xy [n,2] int32 device -> (logits [n,K], pred [n]) views valid until the next call."""
         n = xy.shape[0]
-        if n > self.B:
-            raise lib.DmfError('batch larger than the engine was built for')
+        self._check_batch(n)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         if self.shape.attention:
             lib.forward_attn(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, self.attn_ws, self.logits, self.pred)
@@ -533,8 +578,7 @@ class EvalEngine(_ShardedEval):
         """Sum over the batch of the per-patch cross-entropy (device scalar, float64), from the evaluation launch itself
         (dmf_forward_ce); None where the shape has no such kernel."""
         n = xy.shape[0]
-        if n > self.B:
-            raise lib.DmfError('batch larger than the engine was built for')
+        self._check_batch(n)
         if self.shape.attention or self._no_ce:
             return None
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
@@ -545,44 +589,11 @@ class EvalEngine(_ShardedEval):
             return None
         return self.ce[:n].double().sum()
 
-    def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
-        """Confusion matrix [K,K] int64 (rows = prediction) over all given pixels; one D2H at the end.
-        With a process group every rank classifies its contiguous shard of the pixels and the matrices are summed."""
-        from .parallel import allreduce_sum_
-        dev = self.scene.device
-        K = self.net.arch['K']
-        xy_all = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
-        labels_all = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        xy_all, labels_all = self._shard(process_group, xy_all, labels_all)
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_all.cpu().numpy())
-        if matrix is None:
-            matrix = torch.zeros(K, K, dtype=torch.int64, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            _, pred = self.predict(xy)
-            lib.confusion_accum(pred, labels_all[i:i + self.B], K, matrix)
-        self._all_reduce(matrix, process_group, allreduce_sum_)
-        return matrix
-
-    def label_map(self, xy_all, H, W, label_map=None, process_group=None):
-        """Predicted class of every given pixel written at (x, y) of an [H, W] int32 map (mainsolver.py:171-183).
-        With a process group the pixels are sharded and the tiles merged (every pixel is written by one rank)."""
-        from .parallel import allreduce_max_
-        dev = self.scene.device
-        xy_all = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
-        xy_all, = self._shard(process_group, xy_all)
-        xy_host = xy_all.cpu().numpy()
+    def _check_bounds(self, xy_host):
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)
-        if len(xy_host) and (int(xy_host[:, 0].max()) >= H or int(xy_host[:, 1].max()) >= W):
-            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))      # labelmap_kernel writes map[x * W + y]
-        if label_map is None:
-            label_map = torch.zeros(H, W, dtype=torch.int32, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            _, pred = self.predict(xy)
-            lib.labelmap_write(pred, xy, W, label_map)
-        self._all_reduce(label_map, process_group, allreduce_max_)
-        return label_map
+
+    def _chunk_pred(self, xy):
+        return self.predict(xy)[1]
 
 
 # ====================================================================== stage 2 of the two-stage path
@@ -605,15 +616,12 @@ class QuaScene:
         self.device = torch.device(device)
 
     def stack_xy(self, xy, streams=4):
-        """[n, 2] pixel coordinates -> [streams*n, 2] coordinates in the tall scene, stream-major like
-        `torch.concat([data1, data2, data3, data4])` (tostagesolver.py:272)."""
+        """[n, 2] pixel coordinates -> [streams*n, 2] int32 coordinates in the tall scene, on the device `xy` lives on,
+        stream-major like `torch.concat([data1, data2, data3, data4])` (tostagesolver.py:272)."""
         xy = torch.as_tensor(xy).to(torch.int32)
-        off = torch.zeros_like(xy)
-        out = []
-        for k in range(streams):
-            off[:, 0] = k * self.Hp
-            out.append(xy + off)
-        return torch.cat(out)
+        out = xy.repeat(streams, 1).view(streams, xy.shape[0], 2)
+        out[:, :, 0] += (torch.arange(streams, dtype=torch.int32, device=xy.device) * self.Hp)[:, None]   # stream k: k*Hp rows down
+        return out.view(-1, 2)
 
 
 class QuaTrainEngine(_PlanEngine):
@@ -767,74 +775,27 @@ class QuaEvalEngine(_ShardedEval):
         self.params = lib.qua_params(dqtl) if dqtl is not None else None
 
     def _forward(self, xy, streams, checked=False):
+        """Logits of the first `streams` streams of the pixels xy [n,2] into self.logits[:streams*n]; returns n."""
         n = int(xy.shape[0])
-        if n > self.B:
-            raise lib.DmfError('batch larger than the engine was built for')
-        dev = self.scene.device
-        if checked and torch.is_tensor(xy) and xy.device == dev:        # (whole-set passes: bounds checked once, stacking on the device)
-            off = torch.zeros(1, 2, dtype=torch.int32, device=dev)
-            parts = []
-            for k in range(streams):
-                off[0, 0] = k * self.scene.Hp
-                parts.append(xy + off)
-            xyk = torch.cat(parts).contiguous()
-        else:
-            xyk = self.scene.stack_xy(torch.as_tensor(xy).cpu(), streams).to(dev).contiguous()
+        self._check_batch(n)
+        xyk = self.scene.stack_xy(xy, streams)
+        if not checked:
             lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xyk.cpu().numpy())
-        inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xyk)
+        inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xyk.to(self.scene.device))
         lib.forward(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, self.logits)
         return n
 
-    def _checked_all(self, xy_all):
-        dev = self.scene.device
-        xy_all = torch.as_tensor(xy_all).to(torch.int32)
-        host = xy_all.cpu()
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.stack_xy(host, 2).numpy())
-        return xy_all.to(dev).contiguous(), host.numpy()
+    def _check_bounds(self, xy_host):            # (only the ms and pan streams are read)
+        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.stack_xy(xy_host, 2).numpy())
 
-    def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
-        """Confusion matrix [K,K] int64 (rows = prediction) of the pair prediction over all given pixels, in chunks of the
-        engine's size (tostagesolver.py:331-341).  With a process group every rank classifies its contiguous shard of the
-        pixels and the matrices are summed (a given `matrix` is added to on every rank: pass zeros)."""
-        from .parallel import allreduce_sum_
-        dev = self.scene.device
-        K = self.net.arch['K']
-        xy_all = torch.as_tensor(xy_all).to(torch.int32)
-        labels_all = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        xy_all, labels_all = self._shard(process_group, xy_all, labels_all)
-        xy_all, _ = self._checked_all(xy_all)
-        if matrix is None:
-            matrix = torch.zeros(K, K, dtype=torch.int64, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            n = self._forward(xy_all[i:i + self.B], 2, checked=True)
-            lib.pair_argmax(self.logits, n, self.pred)
-            lib.confusion_accum(self.pred[:n], labels_all[i:i + n], K, matrix)
-        self._all_reduce(matrix, process_group, allreduce_sum_)
-        return matrix
-
-    def label_map(self, xy_all, H, W, label_map=None, process_group=None):
-        """Pair prediction of every given pixel written at (x, y) of an [H, W] int32 map (tostagesolver.py:360-383).
-        With a process group the pixels are sharded and the tiles merged (every pixel is written by one rank)."""
-        from .parallel import allreduce_max_
-        dev = self.scene.device
-        xy_all, = self._shard(process_group, torch.as_tensor(xy_all).to(torch.int32))
-        xy_all, host = self._checked_all(xy_all)
-        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
-            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))
-        if label_map is None:
-            label_map = torch.zeros(H, W, dtype=torch.int32, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            n = self._forward(xy, 2, checked=True)
-            lib.pair_argmax(self.logits, n, self.pred)
-            lib.labelmap_write(self.pred[:n], xy, W, label_map)
-        self._all_reduce(label_map, process_group, allreduce_max_)
-        return label_map
+    def _chunk_pred(self, xy, checked=True):
+        n = self._forward(xy, 2, checked)
+        lib.pair_argmax(self.logits, n, self.pred)
+        return self.pred[:n]
 
     def predict(self, xy):
-        n = self._forward(xy, 2)
-        lib.pair_argmax(self.logits, n, self.pred)
-        return self.logits[:2 * n], self.pred[:n]
+        pred = self._chunk_pred(xy, checked=False)
+        return self.logits[:2 * pred.shape[0]], pred
 
     def loss_value(self, xy, labels):
         """qua_loss of a batch without gradients (the validation loop, tostagesolver.py:288-296); device scalar."""

@@ -73,44 +73,29 @@ class BaseSolver:
 
     def dataloader(self):
         cfg = self.cfg
+
+        def flat(s, base):             # random_split returns Subsets of a Subset; flatten to indices into the full dataset
+            return Subset(self.dataset, indices=np.asarray(base)[np.asarray(s.indices)].tolist())
+
+        color1 = Subset(self.dataset, indices=self.matrix_[1])             # the labelled pixels
+        color2 = Subset(self.dataset, indices=self.matrix_[0])
         if self.data_new:
             # basesolver.py:64-84: the whole train mask trains; the test mask is split (global RNG) into test / valid
-            train_data = Subset(self.dataset, indices=self.traintest_index[1])
+            train = Subset(self.dataset, indices=self.traintest_index[1])
             test_data = Subset(self.dataset, indices=self.traintest_index[2])
             valid_size = int(cfg['verify_rate'] * len(test_data))
-            test_size = len(test_data) - valid_size
-            test_dataset, valid_dataset = torch.utils.data.random_split(test_data, [test_size, valid_size])
-            base = np.asarray(self.traintest_index[2])
-
-            def flat2(s):
-                return Subset(self.dataset, indices=base[np.asarray(s.indices)].tolist())
-
-            self.train_loader, self.train_index_loader = self._loader(train_data, cfg['batchsize'], True)
-            self.test_loader, self.test_index_loader = self._loader(flat2(test_dataset), cfg['test_batchsize'], False)
-            self.valid_loader, self.valid_index_loader = self._loader(flat2(valid_dataset), cfg['color_batchsize'], False)
-            self.color_loader1, self.color_index_loader1 = self._loader(Subset(self.dataset, indices=self.matrix_[1]),
-                                                                        cfg['test_batchsize'], False)
-            self.color_loader2, self.color_index_loader2 = self._loader(Subset(self.dataset, indices=self.matrix_[0]),
-                                                                        cfg['test_batchsize'], False)
-            return
-        train_data = Subset(self.dataset, indices=self.matrix_[1])
-        train_size = int(cfg['train_rate'] * len(train_data))
-        valid_size = int(cfg['verify_rate'] * len(train_data))
-        test_size = len(train_data) - train_size - valid_size
-        train_dataset, test_dataset, valid_dataset = torch.utils.data.random_split(
-            train_data, [train_size, test_size, valid_size])
-        # random_split returns Subsets of `train_data`; flatten to indices into the full dataset
-        base = np.asarray(self.matrix_[1])
-
-        def flat(s):
-            return Subset(self.dataset, indices=base[np.asarray(s.indices)].tolist())
-
-        self.train_loader, self.train_index_loader = self._loader(flat(train_dataset), cfg['batchsize'], True)
-        self.test_loader, self.test_index_loader = self._loader(flat(test_dataset), cfg['test_batchsize'], False)
-        self.valid_loader, self.valid_index_loader = self._loader(flat(valid_dataset), cfg['color_batchsize'], False)
-        color_data = Subset(self.dataset, indices=self.matrix_[0])
-        self.color_loader1, self.color_index_loader1 = self._loader(train_data, cfg['test_batchsize'], False)
-        self.color_loader2, self.color_index_loader2 = self._loader(color_data, cfg['test_batchsize'], False)
+            test, valid = (flat(s, self.traintest_index[2]) for s in torch.utils.data.random_split(
+                test_data, [len(test_data) - valid_size, valid_size]))
+        else:                              # the labelled pixels are split (global RNG) into train / test / valid
+            train_size = int(cfg['train_rate'] * len(color1))
+            valid_size = int(cfg['verify_rate'] * len(color1))
+            train, test, valid = (flat(s, self.matrix_[1]) for s in torch.utils.data.random_split(
+                color1, [train_size, len(color1) - train_size - valid_size, valid_size]))
+        self.train_loader, self.train_index_loader = self._loader(train, cfg['batchsize'], True)
+        self.test_loader, self.test_index_loader = self._loader(test, cfg['test_batchsize'], False)
+        self.valid_loader, self.valid_index_loader = self._loader(valid, cfg['color_batchsize'], False)
+        self.color_loader1, self.color_index_loader1 = self._loader(color1, cfg['test_batchsize'], False)
+        self.color_loader2, self.color_index_loader2 = self._loader(color2, cfg['test_batchsize'], False)
 
     def indicator(self):
         if self.cfg['test']['save_matrix']:

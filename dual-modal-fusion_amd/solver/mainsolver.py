@@ -6,7 +6,8 @@ its running loss exceeds the best one (:62-76), best weights -> `<time>_weights.
 epoch -> `<time>_curweights.pth` ({'state_dict','optimizer'}); `test()` fills `test_matrix[pred][target]` and calls
 `indicator()`; `color()` writes `<time>_pic_1.png` / `_pic_2.png`.
 
-Two execution paths, same arithmetic:
+Two execution paths, same arithmetic; `train()`, `test()` and `color()` choose between them once, by method
+(`_train_epoch_fast` / `_train_epoch_dropin`, `_test_matrix_*`, `_label_map_*`):
   * fast (default on a GPU): resident scene + epoch plan + fused HIP step (dmf/engine.py) — no patch
     materialisation, no per-step host sync, confusion matrix and label maps built on the device;
   * drop-in (`fast_path: 0`): the reference's own loop body (mainsolver.py:49-55) over materialised batches through
@@ -23,6 +24,7 @@ after the first batch, :142 — that stays the default); the t-SNE plot inside `
 helpers (:110-136,211-441) are out of scope; `nohup: 1` does not crash (reference bug at :76).
 """
 import importlib
+import itertools
 import time
 
 import numpy as np
@@ -35,6 +37,11 @@ from utils.utils import epoch_hparams, export_optimizer, make_loss, optim_hparam
 
 
 class Solver(BaseSolver):
+    """What a stage of the two-stage path (solver.tostagesolver) states differently is gathered in the hooks below
+    `train()`: `engine_loss`, `_steps_per_graph`, `_train_engine`, `_eval_engine`, `_rank_batches`, `_step_short`, and for the
+    drop-in path `_train_epoch_dropin`, `_valid_pass`, `_predict_dropin`, `_test_whole_split`."""
+    engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
+
     def __init__(self, cfg):
         super().__init__(cfg)
         self.model = None
@@ -42,7 +49,7 @@ class Solver(BaseSolver):
         self.train_time = 0
         self.test_time = 0
         self.matrix = None
-        self.engine = None
+        self.engine = self.eval_engine = None
         self.process_group = None                      # set by the launcher for data-parallel runs (test.py)
         self.comm = None
         self.rank, self.world = 0, 1
@@ -88,13 +95,11 @@ class Solver(BaseSolver):
         self.cur_model = self.model.to(self.DEVICE)
         if self.fast:
             self._make_engines()
+        train_epoch = self._train_epoch_fast if self.fast else self._train_epoch_dropin
         self.step_losses = []
         while self.epoch < self.EPOCH:
             self.cur_model.train()
-            if self.fast:
-                last = self._train_epoch_fast()
-            else:
-                last = self._train_epoch_dropin()
+            last = train_epoch()
             if save_best:
                 self.cur_model.eval()
                 val_loss = self._valid_pass(best_loss)
@@ -131,55 +136,33 @@ class Solver(BaseSolver):
         return LossScaler(self.DEVICE)
 
     def _make_engines(self):
-        from dmf.engine import EvalEngine, TrainEngine
-        if self.cfg['schedule']['loss'] != 'Criterion':
-            raise ValueError('the fused HIP step implements the Criterion (cross-entropy) loss')
+        if self.cfg['schedule']['loss'] != self.engine_loss:
+            raise ValueError('the fused HIP step of %s implements schedule.loss: %s' % (type(self).__name__, self.engine_loss))
         hp = optim_hparams(self.cfg)                             # ADAM (fused), SGD or RMSprop (utils/utils.py:10-16)
         if self.cfg['batchsize'] % self.world:
             raise ValueError('batchsize %d is not divisible by the %d ranks' % (self.cfg['batchsize'], self.world))
-        scaler = self._loss_scaler(hp)
-        self.engine = TrainEngine(self.cur_model, self.scene, self.cfg['batchsize'] // self.world, lr=hp['lr'], betas=hp['betas'],
-                                  eps=hp['eps'], process_group=self.process_group,
-                                  comm=self.comm if hp['optimizer'] == 'ADAM' and scaler is None else None, scaler=scaler,
-                                  optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99))
-        self.eval_engine = EvalEngine(self.cur_model, self.scene, self._eval_chunk())
-
-    def _eval_chunk(self):
-        """Pixels per evaluation launch of the fast path.  `test_batchsize` / `color_batchsize` size the reference's host-fed
-        loader (mainsolver.py:90-101,155-163); with the scene resident every pixel is independent of its batch, and a launch of
-        256 patches is bound by the host (0.13 of the HBM roof on a 512x512x224 scene) where 16,384 reach 0.62
-        (tools/eval_bench.py; identical class maps)."""
-        big = 4096 if self.cur_model.arch['attention'] else 16384
-        return max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], big)
+        self.engine = self._train_engine(self.cfg['batchsize'] // self.world, dict(
+            lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], process_group=self.process_group, scaler=self._loss_scaler(hp),
+            optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99)))
+        self.eval_engine = self._eval_engine()
 
     def _train_epoch_fast(self):
-        eng, B = self.engine, self.cfg['batchsize'] // self.world
+        eng = self.engine
         hp = epoch_hparams(self.cfg, self.epoch)              # lr (and, under OneCycleLR, beta1 / momentum) of this epoch
         eng.lr = float(hp['lr'])
         if 'betas' in hp:
             eng.b1, eng.b2 = float(hp['betas'][0]), float(hp['betas'][1])
         if eng.optim == 'SGD':
             eng.momentum = float(hp['momentum'])
-        batches = [self._xy_labels(b) for b in self.train_index_loader]      # the epoch's shuffled coordinates
-        if self.world > 1:                                                   # this rank's contiguous shard of every batch
-            cut = []
-            for xy, lab in batches:
-                per = xy.shape[0] // self.world                             # (a remainder is dropped, see the module text)
-                if per:
-                    cut.append((xy[self.rank * per:(self.rank + 1) * per], lab[self.rank * per:(self.rank + 1) * per]))
-            batches = cut
+        # the epoch's shuffled coordinates, as the batches the engine steps on and the size of a full one
+        batches, B = self._rank_batches([self._xy_labels(b) for b in self.train_index_loader])
         full = [b for b in batches if b[0].shape[0] == B]
         losses = []
         if full:
             eng.load_plan(torch.cat([b[0] for b in full]), torch.cat([b[1] for b in full]))
-            # steps_per_graph: N > 0 replays captured hipGraphs of N steps, 0 launches step by step from Python, -1 (default)
-            # hands the whole epoch to the library's launch loop (dmf_train_plan_steps) where that exists, else step by step
-            eng.run_plan(len(full), int(self.cfg.get('steps_per_graph', -1)))
-            losses = eng.mean_losses().tolist()
-        for xy, lab in batches:
-            if xy.shape[0] != B:                                             # DataLoader keeps the short last batch
-                eng.step(xy.to(self.DEVICE), lab.to(self.DEVICE))
-                losses.append(float(eng.loss[:xy.shape[0]].mean().item()))
+            eng.run_plan(len(full), self._steps_per_graph())
+            losses = eng.losses().tolist()
+        losses += [self._step_short(xy, lab) for xy, lab in batches if xy.shape[0] != B]    # DataLoader keeps the short last batch
         self._check_exchange()
         self.step_losses += losses
         return losses[-1] if losses else float('nan')
@@ -197,6 +180,38 @@ class Solver(BaseSolver):
             raise RuntimeError('epoch %d: a gradient exchange timed out on at least one rank; the replicas have diverged. '
                                'Restart from the last checkpoint with xgmi_exchange: 0 (RCCL all-reduce).' % self.epoch)
 
+    # ------------------------------------------------------------------ what a stage states differently: fast path
+    def _steps_per_graph(self):
+        """N > 0 replays captured hipGraphs of N steps, 0 launches step by step from Python, -1 (default) hands the whole
+        epoch to the library's launch loop (dmf_train_plan_steps) where that exists, else step by step."""
+        return int(self.cfg.get('steps_per_graph', -1))
+
+    def _train_engine(self, batch, kw):
+        from dmf.engine import TrainEngine
+        comm = self.comm if kw['optimizer'] == 'ADAM' and kw['scaler'] is None else None
+        return TrainEngine(self.cur_model, self.scene, batch, comm=comm, **kw)
+
+    def _eval_engine(self):
+        """Pixels per evaluation launch of the fast path.  `test_batchsize` / `color_batchsize` size the reference's host-fed
+        loader (mainsolver.py:90-101,155-163); with the scene resident every pixel is independent of its batch, and a launch of
+        256 patches is bound by the host (0.13 of the HBM roof on a 512x512x224 scene) where 16,384 reach 0.62
+        (tools/eval_bench.py; identical class maps)."""
+        from dmf.engine import EvalEngine
+        big = 4096 if self.cur_model.arch['attention'] else 16384
+        return EvalEngine(self.cur_model, self.scene, max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], big))
+
+    def _rank_batches(self, batches):
+        """The solver shards on the host: this rank's contiguous shard of every global batch (a remainder is dropped, see
+        the module text), without the empty ones."""
+        per = [b[0].shape[0] // self.world for b in batches]
+        return ([(xy[self.rank * n:(self.rank + 1) * n], lab[self.rank * n:(self.rank + 1) * n])
+                 for (xy, lab), n in zip(batches, per) if n], self.cfg['batchsize'] // self.world)
+
+    def _step_short(self, xy, lab):
+        self.engine.step(xy.to(self.DEVICE), lab.to(self.DEVICE))
+        return float(self.engine.loss[:xy.shape[0]].mean().item())
+
+    # ------------------------------------------------------------------ ... and drop-in path
     def _train_epoch_dropin(self):
         loader = self._bar(self.train_loader)
         last = float('nan')
@@ -215,40 +230,38 @@ class Solver(BaseSolver):
             self.scheduler.step()
         return last
 
-    def _forward_batch(self, batch):
-        """(logits, target int64 on device, x, y) for a batch of either loader twin."""
-        if self.fast:
-            xy, lab = self._xy_labels(batch)
-            logits, _ = self.eval_engine.predict(xy.to(self.DEVICE))
-            return logits, lab.to(self.DEVICE).long(), batch[0], batch[1]
-        data1, data2, target, x, y = batch
-        return self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE)), target.to(self.DEVICE).long(), x, y
-
     def _valid_pass(self, best_loss):
         ce = torch.nn.CrossEntropyLoss()
-        val_loss = 0.0
-        if self.fast:
-            # The reference adds `loss.item() * n` per batch and stops once the sum passes best_loss (mainsolver.py:65-75):
-            # one host sync per batch.  Here the same double-precision sum stays on the device and is read once; the terms
-            # are non-negative, so "the full sum is below best_loss" decides exactly what the early exit decides.
-            tot = torch.zeros((), dtype=torch.float64, device=self.DEVICE)
-            with torch.no_grad():
-                for batch in self.valid_index_loader:
-                    xy, lab = self._xy_labels(batch)
-                    # the evaluation launch's own per-patch cross-entropy (dmf_forward_ce) where the shape has it ...
-                    part = self.eval_engine.ce_sum(xy.to(self.DEVICE), lab.to(self.DEVICE)) if hasattr(self.eval_engine, 'ce_sum') else None
-                    if part is None:                         # ... else torch's on the logits (attention network)
-                        logits, target, _, _ = self._forward_batch(batch)
-                        part = ce(logits, target).double() * target.shape[0]
-                    tot += part
-            return float(tot.item())
         with torch.no_grad():
-            for batch in (self.valid_index_loader if self.fast else self.valid_loader):
-                logits, target, _, _ = self._forward_batch(batch)
-                val_loss += ce(logits, target).item() * target.shape[0]
+            if self.fast:
+                # The reference adds `loss.item() * n` per batch and stops once the sum passes best_loss (mainsolver.py:65-75):
+                # one host sync per batch.  Here the same double-precision sum stays on the device and is read once; the terms
+                # are non-negative, so "the full sum is below best_loss" decides exactly what the early exit decides.
+                tot = torch.zeros((), dtype=torch.float64, device=self.DEVICE)
+                for batch in self.valid_index_loader:
+                    xy, lab = (t.to(self.DEVICE) for t in self._xy_labels(batch))
+                    # the evaluation launch's own per-patch cross-entropy (dmf_forward_ce) where the shape has it ...
+                    part = self.eval_engine.ce_sum(xy, lab)
+                    if part is None:                         # ... else torch's on the logits (attention network)
+                        part = ce(self.eval_engine.predict(xy)[0], lab.long()).double() * lab.shape[0]
+                    tot += part
+                return float(tot.item())
+            val_loss = 0.0
+            for data1, data2, target, _, _ in self.valid_loader:
+                logits = self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE))
+                val_loss += ce(logits, target.to(self.DEVICE).long()).item() * target.shape[0]
                 if val_loss > best_loss:
                     break
         return val_loss
+
+    def _predict_dropin(self, batch):
+        """(pred [n] on the device, target [n], x, y) of a batch of the materialising loaders."""
+        data1, data2, target, x, y = batch
+        return self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE)).data.max(1)[1], target, x, y
+
+    def _test_whole_split(self):
+        """The reference always stops after the first test batch (mainsolver.py:142); `test.full: 1` takes the whole split."""
+        return bool(self.cfg['test'].get('full', 0))
 
     # ------------------------------------------------------------------ test
     def _load_weights(self, best):
@@ -260,53 +273,39 @@ class Solver(BaseSolver):
         if self.cur_model is None:
             self.init_model()
             self.cur_model = self.model.to(self.DEVICE)
-        if self.fast and getattr(self, 'eval_engine', None) is None:
-            self._make_eval_engine()
-
-    def _make_eval_engine(self):
-        from dmf.engine import EvalEngine
-        self.eval_engine = EvalEngine(self.cur_model, self.scene, self._eval_chunk())
+        if self.fast and self.eval_engine is None:
+            self.eval_engine = self._eval_engine()
 
     def test(self):
         time1 = time.time()
         self._ensure_model()
         self._load_weights(self.cfg['train']['save_best'])
         self.cur_model.eval()
-        K = self.cfg['Categories_Number']
-        full = bool(self.cfg['test'].get('full', 0))
+        whole = self._test_whole_split()
         with torch.no_grad():
-            if self.fast and full:
-                # whole split in evaluation chunks of the engine's own size (data parallel: every rank classifies its part
-                # of the pixels, the matrices are summed)
-                parts = [self._xy_labels(b) for b in self.test_index_loader]
-                matrix = self.eval_engine.confusion(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
-                                                    process_group=self.process_group)
-                test_matrix = matrix.cpu().numpy().astype(np.float64)
-            elif self.fast:
-                from dmf import lib
-                matrix = torch.zeros(K, K, dtype=torch.int64, device=self.DEVICE)
-                for batch in self.test_index_loader:
-                    xy, lab = self._xy_labels(batch)
-                    _, pred = self.eval_engine.predict(xy.to(self.DEVICE))
-                    lib.confusion_accum(pred, lab.to(self.DEVICE), K, matrix)
-                    if not full:
-                        break                                                # mainsolver.py:142
-                test_matrix = matrix.cpu().numpy().astype(np.float64)
-            else:
-                test_matrix = np.zeros([K, K])
-                for batch in self.test_loader:
-                    logits, target, _, _ = self._forward_batch(batch)
-                    pred = logits.data.max(1)[1].cpu().numpy()
-                    np.add.at(test_matrix, (pred, target.cpu().numpy()), 1)
-                    if not full:
-                        break
+            matrix = self._test_matrix_fast(whole) if self.fast else self._test_matrix_dropin(whole)
         self.test_time = time.time() - time1
-        self.test_matrix = test_matrix
+        self.test_matrix = matrix.astype(np.float64)
         if self.rank == 0:
             self.indicator()
         else:
             from indicators.kappa import aa_oa_quiet
-            self.result = list(aa_oa_quiet(test_matrix)) + [None]
+            self.result = list(aa_oa_quiet(self.test_matrix)) + [None]
+
+    def _test_matrix_fast(self, whole):
+        """The whole split in evaluation chunks of the engine's own size (data parallel: every rank classifies its part of
+        the pixels, the matrices are summed), or the first batch alone, which every rank classifies whole."""
+        parts = [self._xy_labels(b) for b in (self.test_index_loader if whole else itertools.islice(self.test_index_loader, 1))]
+        return self.eval_engine.confusion(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
+                                          process_group=self.process_group if whole else None).cpu().numpy()
+
+    def _test_matrix_dropin(self, whole):
+        K = self.cfg['Categories_Number']
+        matrix = np.zeros([K, K])
+        for batch in (self.test_loader if whole else itertools.islice(self.test_loader, 1)):
+            pred, target, _, _ = self._predict_dropin(batch)
+            np.add.at(matrix, (pred.cpu().numpy(), target.long().numpy()), 1)            # test_matrix[pred][target] += 1
+        return matrix
 
     # ------------------------------------------------------------------ colour
     def color(self):
@@ -316,32 +315,30 @@ class Solver(BaseSolver):
         size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
         H, W = int(size[0]), int(size[1])
         lut = np.asarray(self.cfg['DATA_DICT'][self.cfg['data_city']]['color'], dtype=np.uint8)
+        label_map = self._label_map_fast if self.fast else self._label_map_dropin
         maps = []
         with torch.no_grad():
             for use, loaders in ((self.cfg['color']['supervised'], (self.color_index_loader1, self.color_loader1)),
                                  (self.cfg['color']['unsupervised'], (self.color_index_loader2, self.color_loader2))):
-                m = torch.zeros(H, W, dtype=torch.int32, device=self.DEVICE) if self.fast else np.zeros([H, W], dtype=np.int64)
-                if use and self.fast:      # all pixels, in evaluation chunks of the engine's own size (_eval_chunk)
-                    xy_all = torch.cat([self._xy_labels(b)[0] for b in loaders[0]])
-                    m = self.eval_engine.label_map(xy_all, H, W, process_group=self.process_group)
-                elif use:
-                    for batch in loaders[0 if self.fast else 1]:
-                        if self.fast:
-                            from dmf import lib
-                            xy, _ = self._xy_labels(batch)
-                            xy = xy.to(self.DEVICE)
-                            _, pred = self.eval_engine.predict(xy)
-                            lib.labelmap_write(pred, xy, W, m)
-                        else:
-                            logits, _, x, y = self._forward_batch(batch)
-                            m[np.asarray(x), np.asarray(y)] = logits.data.max(1)[1].cpu().numpy()
-                maps.append(m.cpu().numpy() if self.fast else m)
+                maps.append(label_map(loaders, H, W) if use else np.zeros([H, W], dtype=np.int32))
         label_np1 = maps[0]
         label_np2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
         self.label_maps = (label_np1, label_np2)
         if self.cfg['color']['supervised'] and self.rank == 0:
             Image.fromarray(lut[label_np1]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_1.png")
             Image.fromarray(lut[label_np2]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_2.png")
+
+    def _label_map_fast(self, loaders, H, W):
+        """All pixels of the index-only loader, in evaluation chunks of the engine's own size."""
+        return self.eval_engine.label_map(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W,
+                                          process_group=self.process_group).cpu().numpy()
+
+    def _label_map_dropin(self, loaders, H, W):
+        m = np.zeros([H, W], dtype=np.int32)
+        for batch in loaders[1]:
+            pred, _, x, y = self._predict_dropin(batch)
+            m[np.asarray(x), np.asarray(y)] = pred.cpu().numpy()
+        return m
 
     def run(self):
         while self.time < self.TIME:

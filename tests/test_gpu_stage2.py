@@ -163,6 +163,35 @@ def test_tostagesolver_reproduces_reference_trajectory(golden_dir, fast):
         shutil.rmtree(tmp)
 
 
+def test_tostagesolver_test_and_colour_agree_between_the_paths(golden_dir):
+    """Stage 2 with `color.index: 1` on both paths: the drop-in `test()` / `color()` (`net(concat(ms, pan))` + pair_argmax over
+    the materialising `test_loader` / `color_loader*`) against the fast path's (QuaEvalEngine.confusion / label_map over the
+    index-only twins).  The two runs train to weights that differ by rounding only (losses within 1e-5, above); on this scene no
+    prediction flips, so the test matrices and both label maps are identical: 0 differing pixels of 400 on each map."""
+    from solver.tostagesolver import toStageSolver
+    runs = {}
+    for fast in (1, 0):
+        tmp = tempfile.mkdtemp(prefix='dmf_stage2_color_')
+        try:
+            g, cfg = _setup(golden_dir, tmp, fast_path=fast)
+            cfg['color'] = dict(cfg['color'], index=1, supervised=1, unsupervised=1)
+            torch.manual_seed(3407)
+            s = toStageSolver(cfg)
+            s.run()
+            assert os.path.exists(cfg['RESULT_output'] + '0_pic_1.png') and os.path.exists(cfg['RESULT_output'] + '0_pic_2.png')
+            runs[fast] = (s.test_matrix.copy(), np.asarray(s.label_maps[0]), np.asarray(s.label_maps[1]))
+        finally:
+            shutil.rmtree(tmp)
+    lab = g['label']
+    m1, m2 = runs[1][1], runs[1][2]
+    assert m1.shape == lab.shape and (m1[lab == 0] == 0).all() and (m1[lab != 0] != 0).all() and (m2[lab != 0] == m1[lab != 0]).all()
+    print('stage 2 fast vs drop-in: differing pixels %d / %d (supervised map), %d / %d (both maps laid over), differing test predictions %d / %d'
+          % ((runs[1][1] != runs[0][1]).sum(), m1.size, (runs[1][2] != runs[0][2]).sum(), m2.size,
+             np.abs(runs[1][0] - runs[0][0]).sum() // 2, runs[1][0].sum()))
+    assert runs[1][0].sum() > 0 and np.array_equal(runs[1][0], runs[0][0])
+    assert np.array_equal(runs[1][1], runs[0][1]) and np.array_equal(runs[1][2], runs[0][2])
+
+
 def test_stage1_is_refused_loudly(golden_dir):
     from solver.tostagesolver import toStageSolver
     tmp = tempfile.mkdtemp(prefix='dmf_stage1_')

@@ -1071,6 +1071,38 @@ int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, doubl
   return check(hipGetLastError(), "pan2ms launch");
 }
 
+int32_t dmf_scene_minmax(const void* raw, int32_t dtype, int64_t n, void* minmax, void* stream) {
+  if (raw == nullptr || minmax == nullptr) return fail("%s", "null argument");
+  const int es = scene_raw_bytes(dtype);
+  if (es == 0) return fail("%s", "scene_minmax: dtype is not a DMF_RAW_* code");
+  if (n < 1) return fail("%s", "scene_minmax: empty scene");
+  if (reinterpret_cast<uintptr_t>(raw) % es || reinterpret_cast<uintptr_t>(minmax) % es)
+    return fail("%s", "scene_minmax: raw / minmax not aligned to the raw element size");
+  return check(launch_scene_minmax(raw, dtype, n, minmax, static_cast<hipStream_t>(stream)), "scene_minmax launch");
+}
+
+int32_t dmf_scene_prepare(const void* raw, int32_t dtype, int32_t H, int32_t W, int32_t C, const void* minmax, int32_t pad,
+                          int32_t half, void* out, void* stream) {
+  if (raw == nullptr || minmax == nullptr || out == nullptr) return fail("%s", "null argument");
+  const int es = scene_raw_bytes(dtype), os = half ? 2 : 4;
+  if (es == 0) return fail("%s", "scene_prepare: dtype is not a DMF_RAW_* code");
+  if (H < 1 || W < 1 || C < 1 || pad < 0) return fail("%s", "bad scene_prepare geometry");
+  if (pad > H - 1 || pad > W - 1) return fail("%s", "scene_prepare: the reflection needs pad <= H - 1 and pad <= W - 1");
+  const int64_t row = ((int64_t)W + pad) * C;
+  if (row > INT32_MAX) return fail("%s", "scene_prepare: a padded row of more than 2^31 - 1 elements");
+  if (reinterpret_cast<uintptr_t>(raw) % es || reinterpret_cast<uintptr_t>(minmax) % es || reinterpret_cast<uintptr_t>(out) % os)
+    return fail("%s", "scene_prepare: raw / minmax / out not aligned to their element size");
+  ScenePrepArgs a;
+  a.raw = raw; a.minmax = minmax; a.out = out;
+  a.H = H; a.W = W; a.C = C; a.pad = pad;
+  a.row = (int)row;
+  a.shift = (int)((reinterpret_cast<uintptr_t>(out) & 15) / os);
+  a.n_out = ((int64_t)H + pad) * row;
+  a.inv_row = 1.0 / (double)row;
+  if (a.n_out >= ((int64_t)1 << 40)) return fail("%s", "scene_prepare: more than 2^40 output elements");
+  return check(launch_scene_prepare(a, dtype, half != 0, static_cast<hipStream_t>(stream)), "scene_prepare launch");
+}
+
 #ifdef DMF_STAMPS
 int32_t dmf_debug_set_reduce_stamps(void* p) { return check(hipMemcpyToSymbol(HIP_SYMBOL(dmf::g_rstamps), &p, sizeof(p)), "set_reduce_stamps"); }
 int32_t dmf_debug_set_attn_stamps(void* p) { return check(dmf::set_attn_stamps(static_cast<unsigned long long*>(p)), "set_attn_stamps"); }

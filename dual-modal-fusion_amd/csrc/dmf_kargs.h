@@ -115,6 +115,19 @@ hipError_t launch_qua_loss(const QuaArgs& a, hipStream_t st);
 hipError_t launch_pair_argmax(const float* logits, int bs, int K, int32_t* pred, hipStream_t st);
 hipError_t launch_band_mean(const float* x, int layout, int64_t n_img, int64_t n_pix, int C, float* out, hipStream_t st);
 
+// scene preparation (dmf_scene.hip)
+struct ScenePrepArgs {
+  const void* raw; const void* minmax; void* out;
+  int H, W, C, pad;
+  int row;           // elements of one padded output row, (W + pad) * C
+  int shift;         // elements by which `out` lies past a 16-byte boundary
+  int64_t n_out;     // (H + pad) * row
+  double inv_row;    // 1 / row
+};
+int scene_raw_bytes(int dtype);      // element size of a DMF_RAW_* code, 0 for an unknown one
+hipError_t launch_scene_minmax(const void* raw, int dtype, int64_t n, void* minmax, hipStream_t st);
+hipError_t launch_scene_prepare(const ScenePrepArgs& a, int dtype, int half, hipStream_t st);
+
 #ifdef DMF_STAMPS
 hipError_t set_attn_stamps(unsigned long long* p);
 hipError_t set_v2_stamps(unsigned long long* p);

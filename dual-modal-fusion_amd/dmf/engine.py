@@ -47,6 +47,48 @@ def _upload_graph(g):
     return rc == 0
 
 
+def reflect_index(i, n):
+    """Source index of output index i along an axis of n samples padded at its end by reflection without the edge
+    (numpy 'reflect' / cv2.BORDER_REFLECT_101, function.data_padding): the rule of dmf_scene_prepare.  Valid for i <= 2 (n - 1)."""
+    return i if i < n else 2 * (n - 1) - i
+
+
+def prep_route(dtype, H, W, pad, mn=None, mx=None):
+    """Where a raw scene [H, W(, C)] of numpy dtype `dtype` is normalised and padded by `pad`: ('device', '') or
+    ('host', why).  The host keeps what dmf_scene_prepare does not state: a dtype without a DMF_RAW_* code, a pad beyond the
+    reflection's reach (numpy reflects again and again), and an integer scene whose max - min (`mn`, `mx`: its extremes, once
+    they are known) is not representable in the raw type, where numpy's subtraction wraps around."""
+    dtype = np.dtype(dtype)
+    if lib.raw_code(dtype) is None:
+        return 'host', 'dtype %s has no device code' % dtype
+    if pad < 0 or pad > H - 1 or pad > W - 1:
+        return 'host', 'pad %d exceeds the reflection of a %d x %d scene' % (pad, H, W)
+    if mn is not None and dtype.kind in 'iu' and int(mx) - int(mn) > np.iinfo(dtype).max:
+        return 'host', 'max - min = %d wraps around in %s' % (int(mx) - int(mn), dtype)
+    return 'device', ''
+
+
+def _prepare_on_device(raw, pad, out):
+    """out [H+pad, W+pad, C] (device, fp32 / fp16) <- the normalised, padded scene of the raw numpy scene [H, W(, C)], which is
+    uploaded in its own dtype and freed again.  Returns '' or, where only the extremes tell (prep_route), why the host has to
+    do it.  One host sync: the two extremes are read back."""
+    H, W = raw.shape[:2]
+    C = raw.shape[2] if raw.ndim == 3 else 1
+    name = raw.dtype.name
+    raw_d = torch.from_numpy(np.ascontiguousarray(raw).reshape(-1).view(np.uint8)).to(out.device)
+    minmax = torch.empty(16, dtype=torch.uint8, device=out.device)
+    lib.scene_minmax(raw_d, name, minmax)
+    mn, mx = minmax.cpu().numpy().view(raw.dtype)[:2]
+    why = prep_route(raw.dtype, H, W, pad, mn, mx)[1]
+    if not why:
+        lib.scene_prepare(raw_d, name, H, W, C, minmax, pad, out)
+    return why
+
+
+def _host_fallback(why):
+    print('dmf: scene preparation on the host (%s)' % why, flush=True)
+
+
 class Scene:
     """Padded, normalised scenes resident in HBM: A [Hp, Wp, C], B [HpB, WpB, C2] (pixel-major, fp32).
     half: A is kept as IEEE fp16 (`gmf.half`; numpy's float32 -> float16 rounds to nearest even, as the oracle does)."""
@@ -60,6 +102,35 @@ class Scene:
         self.A = torch.from_numpy(A.astype(np.float16) if half else A).to(device)
         self.B = torch.from_numpy(Bm).to(device)
         self.device = torch.device(device)
+
+    @classmethod
+    def from_raw(cls, primary_raw, aux_raw, patch, scale, device, half=False):
+        """The scene of `Scene(data_padding(primary_raw, ..), data_padding_aux(aux_raw, ..), device, half)`, bit for bit, with
+        the normalisation, the padding (patch - 1 / scale * patch - 1) and the conversions done on the device from the raw
+        scenes (`scene_prep: device`).  Falls back to exactly that host call, saying why, where prep_route sends a scene to
+        the host."""
+        primary_raw, aux_raw = np.asarray(primary_raw), np.asarray(aux_raw)
+        if primary_raw.ndim != 3 or aux_raw.ndim not in (2, 3):
+            raise lib.DmfError('from_raw wants a primary scene [H, W, C] and an aux scene [SH, SW] or [SH, SW, C2]')
+        pads = (patch - 1, scale * patch - 1)
+        why = ''
+        for raw, pad in zip((primary_raw, aux_raw), pads):
+            why = why or prep_route(raw.dtype, raw.shape[0], raw.shape[1], pad)[1]
+        if not why:
+            self = cls.__new__(cls)
+            self.half, self.device = bool(half), torch.device(device)
+            tensors = []
+            for raw, pad, dt in zip((primary_raw, aux_raw), pads, (torch.float16 if half else torch.float32, torch.float32)):
+                t = torch.empty(raw.shape[0] + pad, raw.shape[1] + pad, raw.shape[2] if raw.ndim == 3 else 1, dtype=dt, device=device)
+                why = why or _prepare_on_device(raw, pad, t)
+                tensors.append(t)
+            if not why:
+                self.A, self.B = tensors
+                return self
+        _host_fallback(why)
+        from function.function import data_padding, data_padding_aux
+        cfg = {'patch_size': patch, 'scale': scale}
+        return cls(data_padding(primary_raw, cfg, 'ms'), data_padding_aux(aux_raw, cfg), device, half=half)
 
 
 class LossScaler:
@@ -614,6 +685,35 @@ class QuaScene:
         if half:                                      # `gmf.half`: the primary scene is kept as fp16 (round to nearest even)
             self.A = self.A.to(torch.float16)
         self.device = torch.device(device)
+
+    @classmethod
+    def from_raw(cls, scenes_raw, patch, device, half=False):
+        """The scene of `QuaScene([data_padding(s, ..) for s in scenes_raw], device, half)`, bit for bit, prepared on the device:
+        every stream is normalised by its own extremes and written into its own quarter of the tall tensor.  Falls back to
+        exactly that host call, saying why, where prep_route sends a stream to the host."""
+        scenes_raw = [np.asarray(s) for s in scenes_raw]
+        if len(scenes_raw) != 4 or scenes_raw[0].ndim != 3 or any(s.shape != scenes_raw[0].shape for s in scenes_raw):
+            raise lib.DmfError('stage 2 wants four scenes [H, W, C] of one shape')
+        H, W, C = scenes_raw[0].shape
+        pad = patch - 1
+        why = ''
+        for s in scenes_raw:
+            why = why or prep_route(s.dtype, H, W, pad)[1]
+        if not why:
+            Hp = H + pad
+            tall = torch.empty(4 * Hp, W + pad, C, device=device)
+            for k, s in enumerate(scenes_raw):
+                why = why or _prepare_on_device(s, pad, tall[k * Hp:(k + 1) * Hp])
+        if why:
+            _host_fallback(why)
+            from function.function import data_padding
+            cfg = {'patch_size': patch}
+            return cls([data_padding(s, cfg, 'ms') for s in scenes_raw], device, half=half)
+        self = cls.__new__(cls)
+        self.Hp, self.half, self.device = Hp, bool(half), torch.device(device)
+        self.B = lib.band_mean_scene(tall)
+        self.A = tall.to(torch.float16) if half else tall
+        return self
 
     def stack_xy(self, xy, streams=4):
         """[n, 2] pixel coordinates -> [streams*n, 2] int32 coordinates in the tall scene, on the device `xy` lives on,

@@ -90,6 +90,8 @@ def _load():
         'dmf_confusion_accum': (i32, [vp, vp, i32, i32, vp, vp]),
         'dmf_labelmap_write': (i32, [vp, vp, i32, i32, vp, vp]),
         'dmf_pan2ms': (i32, [vp, i32, i32, i32, vp, vp]),
+        'dmf_scene_minmax': (i32, [vp, i32, i64, vp, vp]),
+        'dmf_scene_prepare': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -454,3 +456,49 @@ def labelmap_write(pred, xy, W, label_map):
 
 def pan2ms(pan, H, W, out):
     check(_lib.dmf_pan2ms(_ptr(pan), pan.shape[1], H, W, _ptr(out), _stream()))
+
+
+# DMF_RAW_* (include/dmf.h): the dtypes a raw scene may be uploaded in, by numpy name -> (code, bytes per element)
+RAW_DTYPES = {'uint8': (0, 1), 'uint16': (1, 2), 'int16': (2, 2), 'int32': (3, 4), 'float32': (4, 4), 'float64': (5, 8)}
+
+
+def raw_code(dtype):
+    """DMF_RAW_* code of a numpy dtype, or None where it has none (bool, complex, int64, a foreign byte order ...)."""
+    import numpy as np
+    dtype = np.dtype(dtype)
+    return RAW_DTYPES[dtype.name][0] if dtype.name in RAW_DTYPES and dtype.isnative else None
+
+
+def _raw(raw, dtype_name, n):
+    code, size = RAW_DTYPES[dtype_name]
+    _dev(raw, torch.uint8, 'raw scene (its bytes)')
+    if raw.numel() != n * size:
+        raise DmfError('raw scene: %d bytes for %d %s elements' % (raw.numel(), n, dtype_name))
+    return code, size
+
+
+def scene_minmax(raw, dtype_name, minmax):
+    """raw: the bytes of a raw scene (uint8 tensor) of numpy dtype `dtype_name`; minmax (uint8, >= 2 elements of that
+    dtype) <- {min, max} in the raw dtype."""
+    code, size = RAW_DTYPES[dtype_name]
+    _raw(raw, dtype_name, raw.numel() // size)
+    _dev(minmax, torch.uint8, 'minmax')
+    if minmax.numel() < 2 * size or minmax.device != raw.device:
+        raise DmfError('minmax wants two elements of the raw dtype on the scene\'s device')
+    check(_lib.dmf_scene_minmax(_ptr(raw), code, raw.numel() // size, _ptr(minmax), _stream()))
+
+
+def scene_prepare(raw, dtype_name, H, W, C, minmax, pad, out):
+    """out [H+pad, W+pad, C] (fp32 or fp16) <- the normalised, reflect-padded scene of raw [H, W, C] (its bytes) and the
+    minmax of scene_minmax."""
+    code, size = _raw(raw, dtype_name, H * W * C)
+    _dev(minmax, torch.uint8, 'minmax')
+    if out.dtype not in (torch.float32, torch.float16):
+        raise DmfError('the prepared scene is fp32 or fp16')
+    _dev(out, out.dtype, 'out')
+    if minmax.numel() < 2 * size or minmax.device != raw.device or out.device != raw.device:
+        raise DmfError('raw scene, minmax and out must live on one device')
+    if pad < 0 or out.numel() != (H + pad) * (W + pad) * C:
+        raise DmfError('out must hold [%d, %d, %d] elements' % (H + pad, W + pad, C))
+    check(_lib.dmf_scene_prepare(_ptr(raw), code, H, W, C, _ptr(minmax), pad, int(out.dtype == torch.float16), _ptr(out),
+                                 _stream()))

@@ -6,6 +6,9 @@ train / test / valid, five DataLoaders, `indicator()`.  Additions for the GPU pa
 resident in HBM (`self.scene`), and every loader has an index-only twin (`*_index_loader`) that yields pixel
 coordinates instead of materialised patches.  Iterating either twin consumes the global RNG exactly like the
 reference's loader does, so a seeded run visits the same patches in the same order.
+`scene_prep: device` (NEW; fast path only, the drop-in path ignores it): the resident scene is normalised, padded and converted
+on the GPU from the raw scenes (dmf.engine.Scene.from_raw), and the padded host arrays `self.MS` / `self.PAN` — and with them
+the arrays behind the materialising loaders — are computed only when something asks for them.
 """
 import os
 import time
@@ -33,8 +36,14 @@ class BaseSolver:
 
         self.ms = read_tif(cfg, 'ms')
         self.pan = read_tif(cfg, 'pan')
-        self.MS = data_padding(self.ms, cfg, 'ms')
-        self.PAN = data_padding(self.pan, cfg, 'pan') if self.pan.ndim == 2 else data_padding_aux(self.pan, cfg)
+        self.fast = bool(cfg.get('fast_path', 1)) and str(self.DEVICE).startswith('cuda')
+        prep = cfg.get('scene_prep') or 'host'
+        if prep not in ('host', 'device'):
+            raise ValueError('scene_prep: %s is not one of host, device' % prep)
+        self.device_prep = self.fast and prep == 'device'
+        self._padded = {}
+        if not self.device_prep:
+            self.MS, self.PAN                                   # today's order of work: both padded scenes now
 
         label_path = cfg['data_address'] + 'label.npy'
         if not os.path.exists(label_path):
@@ -53,18 +62,36 @@ class BaseSolver:
         self.xyl = xyl_matrix
         if cfg.get('use_h5'):
             raise AttributeError("not finished")          # as the reference (basesolver.py:45-46)
-        self.dataset = dataset_dual(self.MS, self.PAN, xyl_matrix, cfg)
+        self.dataset = dataset_dual(*((lambda: self.MS, lambda: self.PAN) if self.device_prep else (self.MS, self.PAN)),
+                                    xyl_matrix, cfg)
         self.index_dataset = self.dataset.index_view()
         print('All dataset size:', len(self.dataset))
         self.records = {'Epoch': [], 'PSNR': [], 'SSIM': [], 'Loss': []}
         self.scene = None
-        self.fast = bool(cfg.get('fast_path', 1)) and str(self.DEVICE).startswith('cuda')
         # gmf.half: 1 — the fast path keeps the primary scene in fp16 and trains with the device loss scaler (the drop-in
         # path rounds its patches to fp16 as they are staged, model/gmfnet.py)
         self.half = bool((cfg.get('gmf') or {}).get('half', 0))
         if self.fast:
             from dmf.engine import Scene
-            self.scene = Scene(self.MS, self.PAN, self.DEVICE, half=self.half)
+            if self.device_prep:
+                self.scene = Scene.from_raw(self.ms, self.pan, cfg['patch_size'], int(cfg.get('scale', 4)), self.DEVICE,
+                                            half=self.half)
+            else:
+                self.scene = Scene(self.MS, self.PAN, self.DEVICE, half=self.half)
+
+    @property
+    def MS(self):
+        """The normalised, padded primary scene on the host (computed on first use)."""
+        if 'MS' not in self._padded:
+            self._padded['MS'] = data_padding(self.ms, self.cfg, 'ms')
+        return self._padded['MS']
+
+    @property
+    def PAN(self):
+        """The normalised, padded aux scene on the host (computed on first use)."""
+        if 'PAN' not in self._padded:
+            self._padded['PAN'] = data_padding(self.pan, self.cfg, 'pan') if self.pan.ndim == 2 else data_padding_aux(self.pan, self.cfg)
+        return self._padded['PAN']
 
     def _loader(self, subset, batch, shuffle):
         twin = Subset(self.index_dataset, indices=subset.indices)

@@ -28,6 +28,7 @@ is NOT built.  Run stage 2 on stage-1 outputs that already exist (`dqtl.pre_trai
 under cfg['expo_result'] + cfg['dqtl']['WEIGHTS'], as the reference does at :241-243).  `pan.npy` (:246) is produced
 from the PAN image with `pan2ms` (image_convert/IHS.py:14-19, on the GPU) when the file does not exist.
 `gmf.half: 1` on the fast path: fp16 tall scene and the device loss scaler around the ADAM step (as in solver.mainsolver).
+`scene_prep: device` on the fast path: the tall scene is prepared on the GPU from the four raw scenes (QuaScene.from_raw).
 Data parallel (`test.py` with `solver: toStageSolver` under `torch.distributed.run`, fast path only): every rank iterates the
 same shuffled stream, the engine trains each rank on its contiguous shard of every global batch and evaluates the loss on
 the gathered global batch (dmf.engine.QuaTrainEngine); the short last batch is sharded the same way (a remainder that the
@@ -75,7 +76,18 @@ class toStageSolver(Solver):
             from image_convert.IHS import pan2ms, pan2ms_gpu
             size = [self.ms.shape[0], self.ms.shape[1], 4]
             PAN = pan2ms_gpu(self.pan, size, self.DEVICE) if str(self.DEVICE).startswith('cuda') else pan2ms(self.pan, size)
-        scenes = [data_padding(x, cfg, 'ms') for x in (self.ms, PAN, self.ms_gan, self.pan_gan)]
+        raw = (self.ms, PAN, self.ms_gan, self.pan_gan)
+        padded = []
+
+        def scene(k):                                   # the padded host scenes, all four on the first use of one
+            def get():
+                if not padded:
+                    padded.extend(data_padding(x, cfg, 'ms') for x in raw)
+                return padded[k]
+            return get
+        scenes = [scene(k) for k in range(4)]           # `scene_prep: device`: only the materialising loader calls them
+        if not self.device_prep:
+            scenes = [get() for get in scenes]
         label_np = np.load(cfg['data_address'] + 'label.npy')
         data_show(label_np)
         xyl_matrix, self.matrix_ = split_data_old(label_np, cfg)
@@ -83,7 +95,10 @@ class toStageSolver(Solver):
         self.index_dataset = self.dataset.index_view()
         if self.fast:
             from dmf.engine import QuaScene
-            self.qua_scene = QuaScene(scenes, self.DEVICE, half=self.half)
+            if self.device_prep:
+                self.qua_scene = QuaScene.from_raw(raw, cfg['patch_size'], self.DEVICE, half=self.half)
+            else:
+                self.qua_scene = QuaScene(scenes, self.DEVICE, half=self.half)
 
     # ------------------------------------------------------------------ what stage 2 states differently: fast path
     def _steps_per_graph(self):

@@ -4,22 +4,37 @@
 (train/dataset.py:158-188) with the aux/primary resolution ratio taken from cfg['scale'] (reference: 4).
 `dataset_dual.index_view()` is the same dataset without the patch materialisation: `(x, y, label, index)` as ints —
 the resident-scene fast path gathers the pixels on the GPU, so the host only shuffles coordinates.
+The scenes may be given as zero-argument callables (`scene_prep: device`): they are called on the first patch that is
+materialised, so a run that only uses the index views never builds the padded host arrays.
 """
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
 
+def _resolved(scenes):
+    return tuple(s() if callable(s) else s for s in scenes)
+
+
 class dataset_dual(Dataset):
     def __init__(self, ms, pan, xyl, cfg):
-        self.MS = ms
-        self.PAN = pan
+        self._scenes = (ms, pan)
         self.Label = xyl[2]
         self.x = xyl[0]
         self.y = xyl[1]
         self.scale = int(cfg.get('scale', 4))
         self.ms_size = cfg['patch_size']
         self.pan_size = cfg['patch_size'] * self.scale
+
+    @property
+    def MS(self):
+        self._scenes = _resolved(self._scenes)
+        return self._scenes[0]
+
+    @property
+    def PAN(self):
+        self._scenes = _resolved(self._scenes)
+        return self._scenes[1]
 
     def __getitem__(self, index):
         s = self.scale
@@ -67,12 +82,17 @@ class dataset_qua_dqtl(Dataset):
     """Four co-registered [H,W,4] images -> (ms, pan, ms_gan, pan_gan, label, x, y) (train/dataset.py:191-224)."""
 
     def __init__(self, ms, pan, ms_gan, pan_gan, xyl, cfg):
-        self.images = (ms, pan, ms_gan, pan_gan)
+        self._scenes = (ms, pan, ms_gan, pan_gan)
         self.Label, self.x, self.y = xyl[2], xyl[0], xyl[1]
         self.size = cfg['patch_size']
 
     def index_view(self):
         return _IndexView(self)
+
+    @property
+    def images(self):
+        self._scenes = _resolved(self._scenes)
+        return self._scenes
 
     def __getitem__(self, index):
         p = self.size

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 301   /* 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 302   /* 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -300,6 +300,26 @@ int32_t dmf_labelmap_write(const int32_t* pred, const int32_t* xy, int32_t B, in
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);
+
+/* ---- scene preparation: replaces `to_tensor` + the reflect padding of `data_padding` (function/function.py:99-124) and the
+ * float32 / float16 conversions of the resident scene, for a raw scene uploaded in the dtype the readers deliver. */
+#define DMF_RAW_U8  0
+#define DMF_RAW_U16 1
+#define DMF_RAW_I16 2
+#define DMF_RAW_I32 3
+#define DMF_RAW_F32 4
+#define DMF_RAW_F64 5
+/* minmax[0..2) <- {min, max} of raw[0..n), in the raw dtype (device memory).  Two launches, the result does not depend on
+ * the order of the partial results; a NaN of a float scene propagates as np.min / np.max propagate it.  The partial results
+ * live in library-owned device memory: do not run two of these calls at the same time on different streams. */
+int32_t dmf_scene_minmax(const void* raw, int32_t dtype, int64_t n, void* minmax, void* stream);
+/* out [H + pad, W + pad, C] (fp32, or fp16 when half != 0) <- (raw - min) / (max - min), padded at the bottom and the right by
+ * reflection without the edge (BORDER_REFLECT_101 / numpy 'reflect': row i >= H reads row 2 (H - 1) - i; needs pad <= H - 1 and
+ * pad <= W - 1).  raw [H, W, C] (C = 1 for a 2-D scene) and minmax as dmf_scene_minmax leaves them.  Bit for bit numpy's
+ * result: integer types subtract in the raw type (the caller rules out a max - min that wraps) and divide as float64, f32
+ * in float32, f64 in float64; one rounding to fp32, then for half a second one to fp16.  out needs no 16-byte alignment. */
+int32_t dmf_scene_prepare(const void* raw, int32_t dtype, int32_t H, int32_t W, int32_t C, const void* minmax, int32_t pad,
+                          int32_t half, void* out, void* stream);
 
 #ifdef __cplusplus
 }

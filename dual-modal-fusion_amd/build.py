@@ -17,7 +17,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ('dmf_patch_v2.hip', 'dmf_attention.hip', 'dmf_qua.hip', 'dmf_scene.hip', 'dmf_capi.hip')
+NAMES = ('dmf_patch_v2.hip', 'dmf_attention.hip', 'dmf_qua.hip', 'dmf_loss.hip', 'dmf_scene.hip', 'dmf_capi.hip')
 SRC = [os.path.join(HERE, 'csrc', n) for n in NAMES]
 HDR = [os.path.join(HERE, 'csrc', n) for n in ('dmf_shapes.h', 'dmf_kargs.h', 'dmf_lanes.h', 'dmf_xgmi.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'dmf.h')]
 OUT = os.path.join(HERE, 'dmf', 'libdmf_hip.so')
@@ -81,7 +81,7 @@ def build(force=False, verbose=True, stamps=False, shapes=None, defines=(), suff
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    with ThreadPoolExecutor(max_workers=min(len(jobs), 5) or 1) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), len(SRC)) or 1) as ex:
         list(ex.map(run, jobs))
     run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC'] + objs + ['-o', out])
     with open(tagfile, 'w') as f:

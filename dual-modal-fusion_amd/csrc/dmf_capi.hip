@@ -1032,6 +1032,21 @@ int32_t dmf_qua_loss(const float* logits, int32_t bs, int32_t K, const int32_t* 
   return dmf_qua_loss_scaled(logits, bs, K, labels, cursor, prm, grad_scale, nullptr, loss, loss_hist, dlogits, stream);
 }
 
+int32_t dmf_ce_loss(const float* logits, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K, const int32_t* labels_global,
+                    const int32_t* cursor, const float* class_w, const dmf_ce_params* prm, float grad_scale,
+                    const float* scaler_state, float* loss, float* dlogits, void* stream) {
+  if (logits == nullptr || labels_global == nullptr || prm == nullptr) return fail("%s", "null argument");
+  if (ranks < 1 || rank < 0 || rank >= ranks) return fail("%s", "ce_loss: ranks must be positive and 0 <= rank < ranks");
+  if (bs_r <= 0 || K < 1 || K > KMAX) return fail("%s", "ce_loss: bs must be positive and 1 <= K <= DMF_KMAX");
+  if ((int64_t)ranks * bs_r > INT32_MAX || (int64_t)bs_r * K > INT32_MAX) return fail("%s", "ce_loss: the batch is too large");
+  if (prm->kind != 0 && prm->kind != 1) return fail("%s", "ce_loss: kind must be 0 (cross-entropy) or 1 (focal)");
+  if (!(prm->label_smoothing >= 0.f && prm->label_smoothing < 1.f)) return fail("%s", "ce_loss: label_smoothing must lie in [0, 1)");
+  if (!(prm->gamma == 0.f || (prm->gamma >= 1.f && isfinite(prm->gamma)))) return fail("%s", "ce_loss: gamma must be 0 or >= 1");
+  CeArgs a{logits, labels_global, cursor, class_w, scaler_state, loss, dlogits, ranks, rank, bs_r, K, prm->kind,
+           prm->kind == 0 ? prm->label_smoothing : 0.f, prm->kind == 1 ? prm->gamma : 0.f, grad_scale};
+  return check(launch_ce_loss(a, static_cast<hipStream_t>(stream)), "ce_loss launch");
+}
+
 int32_t dmf_pair_argmax(const float* logits, int32_t bs, int32_t K, int32_t* pred, void* stream) {
   if (logits == nullptr || pred == nullptr) return fail("%s", "null argument");
   if (bs <= 0) return 0;

@@ -115,6 +115,19 @@ hipError_t launch_qua_loss(const QuaArgs& a, hipStream_t st);
 hipError_t launch_pair_argmax(const float* logits, int bs, int K, int32_t* pred, hipStream_t st);
 hipError_t launch_band_mean(const float* x, int layout, int64_t n_img, int64_t n_pix, int C, float* out, hipStream_t st);
 
+// per-sample classification losses of the unit-gradient step (dmf_loss.hip)
+struct CeArgs {
+  const float* logits;   // [bs_r][K], this rank's rows
+  const int32_t* labels; const int32_t* cursor;   // labels[(*cursor) * ranks * bs_r + r * bs_r + i]: the GLOBAL batch, rank-major
+  const float* class_w;  // [K], nullable = all ones
+  const float* scaler;   // nullable: device loss-scaler state, [0] multiplies grad_scale
+  float* loss;           // [bs_r] nullable
+  float* dlogits;        // [bs_r][K] nullable
+  int ranks, rank, bs_r, K, kind;
+  float eps, gamma, grad_scale;
+};
+hipError_t launch_ce_loss(const CeArgs& a, hipStream_t st);
+
 // scene preparation (dmf_scene.hip)
 struct ScenePrepArgs {
   const void* raw; const void* minmax; void* out;

@@ -153,6 +153,40 @@ class LossScaler:
         return (self.growth_factor, self.backoff_factor, self.growth_interval)
 
 
+class Criterion:
+    """A classification criterion beyond the plain cross-entropy fused into the patch kernel, as dmf_ce_loss takes it
+    (DESIGN.md §12).  spec: dict(kind, label_smoothing, gamma, class_weights) —
+      kind           'ce' (0): nn.CrossEntropyLoss(weight=class_weights, label_smoothing=label_smoothing);
+                     'focal' (1): w[y] (1 - p_y)^gamma (-log p_y), mean over the batch by the same denominator sum_j w[y_j]
+      class_weights  K floats, every one finite and > 0 (the denominator of every batch is then > 0), or None = all ones.
+    A missing key is its neutral value."""
+
+    def __init__(self, spec, K, device):
+        kind = spec.get('kind', 'ce')
+        kind = {0: 'ce', 1: 'focal'}.get(kind, kind)
+        eps, gamma = float(spec.get('label_smoothing') or 0.0), float(spec.get('gamma') or 0.0)
+        if kind not in lib.CE_KINDS:
+            raise lib.DmfError('criterion kind %r is not one of %s' % (kind, sorted(lib.CE_KINDS)))
+        if not 0.0 <= eps < 1.0:
+            raise lib.DmfError('label_smoothing %r is not in [0, 1)' % eps)
+        if not (gamma == 0.0 or (gamma >= 1.0 and np.isfinite(gamma))):
+            raise lib.DmfError('focal gamma %r is neither 0 nor >= 1' % gamma)
+        if (kind == 'ce' and gamma != 0.0) or (kind == 'focal' and eps != 0.0):
+            raise lib.DmfError('label smoothing belongs to kind ce, gamma to kind focal: got kind %s, label_smoothing %g, gamma %g'
+                               % (kind, eps, gamma))
+        self.kind, self.label_smoothing, self.gamma = kind, eps, gamma
+        self.params = lib.ce_params(kind, eps, gamma)
+        self.class_w = None
+        w = spec.get('class_weights')
+        if w is not None:
+            w = np.asarray(w, dtype=np.float32).reshape(-1)
+            if w.size != K:
+                raise lib.DmfError('class_weights holds %d weights for %d classes' % (w.size, K))
+            if not (np.isfinite(w).all() and (w > 0).all()):
+                raise lib.DmfError('class_weights must be finite and > 0 (as float32), got %s' % w.tolist())
+            self.class_w = torch.from_numpy(w.copy()).to(device)
+
+
 class _PlanEngine:
     """What both train engines share: parameters and optimiser state, the epoch plan on the device, and the hipGraph that
     replays steps of it.  A subclass says how one step is launched (`_plan_launch`) and what differs around a capture."""
@@ -396,9 +430,15 @@ class _PlanEngine:
 
 class TrainEngine(_PlanEngine):
     def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
-                 optimizer='ADAM', momentum=0.0, alpha=0.99):
+                 optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None):
         """optimizer: 'ADAM', or the reference's other two (utils/utils.py:13-16) — 'SGD' (`momentum`) and 'RMSprop'
-        (`alpha`, eps 1e-8).  The launches after the backward: _PlanEngine._update."""
+        (`alpha`, eps 1e-8).  The launches after the backward: _PlanEngine._update.
+        criterion: None = the plain cross-entropy fused into the patch kernel (two launches per step).  A spec of `Criterion`
+        (class weights, label smoothing, focal term) trains by the unit-gradient step instead: dmf_forward_unit -> dmf_ce_loss
+        -> dmf_backward_unit -> the update, eagerly or from captured graphs whose steps read plan[cursor] (no native launch
+        loop, no xgmi exchange).  Data parallel it takes GLOBAL batches like QuaTrainEngine: `load_plan` / `step` get the
+        pixels and labels of all ranks, every rank trains on its contiguous shard of each batch, and the loss kernel, which
+        divides by the global batch's weight sum, reads the global labels."""
         super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
@@ -419,10 +459,30 @@ class TrainEngine(_PlanEngine):
         if self.comm is not None and (self.comm.world != self.world or self.comm.capacity < self.theta.numel()):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
         self.plan_pack = self.win = None
+        self.criterion = None
+        if criterion is not None:
+            if self.shape.attention:
+                raise lib.DmfError('a criterion with class weights, label smoothing or a focal term trains by the unit-gradient '
+                                   'step, which the attention network does not have')
+            if not lib.unit_supported(self.shape):
+                raise lib.DmfError('a criterion with class weights, label smoothing or a focal term needs the unit-gradient '
+                                   'kernel (dmf_unit_supported), which this shape does not have')
+            if comm is not None:
+                raise lib.DmfError('a criterion with class weights, label smoothing or a focal term: single GPU or a process '
+                                   'group (not the xgmi exchange)')
+            self.criterion = Criterion(criterion, K, dev)
+            self.dlogits = torch.empty(self.B, K, device=dev)
 
     # ------------------------------------------------------------------ eager step (host-side step count)
     def step(self, xy, labels, check=True):
-        """One optimiser step on the patches at `xy` [B,2] int32 (device) with `labels` [B] int32 (device)."""
+        """One optimiser step on the patches at `xy` [B,2] int32 (device) with `labels` [B] int32 (device).  With a criterion
+        and a process group `xy` / `labels` are the GLOBAL batch (the same on every rank): every rank trains on its contiguous
+        shard of len // world pixels, and the remainder that the world size does not divide is dropped."""
+        if self.criterion is not None:
+            n = xy.shape[0] // self.world
+            if n == 0:
+                raise lib.DmfError('a batch of %d pixels gives the %d ranks no pixel each' % (xy.shape[0], self.world))
+            xy, labels = xy[self.rank * n:(self.rank + 1) * n].contiguous(), labels[:self.world * n].contiguous()
         if xy.shape[0] > self.B:
             raise lib.DmfError('engine was built for batches of at most %d, got %d' % (self.B, xy.shape[0]))
         if check:     # one D2H copy per call; load_plan() validates a whole epoch at once and run_plan() skips this
@@ -432,7 +492,10 @@ class TrainEngine(_PlanEngine):
         self._launch(inp, labels, None, None)
 
     def step_patches(self, a, b, labels):
-        """Same step from materialised patch tensors (the reference dataloader's batch)."""
+        """Same step from materialised patch tensors (the reference dataloader's batch).  With a criterion: one rank only (the
+        loss kernel needs the global batch's labels, and nothing shards materialised patches)."""
+        if self.criterion is not None and self.world > 1:
+            raise lib.DmfError('step_patches with a criterion: one rank only (use step / load_plan, which take the global batch)')
         inp = lib.input_patches(self.shape, a, b)
         self._launch(inp, labels, None, None)
 
@@ -444,6 +507,16 @@ class TrainEngine(_PlanEngine):
     def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
         dev_step = self._count_step(dev_step)
         sc, nB = self.scaler, inp.B
+        if self.criterion is not None:
+            # the unit-gradient step around the loss kernel; labels: the GLOBAL batch's ([world * nB] at row dev_cursor).  The
+            # kernel has divided by the global batch's weight sum already: the sum over the ranks is the gradient
+            cr = self.criterion
+            lib.forward_unit(self.shape, inp, self.theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
+            lib.ce_loss(self.logits[:nB], self.world, self.rank, labels, cr.params, class_w=cr.class_w, loss=self.loss,
+                        dlogits=self.dlogits[:nB], cursor=dev_cursor, scaler_state=sc.state if sc is not None else None)
+            lib.backward_unit(self.shape, nB, self.theta, self.dlogits, self.ws)
+            self._update(nB, dev_step, dev_cursor, 1.0, self.loss if loss_hist is not None else None, loss_hist)
+            return
         if self.shape.attention:
             lib.train_attn_fwd_bwd(self.shape, inp, self.theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits,
                                    self.loss, self.ws, self.attn_ws, adam_step_dev=dev_step)
@@ -455,8 +528,23 @@ class TrainEngine(_PlanEngine):
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def load_plan(self, xy_all, labels_all):
-        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type)."""
+        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type).  With a
+        criterion: an epoch of GLOBAL batches, [n*B*world] each; rank r keeps rows [r*B, (r+1)*B) of every batch's pixels and
+        the labels of the whole batches."""
         dev = self.scene.device
+        if self.criterion is not None:
+            W = self.world
+            xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
+            lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
+            if xy.shape[0] % (self.B * W) or xy.shape[0] != lab.shape[0]:
+                raise lib.DmfError('plan length must be a multiple of the (global) batch size')
+            n = xy.shape[0] // (self.B * W)
+            if W > 1:
+                xy = xy.view(n, W, self.B, 2)[:, self.rank].reshape(-1, 2)
+            lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
+            self._check_labels(lab)
+            self._install_plan(n, plan_xy=xy.to(dev).contiguous(), plan_labels=lab)
+            return n
         xy = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
         lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
         if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
@@ -476,6 +564,8 @@ class TrainEngine(_PlanEngine):
 
     def _fill_window(self, n):
         """Copy the next n steps of the plan into the fixed window the captured graph reads (one small async copy)."""
+        if self.criterion is not None:
+            return
         self.win.copy_(self.plan_pack[self.host_cursor:self.host_cursor + n])
 
     def run_plan(self, steps=None, steps_per_graph=0):
@@ -496,8 +586,9 @@ class TrainEngine(_PlanEngine):
         return steps
 
     def _native_loop_ok(self):
-        """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler."""
-        return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention
+        """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler,
+        the fused cross-entropy."""
+        return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.criterion is None
 
     def _graphable(self):
         """Can a step be captured in a hipGraph?  One GPU: yes.  The one-shot exchange: yes (it is part of the reduce launch).
@@ -510,6 +601,8 @@ class TrainEngine(_PlanEngine):
         return self._rccl_capturable()
 
     def _prepare_capture(self, n):
+        if self.criterion is not None:             # the graph's steps read plan[cursor] like eager plan steps: no window
+            return
         if self.comm is not None:                  # the eager step used up an exchange sequence number; the bias is
             self.comm.rewind(1)                    # a launch argument, so it has to move BEFORE the capture
         # Inside the graph step k reads its coordinates and labels from slot k of a FIXED window (plain pointers baked
@@ -523,6 +616,8 @@ class TrainEngine(_PlanEngine):
             self.win.zero_()
 
     def _graph_step(self, k):
+        if self.criterion is not None:
+            return self._plan_launch()
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.win[k, :2 * self.B].view(self.B, 2))
         self._launch(inp, self.win[k, 2 * self.B:], self.dev_step, self.dev_cursor, self.loss_hist)
 
@@ -620,12 +715,14 @@ class _ShardedEval:
 class EvalEngine(_ShardedEval):
     """Forward + argmax + on-device confusion matrix / label map (mainsolver.py:102-147,164-197)."""
 
-    def __init__(self, net, scene, batch):
+    def __init__(self, net, scene, batch, criterion=None):
+        """criterion (a spec of `Criterion`, default None = plain cross-entropy): what `ce_sum` evaluates."""
         self.net, self.scene, self.B = net, scene, int(batch)
         self.shape = net.shape
         lib.shape_supported(self.shape)
         dev = scene.device
         K = net.arch['K']
+        self.criterion = Criterion(criterion, K, dev) if criterion is not None else None
         self.logits = torch.empty(self.B, K, device=dev)
         self.pred = torch.empty(self.B, dtype=torch.int32, device=dev)
         self.attn_ws = None
@@ -647,9 +744,17 @@ class EvalEngine(_ShardedEval):
 
     def ce_sum(self, xy, labels):
         """Sum over the batch of the per-patch cross-entropy (device scalar, float64), from the evaluation launch itself
-        (dmf_forward_ce); None where the shape has no such kernel."""
+        (dmf_forward_ce); None where the shape has no such kernel.  With a criterion: n times the criterion's batch loss of
+        these n patches, `criterion(output, target) * n` of the reference's validation loop (mainsolver.py:70-71), from
+        dmf_ce_loss on the logits."""
         n = xy.shape[0]
         self._check_batch(n)
+        if self.criterion is not None:
+            cr = self.criterion
+            if n == 0:
+                return torch.zeros((), dtype=torch.float64, device=self.scene.device)
+            lib.ce_loss(self.predict(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
+            return self.ce[:n].double().sum()          # loss[i] = n t_i / D
         if self.shape.attention or self._no_ce:
             return None
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)

@@ -30,6 +30,10 @@ class QuaParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ('alpha', 'beta', 'gamma', 'epsilon', 'tao')]
 
 
+class CeParams(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('label_smoothing', C.c_float), ('gamma', C.c_float)]
+
+
 class Input(C.Structure):
     _fields_ = [('mode', C.c_int32), ('B', C.c_int32), ('a', C.c_void_p), ('b', C.c_void_p), ('sceneA', C.c_void_p),
                 ('sceneB', C.c_void_p), ('xy', C.c_void_p), ('Wp', C.c_int32), ('WpB', C.c_int32), ('cursor', C.c_void_p),
@@ -85,6 +89,7 @@ def _load():
         'dmf_grad_reduce_xgmi_adam': (i32, [SP, i32, vp, vp, vp, vp, C.POINTER(XgmiComm), f32, f32, f32, f32, f32, vp, vp,
                                             vp, vp, vp]),
         'dmf_qua_loss': (i32, [vp, i32, i32, vp, vp, C.POINTER(QuaParams), f32, vp, vp, vp, vp]),
+        'dmf_ce_loss': (i32, [vp, i32, i32, i32, i32, vp, vp, vp, C.POINTER(CeParams), f32, vp, vp, vp, vp]),
         'dmf_pair_argmax': (i32, [vp, i32, i32, vp, vp]),
         'dmf_band_mean': (i32, [vp, i32, i64, i64, i32, vp, vp]),
         'dmf_confusion_accum': (i32, [vp, vp, i32, i32, vp, vp]),
@@ -420,6 +425,45 @@ def qua_loss_ranks(gathered, ranks, rank, bs_r, labels_global, params, loss=None
     check(_lib.dmf_qua_loss_ranks(_ptr(gathered), ranks, rank, bs_r, gathered.shape[1], _ptr(labels_global), _ptr(cursor),
                                   C.byref(params), grad_scale, _ptr(scaler_state), _ptr(loss), _ptr(loss_hist), _ptr(dlogits),
                                   _stream()))
+
+
+CE_KINDS = {'ce': 0, 'focal': 1}
+
+
+def ce_params(kind='ce', label_smoothing=0.0, gamma=0.0):
+    """-> CeParams (include/dmf.h: dmf_ce_params); kind 'ce' (class weights, label smoothing) or 'focal' (class weights, gamma)."""
+    if kind not in CE_KINDS:
+        raise DmfError('criterion kind %r is not one of %s' % (kind, sorted(CE_KINDS)))
+    return CeParams(kind=CE_KINDS[kind], label_smoothing=float(label_smoothing), gamma=float(gamma))
+
+
+def ce_loss(logits, ranks, rank, labels_global, params, class_w=None, loss=None, dlogits=None, grad_scale=1.0, cursor=None,
+            scaler_state=None):
+    """The weighted / smoothed cross-entropy or focal loss (dmf_ce_loss) of rank `rank`'s logits [bs_r, K] inside the GLOBAL
+    batch of ranks * bs_r samples whose labels are labels_global (at row *cursor of a plan, rank-major): loss [bs_r] <-
+    ranks * bs_r * t_i / D, dlogits [bs_r, K] <- d(batch loss) / d logits * grad_scale * scaler_state[0]."""
+    _dev(logits, torch.float32, 'logits'); _dev(labels_global, torch.int32, 'labels_global')
+    if logits.dim() != 2 or logits.shape[0] < 1:
+        raise DmfError('ce_loss wants logits [bs_r, K] with at least one row')
+    bs_r, K = logits.shape
+    if not 0 <= rank < ranks:
+        raise DmfError('ce_loss: rank %d of %d ranks' % (rank, ranks))
+    if cursor is None and labels_global.numel() < ranks * bs_r:
+        raise DmfError('ce_loss wants one label per sample of the global batch')
+    if class_w is not None:
+        _dev(class_w, torch.float32, 'class_w')
+        if class_w.numel() != K:
+            raise DmfError('class_w must hold one weight per class (%d), got %d' % (K, class_w.numel()))
+    if loss is not None:
+        _dev(loss, torch.float32, 'loss')
+        if loss.numel() < bs_r:
+            raise DmfError('loss must hold one term per row')
+    if dlogits is not None:
+        _dev(dlogits, torch.float32, 'dlogits')
+        if dlogits.shape != logits.shape:
+            raise DmfError('dlogits must have the shape of logits')
+    check(_lib.dmf_ce_loss(_ptr(logits), ranks, rank, bs_r, K, _ptr(labels_global), _ptr(cursor), _ptr(class_w),
+                           C.byref(params), grad_scale, _ptr(scaler_state), _ptr(loss), _ptr(dlogits), _stream()))
 
 
 def pair_argmax(logits, bs, pred):

@@ -15,6 +15,11 @@ Two execution paths, same arithmetic; `train()`, `test()` and `color()` choose b
 `gmf.half: 1` on the fast path: fp16 resident scene and the device loss scaler (dmf.engine.LossScaler with GradScaler's
 defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gives the switch; SGD / RMSprop are refused
 (the scaler step is ADAM), and the one-shot xgmi exchange is not used (it does not carry the scaler).
+`schedule.class_weights` (a list, or `balanced`: from the train split of each `dataloader()` call), `schedule.label_smoothing`,
+`schedule.focal_gamma` (NEW, all optional): the criterion becomes `nn.CrossEntropyLoss(weight=, label_smoothing=)` or the focal
+loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
+`dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
+then steps eagerly from Python —, no xgmi exchange, the engine shards the batches).  Keys that are all neutral change nothing.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -33,7 +38,7 @@ from PIL import Image
 from tqdm import tqdm
 
 from solver.basesolver import BaseSolver
-from utils.utils import epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
+from utils.utils import criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
 
 
 class Solver(BaseSolver):
@@ -43,7 +48,13 @@ class Solver(BaseSolver):
     engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
 
     def __init__(self, cfg):
+        keys = criterion_keys(cfg)
+        if keys and (self.engine_loss != 'Criterion' or cfg['schedule']['loss'] != 'Criterion'):
+            raise ValueError('schedule.%s belongs to schedule.loss: Criterion of Solver; %s trains with %s'
+                             % (keys[0], type(self).__name__, cfg['schedule']['loss']))
         super().__init__(cfg)
+        self.criterion = None                          # criterion_spec of the cfg, made by dataloader() (None: plain cross-entropy)
+        self.train_labels = None
         self.model = None
         self.cur_model = None
         self.train_time = 0
@@ -60,8 +71,26 @@ class Solver(BaseSolver):
         lib = importlib.import_module('model.' + self.cfg['model_name'].lower())
         self.model = lib.Net(args=self.cfg)
         self.optimizer = make_optimizer(self.cfg, self.model.parameters())
-        self.loss = make_loss(self.cfg['schedule']['loss'], self.cfg)
+        self.loss = self._make_loss()
         self.scheduler = make_scheduler(self.optimizer, self.cfg)
+
+    def _make_loss(self):
+        """schedule.loss as a torch module; `class_weights: balanced` needs the train split, so a model that is built before
+        dataloader() has run gets its criterion there."""
+        if self.cfg['schedule'].get('class_weights') == 'balanced' and self.train_labels is None:
+            return None
+        return make_loss(self.cfg['schedule']['loss'], self.cfg, self.train_labels)
+
+    def dataloader(self):
+        """BaseSolver's splits and loaders; with criterion keys in cfg['schedule'] also the criterion of this split
+        (`class_weights: balanced` is computed here, once per call, from the train split's labels: the same numbers on every
+        rank of a data-parallel run, which all draw the same split)."""
+        super().dataloader()
+        if criterion_keys(self.cfg):
+            self.train_labels = self.index_dataset.label[np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)]
+            self.criterion = criterion_spec(self.cfg, self.train_labels)
+            if self.model is not None:
+                self.loss = self._make_loss()
 
     # ------------------------------------------------------------------ helpers of the fast path
     def _bar(self, it):
@@ -93,6 +122,8 @@ class Solver(BaseSolver):
         if not self.cfg['train']['pretrained']:
             self.init_model()
         self.cur_model = self.model.to(self.DEVICE)
+        if self.criterion is not None:
+            self.loss = self.loss.to(self.DEVICE)             # (the class weights are a buffer of the module)
         if self.fast:
             self._make_engines()
         train_epoch = self._train_epoch_fast if self.fast else self._train_epoch_dropin
@@ -188,7 +219,10 @@ class Solver(BaseSolver):
 
     def _train_engine(self, batch, kw):
         from dmf.engine import TrainEngine
-        comm = self.comm if kw['optimizer'] == 'ADAM' and kw['scaler'] is None else None
+        # (the one-shot exchange carries neither the scaler nor the unit-gradient step of a criterion)
+        comm = self.comm if kw['optimizer'] == 'ADAM' and kw['scaler'] is None and self.criterion is None else None
+        if self.criterion is not None:
+            kw = dict(kw, criterion=self.criterion)
         return TrainEngine(self.cur_model, self.scene, batch, comm=comm, **kw)
 
     def _eval_engine(self):
@@ -198,18 +232,23 @@ class Solver(BaseSolver):
         (tools/eval_bench.py; identical class maps)."""
         from dmf.engine import EvalEngine
         big = 4096 if self.cur_model.arch['attention'] else 16384
-        return EvalEngine(self.cur_model, self.scene, max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], big))
+        kw = {} if self.criterion is None else {'criterion': self.criterion}
+        return EvalEngine(self.cur_model, self.scene, max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], big), **kw)
 
     def _rank_batches(self, batches):
         """The solver shards on the host: this rank's contiguous shard of every global batch (a remainder is dropped, see
-        the module text), without the empty ones."""
+        the module text), without the empty ones.  With a criterion the engine shards (its loss reads the global batch's
+        labels): global batches, a full one is batchsize, and one with no pixel for some rank is left out."""
+        if self.criterion is not None:
+            return [b for b in batches if b[0].shape[0] >= self.world], self.cfg['batchsize']
         per = [b[0].shape[0] // self.world for b in batches]
         return ([(xy[self.rank * n:(self.rank + 1) * n], lab[self.rank * n:(self.rank + 1) * n])
                  for (xy, lab), n in zip(batches, per) if n], self.cfg['batchsize'] // self.world)
 
     def _step_short(self, xy, lab):
         self.engine.step(xy.to(self.DEVICE), lab.to(self.DEVICE))
-        return float(self.engine.loss[:xy.shape[0]].mean().item())
+        rows = xy.shape[0] // self.world if self.criterion is not None else xy.shape[0]      # (a criterion: xy is the global batch)
+        return float(self.engine.loss[:rows].mean().item())
 
     # ------------------------------------------------------------------ ... and drop-in path
     def _train_epoch_dropin(self):
@@ -231,7 +270,7 @@ class Solver(BaseSolver):
         return last
 
     def _valid_pass(self, best_loss):
-        ce = torch.nn.CrossEntropyLoss()
+        ce = self.loss if self.criterion is not None else torch.nn.CrossEntropyLoss()
         with torch.no_grad():
             if self.fast:
                 # The reference adds `loss.item() * n` per batch and stops once the sum passes best_loss (mainsolver.py:65-75):

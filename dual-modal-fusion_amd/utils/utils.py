@@ -73,8 +73,95 @@ def make_optimizer(cfg, params):
     return _pick(_OPTIMIZERS, cfg['schedule']['optimizer'], 'optimizer')(cfg['schedule'], params)
 
 
-def make_loss(loss_type, cfg):
-    return _pick(_LOSSES, loss_type, 'loss')()
+CRITERION_KEYS = ('class_weights', 'label_smoothing', 'focal_gamma')      # optional keys of cfg['schedule'] (NEW)
+
+
+def criterion_keys(cfg):
+    """The criterion keys that cfg['schedule'] states."""
+    return [k for k in CRITERION_KEYS if k in (cfg.get('schedule') or {})]
+
+
+def balanced_weights(labels, K):
+    """`class_weights: balanced`: w_c = n / (n_present * n_c) for the classes present among `labels` (n of them, n_present
+    distinct), 1 for the absent ones."""
+    counts = np.bincount(np.asarray(labels).reshape(-1).astype(np.int64), minlength=K)[:K].astype(np.float64)
+    present = counts > 0
+    w = np.ones(K)
+    w[present] = counts.sum() / (present.sum() * counts[present])
+    return w.tolist()
+
+
+def criterion_spec(cfg, train_labels=None):
+    """cfg['schedule'] -> dict(kind, label_smoothing, gamma, class_weights) as dmf.engine.Criterion and `criterion_module` take
+    it, or None when none of the keys is stated or every stated one has its neutral value (`class_weights: null`, 0, 0): then
+    everything stays the plain cross-entropy and the fused step.  train_labels: the train
+    split's labels, which `class_weights: balanced` is computed from."""
+    if not criterion_keys(cfg):
+        return None
+    s, K = cfg['schedule'], int(cfg['Categories_Number'])
+    eps, gamma = float(s.get('label_smoothing') or 0.0), float(s.get('focal_gamma') or 0.0)
+    if eps != 0.0 and gamma != 0.0:
+        raise ValueError('schedule.focal_gamma and schedule.label_smoothing cannot both be non-zero (got %g and %g)' % (gamma, eps))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError('schedule.label_smoothing %g is not in [0, 1)' % eps)
+    if not (gamma == 0.0 or (gamma >= 1.0 and np.isfinite(gamma))):
+        raise ValueError('schedule.focal_gamma %g is neither 0 nor >= 1' % gamma)
+    w = s.get('class_weights')
+    if isinstance(w, str):
+        if w != 'balanced':
+            raise ValueError('schedule.class_weights: %r is neither a list of %d floats nor balanced' % (w, K))
+        if train_labels is None:
+            raise ValueError('schedule.class_weights: balanced is computed from the train split, which does not exist yet')
+        w = balanced_weights(train_labels, K)
+    elif w is not None:
+        w = [float(x) for x in w]
+        if len(w) != K:
+            raise ValueError('schedule.class_weights holds %d weights for Categories_Number %d' % (len(w), K))
+    if w is not None and not all(np.isfinite(x) and x > 0 for x in w):
+        raise ValueError('schedule.class_weights must be finite and > 0, got %s' % w)
+    if w is None and eps == 0.0 and gamma == 0.0:
+        return None                # every key at its neutral value: the plain cross-entropy, which the fused step trains
+    return {'kind': 'focal' if gamma != 0.0 else 'ce', 'label_smoothing': eps, 'gamma': gamma, 'class_weights': w}
+
+
+class FocalLoss(nn.Module):
+    """sum_i w[y_i] (1 - p_i)^gamma (-log p_i) / sum_i w[y_i], p_i = softmax(output_i)[y_i]: the focal loss with class weights,
+    averaged like nn.CrossEntropyLoss(weight=w) (gamma = 0 is that loss).  1 - p_i is formed as the sum of the other classes'
+    probabilities, which stays accurate when p_i -> 1."""
+
+    def __init__(self, gamma, weight=None):
+        super().__init__()
+        self.gamma = float(gamma)
+        self.register_buffer('weight', weight)
+
+    def forward(self, output, target):
+        logp = torch.log_softmax(output, dim=1)
+        hit = torch.zeros_like(logp, dtype=torch.bool).scatter_(1, target.view(-1, 1), True)
+        q = logp.exp().masked_fill(hit, 0.0).sum(1)
+        w = self.weight[target] if self.weight is not None else torch.ones_like(q)
+        nlp = -logp.gather(1, target.view(-1, 1)).squeeze(1)
+        return (w * q.pow(self.gamma) * nlp).sum() / w.sum()
+
+
+def criterion_module(spec):
+    """The torch module of a criterion_spec: nn.CrossEntropyLoss(weight=, label_smoothing=) or FocalLoss."""
+    w = None if spec['class_weights'] is None else torch.tensor(spec['class_weights'], dtype=torch.float32)
+    if spec['kind'] == 'focal':
+        return FocalLoss(spec['gamma'], w)
+    return nn.CrossEntropyLoss(weight=w, label_smoothing=spec['label_smoothing'])
+
+
+def make_loss(loss_type, cfg, train_labels=None):
+    """schedule.loss as a torch module.  `Criterion` with criterion keys in cfg['schedule'] (class_weights, label_smoothing,
+    focal_gamma): criterion_module(criterion_spec(cfg, train_labels)); no other loss takes those keys."""
+    make = _pick(_LOSSES, loss_type, 'loss')
+    if criterion_keys(cfg):
+        if loss_type != 'Criterion':
+            raise ValueError('schedule.%s belongs to schedule.loss: Criterion, not %s' % (criterion_keys(cfg)[0], loss_type))
+        spec = criterion_spec(cfg, train_labels)
+        if spec is not None:
+            return criterion_module(spec)
+    return make()
 
 
 def make_scheduler(optimizer, cfg):

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 302   /* 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 303   /* 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -144,6 +144,29 @@ int32_t dmf_forward_unit(const dmf_shape* shape, const dmf_input* in, const floa
                          float* logits, void* workspace, int32_t* adam_step_dev, void* stream);
 int32_t dmf_backward_unit(const dmf_shape* shape, int32_t B, const float* theta, const float* dlogits, void* workspace,
                           void* stream);
+
+/* The loss kernel of that step for classification with class weights, label smoothing or a focal term — the criteria the
+ * patch kernel's fused cross-entropy does not state (`nn.CrossEntropyLoss(weight=, label_smoothing=)`, utils/utils.py:29).
+ * With p = softmax(logits[i]), y = the sample's label and w = class_w (NULL: all ones), the per-sample term is
+ *   kind 0   t_i = (1 - eps) w[y] (-log p_y) + (eps / K) sum_c w[c] (-log p_c)
+ *   kind 1   t_i = w[y] (1 - p_y)^gamma (-log p_y)                                    (gamma = 0: kind 0 with eps = 0)
+ * and the batch loss is sum_i t_i / D, D = sum_j w[y_j] over the GLOBAL batch of ranks * bs_r samples — torch's
+ * reduction='mean' (the smoothing term is not part of the denominator).  logits [bs_r, K] are rank `rank`'s rows; the global
+ * batch's labels are labels_global[(*cursor) * ranks * bs_r + r * bs_r + i] (rank-major as in dmf_qua_loss_ranks; cursor may be
+ * NULL).  loss [bs_r] (may be NULL) gets ranks * bs_r * t_i / D: its mean over the rows, averaged over the ranks, is the batch
+ * loss (what dmf_grad_reduce* put into loss_hist).  dlogits [bs_r, K] (NULL: value only, the validation pass) gets
+ * d(batch loss)/d logits times grad_scale * (scaler_state ? scaler_state[0] : 1).  One launch, no collective: every rank
+ * computes the same D from the labels, and its rows are bit-identical to those of a one-rank call on the whole batch.
+ * Fails unless 1 <= K <= DMF_KMAX, eps in [0, 1), gamma == 0 or gamma >= 1, kind 0 or 1.  Every w must be > 0. */
+typedef struct dmf_ce_params {
+  int32_t kind;             /* 0 cross-entropy (weights and label smoothing apply), 1 focal (weights and gamma apply) */
+  float   label_smoothing;  /* eps in [0, 1), kind 0 */
+  float   gamma;            /* kind 1: 0 or >= 1 */
+} dmf_ce_params;
+int32_t dmf_ce_loss(const float* logits, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,
+                    const int32_t* labels_global, const int32_t* cursor, const float* class_w,
+                    const dmf_ce_params* params, float grad_scale, const float* scaler_state,
+                    float* loss, float* dlogits, void* stream);
 
 /* 0 if the fp16-scene kernels (dmf_input.half) exist for this shape. */
 int32_t dmf_half_supported(const dmf_shape* shape);

@@ -17,7 +17,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ('dmf_patch_v2.hip', 'dmf_attention.hip', 'dmf_qua.hip', 'dmf_loss.hip', 'dmf_scene.hip', 'dmf_capi.hip')
+NAMES = ('dmf_patch_v2.hip', 'dmf_attention.hip', 'dmf_qua.hip', 'dmf_loss.hip', 'dmf_scene.hip', 'dmf_reduce.hip', 'dmf_capi.hip')
 SRC = [os.path.join(HERE, 'csrc', n) for n in NAMES]
 HDR = [os.path.join(HERE, 'csrc', n) for n in ('dmf_shapes.h', 'dmf_kargs.h', 'dmf_lanes.h', 'dmf_xgmi.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'dmf.h')]
 OUT = os.path.join(HERE, 'dmf', 'libdmf_hip.so')
@@ -26,7 +26,7 @@ OBJ = os.path.join(HERE, 'build')
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function', '-Wno-pass-failed']
 # per-file extras: the reduce launch and the v2 patch kernel take their hot scalars as leading kernel arguments and have
 # them preloaded into SGPRs at wave launch (see grad_reduce_kernel, patch_v2_kernel)
-EXTRA = {'dmf_capi.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=14'], 'dmf_patch_v2.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=14']}
+EXTRA = {'dmf_reduce.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=14'], 'dmf_patch_v2.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=14']}
 
 
 def extra_shapes(path):

@@ -1,5 +1,5 @@
 // Kernel argument blocks and internal entry points shared by the translation units of libdmf_hip.so.
-// ONE definition each: dmf_capi.hip fills these structs, the kernel files read them.
+// ONE definition each: dmf_capi.hip fills these structs and calls the launchers, the kernel files define both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +8,7 @@
 
 #include "../../include/dmf.h"
 #include "dmf_shapes.h"
+#include "dmf_xgmi.h"
 
 namespace dmf {
 
@@ -99,6 +100,40 @@ hipError_t attn_train_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int g
 hipError_t attn_forward_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st);
 int attn_shape_supported(const dmf_shape& s);
 
+// ------------------------------------------------------------------------------ gradient reduction (+Adam)
+//   conv params  : grad[p] = sum_blk slab[blk][p]
+//   fc1.weight   : grad = sum_b dh[b][j] * z[b][i]      fc1.bias: sum_b dh[b][j]
+//   fc2.weight   : grad = sum_b dl[b][k] * h[b][j]      fc2.bias: sum_b dl[b][k]
+// (the conv slabs and head vectors z / h / dh / dl reach the kernel as leading scalar arguments: launch_grad_reduce)
+struct ReduceArgs {
+  int B, NCONV, F2, H, K;
+  int64_t oFc1w, oFc1b, oFc2w, oFc2b;
+  float* grad;
+  float* theta; float* m; float* v;   // Adam (theta == nullptr: reduce only)
+  float lr, b1, b2, eps, bc1, bc2_sqrt;
+  const int32_t* step_dev;            // optional device-side step count (overrides bc1 / bc2_sqrt)
+  int32_t* cursor_dev;                // optional epoch-plan cursor to advance
+  const float* loss; float* loss_hist;
+  const float* aslab; int nablk, ASLAB; int64_t oAttn;   // attention weights: sum of the attention kernel's slabs
+  XgmiDev x;                          // x.world > 1: exchange the gradient with the peer ranks before Adam
+  float grad_scale; int seq_bias;
+  float* scaler;                      // loss-scaler state (dmf_grad_reduce_scaled): grad <- sum / scaler[0], non-finite -> scaler[2]
+};
+// dmf_reduce.hip.  launch_grad_reduce carves the head vectors and conv slabs out of the workspace `ws` itself; a geometry
+// its block packing cannot hold is refused with hipErrorInvalidValue and *refusal set to the reason (else null).
+hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal);
+hipError_t launch_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                       float bc1, float bc2_sqrt, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, hipStream_t st);
+hipError_t launch_sgd(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum, float grad_scale,
+                      const int32_t* step_dev, int32_t step, int32_t* cursor_dev, hipStream_t st);
+hipError_t launch_rmsprop(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha, float eps,
+                          float grad_scale, int32_t* cursor_dev, hipStream_t st);
+hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st);
+hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                               float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
+                               int32_t* cursor_dev, hipStream_t st);
+hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
+
 // stage-2 kernels (dmf_qua.hip)
 struct QuaArgs {
   const float* logits; int bs, K;
@@ -114,6 +149,8 @@ struct QuaArgs {
 hipError_t launch_qua_loss(const QuaArgs& a, hipStream_t st);
 hipError_t launch_pair_argmax(const float* logits, int bs, int K, int32_t* pred, hipStream_t st);
 hipError_t launch_band_mean(const float* x, int layout, int64_t n_img, int64_t n_pix, int C, float* out, hipStream_t st);
+hipError_t launch_confusion(const int32_t* pred, const int32_t* target, int B, int K, unsigned long long* matrix, hipStream_t st);
+hipError_t launch_labelmap(const int32_t* pred, const int32_t* xy, int B, int W, int32_t* map, hipStream_t st);
 
 // per-sample classification losses of the unit-gradient step (dmf_loss.hip)
 struct CeArgs {
@@ -140,10 +177,12 @@ struct ScenePrepArgs {
 int scene_raw_bytes(int dtype);      // element size of a DMF_RAW_* code, 0 for an unknown one
 hipError_t launch_scene_minmax(const void* raw, int dtype, int64_t n, void* minmax, hipStream_t st);
 hipError_t launch_scene_prepare(const ScenePrepArgs& a, int dtype, int half, hipStream_t st);
+hipError_t launch_pan2ms(const double* pan, int pitch, int H, int W, double* out, hipStream_t st);
 
 #ifdef DMF_STAMPS
 hipError_t set_attn_stamps(unsigned long long* p);
 hipError_t set_v2_stamps(unsigned long long* p);
+hipError_t set_reduce_stamps(unsigned long long* p);
 #endif
 
 }  // namespace dmf

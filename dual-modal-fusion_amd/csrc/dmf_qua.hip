@@ -3,6 +3,7 @@
 //                       stacked streams [4*bs, K]
 //   pair_argmax_kernel: `(output[:bs] + output[bs:2*bs]).softmax(-1).max(1)` (tostagesolver.py:337,366,378)
 //   band_mean_kernel  : per-pixel mean over bands, the auxiliary input of the single-stream net (oracle/gmfnet_ref.py)
+//   confusion_kernel / labelmap_kernel: the evaluation's confusion matrix and label map, filled on the device
 //
 // The loss couples all samples of a batch through six batch-mean KL terms, the sign of two of their differences and
 // a mean over all probabilities, so it cannot live inside the per-patch kernel.  It is tiny (4*bs*K logits), so one
@@ -493,6 +494,31 @@ __global__ __launch_bounds__(256) void band_mean_kernel(const float* x, int layo
 hipError_t launch_band_mean(const float* x, int layout, int64_t n_img, int64_t n_pix, int C, float* out, hipStream_t st) {
   hipLaunchKernelGGL(band_mean_kernel, dim3((unsigned)((n_img * n_pix + 255) / 256)), dim3(256), 0, st, x, layout, n_img,
                      n_pix, C, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ eval helpers
+__global__ __launch_bounds__(256) void confusion_kernel(const int32_t* pred, const int32_t* target, int B, int K,
+                                                        unsigned long long* matrix) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < B) {
+    const int p = pred[i], t = target[i];
+    if (p >= 0 && p < K && t >= 0 && t < K) atomicAdd(&matrix[(size_t)p * K + t], 1ull);   // rows = prediction
+  }
+}
+
+__global__ __launch_bounds__(256) void labelmap_kernel(const int32_t* pred, const int32_t* xy, int B, int W, int32_t* map) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < B) map[(size_t)xy[2 * i] * W + xy[2 * i + 1]] = pred[i];
+}
+
+hipError_t launch_confusion(const int32_t* pred, const int32_t* target, int B, int K, unsigned long long* matrix, hipStream_t st) {
+  hipLaunchKernelGGL(confusion_kernel, dim3((B + 255) / 256), dim3(256), 0, st, pred, target, B, K, matrix);
+  return hipGetLastError();
+}
+
+hipError_t launch_labelmap(const int32_t* pred, const int32_t* xy, int B, int W, int32_t* map, hipStream_t st) {
+  hipLaunchKernelGGL(labelmap_kernel, dim3((B + 255) / 256), dim3(256), 0, st, pred, xy, B, W, map);
   return hipGetLastError();
 }
 

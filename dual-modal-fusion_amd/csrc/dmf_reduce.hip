@@ -1,0 +1,506 @@
+// dmf_reduce.hip — the batch-level launches behind the patch and attention kernels: the slab / outer-product gradient
+// reduction with its fused Adam (grad_reduce_kernel), the stand-alone optimiser kernels (Adam, SGD, RMSprop), the loss-scaler
+// pair and the small xgmi all-reduce.  dmf_capi.hip validates and calls the launch_* functions at the end of this file.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "dmf_kargs.h"
+#include "dmf_lanes.h"
+#include "dmf_xgmi.h"
+
+namespace dmf {
+
+// bias corrections from a device-resident step count, in double like torch's host-side scalars
+__device__ __forceinline__ void bias_corrections(int step, float b1, float b2, float& bc1, float& bc2_sqrt) {
+  bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
+}
+
+__device__ __forceinline__ void adam_update(float* theta, float* m, float* v, int64_t p, float g,
+                                            float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt) {
+  // torch.optim.Adam single-tensor path: exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
+  // denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m / denom
+  const float mo = m[p], vo = v[p];
+  const float mn = mo + (g - mo) * (1.f - b1);
+  const float vn = vo * b2 + (1.f - b2) * g * g;
+  m[p] = mn;
+  v[p] = vn;
+  const float denom = sqrtf(vn) / bc2_sqrt + eps;
+  theta[p] -= (lr / bc1) * (mn / denom);
+}
+
+// ---- the reduce launch.  What bounds it (tools/reduce_phase_profile.py, stamps of round 3): ONE CU takes in only ~15 bytes
+// per clock from the Infinity Cache (about 64 lines in flight x ~550 cycles), and the 2.2 MB the patch kernel left behind are
+// nowhere else.  The first forms (16 or 64 parameters per block, 64-byte pieces of 7-KB rows, 64 KB fetched per block) spent
+// 4.5 K of their 6.8 K cycles waiting for that; so the producers now lay their results out for THIS kernel (dmf_shapes.h):
+//   * conv slabs piece-major: one block per 16 parameters reads rows x 64 contiguous bytes (16 KB at batch 256) — a lane
+//     holds one 16-byte piece of up to 4 rows, rows are summed per lane, then over the 16 row lanes by DPP and the row /
+//     half swaps, then over the 4 waves through LDS: a fixed order;
+//   * fc1.weight / fc2.weight = dh^T z / dl^T h: one 8x8 output tile per block — 2 x 8 KB of contiguous strip-major head
+//     vectors at batch 256 (a 16x16 tile needs 2 x 16 KB: twice the wait).  It still runs on the fp32 matrix cores
+//     (v_mfma_f32_16x16x4_f32: bit for bit a k-ordered fmaf chain) with the two HALVES of the batch packed into one
+//     instruction: rows 0-7 / columns 0-7 carry the first half, rows 8-15 / columns 8-15 the second, the two diagonal 8x8
+//     blocks of the result are the two partial tiles (the off-diagonal blocks are discarded); wave w carries a quarter of each
+//     half in two accumulators.  The tiles of the first column also sum their dh / dl strip: fc1.bias / fc2.bias;
+//   * attention slabs keep the row-major form (64 parameters per block): 15.7 MB per step, bound by the chip, not the CU;
+//   * ADAM's bias corrections: b^step by repeated squaring in double on two lanes of a fifth wave (beta1 / beta2 side by
+//     side) beside the gradient loads, instead of two calls of the general pow() on one lane in front of the barrier.
+// Block order: fc tiles first (the longest chains), then slabs, the bookkeeping block last.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ double powi_double(double b, int n) {   // b^n, n >= 0, by squaring (relative error ~ 2 log2(n) ulp)
+  double r = 1.0;
+  while (n > 0) {
+    if (n & 1) r *= b;
+    b *= b;
+    n >>= 1;
+  }
+  return r;
+}
+
+// the fixed combine of 16 chunk partials ((0+8)+(4+12)) + ... (attention slabs)
+__device__ __forceinline__ float tree16(float (&t)[16]) {
+#pragma unroll
+  for (int w = 8; w > 0; w >>= 1)
+#pragma unroll
+    for (int i = 0; i < w; ++i) t[i] += t[i + w];
+  return t[0];
+}
+
+// One 8 x 8 tile of out[m][n] = sum_b U[b][m0 + m] * W[b][n0 + n] (U, W strip-major: hv_index; m0, n0 multiples of 8).
+// MFMA row / column q < 8 works on the patches [0, Bh), q >= 8 on [Bh, B); wave w takes a quarter of each half's k-steps (4
+// patches each), 8 steps per batch.  issue(): the 16 loads of one batch; consume(): its 8 MFMAs (two accumulators) and the
+// running sum of the U operand (the bias gradient).  Rows >= mlim read as zero.  Threads 0..255.
+struct FcTile {
+  const float* up; const float* wp;
+  int bbase, blim, kk, s1, sb_;
+  bool mok;
+  f32x4_t acc0, acc1;
+  float bs;
+  float av[8], bv[8];
+  __device__ __forceinline__ int init(const float* U, int m0, int mlim, const float* W, int n0, int B) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int q8 = lane & 7, half = (lane >> 3) & 1;
+    kk = lane >> 4;
+    mok = m0 + q8 < mlim;
+    const int Bh = (((B + 1) >> 1) + 3) & ~3;                 // first half: a multiple of 4 patches
+    bbase = half ? Bh : 0; blim = half ? B : min(Bh, B);
+    up = U + (size_t)(m0 >> 3) * B * 8 + q8;                  // strip m0 / 8: element (b, m) at b * 8 + m
+    wp = W + (size_t)(n0 >> 3) * B * 8 + q8;
+    const int nk = Bh / 4, nkw = (nk + 3) / 4;                // k-steps per half: all, per wave
+    const int s0 = w * nkw;
+    s1 = min(nk, s0 + nkw);
+    acc0 = (f32x4_t){0.f, 0.f, 0.f, 0.f}; acc1 = acc0; bs = 0.f;
+    return s0;
+  }
+  // (loads are UNCONDITIONAL, from a clamped patch index, and masked in consume(): a load under a lane condition becomes a
+  // branch around it, and the compiler then waits for the loads of one branch before it enters the next)
+  __device__ __forceinline__ void issue(int sb) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int b = min(bbase + 4 * (sb + q) + kk, blim - 1);
+      av[q] = up[(size_t)(b < 0 ? 0 : b) * 8];
+      bv[q] = wp[(size_t)(b < 0 ? 0 : b) * 8];
+    }
+    sb_ = sb;
+  }
+  __device__ __forceinline__ void consume() {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const bool in = sb_ + q < s1 && bbase + 4 * (sb_ + q) + kk < blim;
+      av[q] = (in && mok) ? av[q] : 0.f;
+      bv[q] = in ? bv[q] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q += 2) {
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q + 1], bv[q + 1], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) bs += av[q];
+  }
+};
+
+// (adam_update's arithmetic, stated again on purpose: through a shared helper the reduce kernel gets another register
+// allocation and six more instructions)
+__device__ __forceinline__ void adam_apply(const ReduceArgs& a, int64_t p, float g, float th0, float m_0, float v_0, const float* bcs) {
+  if (a.scaler != nullptr) {                         // unscale_ + the found_inf check of GradScaler, in the reduce
+    g *= 1.f / a.scaler[0];
+    if (!isfinite(g)) a.scaler[2] = 1.f;             // (every writer stores the same value)
+  }
+  if (a.grad != nullptr) a.grad[p] = g;
+  if (a.theta != nullptr) {
+    const float mn = m_0 + (g - m_0) * (1.f - a.b1);
+    const float vn = v_0 * a.b2 + (1.f - a.b2) * g * g;
+    a.m[p] = mn;
+    a.v[p] = vn;
+    a.theta[p] = th0 - (a.lr / bcs[0]) * (mn / (sqrtf(vn) / bcs[1] + a.eps));
+  }
+}
+
+// Diagnostic build only (-DDMF_STAMPS, tools/reduce_phase_profile.py): clock stamps of every wave of the reduce launch in
+// scalar registers, dumped by lane 0 right before the wave ends.  [block][5 waves][8]: 0 entry, 2 kernel arguments in registers, 1 role known, 3 partials
+// written (loads landed), 4 behind the barrier, 5 stores issued, 6 end; 7 s_memrealtime at entry.
+#ifdef DMF_STAMPS
+__device__ unsigned long long* g_rstamps = nullptr;
+#define RSTAMP_DECL unsigned long long rst_[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}
+#define RSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rst_[i]) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define RSTAMP_RT(i) do { asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rst_[i])); } while (0)
+#define RSTAMP_DUMP() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); RSTAMP(6); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+    if ((threadIdx.x & 63) == 0 && g_rstamps != nullptr) { _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) \
+      g_rstamps[((size_t)blockIdx.x * 5 + (threadIdx.x >> 6)) * 8 + i_] = rst_[i_]; } } while (0)
+#else
+#define RSTAMP_DECL do { } while (0)
+#define RSTAMP(i) do { } while (0)
+#define RSTAMP_RT(i) do { } while (0)
+#define RSTAMP_DUMP() do { } while (0)
+#endif
+
+// 320 threads: waves 0-3 reduce, wave 4 only forms ADAM's bias corrections (beside the other waves' gradient loads).
+// The first nine arguments are everything a block needs to find its role and ISSUE its gradient loads; they are plain scalars
+// in front of the argument struct so that the compiler's kernarg preload (-mllvm -amdgpu-kernarg-preload-count, build.py) puts
+// them into scalar registers at wave launch: a kernel argument fetched by the wave itself arrives ~1.0 K cycles after wave
+// entry (stamps), and every load of this kernel was waiting behind that.  w0 = nFc1 | t1n << 16, w1 = nFc2 | t2n << 16,
+// w2 = nConv | nAttn << 16 (blocks per kind, tiles per row).
+__global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ dh,
+                                                          const float* __restrict__ z, const float* __restrict__ dl,
+                                                          const float* __restrict__ h, int w0, int w1, int w2, int B, const ReduceArgs a) {
+  __shared__ float vbuf[4][256];        // tile partials of the four waves / [16 chunks][64] attention-slab partials / [4][16] piece partials
+  __shared__ float bbuf[4][16];         // bias partials of the four waves
+  __shared__ float bcs[2];
+  const int tid = threadIdx.x;
+  int blk = blockIdx.x;
+  RSTAMP_DECL;
+  RSTAMP_RT(7);
+  RSTAMP(0);
+  const int nFc1 = w0 & 0xffff, t1n = w0 >> 16, nFc2 = w1 & 0xffff, t2n = w1 >> 16, nConv = w2 & 0xffff, nAttn = w2 >> 16;
+  const int nTotal = nFc1 + nFc2 + nConv + nAttn + 1;
+  const int nblk = B < MAX_BLOCKS ? B : MAX_BLOCKS;  // slab rows: the patch kernel's grid
+  if (blk == nTotal - 1) {                           // bookkeeping block
+    const int cur = a.cursor_dev != nullptr ? *a.cursor_dev : 0;
+    if (a.loss != nullptr && a.loss_hist != nullptr) {
+      float s = 0.f;
+      float* red = &vbuf[0][0];
+      if (tid < 256) {
+        for (int b = tid; b < a.B; b += 256) s += a.loss[b];
+        red[tid] = s;
+      }
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+      }
+      if (tid == 0) a.loss_hist[cur] = red[0] / (float)a.B;
+    }
+    if (tid == 0 && a.cursor_dev != nullptr) *a.cursor_dev = cur + 1;
+    return;
+  }
+  int kind, sub;                                     // 0 fc1.weight tile, 1 fc2.weight tile, 2 conv slab piece, 3 attention slab
+  if (blk < nFc1) { kind = 0; sub = blk; }
+  else if ((blk -= nFc1) < nFc2) { kind = 1; sub = blk; }
+  else if ((blk -= nFc2) < nConv) { kind = 2; sub = blk; }
+  else { kind = 3; sub = blk - nConv; }
+  // ---- the first batch of gradient loads goes out before anything else is looked at
+  int m0 = 0, n0 = 0;
+  FcTile ft;
+  int sb = 0;
+  float4 cv[4];
+  const int lane = tid & 63, wv = tid >> 6, c4 = lane & 3, r16 = lane >> 2;
+  const float* csrc = slab + (size_t)sub * nblk * 16 + 4 * c4;       // conv piece `sub` of every row: rows x 16 floats, contiguous
+  if (kind < 2) {
+    const int tn = kind == 0 ? t1n : t2n;
+    const int mt = (int)((float)sub / (float)tn + 0.01f);            // (exact for the few hundred tiles there are)
+    m0 = 8 * mt; n0 = 8 * (sub - mt * tn);
+    if (tid < 256) {
+      sb = kind == 0 ? ft.init(dh, m0, a.H, z, n0, B) : ft.init(dl, m0, a.K, h, n0, B);
+      ft.issue(sb);
+    }
+  } else if (kind == 2 && tid < 256) {
+    // lane = (16-byte quarter c4, row lane r16); wave wv, load i: rows (4 i + wv) * 16 + r16 — every wave-level load is 1 KiB
+    // of contiguous bytes
+#pragma unroll
+    for (int i = 0; i < 4; ++i)                          // (unconditional, clamped row; masked where they are summed)
+      cv[i] = *reinterpret_cast<const float4*>(csrc + (size_t)min((4 * i + wv) * 16 + r16, nblk - 1) * 16);
+  }
+  __builtin_amdgcn_sched_barrier(0);                 // (nothing that waits for these loads may move up here)
+  RSTAMP(2);
+  // ---- which parameter(s) this thread finishes (p, own; p2, own2: the bias of a first-column tile), and their ADAM state
+  int64_t p = 0, p2 = 0;
+  bool own = false, own2 = false;
+  if (kind == 0) {
+    const int j = m0 + ((tid >> 3) & 7), i = n0 + (tid & 7);
+    own = tid < 64 && j < a.H && i < a.F2;
+    p = a.oFc1w + (int64_t)j * a.F2 + i;
+    own2 = n0 == 0 && tid < 8 && m0 + tid < a.H;
+    p2 = a.oFc1b + m0 + tid;
+  } else if (kind == 1) {
+    const int k = m0 + ((tid >> 3) & 7), j = n0 + (tid & 7);
+    own = tid < 64 && k < a.K && j < a.H;
+    p = a.oFc2w + (int64_t)k * a.H + j;
+    own2 = n0 == 0 && tid < 8 && m0 + tid < a.K;
+    p2 = a.oFc2b + m0 + tid;
+  } else if (kind == 2) {
+    p = (int64_t)16 * sub + tid;
+    own = tid < 16 && p < a.NCONV;
+  } else {
+    p = a.oAttn + (int64_t)64 * sub + tid;
+    own = tid < 64 && 64 * sub + tid < a.ASLAB;
+  }
+  RSTAMP(1);
+  float th0 = 0.f, m_0 = 0.f, v_0 = 0.f, th2 = 0.f, m_2 = 0.f, v_2 = 0.f;
+  if (a.theta != nullptr) {
+    if (own) { th0 = a.theta[p]; m_0 = a.m[p]; v_0 = a.v[p]; }
+    if (own2) { th2 = a.theta[p2]; m_2 = a.m[p2]; v_2 = a.v[p2]; }
+  }
+  float* part = &vbuf[0][0];
+  if (tid >= 256) {
+    // bias corrections (lanes 0 / 1 of wave 4: beta1 / beta2 side by side), b^step by repeated squaring in double
+    if (a.theta != nullptr && tid < 258) {
+      float bc = tid == 256 ? a.bc1 : a.bc2_sqrt;
+      if (a.step_dev != nullptr) {
+        const double pw = powi_double((double)(tid == 256 ? a.b1 : a.b2), *a.step_dev);
+        bc = tid == 256 ? (float)(1.0 - pw) : (float)sqrt(1.0 - pw);
+      }
+      bcs[tid - 256] = bc;
+    }
+  } else if (kind < 2) {
+    ft.consume();
+    for (sb += 8; sb < ft.s1; sb += 8) { ft.issue(sb); ft.consume(); }
+    const f32x4_t v = ft.acc0 + ft.acc1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) vbuf[wv][(4 * ft.kk + r) * 16 + (lane & 15)] = v[r];   // C layout: row 4 (lane >> 4) + r, column lane & 15
+    const float bias = swap_add32(swap_add16(ft.bs));                                  // over the four k lanes of a row
+    if (lane < 16) bbuf[wv][lane] = bias;                                              // [wave][half * 8 + row]
+  } else if (kind == 2) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i0 = 0;;) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool in = (4 * (i0 + i) + wv) * 16 + r16 < nblk;
+        acc.x += in ? cv[i].x : 0.f; acc.y += in ? cv[i].y : 0.f; acc.z += in ? cv[i].z : 0.f; acc.w += in ? cv[i].w : 0.f;
+      }
+      i0 += 4;
+      if ((4 * i0 + wv) * 16 >= nblk) break;                           // (more than 256 rows: not with today's MAX_BLOCKS)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        cv[i] = *reinterpret_cast<const float4*>(csrc + (size_t)min((4 * (i0 + i) + wv) * 16 + r16, nblk - 1) * 16);
+    }
+    // over the 16 row lanes (lane bits 2..5): xor 4 / xor 8 inside a 16-lane row by row rotations, then the row / half swaps
+    float e[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float x = e[k];
+      x = DMF_DPP_ADD(x, 0x124);     // row_ror:4
+      x = DMF_DPP_ADD(x, 0x128);     // row_ror:8
+      e[k] = swap_add32(swap_add16(x));
+    }
+    if (lane < 4) *reinterpret_cast<float4*>(part + wv * 16 + 4 * c4) = make_float4(e[0], e[1], e[2], e[3]);
+  } else {
+    const int pitch = a.ASLAB, nb = a.nablk;
+    const int q4 = tid & 15, ch = tid >> 4;
+    const bool in_row = 64 * sub + 4 * q4 < pitch;
+    const float* sl = a.aslab + 64 * sub + 4 * q4;
+    const int per = (nb + 15) / 16;
+    const int lo = ch * per, hi = min(nb, lo + per);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int b0 = lo; b0 < hi; b0 += 16) {
+      float4 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        v[i] = (in_row && b0 + i < hi) ? *reinterpret_cast<const float4*>(sl + (size_t)(b0 + i) * pitch) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { acc.x += v[i].x; acc.y += v[i].y; acc.z += v[i].z; acc.w += v[i].w; }
+    }
+    *reinterpret_cast<float4*>(part + ch * 64 + 4 * q4) = acc;          // [16 chunks][64]
+  }
+  RSTAMP(3);
+  __syncthreads();
+  RSTAMP(4);
+  float g = 0.f, g2 = 0.f;
+  if (tid < 256) {
+    if (kind < 2) {
+      if (tid < 64) {                                  // the two diagonal blocks of every wave's result, in wave order
+        const int e0 = (tid >> 3) * 16 + (tid & 7), e1 = e0 + 8 * 16 + 8;
+        g = ((vbuf[0][e0] + vbuf[0][e1]) + (vbuf[1][e0] + vbuf[1][e1])) + ((vbuf[2][e0] + vbuf[2][e1]) + (vbuf[3][e0] + vbuf[3][e1]));
+      }
+      if (tid < 8) g2 = ((bbuf[0][tid] + bbuf[0][8 + tid]) + (bbuf[1][tid] + bbuf[1][8 + tid])) +
+                        ((bbuf[2][tid] + bbuf[2][8 + tid]) + (bbuf[3][tid] + bbuf[3][8 + tid]));
+    } else if (kind == 2) {
+      if (tid < 16) g = (part[tid] + part[16 + tid]) + (part[32 + tid] + part[48 + tid]);
+    } else if (tid < 64) {
+      float t[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) t[i] = part[i * 64 + tid];
+      g = tree16(t);
+    }
+  }
+  if (a.x.world > 1) {                               // (the owning lanes exchange; no barriers inside)
+    const int seq = *a.step_dev + a.seq_bias;
+    g = xgmi_exchange(a.x, 0, seq, p, own, g) * a.grad_scale;
+    if (kind < 2 && n0 == 0) g2 = xgmi_exchange(a.x, 0, seq, p2, own2, g2) * a.grad_scale;
+  }
+  if (own) adam_apply(a, p, g, th0, m_0, v_0, bcs);
+  if (own2) adam_apply(a, p2, g2, th2, m_2, v_2, bcs);
+  RSTAMP(5);
+  RSTAMP_DUMP();
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* theta, const float* grad, float* m, float* v, int64_t n,
+                                                   float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                                   float grad_scale, const int32_t* step_dev, int32_t* cursor_dev) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (step_dev != nullptr) bias_corrections(*step_dev, b1, b2, bc1, bc2_sqrt);
+  if (p < n) adam_update(theta, m, v, p, grad[p] * grad_scale, lr, b1, b2, eps, bc1, bc2_sqrt);
+  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
+}
+
+// ------------------------------------------------------------------------------ the reference's other two optimisers
+// torch.optim.SGD(lr, momentum) (dampening 0, no Nesterov, no weight decay): buf = g on the first step, else m buf + g;
+// p -= lr buf.  torch.optim.RMSprop(lr, alpha) (eps 1e-8, momentum 0, not centred): sq = alpha sq + (1 - alpha) g g;
+// p -= lr g / (sqrt(sq) + eps).   (utils/utils.py:13-16)
+__global__ __launch_bounds__(256) void sgd_kernel(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum,
+                                                  float grad_scale, const int32_t* step_dev, int32_t step, int32_t* cursor_dev) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int st = step_dev != nullptr ? *step_dev : step;
+  if (p < n) {
+    const float g = grad[p] * grad_scale;
+    float b = g;
+    if (momentum != 0.f) { b = st <= 1 ? g : momentum * buf[p] + g; buf[p] = b; }
+    theta[p] -= lr * b;
+  }
+  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
+}
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha,
+                                                      float eps, float grad_scale, int32_t* cursor_dev) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p < n) {
+    const float g = grad[p] * grad_scale;
+    const float s = alpha * sq[p] + (1.f - alpha) * g * g;
+    sq[p] = s;
+    theta[p] -= lr * (g / (sqrtf(s) + eps));
+  }
+  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
+}
+
+// ------------------------------------------------------------------------------ dynamic loss scaling (GradScaler's role)
+// state: [0] scale  [1] growth tracker  [2] found_inf  [3] skipped steps  [4] ticket (int bits)
+__global__ __launch_bounds__(256) void unscale_check_kernel(float* grad, int64_t n, float grad_scale, float* state) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const float g = grad[p] * (grad_scale / state[0]);
+  grad[p] = g;
+  if (!isfinite(g)) state[2] = 1.f;                 // (every writer stores the same value)
+}
+
+__global__ __launch_bounds__(256) void scaled_adam_kernel(float* theta, const float* grad, float* m, float* v, int64_t n,
+                                                          float lr, float b1, float b2, float eps, float* state,
+                                                          float growth, float backoff, int interval,
+                                                          int32_t* step_dev, int32_t* cursor_dev) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool skip = state[2] != 0.f;
+  if (!skip && p < n) {
+    float bc1, bc2s;
+    bias_corrections(*step_dev, b1, b2, bc1, bc2s);
+    adam_update(theta, m, v, p, grad[p], lr, b1, b2, eps, bc1, bc2s);
+  }
+  // the last block to get here has seen every other block read found_inf and the step count: it closes the step
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    int* ticket = reinterpret_cast<int*>(state + 4);
+    if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) {
+      *ticket = 0;
+      if (skip) {
+        state[0] *= backoff; state[1] = 0.f; state[3] += 1.f;
+        *step_dev -= 1;                               // a skipped step does not count for the bias corrections
+      } else {
+        const float t = state[1] + 1.f;
+        if (t >= (float)interval) { state[0] *= growth; state[1] = 0.f; }
+        else state[1] = t;
+      }
+      state[2] = 0.f;
+      if (cursor_dev != nullptr) *cursor_dev += 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void xgmi_allreduce_kernel(const XgmiDev x, float* buf, int64_t n, int seq) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < n;
+  const float s = xgmi_exchange(x, 1, seq, i, valid, valid ? buf[i] : 0.f);
+  if (valid) buf[i] = s;
+}
+
+
+// ------------------------------------------------------------------------------ launchers
+// Blocks per kind, tiles per row, packed for the kernel's preloaded scalars.  A geometry the packing cannot hold is refused:
+// hipErrorInvalidValue, and *refusal names the reason.
+hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal) {
+  *refusal = nullptr;
+  if (L.H % 8 != 0 || L.F2 % 8 != 0) {
+    *refusal = "grad_reduce: hidden width and 2 x gmf.width must be multiples of 8";
+    return hipErrorInvalidValue;
+  }
+  const int t1n = L.F2 / 8, t2n = L.H / 8;
+  const int nFc1 = (L.H / 8) * t1n, nFc2 = ((L.K + 7) / 8) * t2n, nConv = (L.NCONV + 15) / 16;
+  const int nAttn = L.attention ? (a.ASLAB + 63) / 64 : 0;
+  if (nFc1 > 0xffff || nFc2 > 0xffff || nConv > 0xffff || nAttn > 0x7fff) {
+    *refusal = "grad_reduce: too many blocks of one kind";
+    return hipErrorInvalidValue;
+  }
+  const WsLayout w = make_ws(L, B);
+  const int grid = nFc1 + nFc2 + nConv + nAttn + 1;   // + the bookkeeping block
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3(grid), dim3(320), 0, st, ws + w.slab, ws + w.dh, ws + w.z, ws + w.dl, ws + w.h,
+                     nFc1 | (t1n << 16), nFc2 | (t2n << 16), nConv | (nAttn << 16), B, a);
+  return hipGetLastError();
+}
+
+static dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+hipError_t launch_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                       float bc1, float bc2_sqrt, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, hipStream_t st) {
+  hipLaunchKernelGGL(adam_kernel, blocks256(n), dim3(256), 0, st, theta, grad, m, v, n, lr, b1, b2, eps, bc1, bc2_sqrt,
+                     grad_scale, step_dev, cursor_dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_sgd(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum, float grad_scale,
+                      const int32_t* step_dev, int32_t step, int32_t* cursor_dev, hipStream_t st) {
+  hipLaunchKernelGGL(sgd_kernel, blocks256(n), dim3(256), 0, st, theta, grad, buf, n, lr, momentum, grad_scale, step_dev, step,
+                     cursor_dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_rmsprop(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha, float eps,
+                          float grad_scale, int32_t* cursor_dev, hipStream_t st) {
+  hipLaunchKernelGGL(rmsprop_kernel, blocks256(n), dim3(256), 0, st, theta, grad, sq, n, lr, alpha, eps, grad_scale, cursor_dev);
+  return hipGetLastError();
+}
+
+// the two launches of dmf_unscale_adam: unscale + found_inf check (skipped when the reduce has done it), then the Adam step
+// that closes the scaler's step
+hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st) {
+  hipLaunchKernelGGL(unscale_check_kernel, blocks256(n), dim3(256), 0, st, grad, n, grad_scale, state);
+  return hipGetLastError();
+}
+
+hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                               float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
+                               int32_t* cursor_dev, hipStream_t st) {
+  hipLaunchKernelGGL(scaled_adam_kernel, blocks256(n), dim3(256), 0, st, theta, grad, m, v, n, lr, b1, b2, eps, state, growth,
+                     backoff, interval, step_dev, cursor_dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st) {
+  hipLaunchKernelGGL(xgmi_allreduce_kernel, blocks256(n), dim3(256), 0, st, x, buf, n, seq);
+  return hipGetLastError();
+}
+
+#ifdef DMF_STAMPS
+hipError_t set_reduce_stamps(unsigned long long* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_rstamps), &p, sizeof(p)); }
+#endif
+
+}  // namespace dmf

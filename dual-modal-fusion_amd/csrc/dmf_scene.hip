@@ -6,6 +6,7 @@
 // The arithmetic is numpy's for each dtype (function.to_tensor under numpy 2): integer types subtract in the raw integer
 // type and divide the two values as float64, float32 stays float32, float64 stays float64; then ONE rounding to fp32 and,
 // for an fp16 scene, a second one from fp32 to fp16 — the host path's double rounding, kept on purpose.
+// pan2ms_kernel (image_convert/IHS.py) lives here too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -233,6 +234,26 @@ hipError_t launch_scene_prepare(const ScenePrepArgs& a, int dtype, int half, hip
     case 5: return prepare_typed<double>(a, half, st);
     default: return hipErrorInvalidValue;
   }
+}
+
+// pan2ms (image_convert/IHS.py:14-19): p = 2x2 mean pool of pan; out[:, :, i] = p[i%2::2, i//2::2]
+//   => out[h, w, i] = mean(pan[4h + 2(i%2) + {0,1}, 4w + 2(i//2) + {0,1}])
+__global__ __launch_bounds__(256) void pan2ms_kernel(const double* pan, int pitch, int H, int W, double* out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)H * W * 4) return;
+  const int i = (int)(e & 3);
+  const int64_t hw = e >> 2;
+  const int h = (int)(hw / W), w = (int)(hw - (int64_t)h * W);
+  const int r = 4 * h + 2 * (i % 2), c = 4 * w + 2 * (i / 2);
+  const double* p0 = pan + (size_t)r * pitch + c;
+  // numpy.mean over a 2x2 block: running sum in row-major order, then / 4
+  out[e] = (((p0[0] + p0[1]) + p0[pitch]) + p0[pitch + 1]) / 4.0;
+}
+
+hipError_t launch_pan2ms(const double* pan, int pitch, int H, int W, double* out, hipStream_t st) {
+  const int64_t n = (int64_t)H * W * 4;
+  hipLaunchKernelGGL(pan2ms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pan, pitch, H, W, out);
+  return hipGetLastError();
 }
 
 }  // namespace dmf

@@ -181,11 +181,15 @@ def param_layout(shape):
     return list(off)
 
 
-def workspace_bytes(shape, B):
-    n = _lib.dmf_workspace_bytes(C.byref(shape), B)
+def _bytes(fn, name, shape, B):
+    n = fn(C.byref(shape), B)
     if n < 0:
-        raise DmfError('dmf_workspace_bytes failed')
+        raise DmfError(name + ' failed')
     return n
+
+
+def workspace_bytes(shape, B):
+    return _bytes(_lib.dmf_workspace_bytes, 'dmf_workspace_bytes', shape, B)
 
 
 def _ptr(t):
@@ -245,7 +249,7 @@ def forward(shape, inp, theta, pool_w, logits, pred=None):
 
 
 def attn_workspace_bytes(shape, B):
-    return _lib.dmf_attn_workspace_bytes(C.byref(shape), B)
+    return _bytes(_lib.dmf_attn_workspace_bytes, 'dmf_attn_workspace_bytes', shape, B)
 
 
 def forward_attn(shape, inp, theta, pool_w, ws, logits, pred=None):
@@ -264,10 +268,7 @@ def train_fwd_bwd(shape, inp, theta, pool_w, labels, loss_scale, logits, loss, w
 
 
 def attn_train_workspace_bytes(shape, B):
-    n = _lib.dmf_attn_train_workspace_bytes(C.byref(shape), B)
-    if n < 0:
-        raise DmfError('dmf_attn_train_workspace_bytes failed')
-    return n
+    return _bytes(_lib.dmf_attn_train_workspace_bytes, 'dmf_attn_train_workspace_bytes', shape, B)
 
 
 def train_attn_fwd_bwd(shape, inp, theta, pool_w, labels, dlogits, loss_scale, logits, loss, ws, attn_ws,

@@ -189,7 +189,14 @@ class Criterion:
 
 class _PlanEngine:
     """What both train engines share: parameters and optimiser state, the epoch plan on the device, and the hipGraph that
-    replays steps of it.  A subclass says how one step is launched (`_plan_launch`) and what differs around a capture."""
+    replays steps of it.  A subclass says how one step is launched (`_plan_launch`) and what differs around a capture.
+    Two kinds of step:
+      * the fused step (TrainEngine without a criterion), cross-entropy inside the patch kernel: `step` / `load_plan` take
+        PER-RANK batches (every rank is handed its own pixels), a captured graph reads a fixed window refilled before each
+        replay, and the library's own launch loop may run the plan;
+      * the unit-gradient step (TrainEngine with a criterion, QuaTrainEngine), `_unit_step` around a loss kernel that sees
+        the whole batch: `step` / `load_plan` take GLOBAL batches, the same on every rank, of which rank r trains on its
+        contiguous rows (`_rank_shard`, `_load_global_plan`), and a captured graph's steps read plan[cursor]."""
 
     def __init__(self, net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha):
         if optimizer not in ('ADAM', 'SGD', 'RMSprop'):
@@ -285,6 +292,47 @@ class _PlanEngine:
             else:
                 lib.adam_step(self.theta, self.grad, self.m, self.v, *hp, self.step_count, grad_scale=sum_scale,
                               adam_step_dev=dev_step, cursor_dev=cursor)
+
+    # ------------------------------------------------------------------ the unit-gradient step on global batches
+    def _unit_step(self, inp, rows, loss_launch, dev_step, cursor, loss=None, loss_hist=None):
+        """dmf_forward_unit (forward of the `rows` patches + the conv backward for a unit gradient per pooled feature) ->
+        `loss_launch()` (self.logits -> value and self.dlogits) -> dmf_backward_unit (dh, dz, scaled slab rows) -> the update:
+        the patches are visited ONCE.  The loss kernel has divided by the GLOBAL batch: the ranks' sum is the gradient."""
+        lib.forward_unit(self.shape, inp, self.theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
+        loss_launch()
+        lib.backward_unit(self.shape, rows, self.theta, self.dlogits, self.ws)
+        self._update(rows, dev_step, cursor, 1.0, loss, loss_hist)
+
+    def _rank_shard(self, xy, labels, cap):
+        """Of a global eager batch (host or device): this rank's len // world rows of `xy` and, on the device, the labels of
+        all ranks' rows.  The remainder that the world size does not divide is dropped."""
+        xy = torch.as_tensor(xy)
+        n = xy.shape[0] // self.world
+        if n > cap:
+            raise lib.DmfError('engine was built for batches of at most %d, got %d' % (cap, n))
+        if n == 0:
+            raise lib.DmfError('a batch of %d pixels gives the %d ranks no pixel each' % (xy.shape[0], self.world))
+        lab = torch.as_tensor(labels)[:self.world * n].to(device=self.scene.device, dtype=torch.int32)
+        return xy[self.rank * n:(self.rank + 1) * n].contiguous(), lab.contiguous()
+
+    def _load_global_plan(self, xy_all, labels_all, per_rank, rows=None):
+        """An epoch of full GLOBAL batches: xy_all [n*per_rank*world, 2], labels_all [n*per_rank*world] (host or device, any
+        int type).  Rank r keeps rows [r*per_rank, (r+1)*per_rank) of every batch's pixels, as the plan coordinates
+        `rows(pixels)` where the step does not gather at the pixels themselves, and the labels of the whole batches."""
+        dev, W = self.scene.device, self.world
+        xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
+        lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
+        if xy.shape[0] % (per_rank * W) or xy.shape[0] != lab.shape[0]:
+            raise lib.DmfError('plan length must be a multiple of the (global) batch size')
+        n = xy.shape[0] // (per_rank * W)
+        if W > 1:
+            xy = xy.view(n, W, per_rank, 2)[:, self.rank].reshape(-1, 2)
+        if rows is not None:
+            xy = rows(xy)
+        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
+        self._check_labels(lab)
+        self._install_plan(n, plan_xy=xy.to(dev).contiguous(), plan_labels=lab)
+        return n
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def _install_plan(self, n, **plan):
@@ -429,16 +477,15 @@ class _PlanEngine:
 
 
 class TrainEngine(_PlanEngine):
+    """The single-stage train step on a resident scene: the fused step, or with a `criterion` the unit-gradient step around
+    dmf_ce_loss (_PlanEngine: what each takes).  `self.fused`, set once by the constructor, says which."""
+
     def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
                  optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None):
         """optimizer: 'ADAM', or the reference's other two (utils/utils.py:13-16) — 'SGD' (`momentum`) and 'RMSprop'
         (`alpha`, eps 1e-8).  The launches after the backward: _PlanEngine._update.
         criterion: None = the plain cross-entropy fused into the patch kernel (two launches per step).  A spec of `Criterion`
-        (class weights, label smoothing, focal term) trains by the unit-gradient step instead: dmf_forward_unit -> dmf_ce_loss
-        -> dmf_backward_unit -> the update, eagerly or from captured graphs whose steps read plan[cursor] (no native launch
-        loop, no xgmi exchange).  Data parallel it takes GLOBAL batches like QuaTrainEngine: `load_plan` / `step` get the
-        pixels and labels of all ranks, every rank trains on its contiguous shard of each batch, and the loss kernel, which
-        divides by the global batch's weight sum, reads the global labels."""
+        (class weights, label smoothing, focal term) trains by the unit-gradient step instead (no xgmi exchange)."""
         super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
@@ -460,7 +507,8 @@ class TrainEngine(_PlanEngine):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
         self.plan_pack = self.win = None
         self.criterion = None
-        if criterion is not None:
+        self.fused = criterion is None
+        if not self.fused:
             if self.shape.attention:
                 raise lib.DmfError('a criterion with class weights, label smoothing or a focal term trains by the unit-gradient '
                                    'step, which the attention network does not have')
@@ -475,14 +523,10 @@ class TrainEngine(_PlanEngine):
 
     # ------------------------------------------------------------------ eager step (host-side step count)
     def step(self, xy, labels, check=True):
-        """One optimiser step on the patches at `xy` [B,2] int32 (device) with `labels` [B] int32 (device).  With a criterion
-        and a process group `xy` / `labels` are the GLOBAL batch (the same on every rank): every rank trains on its contiguous
-        shard of len // world pixels, and the remainder that the world size does not divide is dropped."""
-        if self.criterion is not None:
-            n = xy.shape[0] // self.world
-            if n == 0:
-                raise lib.DmfError('a batch of %d pixels gives the %d ranks no pixel each' % (xy.shape[0], self.world))
-            xy, labels = xy[self.rank * n:(self.rank + 1) * n].contiguous(), labels[:self.world * n].contiguous()
+        """One optimiser step on the patches at `xy` [B,2] int32 (device) with `labels` [B] int32 (device); the unit-gradient
+        step: the global batch."""
+        if not self.fused:
+            xy, labels = self._rank_shard(xy, labels, self.B)
         if xy.shape[0] > self.B:
             raise lib.DmfError('engine was built for batches of at most %d, got %d' % (self.B, xy.shape[0]))
         if check:     # one D2H copy per call; load_plan() validates a whole epoch at once and run_plan() skips this
@@ -494,7 +538,7 @@ class TrainEngine(_PlanEngine):
     def step_patches(self, a, b, labels):
         """Same step from materialised patch tensors (the reference dataloader's batch).  With a criterion: one rank only (the
         loss kernel needs the global batch's labels, and nothing shards materialised patches)."""
-        if self.criterion is not None and self.world > 1:
+        if not self.fused and self.world > 1:
             raise lib.DmfError('step_patches with a criterion: one rank only (use step / load_plan, which take the global batch)')
         inp = lib.input_patches(self.shape, a, b)
         self._launch(inp, labels, None, None)
@@ -506,17 +550,13 @@ class TrainEngine(_PlanEngine):
 
     def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
         dev_step = self._count_step(dev_step)
-        sc, nB = self.scaler, inp.B
-        if self.criterion is not None:
-            # the unit-gradient step around the loss kernel; labels: the GLOBAL batch's ([world * nB] at row dev_cursor).  The
-            # kernel has divided by the global batch's weight sum already: the sum over the ranks is the gradient
-            cr = self.criterion
-            lib.forward_unit(self.shape, inp, self.theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
-            lib.ce_loss(self.logits[:nB], self.world, self.rank, labels, cr.params, class_w=cr.class_w, loss=self.loss,
-                        dlogits=self.dlogits[:nB], cursor=dev_cursor, scaler_state=sc.state if sc is not None else None)
-            lib.backward_unit(self.shape, nB, self.theta, self.dlogits, self.ws)
-            self._update(nB, dev_step, dev_cursor, 1.0, self.loss if loss_hist is not None else None, loss_hist)
-            return
+        sc, nB, cr = self.scaler, inp.B, self.criterion
+        loss = self.loss if loss_hist is not None else None
+        if not self.fused:                     # labels: the GLOBAL batch's ([world * nB] at row dev_cursor)
+            return self._unit_step(inp, nB, lambda: lib.ce_loss(
+                self.logits[:nB], self.world, self.rank, labels, cr.params, class_w=cr.class_w, loss=self.loss,
+                dlogits=self.dlogits[:nB], cursor=dev_cursor, scaler_state=sc.state if sc is not None else None),
+                dev_step, dev_cursor, loss, loss_hist)
         if self.shape.attention:
             lib.train_attn_fwd_bwd(self.shape, inp, self.theta, self.net.pool_w, labels, None, 1.0 / nB, self.logits,
                                    self.loss, self.ws, self.attn_ws, adam_step_dev=dev_step)
@@ -524,27 +564,15 @@ class TrainEngine(_PlanEngine):
             lib.train_fwd_bwd(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / nB, self.logits, self.loss, self.ws,
                               adam_step_dev=dev_step, scaler_state=sc.state if sc is not None else None)
         # the loss is this rank's mean: the sum over the ranks is scaled by 1/world
-        self._update(nB, dev_step, dev_cursor, 1.0 / self.world, self.loss if loss_hist is not None else None, loss_hist)
+        self._update(nB, dev_step, dev_cursor, 1.0 / self.world, loss, loss_hist)
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def load_plan(self, xy_all, labels_all):
-        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type).  With a
-        criterion: an epoch of GLOBAL batches, [n*B*world] each; rank r keeps rows [r*B, (r+1)*B) of every batch's pixels and
-        the labels of the whole batches."""
+        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type); the
+        unit-gradient step: an epoch of global batches (_load_global_plan)."""
+        if not self.fused:
+            return self._load_global_plan(xy_all, labels_all, self.B)
         dev = self.scene.device
-        if self.criterion is not None:
-            W = self.world
-            xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
-            lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-            if xy.shape[0] % (self.B * W) or xy.shape[0] != lab.shape[0]:
-                raise lib.DmfError('plan length must be a multiple of the (global) batch size')
-            n = xy.shape[0] // (self.B * W)
-            if W > 1:
-                xy = xy.view(n, W, self.B, 2)[:, self.rank].reshape(-1, 2)
-            lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
-            self._check_labels(lab)
-            self._install_plan(n, plan_xy=xy.to(dev).contiguous(), plan_labels=lab)
-            return n
         xy = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
         lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
         if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
@@ -564,8 +592,6 @@ class TrainEngine(_PlanEngine):
 
     def _fill_window(self, n):
         """Copy the next n steps of the plan into the fixed window the captured graph reads (one small async copy)."""
-        if self.criterion is not None:
-            return
         self.win.copy_(self.plan_pack[self.host_cursor:self.host_cursor + n])
 
     def run_plan(self, steps=None, steps_per_graph=0):
@@ -588,7 +614,7 @@ class TrainEngine(_PlanEngine):
     def _native_loop_ok(self):
         """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler,
         the fused cross-entropy."""
-        return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.criterion is None
+        return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.fused
 
     def _graphable(self):
         """Can a step be captured in a hipGraph?  One GPU: yes.  The one-shot exchange: yes (it is part of the reduce launch).
@@ -601,7 +627,7 @@ class TrainEngine(_PlanEngine):
         return self._rccl_capturable()
 
     def _prepare_capture(self, n):
-        if self.criterion is not None:             # the graph's steps read plan[cursor] like eager plan steps: no window
+        if not self.fused:                         # the graph's steps read plan[cursor] like eager plan steps: no window
             return
         if self.comm is not None:                  # the eager step used up an exchange sequence number; the bias is
             self.comm.rewind(1)                    # a launch argument, so it has to move BEFORE the capture
@@ -616,13 +642,14 @@ class TrainEngine(_PlanEngine):
             self.win.zero_()
 
     def _graph_step(self, k):
-        if self.criterion is not None:
+        if not self.fused:
             return self._plan_launch()
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.win[k, :2 * self.B].view(self.B, 2))
         self._launch(inp, self.win[k, 2 * self.B:], self.dev_step, self.dev_cursor, self.loss_hist)
 
     def _before_replay(self, n):
-        self._fill_window(n)
+        if self.fused:
+            self._fill_window(n)
 
     def warm_graph(self):
         """One replay of the captured graph that leaves no trace (weights, optimiser state, cursors and loss history are put
@@ -632,7 +659,8 @@ class TrainEngine(_PlanEngine):
         if self.graph is None or not self._single() or self.host_cursor + self.graph_steps > self.plan_steps:
             return False
         with self._state_kept():
-            self._fill_window(self.graph_steps)
+            if self.fused:
+                self._fill_window(self.graph_steps)
             self.graph.replay()
             torch.cuda.synchronize()
         torch.cuda.synchronize()
@@ -832,13 +860,11 @@ class QuaScene:
 class QuaTrainEngine(_PlanEngine):
     """Stage-2 train step (tostagesolver.py:268-278) on the resident tall scene, no host sync.  The loss couples the whole
     batch, so it cannot ride inside the per-patch kernel like cross-entropy does.  Two forms:
-      * unit-gradient step (shapes with a v2 kernel): `dmf_forward_unit` (forward of the 4*bs stacked patches + the conv
-        backward for a unit gradient per pooled feature) -> `dmf_qua_loss_ranks` (value + d/dlogits) -> `dmf_backward_unit`
-        (dh, dz, scaled slab rows) -> the update: the patches are visited ONCE, and the step replays from a captured
-        hipGraph (`run_plan(steps, steps_per_graph)`);
+      * unit-gradient step (shapes with a v2 kernel): `_unit_step` on the 4*bs stacked patches around `dmf_qua_loss_ranks`;
+        the step replays from a captured hipGraph (`run_plan(steps, steps_per_graph)`);
       * otherwise `dmf_forward` -> `dmf_qua_loss_ranks` -> `dmf_backward_dlogits` (recomputes the forward) -> the update.
-    Data parallel (process_group): every rank takes its shard of each global batch; `all_gather_into_tensor` of the logits
-    into a buffer allocated once (gloo: a host gather and one H2D copy into it) feeds the loss of the GLOBAL batch, which
+    `step` / `load_plan` take GLOBAL batches (see _PlanEngine).  Data parallel (process_group): `all_gather_into_tensor` of the
+    logits into a buffer allocated once (gloo: a host gather and one H2D copy into it) feeds the loss of the GLOBAL batch, which
     writes this rank's rows of d loss / d logits.  Over RCCL the whole step replays from a captured hipGraph like the
     single-GPU one.  The update after the backward (optimiser, loss scaler, all-reduce): _PlanEngine._update."""
 
@@ -858,7 +884,6 @@ class QuaTrainEngine(_PlanEngine):
         self.dlogits = torch.empty(4 * self.bs, K, device=dev)
         self.loss = torch.zeros(1, device=dev)
         self.ws = torch.empty(lib.workspace_bytes(self.shape, 4 * self.bs) // 4, device=dev)
-        self.plan_labels_global = None
         # data parallel: the logits of all ranks, rank-major [world][4][bs][K] as all_gather_into_tensor leaves them
         self.gathered = torch.empty(self.world * 4 * self.bs, K, device=dev) if process_group is not None else None
 
@@ -877,67 +902,40 @@ class QuaTrainEngine(_PlanEngine):
     def _step(self, inp, bs, labels, cursor, loss_hist, dev_step=None):
         """One step on this rank's 4*bs stacked patches; labels: the GLOBAL batch's ([world*bs] at row cursor)."""
         dev_step = self._count_step(dev_step)
+
+        def loss_launch():
+            # the loss of the global batch from the logits of all ranks (one GPU: its own logits, world 1, rank 0)
+            logits = self.logits[:4 * bs] if self._single() else self._gather(bs)
+            lib.qua_loss_ranks(logits, self.world, self.rank, bs, labels, self.params, loss=self.loss,
+                               dlogits=self.dlogits[:4 * bs], cursor=cursor, loss_hist=loss_hist,
+                               scaler_state=self.scaler.state if self.scaler is not None else None)
         if self.unit:
-            lib.forward_unit(self.shape, inp, self.theta, self.net.pool_w, self.logits, self.ws, adam_step_dev=dev_step)
-        else:
-            lib.forward(self.shape, inp, self.theta, self.net.pool_w, self.logits)
-        # the loss of the global batch from the logits of all ranks (one GPU: its own logits, world 1, rank 0)
-        logits = self.logits[:4 * bs] if self._single() else self._gather(bs)
-        lib.qua_loss_ranks(logits, self.world, self.rank, bs, labels, self.params, loss=self.loss,
-                           dlogits=self.dlogits[:4 * bs], cursor=cursor, loss_hist=loss_hist,
-                           scaler_state=self.scaler.state if self.scaler is not None else None)
-        if self.unit:
-            lib.backward_unit(self.shape, 4 * bs, self.theta, self.dlogits, self.ws)
-        else:
-            lib.backward_dlogits(self.shape, inp, self.theta, self.net.pool_w, self.dlogits, self.ws)
-        # the loss kernel already divided by the GLOBAL batch: the sum over the ranks is the gradient.  dmf_forward does not
-        # count steps: the non-unit form updates by the host count
-        self._update(4 * bs, dev_step if self.unit else None, cursor, 1.0)
+            return self._unit_step(inp, 4 * bs, loss_launch, dev_step, cursor)
+        lib.forward(self.shape, inp, self.theta, self.net.pool_w, self.logits)
+        loss_launch()
+        lib.backward_dlogits(self.shape, inp, self.theta, self.net.pool_w, self.dlogits, self.ws)
+        # dmf_forward does not count steps: the non-unit form updates by the host count
+        self._update(4 * bs, None, cursor, 1.0)
 
     def step(self, xy, labels):
-        """One step on the bs pixels `xy` [bs, 2] (host or device ints) with `labels` [bs].  Data parallel: `xy` / `labels`
-        are the GLOBAL batch (the same on every rank, e.g. the solver's short last batch); every rank trains on its
-        contiguous shard of len // world pixels, and the remainder that the world size does not divide is dropped."""
-        n = int(xy.shape[0])
-        W = 1 if self._single() else self.world
-        bs = n // W
-        if bs > self.bs:
-            raise lib.DmfError('engine was built for batches of at most %d' % self.bs)
-        if bs == 0:
-            raise lib.DmfError('a batch of %d pixels gives the %d ranks no pixel each' % (n, W))
-        dev = self.scene.device
-        lo = 0 if W == 1 else self.rank * bs
-        xy4 = self.scene.stack_xy(torch.as_tensor(xy).cpu()[lo:lo + bs]).to(dev).contiguous()
+        """One step on the global batch `xy` [world*bs, 2] (host or device ints) with `labels` [world*bs], e.g. the solver's
+        short last batch."""
+        xy, lab = self._rank_shard(xy, labels, self.bs)
+        xy4 = self.scene.stack_xy(xy.cpu()).to(self.scene.device).contiguous()
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.cpu().numpy())
-        lab = torch.as_tensor(labels).to(device=dev, dtype=torch.int32)[:W * bs].contiguous()
         self._check_labels(lab)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy4)
-        self._step(inp, bs, lab, None, None)
+        self._step(inp, xy.shape[0], lab, None, None)
 
     def load_plan(self, xy_all, labels_all):
-        """An epoch of full GLOBAL batches: xy_all [n*bs*world, 2], labels_all [n*bs*world]; rank r trains on rows
-        [r*bs, (r+1)*bs) of every global batch, and the loss reads the global batch's labels."""
-        dev = self.scene.device
-        W = self.world
-        xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
-        lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        if xy.shape[0] % (self.bs * W) or xy.shape[0] != lab.shape[0]:
-            raise lib.DmfError('plan length must be a multiple of the (global) batch size')
-        n = xy.shape[0] // (self.bs * W)
-        self._check_labels(lab)
-        if W > 1:
-            xy = xy.view(n, W, self.bs, 2)[:, self.rank].reshape(-1, 2)
-        xy4 = torch.cat([self.scene.stack_xy(xy[i * self.bs:(i + 1) * self.bs]) for i in range(n)]) if n else xy
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy4.numpy())
-        # (the labels as one tensor that a captured graph keeps reading: a plan of the same shape is copied into it)
-        self._install_plan(n, plan_xy=xy4.to(dev).contiguous(), plan_labels_global=lab)
-        self.plan_labels = self.plan_labels_global
-        return n
+        """An epoch of full global batches (_load_global_plan); the plan holds every batch's 4*bs stacked coordinates."""
+        return self._load_global_plan(xy_all, labels_all, self.bs, rows=lambda xy: torch.cat(
+            [self.scene.stack_xy(batch) for batch in xy.split(self.bs)]))
 
     def _plan_launch(self):
         # (the captured graph runs these same launches: its steps read plan[cursor])
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=4 * self.bs, cursor=self.dev_cursor)
-        self._step(inp, self.bs, self.plan_labels_global, self.dev_cursor, self.loss_hist, self.dev_step)
+        self._step(inp, self.bs, self.plan_labels, self.dev_cursor, self.loss_hist, self.dev_step)
 
     def _graphable(self):
         """The unit-gradient form on one GPU, or over an RCCL group (its all-gather and all-reduce are captured with the

@@ -1,5 +1,6 @@
 """CPU: the launch sequence of one train step of both train engines, for every optimiser, loss-scaler, group and net form
-they accept — eager (`step`) and from the plan (`run_plan(1, 0)`).
+they accept — eager (`step`) and from the plan (`run_plan(1, 0)`), TrainEngine's criterion step included — and how the two
+engines that take GLOBAL batches (TrainEngine with a criterion, QuaTrainEngine) cut this rank's shard out of them.
 
 The library's entry points are replaced by a recorder: the host-only queries still reach the real library, every launch
 returns 0 and is recorded with its scalar arguments and its pointer arguments named by the engine attribute they point
@@ -46,7 +47,7 @@ class Recorder:
             if isinstance(obj, lib.Input):
                 return ('input', obj.mode, obj.B) + tuple(None if p is None else Ptr(p) for p in (obj.sceneA, obj.sceneB, obj.xy)) + (
                     obj.Wp, obj.WpB, None if obj.cursor is None else Ptr(obj.cursor), obj.half)
-            return {lib.Shape: 'shape', lib.QuaParams: 'params', lib.XgmiComm: 'comm'}[type(obj)]
+            return {lib.Shape: 'shape', lib.QuaParams: 'params', lib.XgmiComm: 'comm', lib.CeParams: 'ce_params'}[type(obj)]
         return a
 
     def __getattr__(self, entry):
@@ -71,6 +72,8 @@ class Recorder:
         tensors.update(pool_w=eng.net.pool_w, sceneA=eng.scene.A, sceneB=eng.scene.B, **extra)
         if eng.scaler is not None:
             tensors['scaler'] = eng.scaler.state
+        if getattr(getattr(eng, 'criterion', None), 'class_w', None) is not None:
+            tensors['class_w'] = eng.criterion.class_w
 
         def name(a):
             if isinstance(a, tuple):
@@ -274,3 +277,167 @@ def test_stage2_engine_step_launches(form, rec, group, monkeypatch):
     assert eng.run_plan(1, 0) == 1
     assert rec.take(eng) == _f32(launches('dev_step', 'plan_xy', 'plan_labels', 'dev_cursor', 'loss_hist'))
     assert eng.step_count == 2 and eng.host_cursor == 1
+
+
+# ------------------------------------------------------------------------------------------------ TrainEngine, criterion step
+K17 = 17
+CRITERIA = {'ce': {'kind': 'ce', 'label_smoothing': 0.1, 'class_weights': np.linspace(0.5, 2.0, K17).tolist()},
+            'focal': {'kind': 'focal', 'gamma': 2.0, 'class_weights': np.linspace(2.0, 0.5, K17).tolist()}}
+
+
+def _criterion_engine(spec, group=None, scaler=None, optimizer='ADAM', B=8):
+    """TrainEngine with a criterion on the late-fusion shape 200/1/11/1/40/10 (the shape of the test above), K = 17."""
+    from dmf.engine import Scene, TrainEngine
+    from model.gmfnet import Net
+    cfg = {'patch_size': 11, 'Categories_Number': K17, 'data_city': 's', 'DATA_DICT': {'s': {'size': [40, 40, 200]}},
+           'scale': 1, 'aux_bands': 1, 'gmf': {'width': 40, 'hidden': 64, 'pool_sigma': 2.5, 'attention': 0},
+           'trans': {'embed_dim': 96, 'num_head': 3}}
+    torch.manual_seed(0)
+    scene = Scene(np.zeros((50, 50, 200), np.float32), np.zeros((50, 50, 1), np.float32), 'cpu')
+    return TrainEngine(Net(cfg), scene, B, lr=2e-3, process_group=group, scaler=scaler, optimizer=optimizer, momentum=0.5,
+                       criterion=CRITERIA[spec])
+
+
+def _criterion_forms():
+    for form in _forms():
+        optim, use_scaler, grp, net_kind = _parse(form)
+        if net_kind == 'late' and grp != 'xgmi':
+            for spec in CRITERIA:
+                yield '%s-%s-%s-%s' % (optim, 'scaler' if use_scaler else 'fp32', grp, spec)
+
+
+@pytest.mark.parametrize('form', list(_criterion_forms()))
+def test_train_engine_criterion_step_launches(form, rec, group):
+    from dmf.engine import LossScaler
+    optim, use_scaler, grp, spec = _parse(form)
+    B, K = 8, K17
+    collective = grp != 'single'
+    eng = _criterion_engine(spec, group if collective else None, LossScaler('cpu') if use_scaler else None, optim, B)
+    eng._force_collective = collective
+    rng = np.random.default_rng(0)
+    xy = torch.from_numpy(rng.integers(0, 30, (B, 2)).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, K, B).astype(np.int32))
+
+    def launches(dev_step, xy_name, labels_name, cursor, loss, loss_hist):
+        inp = ('input', 1, B, 'sceneA', 'sceneB', xy_name, 50, 50, cursor, 0)
+        return [('dmf_forward_unit', 'shape', inp, 'theta', 'pool_w', 'logits', 'ws', dev_step, None),
+                ('dmf_ce_loss', 'logits', 1, 0, B, K, labels_name, cursor, 'class_w', 'ce_params', 1.0,
+                 'scaler' if use_scaler else None, 'loss', 'dlogits', None),
+                ('dmf_backward_unit', 'shape', B, 'theta', 'dlogits', 'ws', None)
+                ] + expected_update(eng, B, dev_step, cursor, 1.0, loss, loss_hist, collective, False)
+
+    rec.take(eng)
+    eng.step(xy, labels)
+    dev = 'dev_step' if eng._counts_on_device() else None
+    assert (dev is not None) == (use_scaler or optim != 'ADAM')
+    assert rec.take(eng, xy=xy, labels=labels) == _f32(launches(dev, 'xy', 'labels', None, None, None))
+
+    eng.load_plan(rng.integers(0, 30, (2 * B, 2)).astype(np.int32), rng.integers(0, K, 2 * B).astype(np.int32))
+    rec.take(eng)
+    assert eng.run_plan(1, 0) == 1
+    assert rec.take(eng) == _f32(launches('dev_step', 'plan_xy', 'plan_labels', 'dev_cursor', 'loss', 'loss_hist'))
+    assert eng.step_count == 2 and eng.host_cursor == 1
+
+
+# ------------------------------------------------------------------------------------------------ this rank's shard of a global batch
+WORLD = 3
+
+
+def _qua_engine(group, bs=8):
+    from dmf.engine import QuaScene, QuaTrainEngine
+    from model.gmfnet import Net
+    cfg = {'patch_size': 16, 'Categories_Number': 5, 'data_city': 's', 'DATA_DICT': {'s': {'size': [20, 20, 4]}},
+           'gmf': {'width': 40, 'single_input': 1}}
+    torch.manual_seed(0)
+    scene = QuaScene([np.zeros((36, 36, 4), np.float32)] * 4, 'cpu')
+    return QuaTrainEngine(Net(cfg), scene, bs, DQTL, lr=2e-3, process_group=group)
+
+
+def _as_rank(eng, rank):
+    """A one-rank engine that believes it is `rank` of WORLD ranks (its collectives still run on the one-rank group)."""
+    eng.world, eng.rank = WORLD, rank
+    return eng
+
+
+@pytest.mark.parametrize('rank', [0, WORLD - 1])
+def test_criterion_load_plan_keeps_this_ranks_rows(rank, group):
+    B, n = 8, 2
+    eng = _as_rank(_criterion_engine('ce', group, B=B), rank)
+    rng = np.random.default_rng(1)
+    xy = rng.integers(0, 30, (n * B * WORLD, 2)).astype(np.int32)
+    labels = rng.integers(0, K17, n * B * WORLD).astype(np.int32)
+    assert eng.load_plan(xy, labels) == n
+    assert np.array_equal(eng.plan_xy.numpy(), xy.reshape(n, WORLD, B, 2)[:, rank].reshape(-1, 2))
+    assert eng.plan_xy.dtype == torch.int32 and eng.plan_xy.is_contiguous()
+    assert np.array_equal(eng.plan_labels.numpy(), labels) and eng.plan_labels.dtype == torch.int32
+
+
+@pytest.mark.parametrize('rank', [0, WORLD - 1])
+def test_stage2_load_plan_keeps_this_ranks_rows(rank, rec, group):          # (rec: QuaScene launches the band mean)
+    bs, n = 8, 2
+    eng = _as_rank(_qua_engine(group, bs), rank)
+    rng = np.random.default_rng(1)
+    xy = rng.integers(0, 20, (n * bs * WORLD, 2)).astype(np.int32)
+    labels = rng.integers(0, 5, n * bs * WORLD).astype(np.int32)
+    assert eng.load_plan(xy, labels) == n
+    mine = torch.from_numpy(xy.reshape(n, WORLD, bs, 2)[:, rank].copy())
+    want = torch.cat([eng.scene.stack_xy(mine[i]) for i in range(n)])
+    assert torch.equal(eng.plan_xy, want) and eng.plan_xy.dtype == torch.int32 and eng.plan_xy.is_contiguous()
+    assert np.array_equal(eng.plan_labels.numpy(), labels) and eng.plan_labels.dtype == torch.int32
+
+
+def _spy(monkeypatch, module, entry, seen):
+    real = getattr(module, entry)
+
+    def call(*args, **kw):
+        seen.append(args)
+        return real(*args, **kw)
+    monkeypatch.setattr(module, entry, call)
+
+
+@pytest.mark.parametrize('rank', [0, WORLD - 1])
+def test_criterion_step_trains_on_this_ranks_shard(rank, rec, group, monkeypatch):
+    from dmf import lib
+    B = 8
+    eng = _as_rank(_criterion_engine('ce', group, B=B), rank)
+    rng = np.random.default_rng(2)
+    xy = torch.from_numpy(rng.integers(0, 30, (WORLD * B + 1, 2)).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, K17, WORLD * B + 1).astype(np.int32))
+    losses = []
+    _spy(monkeypatch, lib, 'ce_loss', losses)
+    rec.take(eng)
+    eng.step(xy, labels)
+    calls = rec.take(eng, xy=xy, labels=labels)
+    at = 'xy+%d' % (rank * B * 8) if rank else 'xy'
+    assert calls[0] == ('dmf_forward_unit', 'shape', ('input', 1, B, 'sceneA', 'sceneB', at, 50, 50, None, 0), 'theta',
+                        'pool_w', 'logits', 'ws', 'dev_step' if eng._counts_on_device() else None, None)
+    assert calls[1][:7] == ('dmf_ce_loss', 'logits', WORLD, rank, B, K17, 'labels')
+    (args,) = losses
+    assert args[3].numel() == WORLD * B and torch.equal(args[3], labels[:WORLD * B])
+    with pytest.raises(lib.DmfError, match='no pixel each'):
+        eng.step(xy[:WORLD - 1], labels[:WORLD - 1])
+
+
+@pytest.mark.parametrize('rank', [0, WORLD - 1])
+def test_stage2_step_trains_on_this_ranks_shard(rank, rec, group, monkeypatch):
+    from dmf import lib
+    bs, K = 8, 5
+    eng = _as_rank(_qua_engine(group, bs), rank)
+    # (the logits of the other ranks: nothing gathers them in a one-rank group)
+    eng._gather = lambda n: torch.zeros(WORLD * 4 * n, K)
+    rng = np.random.default_rng(2)
+    xy = torch.from_numpy(rng.integers(0, 20, (WORLD * bs + 1, 2)).astype(np.int32))
+    labels = torch.from_numpy(rng.integers(0, K, WORLD * bs + 1).astype(np.int32))
+    gathers, losses = [], []
+    _spy(monkeypatch, lib, 'input_gather', gathers)
+    _spy(monkeypatch, lib, 'qua_loss_ranks', losses)
+    rec.take(eng)
+    eng.step(xy, labels)
+    calls = rec.take(eng, labels=labels)
+    (gather,), (loss,) = gathers, losses
+    assert torch.equal(gather[3], eng.scene.stack_xy(xy[rank * bs:(rank + 1) * bs])) and gather[3].dtype == torch.int32
+    assert calls[0][2][:3] == ('input', 1, 4 * bs)
+    assert loss[1:4] == (WORLD, rank, bs)
+    assert loss[4].numel() == WORLD * bs and torch.equal(loss[4], labels[:WORLD * bs])
+    with pytest.raises(lib.DmfError, match='no pixel each'):
+        eng.step(xy[:WORLD - 1], labels[:WORLD - 1])

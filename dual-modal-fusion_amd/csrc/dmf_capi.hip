@@ -618,6 +618,23 @@ int32_t dmf_confusion_accum(const int32_t* pred, const int32_t* target, int32_t 
                "confusion launch");
 }
 
+int32_t dmf_valid_accum(const float* loss, int32_t n, double* acc, void* stream) {
+  if (loss == nullptr || acc == nullptr) return fail("%s", "null argument");
+  if (n < 0) return fail("%s", "valid_accum: negative n");
+  if (n == 0) return 0;
+  return check(launch_valid_accum(loss, n, acc, static_cast<hipStream_t>(stream)), "valid_accum launch");
+}
+
+int32_t dmf_keep_best(double* acc, double* best, int32_t* best_epoch, int32_t epoch, const float* theta, float* best_theta,
+                      int64_t n, double* val_hist, void* stream) {
+  if (acc == nullptr || best == nullptr || best_epoch == nullptr || theta == nullptr || best_theta == nullptr || val_hist == nullptr)
+    return fail("%s", "null argument");
+  if (epoch < 0 || n < 0) return fail("%s", "keep_best: negative epoch or n");
+  if (theta == best_theta) return fail("%s", "keep_best: best_theta must not be theta");
+  return check(launch_keep_best(acc, best, best_epoch, epoch, theta, best_theta, n, val_hist, static_cast<hipStream_t>(stream)),
+               "keep_best launch");
+}
+
 int32_t dmf_labelmap_write(const int32_t* pred, const int32_t* xy, int32_t B, int32_t W, int32_t* map, void* stream) {
   if (pred == nullptr || xy == nullptr || map == nullptr) return fail("%s", "null argument");
   if (B <= 0) return 0;

@@ -133,6 +133,10 @@ hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float*
                                float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
                                int32_t* cursor_dev, hipStream_t st);
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
+// the validation sum of an epoch and what its end decides (dmf_valid_accum, dmf_keep_best): one workgroup each
+hipError_t launch_valid_accum(const float* loss, int n, double* acc, hipStream_t st);
+hipError_t launch_keep_best(double* acc, double* best, int32_t* best_epoch, int32_t epoch, const float* theta, float* best_theta,
+                            int64_t n, double* val_hist, hipStream_t st);
 
 // stage-2 kernels (dmf_qua.hip)
 struct QuaArgs {

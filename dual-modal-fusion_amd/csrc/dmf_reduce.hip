@@ -433,6 +433,49 @@ __global__ __launch_bounds__(256) void xgmi_allreduce_kernel(const XgmiDev x, fl
   if (valid) buf[i] = s;
 }
 
+// ------------------------------------------------------------------------------ validation sum and best weights on the device
+// acc[0] += sum_i (double)loss[i], ONE workgroup: lane t adds loss[t], loss[t + 256], ... in index order, then the 256 partial
+// sums meet in a fixed tree: the same bits on every run.  Lane 0 alone reads, adds to and writes acc[0]; the launches before
+// and after are ordered by the stream.
+__global__ __launch_bounds__(256) void valid_accum_kernel(const float* __restrict__ loss, int n, double* acc) {
+  __shared__ double part[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < n; i += 256) s += (double)loss[i];
+  part[t] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) part[t] += part[t + w];
+    __syncthreads();
+  }
+  if (t == 0) acc[0] += part[0];
+}
+
+// The end of an epoch's validation pass, ONE workgroup (nobody else can read *best while it changes): val = acc[0] goes into
+// val_hist[epoch]; a val strictly below *best (a NaN never is) becomes the best, with its epoch and a copy of theta; acc[0] is
+// cleared for the next epoch.  Every lane has read acc[0] and *best before the barrier, lane 0 writes them after it.
+__global__ __launch_bounds__(1024) void keep_best_kernel(double* acc, double* best, int32_t* best_epoch, int32_t epoch,
+                                                         const float* __restrict__ theta, float* __restrict__ best_theta,
+                                                         int64_t n, double* val_hist) {
+  const double val = acc[0];
+  const bool better = val < *best;
+  __syncthreads();
+  if (better) {
+    // 16-byte pieces where both vectors allow it, then (or instead) the single floats
+    const bool vec = ((reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(best_theta)) & 15) == 0;
+    const int64_t n4 = vec ? n / 4 : 0;
+    const float4* src = reinterpret_cast<const float4*>(theta);
+    float4* dst = reinterpret_cast<float4*>(best_theta);
+    for (int64_t i = threadIdx.x; i < n4; i += 1024) dst[i] = src[i];
+    for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += 1024) best_theta[i] = theta[i];
+  }
+  if (threadIdx.x == 0) {
+    val_hist[epoch] = val;
+    if (better) { *best = val; *best_epoch = epoch; }
+    acc[0] = 0.0;
+  }
+}
+
 
 // ------------------------------------------------------------------------------ launchers
 // Blocks per kind, tiles per row, packed for the kernel's preloaded scalars.  A geometry the packing cannot hold is refused:
@@ -496,6 +539,17 @@ hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float*
 
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st) {
   hipLaunchKernelGGL(xgmi_allreduce_kernel, blocks256(n), dim3(256), 0, st, x, buf, n, seq);
+  return hipGetLastError();
+}
+
+hipError_t launch_valid_accum(const float* loss, int n, double* acc, hipStream_t st) {
+  hipLaunchKernelGGL(valid_accum_kernel, dim3(1), dim3(256), 0, st, loss, n, acc);
+  return hipGetLastError();
+}
+
+hipError_t launch_keep_best(double* acc, double* best, int32_t* best_epoch, int32_t epoch, const float* theta, float* best_theta,
+                            int64_t n, double* val_hist, hipStream_t st) {
+  hipLaunchKernelGGL(keep_best_kernel, dim3(1), dim3(1024), 0, st, acc, best, best_epoch, epoch, theta, best_theta, n, val_hist);
   return hipGetLastError();
 }
 

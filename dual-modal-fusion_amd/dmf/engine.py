@@ -9,7 +9,11 @@ What it removes from the reference's hot loop (solver/mainsolver.py:49-58):
   * `loss.item()` every step                               -> per-step mean loss kept on the device;
   * per-launch host work                                   -> an epoch plan (shuffled coordinates + labels) is
     uploaded once and a captured hipGraph of `steps_per_graph` steps is replayed; batch cursor and the
-    Adam step count live in device memory.
+    Adam step count live in device memory;
+  * the host between the phases of an epoch                -> `train.epoch_block`: the plan holds the full batches of several
+    epochs (`TrainEngine.load_block`, checked on the host copy), the short last batch is stepped from the device copy
+    (`step_short`), the validation sum is formed by `EvalEngine.valid_accum` and judged by `dmf_keep_best`: no host sync
+    until the block ends.
 Data parallel (world_size > 1) gives identical updates on every rank, from ONE flat fp32 gradient per step: exchanged
 inside the reduce + Adam launch by a `dmf.xgmi.Communicator`, or all-reduced over the process group.  What runs after the
 backward, for every optimiser, loss-scaler and group form of both train engines: `_PlanEngine._update`.
@@ -506,6 +510,7 @@ class TrainEngine(_PlanEngine):
         if self.comm is not None and (self.comm.world != self.world or self.comm.capacity < self.theta.numel()):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
         self.plan_pack = self.win = None
+        self.short_xy = self.short_labels = self.short_hist = None       # load_block: the epochs' short last batches
         self.criterion = None
         self.fused = criterion is None
         if not self.fused:
@@ -585,6 +590,71 @@ class TrainEngine(_PlanEngine):
         pack = torch.cat([xy.view(n, 2 * self.B), lab.view(n, self.B)], 1).contiguous()
         self._install_plan(n, plan_xy=xy, plan_labels=lab, plan_pack=pack)
         return n
+
+    # ------------------------------------------------------------------ a block of epochs as one plan (train.epoch_block)
+    def _host_ints(self, t, what):
+        t = torch.as_tensor(t)
+        if t.is_cuda:
+            raise lib.DmfError('load_block takes host arrays (%s is on the device): its checks run before the upload' % what)
+        return t.to(torch.int32).contiguous()
+
+    def _check_host(self, xy, lab):
+        """load_plan's two checks on the host copy: no device tensor is read."""
+        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
+        K = self.net.arch['K']
+        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
+            raise lib.DmfError('label outside [0, %d)' % K)
+
+    def load_block(self, xy_all, labels_all, short_xy=None, short_labels=None, capacity=None):
+        """The epoch-block form of load_plan: the full batches of SEVERAL consecutive epochs as one plan, xy_all [n*B, 2] and
+        labels_all [n*B] (host arrays, epoch after epoch), and the epochs' short last batches short_xy [E, r, 2], short_labels
+        [E, r] (0 < r < B; None: the epochs have none).  Bounds and labels are checked on the HOST copy before the upload, so
+        loading reads nothing back from the device.  `run_plan(steps, steps_per_graph)` then runs one epoch's steps at a time
+        on the running cursor, with that epoch's lr / betas set on the engine; `step_short(e)` steps epoch e's short batch;
+        `block_losses()` reads everything at the block's end.  loss_hist holds the whole block.
+        capacity (steps, default n): the plan tensors are sized for it, so that blocks of different lengths keep one shape
+        and with it the captured graph.  One GPU only."""
+        if self.world != 1:
+            raise lib.DmfError('load_block: one GPU only (the ranks of a data-parallel run check their exchange every epoch)')
+        xy, lab = self._host_ints(xy_all, 'xy_all').reshape(-1, 2), self._host_ints(labels_all, 'labels_all').reshape(-1)
+        if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
+            raise lib.DmfError('plan length must be a multiple of the batch size')
+        n = xy.shape[0] // self.B
+        self._check_host(xy, lab)
+        self.short_xy = self.short_labels = self.short_hist = None
+        if short_xy is not None:
+            sxy, slab = self._host_ints(short_xy, 'short_xy'), self._host_ints(short_labels, 'short_labels')
+            if sxy.dim() != 3 or sxy.shape[2] != 2 or tuple(slab.shape) != tuple(sxy.shape[:2]) or not 0 < sxy.shape[1] <= self.B:
+                raise lib.DmfError('short batches: short_xy [E, r, 2] and short_labels [E, r] with 0 < r <= %d' % self.B)
+            self._check_host(sxy.reshape(-1, 2), slab.reshape(-1))
+        cap = max(int(capacity or n), n, 1)
+        if cap > n:            # rows past the plan's end are never stepped on (plan_steps = n); pixel (0, 0), label 0
+            xy = torch.cat([xy, torch.zeros((cap - n) * self.B, 2, dtype=torch.int32)])
+            lab = torch.cat([lab, torch.zeros((cap - n) * self.B, dtype=torch.int32)])
+        dev = self.scene.device
+        plan = dict(plan_xy=xy.to(dev), plan_labels=lab.to(dev))
+        if self.fused:         # (load_plan: the window of a captured graph is refilled from the packed stream)
+            plan['plan_pack'] = torch.cat([xy.view(cap, 2 * self.B), lab.view(cap, self.B)], 1).contiguous().to(dev)
+        self._install_plan(cap, **plan)
+        self.plan_steps = n
+        if short_xy is not None:
+            self.short_xy, self.short_labels = sxy.to(dev), slab.to(dev)
+            self.short_hist = torch.zeros(sxy.shape[0], device=dev)
+        return n
+
+    def step_short(self, e):
+        """The short last batch of epoch e of the loaded block: one eager step on the device copy (load_block has checked it);
+        its mean loss stays in short_hist[e].  No host synchronisation."""
+        xy = self.short_xy[e]
+        self.step(xy, self.short_labels[e], check=False)
+        self.short_hist[e:e + 1].copy_(self.loss[:xy.shape[0]].mean().reshape(1))
+        if not self._counts_on_device():             # the eager step counted on the host: the plan steps that follow read the
+            self.dev_step.fill_(self.step_count)     # device counter (load_plan does this once per epoch)
+
+    def block_losses(self):
+        """(per-step mean losses of the plan steps run so far, the short batches' mean losses or None), on the host: the
+        block's two device-to-host copies."""
+        return self.loss_hist[:self.host_cursor].cpu(), None if self.short_hist is None else self.short_hist.cpu()
 
     def _plan_launch(self):
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=self.B, cursor=self.dev_cursor)
@@ -792,6 +862,28 @@ class EvalEngine(_ShardedEval):
             self._no_ce = True
             return None
         return self.ce[:n].double().sum()
+
+    def valid_accum(self, xy, labels, acc):
+        """acc [1] (device, float64) += what `ce_sum` gives for these n patches (xy [n, 2], labels [n]: int32 on the device,
+        checked by the caller), summed by dmf_valid_accum.  Which of the three forms applies is a property of the engine:
+          a criterion            dmf_ce_loss on the logits (loss[i] = n t_i / D);
+          the attention network  torch's cross-entropy on the device logits, times n, added on the device;
+          otherwise              the evaluation launch's own per-patch cross-entropy (dmf_forward_ce).
+        Returns nothing and does not synchronise."""
+        n = xy.shape[0]
+        self._check_batch(n)
+        if n == 0:
+            return
+        if self.criterion is not None:
+            cr = self.criterion
+            lib.ce_loss(self.predict(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
+        elif self.shape.attention:
+            acc += torch.nn.functional.cross_entropy(self.predict(xy)[0], labels.long()).double() * n
+            return
+        else:
+            inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
+            lib.forward_ce(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
+        lib.valid_accum(self.ce, n, acc)
 
     def _check_bounds(self, xy_host):
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)

@@ -94,6 +94,8 @@ def _load():
         'dmf_band_mean': (i32, [vp, i32, i64, i64, i32, vp, vp]),
         'dmf_confusion_accum': (i32, [vp, vp, i32, i32, vp, vp]),
         'dmf_labelmap_write': (i32, [vp, vp, i32, i32, vp, vp]),
+        'dmf_valid_accum': (i32, [vp, i32, vp, vp]),
+        'dmf_keep_best': (i32, [vp, vp, vp, i32, vp, vp, i64, vp, vp]),
         'dmf_pan2ms': (i32, [vp, i32, i32, i32, vp, vp]),
         'dmf_scene_minmax': (i32, [vp, i32, i64, vp, vp]),
         'dmf_scene_prepare': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
@@ -497,6 +499,28 @@ def confusion_accum(pred, target, K, matrix):
 
 def labelmap_write(pred, xy, W, label_map):
     check(_lib.dmf_labelmap_write(_ptr(pred), _ptr(xy), pred.numel(), W, _ptr(label_map), _stream()))
+
+
+def valid_accum(loss, n, acc):
+    """acc [1] float64 += the double-precision sum of loss[:n] (float32), in a fixed order (dmf_valid_accum)."""
+    _dev(loss, torch.float32, 'loss'); _dev(acc, torch.float64, 'acc')
+    if n > loss.numel() or acc.numel() < 1:
+        raise DmfError('valid_accum: loss holds %d terms, %d asked for' % (loss.numel(), n))
+    check(_lib.dmf_valid_accum(_ptr(loss), n, _ptr(acc), _stream()))
+
+
+def keep_best(acc, best, best_epoch, epoch, theta, best_theta, val_hist):
+    """The end of an epoch's validation pass (dmf_keep_best): val_hist[epoch] <- acc[0]; a sum strictly below best[0] becomes
+    the best, with best_epoch[0] and a copy of theta in best_theta; acc[0] <- 0.  Every tensor lives on the device."""
+    for t, dt, name in ((acc, torch.float64, 'acc'), (best, torch.float64, 'best'), (best_epoch, torch.int32, 'best_epoch'),
+                        (theta, torch.float32, 'theta'), (best_theta, torch.float32, 'best_theta'), (val_hist, torch.float64, 'val_hist')):
+        _dev(t, dt, name)
+    if not 0 <= epoch < val_hist.numel():
+        raise DmfError('keep_best: epoch %d outside the validation history of %d' % (epoch, val_hist.numel()))
+    if best_theta.numel() != theta.numel() or min(acc.numel(), best.numel(), best_epoch.numel()) < 1:
+        raise DmfError('keep_best: best_theta must have the size of theta; acc, best and best_epoch one element')
+    check(_lib.dmf_keep_best(_ptr(acc), _ptr(best), _ptr(best_epoch), epoch, _ptr(theta), _ptr(best_theta), theta.numel(),
+                             _ptr(val_hist), _stream()))
 
 
 def pan2ms(pan, H, W, out):

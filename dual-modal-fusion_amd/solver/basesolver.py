@@ -5,7 +5,8 @@ build the row-major pixel table, `dataset_dual`, `random_split` of the labelled 
 train / test / valid, five DataLoaders, `indicator()`.  Additions for the GPU path: the padded scenes are also kept
 resident in HBM (`self.scene`), and every loader has an index-only twin (`*_index_loader`) that yields pixel
 coordinates instead of materialised patches.  Iterating either twin consumes the global RNG exactly like the
-reference's loader does, so a seeded run visits the same patches in the same order.
+reference's loader does, so a seeded run visits the same patches in the same order.  `_epoch_streams` gives the train twin's
+next passes as arrays, without the loader and with the same RNG stream (`train.epoch_block`, solver.mainsolver).
 `scene_prep: device` (NEW; fast path only, the drop-in path ignores it): the resident scene is normalised, padded and converted
 on the GPU from the raw scenes (dmf.engine.Scene.from_raw), and the padded host arrays `self.MS` / `self.PAN` — and with them
 the arrays behind the materialising loaders — are computed only when something asks for them.
@@ -20,6 +21,26 @@ from torch.utils.data import DataLoader, Subset
 from function.function import data_padding, data_padding_aux, data_show, label_mat2np, read_tif, split_data, split_data_old
 from indicators.kappa import aa_oa, expo_result
 from train.dataset import collate_batched, dataset_dual
+
+
+def epoch_orders(n, epochs, draws_after=0):
+    """The orders (int64 [epochs, n]) in which a `DataLoader(shuffle=True)` over n items visits them in its next `epochs`
+    passes, consuming the GLOBAL torch RNG exactly as iterating that loader `epochs` times would.  A pass draws twice from
+    it, each time as `torch.empty((), dtype=torch.int64).random_()`: the loader iterator's base seed, then the sampler's
+    seed, which seeds a fresh torch.Generator for `torch.randperm(n, generator=g)`.  draws_after: that many further draws
+    after every pass, the base seeds of loaders WITHOUT shuffling that are iterated once between two passes (the validation
+    loader of an epoch).  tests/test_epoch_block_host.py pins this against the real loader."""
+    def draw():
+        return int(torch.empty((), dtype=torch.int64).random_().item())
+    orders = torch.empty(epochs, n, dtype=torch.int64)
+    for e in range(epochs):
+        draw()
+        g = torch.Generator()
+        g.manual_seed(draw())
+        orders[e] = torch.randperm(n, generator=g)
+        for _ in range(draws_after):
+            draw()
+    return orders
 
 
 class BaseSolver:
@@ -123,6 +144,16 @@ class BaseSolver:
         self.valid_loader, self.valid_index_loader = self._loader(valid, cfg['color_batchsize'], False)
         self.color_loader1, self.color_index_loader1 = self._loader(color1, cfg['test_batchsize'], False)
         self.color_loader2, self.color_index_loader2 = self._loader(color2, cfg['test_batchsize'], False)
+
+    def _epoch_streams(self, epochs, draws_after=0):
+        """The next `epochs` passes over `train_index_loader` without the loader: (xy [epochs, n, 2], labels [epochs, n]) int32
+        on the host, row for row what iterating it gives (`epoch_orders`: same order, same RNG stream), taken from the index
+        dataset's arrays by fancy indexing.  Rows [k * batchsize, (k + 1) * batchsize) of a pass are its k-th batch."""
+        rows = np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)
+        rows = rows[epoch_orders(len(rows), epochs, draws_after).numpy()]
+        d = self.index_dataset
+        return (torch.from_numpy(np.stack([d.x[rows], d.y[rows]], -1).astype(np.int32)),
+                torch.from_numpy(d.label[rows].astype(np.int32)))
 
     def indicator(self):
         if self.cfg['test']['save_matrix']:

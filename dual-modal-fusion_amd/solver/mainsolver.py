@@ -20,6 +20,17 @@ defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gi
 loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
 `dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
 then steps eagerly from Python —, no xgmi exchange, the engine shards the batches).  Keys that are all neutral change nothing.
+`train.epoch_block: E` (NEW, default 1 = everything above unchanged): on the fast path `train()` works in blocks of up to E
+consecutive epochs (`block_length`: a block also ends where `<t>_curweights.pth` is due under `train.save_every`).  Inside a
+block the host only enqueues (`_enqueue_block`): the batch order comes from `BaseSolver._epoch_streams`, not from the
+DataLoader, the plan of all the block's epochs is checked on the host and uploaded once, the validation sum is formed by
+dmf_valid_accum and judged by dmf_keep_best, which keeps the best loss, its epoch and a copy of the best weights on the device.
+`_collect_block` waits for the device once and then does what the epochs would have done one by one: `step_losses`, the printed
+lines, `<t>_weights.pth`, `<t>_curweights.pth`, all with the same contents and the same RNG stream.  One difference:
+`<t>_weights.pth` appears at the end of the block in which the best epoch lies, not at that epoch (an interrupted run loses at
+most one block; a completed one leaves the same file).  With a scheduler and `steps_per_graph` > 0 the engine re-captures its
+graph whenever lr changes, and a capture synchronises (as it does with E = 1); the library's launch loop and a constant lr
+have no sync.  toStageSolver and data-parallel runs refuse E > 1; the drop-in path ignores the key.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -41,17 +52,26 @@ from solver.basesolver import BaseSolver
 from utils.utils import criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
 
 
+def block_length(epoch, epoch_block, save_every, epochs):
+    """Epochs in the block that starts at `epoch`: at most `epoch_block`, not past the epoch after which `<t>_curweights.pth`
+    is next due (every `save_every`-th), not past the last of `epochs`.  save_every 1 makes every block one epoch long."""
+    return max(1, min(epoch_block, save_every - epoch % save_every, epochs - epoch))
+
+
 class Solver(BaseSolver):
     """What a stage of the two-stage path (solver.tostagesolver) states differently is gathered in the hooks below
     `train()`: `engine_loss`, `_steps_per_graph`, `_train_engine`, `_eval_engine`, `_rank_batches`, `_step_short`, and for the
     drop-in path `_train_epoch_dropin`, `_valid_pass`, `_predict_dropin`, `_test_whole_split`."""
     engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
+    epoch_blocks = True                                  # `train.epoch_block` > 1 has a block form for this stage
 
     def __init__(self, cfg):
         keys = criterion_keys(cfg)
         if keys and (self.engine_loss != 'Criterion' or cfg['schedule']['loss'] != 'Criterion'):
             raise ValueError('schedule.%s belongs to schedule.loss: Criterion of Solver; %s trains with %s'
                              % (keys[0], type(self).__name__, cfg['schedule']['loss']))
+        self.cfg, self.rank, self.world = cfg, 0, 1
+        self._epoch_block()                            # (a stage without a block form refuses the key before anything is read)
         super().__init__(cfg)
         self.criterion = None                          # criterion_spec of the cfg, made by dataloader() (None: plain cross-entropy)
         self.train_labels = None
@@ -63,7 +83,8 @@ class Solver(BaseSolver):
         self.engine = self.eval_engine = None
         self.process_group = None                      # set by the launcher for data-parallel runs (test.py)
         self.comm = None
-        self.rank, self.world = 0, 1
+        self._valid_dev = None                         # the validation split on the device (epoch blocks), per dataloader() call
+        self.val_history, self.best_epoch = [], None   # what a blocked train() read back: validation sums, best epoch
         if self.cfg['train']['pretrained']:
             self.init_model()
 
@@ -86,6 +107,7 @@ class Solver(BaseSolver):
         (`class_weights: balanced` is computed here, once per call, from the train split's labels: the same numbers on every
         rank of a data-parallel run, which all draw the same split)."""
         super().dataloader()
+        self._valid_dev = None
         if criterion_keys(self.cfg):
             self.train_labels = self.index_dataset.label[np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)]
             self.criterion = criterion_spec(self.cfg, self.train_labels)
@@ -114,7 +136,21 @@ class Solver(BaseSolver):
                                 eng.step_count, group)
 
     # ------------------------------------------------------------------ train
+    def _epoch_block(self):
+        """train.epoch_block (NEW, default 1): epochs per block of the fast path's block form."""
+        E = int((self.cfg.get('train') or {}).get('epoch_block', 1) or 1)
+        if E < 1:
+            raise ValueError('train.epoch_block: %d is not a positive number of epochs' % E)
+        if E > 1 and not self.epoch_blocks:
+            raise ValueError('train.epoch_block: %d is out of scope for %s (its validation is a batch-coupled loss that is read '
+                             'back per batch): set it to 1' % (E, type(self).__name__))
+        if E > 1 and self.world > 1:
+            raise ValueError('train.epoch_block: %d is out of scope for data-parallel runs (%d ranks: they check their gradient '
+                             'exchange every epoch): set it to 1' % (E, self.world))
+        return E
+
     def train(self):
+        E = self._epoch_block()
         time1 = time.time()
         save_best = self.cfg['train']['save_best']
         best_loss = float('inf') if save_best else None
@@ -128,6 +164,8 @@ class Solver(BaseSolver):
             self._make_engines()
         train_epoch = self._train_epoch_fast if self.fast else self._train_epoch_dropin
         self.step_losses = []
+        if self.fast and E > 1:
+            self._train_blocks(E)                      # every epoch: the loop below finds none left
         while self.epoch < self.EPOCH:
             self.cur_model.train()
             last = train_epoch()
@@ -177,14 +215,18 @@ class Solver(BaseSolver):
             optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99)))
         self.eval_engine = self._eval_engine()
 
-    def _train_epoch_fast(self):
+    def _set_epoch_hparams(self, epoch):
         eng = self.engine
-        hp = epoch_hparams(self.cfg, self.epoch)              # lr (and, under OneCycleLR, beta1 / momentum) of this epoch
+        hp = epoch_hparams(self.cfg, epoch)                   # lr (and, under OneCycleLR, beta1 / momentum) of this epoch
         eng.lr = float(hp['lr'])
         if 'betas' in hp:
             eng.b1, eng.b2 = float(hp['betas'][0]), float(hp['betas'][1])
         if eng.optim == 'SGD':
             eng.momentum = float(hp['momentum'])
+
+    def _train_epoch_fast(self):
+        eng = self.engine
+        self._set_epoch_hparams(self.epoch)
         # the epoch's shuffled coordinates, as the batches the engine steps on and the size of a full one
         batches, B = self._rank_batches([self._xy_labels(b) for b in self.train_index_loader])
         full = [b for b in batches if b[0].shape[0] == B]
@@ -197,6 +239,111 @@ class Solver(BaseSolver):
         self._check_exchange()
         self.step_losses += losses
         return losses[-1] if losses else float('nan')
+
+    # ------------------------------------------------------------------ blocks of epochs without the host (train.epoch_block)
+    def _train_blocks(self, E):
+        """All epochs in blocks (module text).  Best loss, best epoch and best weights live on the device across blocks."""
+        dev, eng = self.DEVICE, self.engine
+        self._acc = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._best = torch.full((1,), float('inf'), dtype=torch.float64, device=dev)
+        self._best_epoch = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._best_theta = torch.zeros_like(eng.theta)
+        self._val_hist = torch.zeros(max(self.EPOCH, 1), dtype=torch.float64, device=dev)
+        self._host_best = float('inf')
+        self.val_history, self.best_epoch = [], 0 if self.cfg['train']['save_best'] else None
+        every = int(self.cfg['train'].get('save_every', 1) or 1)
+        self._block_cap = min(E, every, self.EPOCH)          # no block is longer: the plan keeps one shape
+        while self.epoch < self.EPOCH:
+            self.cur_model.train()
+            self._enqueue_block(self.epoch, block_length(self.epoch, E, every, self.EPOCH))
+            self._collect_block()
+
+    def _valid_split(self):
+        """(xy [n, 2], labels [n]) int32 on the device: the validation split in loader order, checked on the host and uploaded
+        once per dataloader() call."""
+        if self._valid_dev is None:
+            rows = np.asarray(self.valid_index_loader.dataset.indices, dtype=np.int64)
+            d, K = self.index_dataset, self.cur_model.arch['K']
+            xy = np.stack([d.x[rows], d.y[rows]], 1).astype(np.int32)
+            lab = d.label[rows].astype(np.int32)
+            self.eval_engine._check_bounds(xy)
+            if len(lab) and (lab.min() < 0 or lab.max() >= K):
+                raise ValueError('validation label outside [0, %d)' % K)
+            self._valid_dev = (torch.from_numpy(xy).to(self.DEVICE), torch.from_numpy(lab).to(self.DEVICE))
+        return self._valid_dev
+
+    def _enqueue_block(self, first_epoch, n_epochs):
+        """Enqueue epochs [first_epoch, first_epoch + n_epochs): per epoch the plan steps, the short last batch, the validation
+        launches in today's batches of `color_batchsize` rows (with class weights the batching is part of the number) and
+        dmf_keep_best.  NO host synchronisation: the uploads come first, on an idle device, and nothing is read back.  (A
+        captured graph that has to be re-captured, `steps_per_graph` > 0 with a changing lr, synchronises inside the engine.)"""
+        from dmf import lib
+        eng, B, save_best = self.engine, self.cfg['batchsize'], self.cfg['train']['save_best']
+        # the RNG draws of these epochs in today's order: the train loader's two, then the validation loader's base seed
+        xy, lab = self._epoch_streams(n_epochs, draws_after=1 if save_best else 0)
+        n_full, rest = divmod(xy.shape[1], B)
+        short = (xy[:, n_full * B:], lab[:, n_full * B:]) if rest else (None, None)      # DataLoader keeps the short last batch
+        eng.load_block(xy[:, :n_full * B].reshape(-1, 2), lab[:, :n_full * B].reshape(-1), *short,
+                       capacity=self._block_cap * n_full)
+        valid = self._valid_split() if save_best else None
+        vb = self.cfg['color_batchsize']
+        for e in range(n_epochs):
+            self._set_epoch_hparams(first_epoch + e)
+            if n_full:
+                eng.run_plan(n_full, self._steps_per_graph())
+            if rest:
+                eng.step_short(e)
+            if save_best:
+                with torch.no_grad():
+                    for i in range(0, valid[0].shape[0], vb):
+                        self.eval_engine.valid_accum(valid[0][i:i + vb], valid[1][i:i + vb], self._acc)
+                lib.keep_best(self._acc, self._best, self._best_epoch, first_epoch + e, eng.theta, self._best_theta,
+                              self._val_hist)
+        self._block = (first_epoch, n_epochs, n_full)
+
+    def _collect_block(self):
+        """The block's one wait for the device, then what its epochs owe the host, in their order: step losses (per epoch the
+        full batches, then the short one), the printed lines, `<t>_weights.pth` from the device's copy of the best weights if
+        the best moved in this block, `<t>_curweights.pth` where it is due."""
+        first, n_epochs, n_full = self._block
+        eng, cfg, out = self.engine, self.cfg, self.cfg['RESULT_output'] + str(self.time)
+        torch.cuda.synchronize()
+        full, short = eng.block_losses()
+        full, short = full.tolist(), None if short is None else short.tolist()
+        vals = self._val_hist[first:first + n_epochs].tolist() if cfg['train']['save_best'] else None
+        moved = False
+        for e in range(n_epochs):
+            losses = full[e * n_full:(e + 1) * n_full] + ([short[e]] if short is not None else [])
+            self.step_losses += losses
+            if vals is not None:
+                self.val_history.append(vals[e])
+                if vals[e] < self._host_best:                # the comparison dmf_keep_best made, on the same two doubles
+                    self._host_best, self.best_epoch, moved = vals[e], first + e, True
+                    if cfg['nohup']:
+                        print("best epoch now is {}".format(first + e))
+            if cfg['nohup']:
+                print("{} times {}th epoch is trained, loss {:.6f}".format(self.time, first + e, losses[-1] if losses else float('nan')))
+        if moved:
+            if int(self._best_epoch.item()) != self.best_epoch:
+                raise RuntimeError('the device kept epoch %d as the best, the validation history says %d'
+                                   % (int(self._best_epoch.item()), self.best_epoch))
+            torch.save(self._best_state_dict(), out + '_weights.pth')
+        self.epoch = first + n_epochs
+        every = int(cfg['train'].get('save_every', 1) or 1)
+        if self.epoch % every == 0 or self.epoch == self.EPOCH:
+            save_checkpoint(self.cur_model, self._export_optimizer(), out + '_curweights.pth')
+        if vals is not None:
+            self.cur_model.eval()
+
+    def _best_state_dict(self):
+        """The state dict of the best epoch: the net's own keys in their order, every parameter a piece of the device's copy
+        of the best flat vector (the net's name / offset table), the buffers as they are."""
+        net, flat = self.cur_model, self._best_theta.clone()
+        start = dict(zip(net._order(), net._offsets))
+        now = net.state_dict()
+        best = type(now)((k, flat[start[k]:start[k] + v.numel()].view(v.shape) if k in start else v) for k, v in now.items())
+        best._metadata = now._metadata
+        return best
 
     def _check_exchange(self):
         """A timed-out wait of the one-shot gradient exchange leaves the ranks with different weights (the kernel sums what

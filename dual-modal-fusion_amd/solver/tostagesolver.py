@@ -22,6 +22,8 @@ are solver.mainsolver's, with its two execution paths; what stage 2 states diffe
   _predict_dropin       argmax of net(ms, pan)                        pair_argmax of net(concat(ms, pan)) (:337)
   _test_whole_split     only with `test.full: 1` (reference: first    always (:331-341)
                         batch)
+  epoch_blocks          True: `train.epoch_block` > 1 trains in       False: `train.epoch_block` > 1 is refused
+                        blocks of epochs without the host
 
 Stage 1 (:86-238) trains `model.generator` / `model.discriminator`, which the reference does not ship: it
 is NOT built.  Run stage 2 on stage-1 outputs that already exist (`dqtl.pre_trained: 1`: `msgan.npy`, `pangan.npy`
@@ -48,6 +50,7 @@ from train.dataset import dataset_qua_dqtl
 
 class toStageSolver(Solver):
     engine_loss = 'qua_loss'
+    epoch_blocks = False                                 # (its validation is a batch-coupled loss read back per batch)
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 303   /* 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 304   /* 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -316,6 +316,19 @@ int32_t dmf_grad_reduce_xgmi_adam(const dmf_shape* shape, int32_t B, const void*
  * matrix [K, K] int64, rows = prediction. */
 int32_t dmf_confusion_accum(const int32_t* pred, const int32_t* target, int32_t B, int32_t K,
                             int64_t* matrix, void* stream);
+
+/* ---- an epoch's validation pass without the host (mainsolver.py:62-81; `train.epoch_block`) -----------
+ * acc[0] += sum_{i<n} (double)loss[i]: replaces `val_loss += loss.item() * n` per batch (mainsolver.py:70-71) with loss the
+ * per-patch terms dmf_forward_ce / dmf_ce_loss leave.  ONE workgroup, fixed order (lane t adds loss[t], loss[t + 256], ... in
+ * index order, then a fixed tree over the 256 lanes): the same bits on every run.  One lane reads, adds to and writes acc[0];
+ * the stream orders it against its neighbours.  n == 0 is a no-op. */
+int32_t dmf_valid_accum(const float* loss, int32_t n, double* acc, void* stream);
+/* The end of that pass, `if val_loss < best_loss` (mainsolver.py:77-81), in ONE launch of ONE workgroup: val = acc[0];
+ * val_hist[epoch] = val; if val < *best (strict; a NaN is never the best): *best = val, *best_epoch = epoch and
+ * best_theta[0..n) = theta[0..n); acc[0] = 0 for the next epoch.  The caller sizes val_hist (epoch < its length) and starts
+ * *best at +inf.  theta and best_theta must not overlap. */
+int32_t dmf_keep_best(double* acc, double* best, int32_t* best_epoch, int32_t epoch, const float* theta, float* best_theta,
+                      int64_t n, double* val_hist, void* stream);
 
 /* Replaces `label_np[x][y] = pred` (mainsolver.py:171-173,182-183): map [H, W] int32. */
 int32_t dmf_labelmap_write(const int32_t* pred, const int32_t* xy, int32_t B, int32_t W, int32_t* map, void* stream);

@@ -11,9 +11,9 @@ What it removes from the reference's hot loop (solver/mainsolver.py:49-58):
     uploaded once and a captured hipGraph of `steps_per_graph` steps is replayed; batch cursor and the
     Adam step count live in device memory;
   * the host between the phases of an epoch                -> `train.epoch_block`: the plan holds the full batches of several
-    epochs (`TrainEngine.load_block`, checked on the host copy), the short last batch is stepped from the device copy
-    (`step_short`), the validation sum is formed by `EvalEngine.valid_accum` and judged by `dmf_keep_best`: no host sync
-    until the block ends.
+    epochs (`TrainEngine.load_block`: host arrays, checked as they are by the ONE plan upload `_PlanEngine._upload_plan`), the
+    short last batch is stepped from the device copy (`step_short`), the validation sum is formed by `EvalEngine.valid_accum`
+    and judged by `dmf_keep_best`: no host sync until the block ends.
 Data parallel (world_size > 1) gives identical updates on every rank, from ONE flat fp32 gradient per step: exchanged
 inside the reduce + Adam launch by a `dmf.xgmi.Communicator`, or all-reduced over the process group.  What runs after the
 backward, for every optimiser, loss-scaler and group form of both train engines: `_PlanEngine._update`.
@@ -236,7 +236,7 @@ class _PlanEngine:
     def _hparams(self):
         return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha) + (self.scaler.hparams() if self.scaler is not None else ())
 
-    def _check_labels(self, lab):
+    def _check_labels(self, lab):                    # lab on the host, or on the device: its two extremes are then read back
         K = self.net.arch['K']
         if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
             raise lib.DmfError('label outside [0, %d)' % K)
@@ -323,36 +323,58 @@ class _PlanEngine:
         """An epoch of full GLOBAL batches: xy_all [n*per_rank*world, 2], labels_all [n*per_rank*world] (host or device, any
         int type).  Rank r keeps rows [r*per_rank, (r+1)*per_rank) of every batch's pixels, as the plan coordinates
         `rows(pixels)` where the step does not gather at the pixels themselves, and the labels of the whole batches."""
-        dev, W = self.scene.device, self.world
-        xy = torch.as_tensor(xy_all).to(torch.int32).cpu()
-        lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        if xy.shape[0] % (per_rank * W) or xy.shape[0] != lab.shape[0]:
-            raise lib.DmfError('plan length must be a multiple of the (global) batch size')
-        n = xy.shape[0] // (per_rank * W)
-        if W > 1:
-            xy = xy.view(n, W, per_rank, 2)[:, self.rank].reshape(-1, 2)
-        if rows is not None:
-            xy = rows(xy)
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
-        self._check_labels(lab)
-        self._install_plan(n, plan_xy=xy.to(dev).contiguous(), plan_labels=lab)
-        return n
+        def mine(xy, n):
+            if self.world > 1:
+                xy = xy.view(n, self.world, per_rank, 2)[:, self.rank].reshape(-1, 2)
+            return xy if rows is None else rows(xy)
+        return self._upload_plan(xy_all, labels_all, per_rank * self.world, mine=mine)
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
-    def _install_plan(self, n, **plan):
-        """Make `plan` (attribute name -> device tensor) the loaded plan of n steps and rewind to its first step.  A plan of
-        the same shape is copied into the tensors already there: a captured graph keeps reading valid addresses."""
+    def _upload_plan(self, xy_all, labels_all, rows, capacity=None, pack=False, mine=None):
+        """THE plan upload (load_plan, _load_global_plan, load_block): xy_all [n*rows, 2], labels_all [n*rows] (host or device,
+        any int type) become the loaded plan of n steps; returns n.  Bounds and labels are checked on a host copy: the caller's
+        own arrays, or ONE device-to-host copy of its device tensors, which then are the plan without another upload.
+        capacity (steps): the plan tensors are sized for it, padded with pixel (0, 0) and label 0, which are never stepped on.
+        pack: also `plan_pack`, the stream step by step [2*rows coordinates | rows labels]: the window of a captured graph is
+        refilled from it with ONE device copy per replay.  mine(xy, steps): a global plan's host pixels -> this rank's rows."""
+        dev = self.scene.device
+        xy, lab = torch.as_tensor(xy_all).to(torch.int32), torch.as_tensor(labels_all).to(torch.int32)
+        if xy.shape[0] % rows or xy.shape[0] != lab.shape[0]:
+            raise lib.DmfError('plan length must be a multiple of the %sbatch size' % ('' if mine is None else '(global) '))
+        n = xy.shape[0] // rows
+        cap = max(int(capacity or n), n)
+        xy_h, lab_h = xy.cpu(), lab.cpu()
+        if cap > n:
+            xy = xy_h = torch.cat([xy_h, torch.zeros((cap - n) * rows, 2, dtype=torch.int32)])
+            lab = lab_h = torch.cat([lab_h, torch.zeros((cap - n) * rows, dtype=torch.int32)])
+        if mine is not None:
+            xy = xy_h = mine(xy_h, cap)
+        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_h.numpy())
+        self._check_labels(lab_h)
+        plan = dict(plan_xy=xy.to(dev).contiguous(), plan_labels=lab.to(dev).contiguous())
+        if pack:
+            plan['plan_pack'] = torch.cat([plan['plan_xy'].view(cap, 2 * rows), plan['plan_labels'].view(cap, rows)], 1).contiguous()
+        self._install_plan(n, cap, **plan)
+        return n
+
+    def _install_plan(self, n, capacity, **plan):
+        """Make `plan` (attribute name -> device tensor, `capacity` steps long) the loaded plan of n steps and rewind to its first
+        step.  A plan of the same shape is copied into the tensors already there: a captured graph keeps reading valid addresses."""
         if self.plan_xy is not None and self.plan_xy.shape == plan['plan_xy'].shape:
             for name, t in plan.items():
                 getattr(self, name).copy_(t)
         else:
             for name, t in plan.items():
                 setattr(self, name, t)
-            self.loss_hist = torch.empty(max(n, 1), device=self.scene.device)
+            self.loss_hist = torch.empty(max(capacity, 1), device=self.scene.device)
             self.graph = None
         self.loss_hist.zero_()
         self.dev_cursor.zero_()
         self.host_cursor, self.plan_steps = 0, n
+        self._seed_dev_step()
+
+    def _seed_dev_step(self):
+        """Plan steps read the device step counter: where eager steps count on the host, that count goes into it."""
         if not self._counts_on_device():
             self.dev_step.fill_(self.step_count)
 
@@ -573,23 +595,11 @@ class TrainEngine(_PlanEngine):
 
     # ------------------------------------------------------------------ epoch plan + hipGraph replay
     def load_plan(self, xy_all, labels_all):
-        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type); the
-        unit-gradient step: an epoch of global batches (_load_global_plan)."""
+        """Upload an epoch's shuffled stream: xy_all [n*B, 2], labels_all [n*B] (host or device, any int type; _upload_plan);
+        the unit-gradient step: an epoch of global batches (_load_global_plan)."""
         if not self.fused:
             return self._load_global_plan(xy_all, labels_all, self.B)
-        dev = self.scene.device
-        xy = torch.as_tensor(xy_all).to(device=dev, dtype=torch.int32).contiguous()
-        lab = torch.as_tensor(labels_all).to(device=dev, dtype=torch.int32).contiguous()
-        if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
-            raise lib.DmfError('plan length must be a multiple of the batch size')
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.cpu().numpy())
-        self._check_labels(lab)
-        n = xy.shape[0] // self.B
-        # the same stream once more, step by step [n][2B coordinates | B labels]: the window of a captured graph is refilled
-        # from it with ONE device copy per replay
-        pack = torch.cat([xy.view(n, 2 * self.B), lab.view(n, self.B)], 1).contiguous()
-        self._install_plan(n, plan_xy=xy, plan_labels=lab, plan_pack=pack)
-        return n
+        return self._upload_plan(xy_all, labels_all, self.B, pack=True)
 
     # ------------------------------------------------------------------ a block of epochs as one plan (train.epoch_block)
     def _host_ints(self, t, what):
@@ -598,46 +608,27 @@ class TrainEngine(_PlanEngine):
             raise lib.DmfError('load_block takes host arrays (%s is on the device): its checks run before the upload' % what)
         return t.to(torch.int32).contiguous()
 
-    def _check_host(self, xy, lab):
-        """load_plan's two checks on the host copy: no device tensor is read."""
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy.numpy())
-        K = self.net.arch['K']
-        if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= K):
-            raise lib.DmfError('label outside [0, %d)' % K)
-
     def load_block(self, xy_all, labels_all, short_xy=None, short_labels=None, capacity=None):
         """The epoch-block form of load_plan: the full batches of SEVERAL consecutive epochs as one plan, xy_all [n*B, 2] and
-        labels_all [n*B] (host arrays, epoch after epoch), and the epochs' short last batches short_xy [E, r, 2], short_labels
-        [E, r] (0 < r < B; None: the epochs have none).  Bounds and labels are checked on the HOST copy before the upload, so
-        loading reads nothing back from the device.  `run_plan(steps, steps_per_graph)` then runs one epoch's steps at a time
-        on the running cursor, with that epoch's lr / betas set on the engine; `step_short(e)` steps epoch e's short batch;
-        `block_losses()` reads everything at the block's end.  loss_hist holds the whole block.
-        capacity (steps, default n): the plan tensors are sized for it, so that blocks of different lengths keep one shape
-        and with it the captured graph.  One GPU only."""
+        labels_all [n*B] (epoch after epoch), and the epochs' short last batches short_xy [E, r, 2], short_labels [E, r]
+        (0 < r < B; None: the epochs have none).  HOST arrays only, so that loading reads nothing back from the device.
+        `run_plan(steps, steps_per_graph)` then runs one epoch's steps at a time on the running cursor, with that epoch's lr /
+        betas set on the engine; `step_short(e)` steps epoch e's short batch; `block_losses()` reads everything at the block's
+        end.  capacity (steps, default n): blocks of different lengths keep one plan shape and with it the captured graph; the
+        loss history is as long.  One GPU only."""
         if self.world != 1:
             raise lib.DmfError('load_block: one GPU only (the ranks of a data-parallel run check their exchange every epoch)')
         xy, lab = self._host_ints(xy_all, 'xy_all').reshape(-1, 2), self._host_ints(labels_all, 'labels_all').reshape(-1)
-        if xy.shape[0] % self.B or xy.shape[0] != lab.shape[0]:
-            raise lib.DmfError('plan length must be a multiple of the batch size')
-        n = xy.shape[0] // self.B
-        self._check_host(xy, lab)
         self.short_xy = self.short_labels = self.short_hist = None
         if short_xy is not None:
             sxy, slab = self._host_ints(short_xy, 'short_xy'), self._host_ints(short_labels, 'short_labels')
             if sxy.dim() != 3 or sxy.shape[2] != 2 or tuple(slab.shape) != tuple(sxy.shape[:2]) or not 0 < sxy.shape[1] <= self.B:
                 raise lib.DmfError('short batches: short_xy [E, r, 2] and short_labels [E, r] with 0 < r <= %d' % self.B)
-            self._check_host(sxy.reshape(-1, 2), slab.reshape(-1))
-        cap = max(int(capacity or n), n, 1)
-        if cap > n:            # rows past the plan's end are never stepped on (plan_steps = n); pixel (0, 0), label 0
-            xy = torch.cat([xy, torch.zeros((cap - n) * self.B, 2, dtype=torch.int32)])
-            lab = torch.cat([lab, torch.zeros((cap - n) * self.B, dtype=torch.int32)])
-        dev = self.scene.device
-        plan = dict(plan_xy=xy.to(dev), plan_labels=lab.to(dev))
-        if self.fused:         # (load_plan: the window of a captured graph is refilled from the packed stream)
-            plan['plan_pack'] = torch.cat([xy.view(cap, 2 * self.B), lab.view(cap, self.B)], 1).contiguous().to(dev)
-        self._install_plan(cap, **plan)
-        self.plan_steps = n
+            lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, sxy.reshape(-1, 2).numpy())
+            self._check_labels(slab)
+        n = self._upload_plan(xy, lab, self.B, capacity=capacity or 1, pack=self.fused)      # (at least one step: tensors exist)
         if short_xy is not None:
+            dev = self.scene.device
             self.short_xy, self.short_labels = sxy.to(dev), slab.to(dev)
             self.short_hist = torch.zeros(sxy.shape[0], device=dev)
         return n
@@ -648,8 +639,7 @@ class TrainEngine(_PlanEngine):
         xy = self.short_xy[e]
         self.step(xy, self.short_labels[e], check=False)
         self.short_hist[e:e + 1].copy_(self.loss[:xy.shape[0]].mean().reshape(1))
-        if not self._counts_on_device():             # the eager step counted on the host: the plan steps that follow read the
-            self.dev_step.fill_(self.step_count)     # device counter (load_plan does this once per epoch)
+        self._seed_dev_step()
 
     def block_losses(self):
         """(per-step mean losses of the plan steps run so far, the short batches' mean losses or None), on the host: the
@@ -840,50 +830,47 @@ class EvalEngine(_ShardedEval):
             lib.forward(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, self.logits, self.pred)
         return self.logits[:n], self.pred[:n]
 
-    def ce_sum(self, xy, labels):
-        """Sum over the batch of the per-patch cross-entropy (device scalar, float64), from the evaluation launch itself
-        (dmf_forward_ce); None where the shape has no such kernel.  With a criterion: n times the criterion's batch loss of
-        these n patches, `criterion(output, target) * n` of the reference's validation loop (mainsolver.py:70-71), from
-        dmf_ce_loss on the logits."""
-        n = xy.shape[0]
-        self._check_batch(n)
+    def _patch_losses(self, xy, labels):
+        """self.ce[:n] <- one validation term per patch of xy [n, 2] with labels [n] (int32 on the device); False where the
+        shape has no such form, and the caller takes torch's cross-entropy on the logits of `predict`.  A property of the engine:
+          a criterion            dmf_ce_loss on the logits: loss[i] = n t_i / D, in sum `criterion(output, target) * n` of the
+                                 reference's validation loop (mainsolver.py:70-71);
+          the attention network  none;
+          otherwise              the evaluation launch's own per-patch cross-entropy (dmf_forward_ce), or none where the
+                                 library refuses the shape: asked once and remembered."""
         if self.criterion is not None:
             cr = self.criterion
-            if n == 0:
-                return torch.zeros((), dtype=torch.float64, device=self.scene.device)
             lib.ce_loss(self.predict(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
-            return self.ce[:n].double().sum()          # loss[i] = n t_i / D
+            return True
         if self.shape.attention or self._no_ce:
-            return None
+            return False
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         try:
             lib.forward_ce(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
         except lib.DmfError:
             self._no_ce = True
-            return None
-        return self.ce[:n].double().sum()
+            return False
+        return True
+
+    def ce_sum(self, xy, labels):
+        """Sum of `_patch_losses` over the batch (device scalar, float64, torch's reduction); None without a per-patch form."""
+        n = xy.shape[0]
+        self._check_batch(n)
+        if n == 0 and self.criterion is not None:
+            return torch.zeros((), dtype=torch.float64, device=self.scene.device)
+        return self.ce[:n].double().sum() if self._patch_losses(xy, labels) else None
 
     def valid_accum(self, xy, labels, acc):
-        """acc [1] (device, float64) += what `ce_sum` gives for these n patches (xy [n, 2], labels [n]: int32 on the device,
-        checked by the caller), summed by dmf_valid_accum.  Which of the three forms applies is a property of the engine:
-          a criterion            dmf_ce_loss on the logits (loss[i] = n t_i / D);
-          the attention network  torch's cross-entropy on the device logits, times n, added on the device;
-          otherwise              the evaluation launch's own per-patch cross-entropy (dmf_forward_ce).
-        Returns nothing and does not synchronise."""
+        """acc [1] (device, float64) += the sum of `_patch_losses` (dmf_valid_accum), or without a per-patch form torch's
+        cross-entropy on the logits, times n, added on the device.  xy is checked by the caller.  No synchronisation."""
         n = xy.shape[0]
         self._check_batch(n)
         if n == 0:
             return
-        if self.criterion is not None:
-            cr = self.criterion
-            lib.ce_loss(self.predict(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
-        elif self.shape.attention:
-            acc += torch.nn.functional.cross_entropy(self.predict(xy)[0], labels.long()).double() * n
-            return
+        if self._patch_losses(xy, labels):
+            lib.valid_accum(self.ce, n, acc)
         else:
-            inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
-            lib.forward_ce(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
-        lib.valid_accum(self.ce, n, acc)
+            acc += torch.nn.functional.cross_entropy(self.predict(xy)[0], labels.long()).double() * n
 
     def _check_bounds(self, xy_host):
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)

@@ -16,21 +16,19 @@ Two execution paths, same arithmetic; `train()`, `test()` and `color()` choose b
 defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gives the switch; SGD / RMSprop are refused
 (the scaler step is ADAM), and the one-shot xgmi exchange is not used (it does not carry the scaler).
 `schedule.class_weights` (a list, or `balanced`: from the train split of each `dataloader()` call), `schedule.label_smoothing`,
-`schedule.focal_gamma` (NEW, all optional): the criterion becomes `nn.CrossEntropyLoss(weight=, label_smoothing=)` or the focal
+`schedule.focal_gamma` (all optional): the criterion becomes `nn.CrossEntropyLoss(weight=, label_smoothing=)` or the focal
 loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
 `dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
 then steps eagerly from Python —, no xgmi exchange, the engine shards the batches).  Keys that are all neutral change nothing.
-`train.epoch_block: E` (NEW, default 1 = everything above unchanged): on the fast path `train()` works in blocks of up to E
-consecutive epochs (`block_length`: a block also ends where `<t>_curweights.pth` is due under `train.save_every`).  Inside a
-block the host only enqueues (`_enqueue_block`): the batch order comes from `BaseSolver._epoch_streams`, not from the
-DataLoader, the plan of all the block's epochs is checked on the host and uploaded once, the validation sum is formed by
-dmf_valid_accum and judged by dmf_keep_best, which keeps the best loss, its epoch and a copy of the best weights on the device.
-`_collect_block` waits for the device once and then does what the epochs would have done one by one: `step_losses`, the printed
-lines, `<t>_weights.pth`, `<t>_curweights.pth`, all with the same contents and the same RNG stream.  One difference:
-`<t>_weights.pth` appears at the end of the block in which the best epoch lies, not at that epoch (an interrupted run loses at
-most one block; a completed one leaves the same file).  With a scheduler and `steps_per_graph` > 0 the engine re-captures its
-graph whenever lr changes, and a capture synchronises (as it does with E = 1); the library's launch loop and a constant lr
-have no sync.  toStageSolver and data-parallel runs refuse E > 1; the drop-in path ignores the key.
+`train.epoch_block: E` (default 1): `train()` chooses once between two loops that keep ONE epoch ledger (`_record_epoch`,
+`_save_current`).  `_train_epochs` is the loop described above.  It is not "a block of one": toStageSolver (its validation is read
+back per batch), data-parallel runs (the ranks check their exchange every epoch) and the drop-in path have no block form; the
+first two refuse E > 1, the last ignores it.  `_train_blocks` (fast path, E > 1) works in blocks of up to E
+epochs (`block_length`), inside which the host only enqueues (`_enqueue_block`) and then waits once (`_collect_block`): same
+ledger entries, same files, same RNG stream.  One difference: `<t>_weights.pth` appears at the end of the block in which the
+best epoch lies, not at that epoch (an interrupted run loses at most one block; a completed one leaves the same file).  With a
+scheduler and `steps_per_graph` > 0 the engine re-captures its graph whenever lr changes, and a capture synchronises (as with
+E = 1); the library's launch loop and a constant lr have no sync.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -42,6 +40,7 @@ helpers (:110-136,211-441) are out of scope; `nohup: 1` does not crash (referenc
 import importlib
 import itertools
 import time
+import types
 
 import numpy as np
 import torch
@@ -84,7 +83,8 @@ class Solver(BaseSolver):
         self.process_group = None                      # set by the launcher for data-parallel runs (test.py)
         self.comm = None
         self._valid_dev = None                         # the validation split on the device (epoch blocks), per dataloader() call
-        self.val_history, self.best_epoch = [], None   # what a blocked train() read back: validation sums, best epoch
+        self._block = None                             # the device state of a train() in blocks (_train_blocks)
+        self.val_history, self.best_loss, self.best_epoch = [], float('inf'), None     # the epoch ledger (_record_epoch)
         if self.cfg['train']['pretrained']:
             self.init_model()
 
@@ -137,7 +137,7 @@ class Solver(BaseSolver):
 
     # ------------------------------------------------------------------ train
     def _epoch_block(self):
-        """train.epoch_block (NEW, default 1): epochs per block of the fast path's block form."""
+        """train.epoch_block (default 1): epochs per block of the fast path's block form."""
         E = int((self.cfg.get('train') or {}).get('epoch_block', 1) or 1)
         if E < 1:
             raise ValueError('train.epoch_block: %d is not a positive number of epochs' % E)
@@ -152,9 +152,6 @@ class Solver(BaseSolver):
     def train(self):
         E = self._epoch_block()
         time1 = time.time()
-        save_best = self.cfg['train']['save_best']
-        best_loss = float('inf') if save_best else None
-        best_epoch = 0 if save_best else None
         if not self.cfg['train']['pretrained']:
             self.init_model()
         self.cur_model = self.model.to(self.DEVICE)
@@ -162,37 +159,62 @@ class Solver(BaseSolver):
             self.loss = self.loss.to(self.DEVICE)             # (the class weights are a buffer of the module)
         if self.fast:
             self._make_engines()
-        train_epoch = self._train_epoch_fast if self.fast else self._train_epoch_dropin
-        self.step_losses = []
+        self.step_losses, self.val_history, self.best_loss = [], [], float('inf')
+        self.best_epoch = 0 if self.cfg['train']['save_best'] else None
         if self.fast and E > 1:
-            self._train_blocks(E)                      # every epoch: the loop below finds none left
+            self._train_blocks(E)
+        else:
+            self._train_epochs(self._train_epoch_fast if self.fast else self._train_epoch_dropin)
+        self.train_time = time.time() - time1
+        self.epoch = 0
+
+    def _train_epochs(self, train_epoch):
+        """Epoch by epoch: `train.epoch_block: 1`, and whatever has no block form (module text)."""
+        save_best = self.cfg['train']['save_best']
         while self.epoch < self.EPOCH:
             self.cur_model.train()
-            last = train_epoch()
+            losses = train_epoch()
+            val = None
             if save_best:
                 self.cur_model.eval()
-                val_loss = self._valid_pass(best_loss)
-                if val_loss < best_loss:
-                    best_loss, best_epoch = val_loss, self.epoch
-                    if self.rank == 0:
-                        torch.save(self.cur_model.state_dict(), self.cfg['RESULT_output'] + str(self.time) + '_weights.pth')
-                    if self.cfg['nohup']:
-                        print("best epoch now is {}".format(self.epoch))
-            # `<t>_curweights.pth` (model + optimiser, mainsolver.py:83-84) is what an interrupted run resumes from; the reference
-            # writes it after EVERY epoch, which on the fast path is half of a small epoch's wall time (tools/solver_epoch_profile.sh:
-            # 2.8 of 5.6 ms).  train.save_every: N (NEW, default 1 = the reference) writes it every N-th epoch and after the last.
-            every = int(self.cfg['train'].get('save_every', 1) or 1)
-            if self.rank == 0 and ((self.epoch + 1) % every == 0 or self.epoch + 1 == self.EPOCH):
-                opt = self._export_optimizer() if self.fast else self.optimizer
-                save_checkpoint(self.cur_model, opt, self.cfg['RESULT_output'] + str(self.time) + '_curweights.pth')
+                val = self._valid_pass(self.best_loss)
+            if self._record_epoch(self.epoch, losses, val) and self.rank == 0:
+                torch.save(self.cur_model.state_dict(), self.cfg['RESULT_output'] + str(self.time) + '_weights.pth')
+            self._save_current(self.epoch + 1)
             if self.world > 1:
                 import torch.distributed as dist
                 dist.barrier(self.process_group)               # the files exist before any rank goes on to load them
-            if self.cfg['nohup']:
-                print("{} times {}th epoch is trained, loss {:.6f}".format(self.time, self.epoch, last))
             self.epoch += 1
-        self.train_time = time.time() - time1
-        self.epoch = 0
+
+    # ------------------------------------------------------------------ the epoch ledger of both forms
+    def _record_epoch(self, epoch, losses, val=None):
+        """A finished epoch: its step losses, what `_valid_pass` or the device gave for it (None: no `save_best`; the validation
+        sum, or on the drop-in path and in stage 2 the running sum at the early exit), the printed lines.  Returns whether
+        the best moved — strict, the reference's `if val_loss < best_loss` and dmf_keep_best's comparison on the same double: an
+        equal value and a NaN are never the best —; the caller writes `<t>_weights.pth`, at the epoch or at its block's end."""
+        self.step_losses += losses
+        moved = False
+        if val is not None:
+            self.val_history.append(val)
+            moved = val < self.best_loss
+            if moved:
+                self.best_loss, self.best_epoch = val, epoch
+                if self.cfg['nohup']:
+                    print("best epoch now is {}".format(epoch))
+        if self.cfg['nohup']:
+            print("{} times {}th epoch is trained, loss {:.6f}".format(self.time, epoch, losses[-1] if losses else float('nan')))
+        return moved
+
+    def _save_every(self):
+        return int(self.cfg['train'].get('save_every', 1) or 1)
+
+    def _save_current(self, done):
+        """`<t>_curweights.pth` (model + optimiser, mainsolver.py:83-84: what an interrupted run resumes from) after `done` finished
+        epochs, where it is due: after every `train.save_every`-th (default 1 = the reference; on the fast path that is 2.8 of a
+        small epoch's 5.6 ms, tools/solver_epoch_profile.sh) and after the last."""
+        if self.rank == 0 and (done % self._save_every() == 0 or done == self.EPOCH):
+            opt = self._export_optimizer() if self.fast else self.optimizer
+            save_checkpoint(self.cur_model, opt, self.cfg['RESULT_output'] + str(self.time) + '_curweights.pth')
 
     def _loss_scaler(self, hp):
         """gmf.half: 1 on the fast path -> the device loss scaler with GradScaler's defaults; its step is ADAM."""
@@ -237,22 +259,18 @@ class Solver(BaseSolver):
             losses = eng.losses().tolist()
         losses += [self._step_short(xy, lab) for xy, lab in batches if xy.shape[0] != B]    # DataLoader keeps the short last batch
         self._check_exchange()
-        self.step_losses += losses
-        return losses[-1] if losses else float('nan')
+        return losses
 
     # ------------------------------------------------------------------ blocks of epochs without the host (train.epoch_block)
     def _train_blocks(self, E):
-        """All epochs in blocks (module text).  Best loss, best epoch and best weights live on the device across blocks."""
-        dev, eng = self.DEVICE, self.engine
-        self._acc = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._best = torch.full((1,), float('inf'), dtype=torch.float64, device=dev)
-        self._best_epoch = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._best_theta = torch.zeros_like(eng.theta)
-        self._val_hist = torch.zeros(max(self.EPOCH, 1), dtype=torch.float64, device=dev)
-        self._host_best = float('inf')
-        self.val_history, self.best_epoch = [], 0 if self.cfg['train']['save_best'] else None
-        every = int(self.cfg['train'].get('save_every', 1) or 1)
-        self._block_cap = min(E, every, self.EPOCH)          # no block is longer: the plan keeps one shape
+        """All epochs in blocks (module text).  What dmf_valid_accum and dmf_keep_best keep across blocks lives on the device."""
+        dev, f64, every = self.DEVICE, torch.float64, self._save_every()
+        self._block = types.SimpleNamespace(
+            acc=torch.zeros(1, dtype=f64, device=dev), best=torch.full((1,), float('inf'), dtype=f64, device=dev),
+            best_epoch=torch.zeros(1, dtype=torch.int32, device=dev), best_theta=torch.zeros_like(self.engine.theta),
+            val_hist=torch.zeros(max(self.EPOCH, 1), dtype=f64, device=dev),
+            cap=min(E, every, self.EPOCH),               # epochs in the longest block: the plan keeps one shape
+            enqueued=None)                               # (first epoch, epochs, full batches per epoch) of the block under way
         while self.epoch < self.EPOCH:
             self.cur_model.train()
             self._enqueue_block(self.epoch, block_length(self.epoch, E, every, self.EPOCH))
@@ -278,13 +296,13 @@ class Solver(BaseSolver):
         dmf_keep_best.  NO host synchronisation: the uploads come first, on an idle device, and nothing is read back.  (A
         captured graph that has to be re-captured, `steps_per_graph` > 0 with a changing lr, synchronises inside the engine.)"""
         from dmf import lib
-        eng, B, save_best = self.engine, self.cfg['batchsize'], self.cfg['train']['save_best']
+        eng, blk, B, save_best = self.engine, self._block, self.cfg['batchsize'], self.cfg['train']['save_best']
         # the RNG draws of these epochs in today's order: the train loader's two, then the validation loader's base seed
         xy, lab = self._epoch_streams(n_epochs, draws_after=1 if save_best else 0)
         n_full, rest = divmod(xy.shape[1], B)
         short = (xy[:, n_full * B:], lab[:, n_full * B:]) if rest else (None, None)      # DataLoader keeps the short last batch
         eng.load_block(xy[:, :n_full * B].reshape(-1, 2), lab[:, :n_full * B].reshape(-1), *short,
-                       capacity=self._block_cap * n_full)
+                       capacity=blk.cap * n_full)
         valid = self._valid_split() if save_best else None
         vb = self.cfg['color_batchsize']
         for e in range(n_epochs):
@@ -296,49 +314,38 @@ class Solver(BaseSolver):
             if save_best:
                 with torch.no_grad():
                     for i in range(0, valid[0].shape[0], vb):
-                        self.eval_engine.valid_accum(valid[0][i:i + vb], valid[1][i:i + vb], self._acc)
-                lib.keep_best(self._acc, self._best, self._best_epoch, first_epoch + e, eng.theta, self._best_theta,
-                              self._val_hist)
-        self._block = (first_epoch, n_epochs, n_full)
+                        self.eval_engine.valid_accum(valid[0][i:i + vb], valid[1][i:i + vb], blk.acc)
+                lib.keep_best(blk.acc, blk.best, blk.best_epoch, first_epoch + e, eng.theta, blk.best_theta, blk.val_hist)
+        blk.enqueued = (first_epoch, n_epochs, n_full)
 
     def _collect_block(self):
-        """The block's one wait for the device, then what its epochs owe the host, in their order: step losses (per epoch the
-        full batches, then the short one), the printed lines, `<t>_weights.pth` from the device's copy of the best weights if
-        the best moved in this block, `<t>_curweights.pth` where it is due."""
-        first, n_epochs, n_full = self._block
-        eng, cfg, out = self.engine, self.cfg, self.cfg['RESULT_output'] + str(self.time)
+        """The block's one wait for the device, then what its epochs owe the host, in their order: the ledger entries (step
+        losses: per epoch the full batches, then the short one), `<t>_weights.pth` from the device's copy of the best weights
+        if the best moved in this block, `<t>_curweights.pth` where it is due."""
+        blk = self._block
+        first, n_epochs, n_full = blk.enqueued
         torch.cuda.synchronize()
-        full, short = eng.block_losses()
+        full, short = self.engine.block_losses()
         full, short = full.tolist(), None if short is None else short.tolist()
-        vals = self._val_hist[first:first + n_epochs].tolist() if cfg['train']['save_best'] else None
+        vals = blk.val_hist[first:first + n_epochs].tolist() if self.cfg['train']['save_best'] else [None] * n_epochs
         moved = False
         for e in range(n_epochs):
             losses = full[e * n_full:(e + 1) * n_full] + ([short[e]] if short is not None else [])
-            self.step_losses += losses
-            if vals is not None:
-                self.val_history.append(vals[e])
-                if vals[e] < self._host_best:                # the comparison dmf_keep_best made, on the same two doubles
-                    self._host_best, self.best_epoch, moved = vals[e], first + e, True
-                    if cfg['nohup']:
-                        print("best epoch now is {}".format(first + e))
-            if cfg['nohup']:
-                print("{} times {}th epoch is trained, loss {:.6f}".format(self.time, first + e, losses[-1] if losses else float('nan')))
+            moved = self._record_epoch(first + e, losses, vals[e]) or moved
         if moved:
-            if int(self._best_epoch.item()) != self.best_epoch:
+            if int(blk.best_epoch.item()) != self.best_epoch:
                 raise RuntimeError('the device kept epoch %d as the best, the validation history says %d'
-                                   % (int(self._best_epoch.item()), self.best_epoch))
-            torch.save(self._best_state_dict(), out + '_weights.pth')
+                                   % (int(blk.best_epoch.item()), self.best_epoch))
+            torch.save(self._best_state_dict(), self.cfg['RESULT_output'] + str(self.time) + '_weights.pth')
         self.epoch = first + n_epochs
-        every = int(cfg['train'].get('save_every', 1) or 1)
-        if self.epoch % every == 0 or self.epoch == self.EPOCH:
-            save_checkpoint(self.cur_model, self._export_optimizer(), out + '_curweights.pth')
-        if vals is not None:
+        self._save_current(self.epoch)
+        if self.cfg['train']['save_best']:
             self.cur_model.eval()
 
     def _best_state_dict(self):
         """The state dict of the best epoch: the net's own keys in their order, every parameter a piece of the device's copy
         of the best flat vector (the net's name / offset table), the buffers as they are."""
-        net, flat = self.cur_model, self._best_theta.clone()
+        net, flat = self.cur_model, self._block.best_theta.clone()
         start = dict(zip(net._order(), net._offsets))
         now = net.state_dict()
         best = type(now)((k, flat[start[k]:start[k] + v.numel()].view(v.shape) if k in start else v) for k, v in now.items())
@@ -400,7 +407,7 @@ class Solver(BaseSolver):
     # ------------------------------------------------------------------ ... and drop-in path
     def _train_epoch_dropin(self):
         loader = self._bar(self.train_loader)
-        last = float('nan')
+        losses = []
         for data1, data2, target, _, _ in loader:
             data1, data2, target = data1.to(self.DEVICE), data2.to(self.DEVICE), target.to(self.DEVICE)
             self.optimizer.zero_grad()
@@ -408,13 +415,12 @@ class Solver(BaseSolver):
             loss = self.loss(output, target.long())
             loss.backward()
             self.optimizer.step()
-            last = loss.item()
-            self.step_losses.append(last)
+            losses.append(loss.item())
             if not self.cfg['nohup']:
-                loader.set_postfix(ls=last, ep=self.epoch, tm=self.time, m='train', d=self.cfg['device'])
+                loader.set_postfix(ls=losses[-1], ep=self.epoch, tm=self.time, m='train', d=self.cfg['device'])
         if self.cfg['schedule']['if_scheduler']:
             self.scheduler.step()
-        return last
+        return losses
 
     def _valid_pass(self, best_loss):
         ce = self.loss if self.criterion is not None else torch.nn.CrossEntropyLoss()

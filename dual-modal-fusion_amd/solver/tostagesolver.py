@@ -5,7 +5,8 @@ are padded, sliced by `dataset_qua_dqtl`, concatenated on the batch axis and pus
 (`model.<model_name>.Net(args=cfg)` called as `net(data)`; this build's GMFNet takes the band mean of its input as the
 auxiliary modality, cfg['gmf']['single_input'] = 1), trained with `qua_loss` + ADAM, best epoch by the early-stopping
 validation loop, prediction = argmax softmax(out[:bs] + out[bs:2bs]).  `train()`, the fast epoch, `test()` and `color()`
-are solver.mainsolver's, with its two execution paths; what stage 2 states differently is the hooks below, and nothing else:
+are solver.mainsolver's, with its two execution paths, its epoch loop (`_train_epochs`) and its epoch ledger (`_record_epoch`,
+`_save_current`); what stage 2 states differently is the hooks below, and nothing else:
 
   hook                  Solver                                        toStageSolver
   engine_loss             Criterion                                     qua_loss
@@ -17,13 +18,15 @@ are solver.mainsolver's, with its two execution paths; what stage 2 states diffe
   _steps_per_graph      default -1 (the library's launch loop)        default 0, and 0 unless the engine has the unit-gradient step
   _step_short           device tensors; mean per-patch loss           host tensors; the engine's batch loss
   _train_epoch_dropin   net(ms, pan), Criterion (:49-55)              net(concat of the four streams), qua_loss (:268-278; the same
-                                                                      HIP loss kernel behind an autograd Function)
+  (returns the epoch's                                                HIP loss kernel behind an autograd Function)
+  step losses)
   _valid_pass           cross-entropy; fast: summed on the device     qua_loss, read back per batch on both paths (early exit, :288-296)
+  (the ledger's value)  (EvalEngine.ce_sum)
   _predict_dropin       argmax of net(ms, pan)                        pair_argmax of net(concat(ms, pan)) (:337)
   _test_whole_split     only with `test.full: 1` (reference: first    always (:331-341)
                         batch)
-  epoch_blocks          True: `train.epoch_block` > 1 trains in       False: `train.epoch_block` > 1 is refused
-                        blocks of epochs without the host
+  epoch_blocks          True: `train.epoch_block` > 1 trains in       False: `train.epoch_block` > 1 is refused, the epoch loop
+                        blocks of epochs (`_train_blocks`)            is the only one
 
 Stage 1 (:86-238) trains `model.generator` / `model.discriminator`, which the reference does not ship: it
 is NOT built.  Run stage 2 on stage-1 outputs that already exist (`dqtl.pre_trained: 1`: `msgan.npy`, `pangan.npy`
@@ -128,7 +131,7 @@ class toStageSolver(Solver):
     # ------------------------------------------------------------------ ... and drop-in path
     def _train_epoch_dropin(self):
         loader = self._bar(self.train_loader)
-        last = float('nan')
+        losses = []
         for data1, data2, data3, data4, target, _, _ in loader:
             data = torch.concat([data1, data2, data3, data4]).to(self.DEVICE)            # tostagesolver.py:270-272
             target = target.to(self.DEVICE)
@@ -138,13 +141,12 @@ class toStageSolver(Solver):
             loss = self.loss(output, bs, target, self.cfg)
             loss.backward()
             self.optimizer.step()
-            last = loss.item()
-            self.step_losses.append(last)
+            losses.append(loss.item())
             if not self.cfg['nohup']:
-                loader.set_postfix(loss=last, epoch=self.epoch, time=self.time, mode='train')
+                loader.set_postfix(loss=losses[-1], epoch=self.epoch, time=self.time, mode='train')
         if self.cfg['schedule']['if_scheduler']:
             self.scheduler.step()
-        return last
+        return losses
 
     def _valid_pass(self, best_loss):
         val_loss = 0.0

@@ -441,3 +441,147 @@ def test_stage2_step_trains_on_this_ranks_shard(rank, rec, group, monkeypatch):
     assert loss[4].numel() == WORLD * bs and torch.equal(loss[4], labels[:WORLD * bs])
     with pytest.raises(lib.DmfError, match='no pixel each'):
         eng.step(xy[:WORLD - 1], labels[:WORLD - 1])
+
+
+# ------------------------------------------------------------------------------------------------ one plan upload
+def _fused_engine(B=8, attention=0):
+    """TrainEngine with the fused step on the shape of the tests above."""
+    from dmf.engine import Scene, TrainEngine
+    from model.gmfnet import Net
+    cfg = {'patch_size': 11, 'Categories_Number': K17, 'data_city': 's', 'DATA_DICT': {'s': {'size': [40, 40, 200]}},
+           'scale': 1, 'aux_bands': 1, 'gmf': {'width': 40, 'hidden': 64, 'pool_sigma': 2.5, 'attention': attention},
+           'trans': {'embed_dim': 96, 'num_head': 3}}
+    torch.manual_seed(0)
+    scene = Scene(np.zeros((50, 50, 200), np.float32), np.zeros((50, 50, 1), np.float32), 'cpu')
+    return TrainEngine(Net(cfg), scene, B, lr=2e-3)
+
+
+def _stream(n, B, seed=3):
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, 30, (n * B, 2)).astype(np.int32), rng.integers(0, K17, n * B).astype(np.int32)
+
+
+PLAN = ('plan_xy', 'plan_labels', 'plan_pack')
+
+
+@pytest.mark.parametrize('make', [_fused_engine, lambda: _criterion_engine('ce')], ids=['fused', 'criterion'])
+def test_load_block_loads_what_load_plan_loads(make):
+    """The same stream through both loaders: the same plan tensors, step count and loss history; under a capacity the rows past
+    the plan are zeros and are no steps; blocks of different lengths under one capacity stay in the same tensors."""
+    B, n = 8, 3
+    xy, labels = _stream(n, B)
+    a, b = make(), make()
+    assert a.load_plan(xy, labels) == n and b.load_block(xy, labels) == n
+    names = PLAN if a.fused else PLAN[:2]
+    assert (a.plan_pack is None) == (b.plan_pack is None) == (not a.fused)
+    for name in names:
+        ta, tb = getattr(a, name), getattr(b, name)
+        assert ta.dtype == tb.dtype == torch.int32 and ta.is_contiguous() and tb.is_contiguous() and torch.equal(ta, tb), name
+    assert torch.equal(a.plan_xy, torch.from_numpy(xy)) and torch.equal(a.plan_labels, torch.from_numpy(labels))
+    if a.fused:
+        assert torch.equal(a.plan_pack, torch.cat([a.plan_xy.view(n, 2 * B), a.plan_labels.view(n, B)], 1))
+    assert a.plan_steps == b.plan_steps == n and a.loss_hist.shape == b.loss_hist.shape == (n,)
+    assert a.host_cursor == b.host_cursor == 0 and not a.loss_hist.any() and not b.loss_hist.any()
+
+    cap = 5
+    assert b.load_block(xy, labels, capacity=cap) == n and b.plan_steps == n and b.loss_hist.shape == (cap,)
+    for name in names:
+        t = getattr(b, name)
+        assert t.shape[0] == getattr(a, name).shape[0] // n * cap
+        assert torch.equal(t[:getattr(a, name).shape[0]], getattr(a, name)) and not t[getattr(a, name).shape[0]:].any(), name
+    where = {name: getattr(b, name).data_ptr() for name in names + ('loss_hist',)}
+    xy2, labels2 = _stream(cap, B, seed=4)
+    for k in (2, cap, 1):
+        assert b.load_block(xy2[:k * B], labels2[:k * B], capacity=cap) == k and b.plan_steps == k
+        assert {name: getattr(b, name).data_ptr() for name in where} == where, k
+        assert torch.equal(b.plan_xy[:k * B], torch.from_numpy(xy2[:k * B])) and not b.plan_xy[k * B:].any()
+        assert torch.equal(b.plan_labels[:k * B], torch.from_numpy(labels2[:k * B])) and not b.plan_labels[k * B:].any()
+    from dmf import lib
+    with pytest.raises(lib.DmfError, match='plan length must be a multiple of the batch size'):
+        b.load_block(xy[:B + 1], labels[:B + 1])
+    with pytest.raises(lib.DmfError, match='label outside'):
+        b.load_block(xy, labels + K17)
+
+
+def test_step_short_after_plan_steps_reseeds_the_device_step_counter(rec):
+    """An engine that counts on the host (fused ADAM, no scaler): the eager short step takes the host count, and the plan steps
+    after it read a device counter that holds it."""
+    B, n, r = 8, 2, 3
+    eng = _fused_engine(B)
+    assert not eng._counts_on_device()
+    xy, labels = _stream(2 * n, B)
+    sxy, slab = _stream(2, r, seed=5)
+    eng.load_block(xy, labels, sxy.reshape(2, r, 2), slab.reshape(2, r))
+    assert eng.run_plan(n, 0) == n and int(eng.dev_step) == 0       # (the recorder launches nothing: the kernels count it up)
+    rec.take(eng)
+    eng.step_short(0)
+    inp = ('input', 1, r, 'sceneA', 'sceneB', 'short_xy', 50, 50, None, 0)
+    assert rec.take(eng, short_xy=eng.short_xy, short_labels=eng.short_labels) == _f32(
+        [('dmf_train_fwd_bwd', 'shape', inp, 'theta', 'pool_w', 'short_labels', 1.0 / r, 'logits', 'loss', 'ws', None, None)]
+        + expected_update(eng, r, None, None, 1.0, None, None, False, False))
+    assert eng.step_count == n + 1 and int(eng.dev_step) == n + 1 and eng.host_cursor == n
+    assert eng.run_plan(1, 0) == 1
+    launch = rec.take(eng)[0]
+    assert launch[0] == 'dmf_train_fwd_bwd' and launch[-2] == 'dev_step'           # adam_step_dev of the plan step
+
+
+# ------------------------------------------------------------------------------------------------ one validation-loss form
+def _eval_engine(form, B=8):
+    from dmf.engine import EvalEngine
+    train = _criterion_engine('ce', B=B) if form == 'criterion' else _fused_engine(B, attention=int(form == 'attention'))
+    eng = EvalEngine(train.net, train.scene, B, criterion=CRITERIA['ce'] if form == 'criterion' else None)
+    eng.logits.zero_()
+    return eng
+
+
+def _launches(rec, call):
+    rec.calls = []
+    out = call()
+    calls, rec.calls = rec.calls, []
+    return calls, out
+
+
+HELPER = {'plain': ['dmf_forward_ce'], 'criterion': ['dmf_forward', 'dmf_ce_loss'], 'attention': []}
+
+
+@pytest.mark.parametrize('form', sorted(HELPER))
+def test_validation_loss_launches(form, rec):
+    """`ce_sum` and `valid_accum` launch the same per-patch form; `valid_accum` then sums it by dmf_valid_accum.  The attention
+    network has no per-patch form: `ce_sum` says so, `valid_accum` adds torch's cross-entropy of the logits on the device."""
+    n = 5
+    eng = _eval_engine(form)
+    xy, labels = (torch.from_numpy(t) for t in _stream(1, n))
+    acc = torch.zeros(1, dtype=torch.float64)
+    summed, part = _launches(rec, lambda: eng.ce_sum(xy, labels))
+    accum, _ = _launches(rec, lambda: eng.valid_accum(xy, labels, acc))
+    assert [c[0] for c in summed] == HELPER[form]
+    if form == 'attention':
+        assert part is None and [c[0] for c in accum] == ['dmf_forward_attn']
+        assert float(acc) == pytest.approx(n * np.log(K17), rel=1e-6)         # (all logits are zero)
+    else:
+        assert part.dtype == torch.float64 and part.dim() == 0
+        assert accum == summed + [('dmf_valid_accum', eng.ce.data_ptr(), n, acc.data_ptr(), None)]
+        assert float(acc) == 0.0
+    assert _launches(rec, lambda: eng.valid_accum(xy[:0], labels[:0], acc))[0] == []
+
+
+def test_validation_loss_falls_back_once_where_forward_ce_is_refused(rec, monkeypatch):
+    """A shape without dmf_forward_ce: both take torch's cross-entropy on the logits, and the kernel is asked once."""
+    from dmf import lib
+    n, asked = 5, []
+
+    def refused(*args, **kw):
+        asked.append(1)
+        raise lib.DmfError('forward_ce: no kernel for this shape')
+    monkeypatch.setattr(lib, 'forward_ce', refused)
+    xy, labels = (torch.from_numpy(t) for t in _stream(1, n))
+    for first in ('ce_sum', 'valid_accum'):
+        del asked[:]
+        eng = _eval_engine('plain')
+        acc = torch.zeros(1, dtype=torch.float64)
+        for k in range(2):
+            if first == 'ce_sum':
+                assert _launches(rec, lambda: eng.ce_sum(xy, labels)) == ([], None)
+            calls, _ = _launches(rec, lambda: eng.valid_accum(xy, labels, acc))
+            assert [c[0] for c in calls] == ['dmf_forward'] and len(asked) == 1
+            assert float(acc) == pytest.approx((k + 1) * n * np.log(K17), rel=1e-6)

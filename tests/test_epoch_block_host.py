@@ -170,3 +170,55 @@ def test_entry_points_decide_on_the_host_before_any_launch(name, call, message):
         assert rc == 0                      # n == 0: a no-op, nothing is launched
     else:
         assert rc == 1 and lib._lib.dmf_last_error().decode() == message
+
+
+# ---------------------------------------------------------------------------------------------- the epoch ledger
+SUMS = [5.0, 7.0, 5.0, 3.0, float('nan'), 3.0, 2.0]
+
+
+def test_epoch_ledger_keeps_the_strict_best_and_prints_the_two_lines(capsys):
+    """`Solver._record_epoch`, which both the epoch loop and `_collect_block` call: the best epochs are 0, 3, 6 (an equal sum
+    and a NaN are never the best, as dmf_keep_best decides), and the lines are the reference's."""
+    from solver.mainsolver import Solver
+    s = Solver.__new__(Solver)
+    s.cfg, s.time, s.step_losses, s.val_history, s.best_loss, s.best_epoch = {'nohup': 1}, 2, [], [], float('inf'), 0
+    moved = [s._record_epoch(e, [1.0 + e, 0.5 + e], v) for e, v in enumerate(SUMS)]
+    assert moved == [True, False, False, True, False, False, True]
+    assert s.best_epoch == 6 and s.best_loss == 2.0
+    assert np.array_equal(np.array(s.val_history), np.array(SUMS), equal_nan=True)
+    assert s.step_losses == [x + e for e in range(7) for x in (1.0, 0.5)]
+    want = []
+    for e in range(7):
+        want += ['best epoch now is %d' % e] if e in (0, 3, 6) else []
+        want += ['2 times %dth epoch is trained, loss %d.500000' % (e, e)]
+    assert capsys.readouterr().out == '\n'.join(want) + '\n'
+    assert want[:3] == ['best epoch now is 0', '2 times 0th epoch is trained, loss 0.500000', '2 times 1th epoch is trained, loss 1.500000']
+    # no validation (no save_best), an epoch without a step, and nohup: 0
+    assert s._record_epoch(7, [], None) is False and len(s.val_history) == 7 and s.best_epoch == 6
+    assert capsys.readouterr().out == '2 times 7th epoch is trained, loss nan\n'
+    s.cfg = {'nohup': 0}
+    assert s._record_epoch(8, [0.25], 1.0) is True and s.best_epoch == 8 and s.step_losses[-1] == 0.25
+    assert capsys.readouterr().out == ''
+
+
+@pytest.mark.parametrize('epochs,every,due', [(7, 2, [2, 4, 6, 7]), (10, 5, [5, 10]), (7, 1, [1, 2, 3, 4, 5, 6, 7])])
+def test_curweights_are_due_every_nth_epoch_and_after_the_last(epochs, every, due, monkeypatch):
+    """`Solver._save_current`, which both forms call after their finished epochs, with the checkpoint writer recorded."""
+    from solver import mainsolver
+    written = []
+    monkeypatch.setattr(mainsolver, 'save_checkpoint', lambda model, opt, path: written.append(path))
+    s = mainsolver.Solver.__new__(mainsolver.Solver)
+    s.cfg, s.rank, s.fast, s.EPOCH, s.time = {'train': {'save_every': every}, 'RESULT_output': 'out/'}, 0, False, epochs, 3
+    s.cur_model = s.optimizer = None
+    got = []
+    for done in range(1, epochs + 1):
+        s._save_current(done)
+        got += [done] * len(written)
+        del written[:]
+    assert got == due
+    s._save_current(due[0])
+    assert written == ['out/3_curweights.pth']
+    s.rank = 1
+    s._save_current(due[0])
+    assert len(written) == 1                                                       # rank 0 writes the artefacts
+    assert set(due) <= set(np.cumsum(_blocks(epochs, 4, every)).tolist())          # a block ends wherever the file is due

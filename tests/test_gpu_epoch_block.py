@@ -128,8 +128,8 @@ def _read(path):
 
 @functools.lru_cache(maxsize=None)
 def _run(variant, epoch_block, golden_dir, after_train=False):
-    """`Solver.train()` once per (variant, epoch_block), shared by the tests below.  The unblocked run's validation sums are
-    recorded around `_valid_pass` (train() keeps them in locals)."""
+    """`Solver.train()` once per (variant, epoch_block), shared by the tests below.  Both forms keep the epoch ledger: the
+    validation sums in `s.val_history`, the best epoch in `s.best_epoch`."""
     from solver.mainsolver import Solver
     tmp = tempfile.mkdtemp(prefix='dmf_block_')
     try:
@@ -137,20 +137,17 @@ def _run(variant, epoch_block, golden_dir, after_train=False):
         torch.manual_seed(SEED)
         s = Solver(cfg)
         s.dataloader()
-        vals = []
-        if epoch_block == 1:
-            inner = s._valid_pass
-            s._valid_pass = lambda best: vals.append(inner(best)) or vals[-1]
         s.train()
         rng_after = torch.rand(4)
         out = cfg['RESULT_output']
-        r = dict(step_losses=np.array(s.step_losses, dtype=np.float64), rng_after=rng_after,
-                 vals=np.array(vals if epoch_block == 1 else s.val_history),
+        r = dict(step_losses=np.array(s.step_losses, dtype=np.float64), rng_after=rng_after, vals=np.array(s.val_history),
                  best=torch.load(out + '0_weights.pth', map_location='cpu', weights_only=True),
                  cur=torch.load(out + '0_curweights.pth', map_location='cpu', weights_only=True),
                  n_train=len(s.train_index_loader.dataset), n_valid=len(s.valid_index_loader.dataset))
+        assert len(s.val_history) == EPOCHS and s.best_epoch is not None             # filled by both forms
         lows = [k for k, v in enumerate(r['vals']) if v < min([np.inf] + list(r['vals'][:k]))]
-        r['best_epoch'] = lows[-1] if epoch_block == 1 else s.best_epoch
+        assert s.best_epoch == lows[-1] and s.best_loss == r['vals'][lows[-1]]
+        r['best_epoch'] = s.best_epoch
         if after_train:
             s.test()
             s.color()

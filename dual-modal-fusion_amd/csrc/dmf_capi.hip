@@ -557,6 +557,35 @@ int32_t dmf_rmsprop_step(float* theta, const float* grad, float* square_avg, int
                "rmsprop launch");
 }
 
+int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
+                       float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
+                       float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
+                       float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist, void* stream) {
+  if (theta == nullptr || grad == nullptr) return fail("%s", "optim_step: null theta or grad");
+  if (kind != DMF_OPT_ADAM && kind != DMF_OPT_ADAMW && kind != DMF_OPT_SGD && kind != DMF_OPT_RMSPROP)
+    return fail("%s", "optim_step: unknown kind (DMF_OPT_ADAM, _ADAMW, _SGD, _RMSPROP)");
+  const bool adam = kind == DMF_OPT_ADAM || kind == DMF_OPT_ADAMW;
+  if ((adam && (m == nullptr || v == nullptr)) || (kind == DMF_OPT_RMSPROP && m == nullptr) ||
+      (kind == DMF_OPT_SGD && momentum != 0.f && m == nullptr))
+    return fail("%s", "optim_step: null m or v (ADAM / ADAMW need both, RMSprop m, SGD m when momentum != 0)");
+  if (n < 0) return fail("%s", "optim_step: negative n");
+  if (!(weight_decay >= 0.f) || !isfinite(weight_decay)) return fail("%s", "optim_step: weight_decay must be finite and >= 0");
+  if (!isfinite(max_norm)) return fail("%s", "optim_step: max_norm must be finite (<= 0 switches clipping off)");
+  if (scaler_state == nullptr) {
+    if (growth_factor != 0.f || backoff_factor != 0.f || growth_interval != 0 || unscaled != 0)
+      return fail("%s", "optim_step: scaler hyper-parameters (growth, backoff, interval, unscaled) without a scaler state");
+    if (step < 1 && step_dev == nullptr) return fail("%s", "optim_step: step must be positive (or step_dev given)");
+  } else {
+    if (step_dev == nullptr) return fail("%s", "optim_step: a scaler state needs the device step count");
+    if (growth_interval < 1 || !(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f))
+      return fail("%s", "optim_step: bad growth_interval / factors");
+  }
+  if (n == 0) return 0;
+  OptimArgs a{theta, grad, m, v, n, kind, lr, beta1, beta2, eps, momentum, alpha, weight_decay, max_norm, grad_scale,
+              step, step_dev, cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled != 0, norm_hist};
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "optim_step launch");
+}
+
 int32_t dmf_qua_loss_ranks(const float* gathered, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,
                            const int32_t* labels_global, const int32_t* cursor, const dmf_qua_params* prm, float grad_scale,
                            const float* scaler_state, float* loss, float* loss_hist, float* dlogits_rank, void* stream) {

@@ -132,6 +132,17 @@ hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float*
 hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2,
                                float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
                                int32_t* cursor_dev, hipStream_t st);
+// dmf_optim_step: weight decay / AdamW / gradient-norm clipping on the flat gradient, one launch (optim_step_kernel)
+struct OptimArgs {
+  float* theta; const float* grad; float* m; float* v; int64_t n;
+  int kind;                           // DMF_OPT_*
+  float lr, b1, b2, eps, momentum, alpha, weight_decay, max_norm, grad_scale;
+  int32_t step; int32_t* step_dev; int32_t* cursor_dev;
+  float* state;                       // nullable loss-scaler state
+  float growth, backoff; int interval, unscaled;
+  float* norm_hist;                   // nullable: norm_hist[*cursor_dev] = the pre-clip norm
+};
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st);
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
 // the validation sum of an epoch and what its end decides (dmf_valid_accum, dmf_keep_best): one workgroup each
 hipError_t launch_valid_accum(const float* loss, int n, double* acc, hipStream_t st);

@@ -1,6 +1,6 @@
 // dmf_reduce.hip — the batch-level launches behind the patch and attention kernels: the slab / outer-product gradient
 // reduction with its fused Adam (grad_reduce_kernel), the stand-alone optimiser kernels (Adam, SGD, RMSprop), the loss-scaler
-// pair and the small xgmi all-reduce.  dmf_capi.hip validates and calls the launch_* functions at the end of this file.
+// pair, the one-launch step with weight decay and gradient-norm clipping (optim_step_kernel) and the small xgmi all-reduce.  dmf_capi.hip validates and calls the launch_* functions at the end of this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -28,6 +28,19 @@ __device__ __forceinline__ void adam_update(float* theta, float* m, float* v, in
   v[p] = vn;
   const float denom = sqrtf(vn) / bc2_sqrt + eps;
   theta[p] -= (lr / bc1) * (mn / denom);
+}
+
+// the bodies of sgd_kernel and rmsprop_kernel below, for dmf_optim_step (those kernels keep their own statement)
+__device__ __forceinline__ void sgd_update(float* theta, float* buf, int64_t p, float g, float lr, float momentum, int st) {
+  float b = g;
+  if (momentum != 0.f) { b = st <= 1 ? g : momentum * buf[p] + g; buf[p] = b; }
+  theta[p] -= lr * b;
+}
+
+__device__ __forceinline__ void rmsprop_update(float* theta, float* sq, int64_t p, float g, float lr, float alpha, float eps) {
+  const float s = alpha * sq[p] + (1.f - alpha) * g * g;
+  sq[p] = s;
+  theta[p] -= lr * (g / (sqrtf(s) + eps));
 }
 
 // ---- the reduce launch.  What bounds it (tools/reduce_phase_profile.py, stamps of round 3): ONE CU takes in only ~15 bytes
@@ -426,6 +439,113 @@ __global__ __launch_bounds__(256) void scaled_adam_kernel(float* theta, const fl
   }
 }
 
+// ------------------------------------------------------------------------------ weight decay, AdamW, gradient-norm clipping
+// dmf_optim_step (include/dmf.h states the six steps).  A grid like adam_kernel's, but EVERY block first walks the whole
+// gradient — lane t takes g[t], g[t + 256], ... in index order into one double, the 256 doubles meet in a fixed LDS tree — so
+// every block holds the same norm bits and the same skip decision and then updates its own 256 elements: no second launch,
+// no grid barrier, no atomics on data.  (double)g * (double)g is exact, so an fma and a multiply-add give the same sum.  The
+// values a block needs from what the step's end changes (scale, step count) are read before its ticket; the last block to
+// take a ticket closes the step as scaled_adam_kernel does.  Without a scaler state nothing is read that the end changes
+// (block 0 alone reads and advances the cursor), and there is no ticket.
+__device__ __forceinline__ float scaled_grad(const float* __restrict__ grad, int64_t i, float gs) {
+#pragma clang fp contract(off)           // g is a float of its own, as torch's unscale_ / clip_grad_norm_ leave one in memory
+  return grad[i] * gs;
+}
+
+// One instance per kind: with the kind a run-time branch the compiler merges the three updates' last subtraction into one
+// unfused `theta - x`, and ADAM's theta then is an ulp away from adam_kernel's and scaled_adam_kernel's fused form.
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
+  __shared__ double part[256];
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * 256 + t;
+  const int st = a.step_dev != nullptr ? *a.step_dev : a.step;
+  const float gs = (a.state != nullptr && !a.unscaled) ? a.grad_scale / a.state[0] : a.grad_scale;
+  const bool clip = a.max_norm > 0.f;
+  bool skip = false;
+  float norm = 0.f, coef = 1.f;
+  if (a.state != nullptr || clip) {
+    double s = 0.0;
+    int bad = 0;
+    // 16 loads in flight per lane (unconditional, from a clamped index, masked where they are summed: a load under a lane
+    // condition becomes a branch, and one load per trip is one L2 round trip per 256 elements: 32 in a row at n = 8,009,
+    // measured as 8 us per launch); the sum keeps the index order, and a masked element adds +0.0
+    for (int64_t i0 = t; i0 < a.n; i0 += 16 * 256) {
+      float gq[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int64_t i = i0 + (int64_t)q * 256;
+        gq[q] = scaled_grad(a.grad, i < a.n ? i : a.n - 1, gs);
+      }
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const bool in = i0 + (int64_t)q * 256 < a.n;
+        const float g = in ? gq[q] : 0.f;
+        bad |= !isfinite(g);
+        s += (double)g * (double)g;
+      }
+    }
+    part[t] = s;
+    skip = __syncthreads_or(bad) != 0 && a.state != nullptr;
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) part[t] += part[t + w];
+      __syncthreads();
+    }
+    if (clip) {
+      norm = (float)sqrt(part[0]);
+      const float c = a.max_norm / (norm + 1e-6f);
+      coef = c > 1.f ? 1.f : c;                        // (a NaN norm stays a NaN coefficient: torch's clamp)
+    }
+  }
+  if (!skip && p < a.n) {
+    float g = scaled_grad(a.grad, p, gs);
+    {
+#pragma clang fp contract(off)
+      if (clip) g *= coef;
+      if (a.weight_decay != 0.f) {
+        const float th = a.theta[p];
+        if (KIND == DMF_OPT_ADAMW) a.theta[p] = th * (float)(1.0 - (double)a.lr * (double)a.weight_decay);
+        else g += a.weight_decay * th;
+      }
+    }
+    if (KIND == DMF_OPT_SGD) sgd_update(a.theta, a.m, p, g, a.lr, a.momentum, st);
+    else if (KIND == DMF_OPT_RMSPROP) rmsprop_update(a.theta, a.m, p, g, a.lr, a.alpha, a.eps);
+    else {
+      float bc1, bc2s;
+      bias_corrections(st, a.b1, a.b2, bc1, bc2s);
+      adam_update(a.theta, a.m, a.v, p, g, a.lr, a.b1, a.b2, a.eps, bc1, bc2s);
+    }
+  }
+  bool closer = blockIdx.x == 0 && t == 0;
+  if (a.state != nullptr) {
+    // the last block to get here has seen every other block read the scale and the step count: it closes the step
+    __syncthreads();
+    closer = false;
+    if (t == 0) {
+      __threadfence();
+      int* ticket = reinterpret_cast<int*>(a.state + 4);
+      if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) {
+        *ticket = 0;
+        closer = true;
+        if (skip) {
+          a.state[0] *= a.backoff; a.state[1] = 0.f; a.state[3] += 1.f;
+          *a.step_dev -= 1;                             // a skipped step does not count for the bias corrections
+        } else {
+          const float tr = a.state[1] + 1.f;
+          if (tr >= (float)a.interval) { a.state[0] *= a.growth; a.state[1] = 0.f; }
+          else a.state[1] = tr;
+        }
+        a.state[2] = 0.f;
+      }
+    }
+  }
+  if (closer) {
+    const int cur = a.cursor_dev != nullptr ? *a.cursor_dev : 0;
+    if (clip && a.norm_hist != nullptr) a.norm_hist[cur] = norm;
+    if (a.cursor_dev != nullptr) *a.cursor_dev = cur + 1;
+  }
+}
+
 __global__ __launch_bounds__(256) void xgmi_allreduce_kernel(const XgmiDev x, float* buf, int64_t n, int seq) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool valid = i < n;
@@ -534,6 +654,18 @@ hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float*
                                int32_t* cursor_dev, hipStream_t st) {
   hipLaunchKernelGGL(scaled_adam_kernel, blocks256(n), dim3(256), 0, st, theta, grad, m, v, n, lr, b1, b2, eps, state, growth,
                      backoff, interval, step_dev, cursor_dev);
+  return hipGetLastError();
+}
+
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st) {
+  const dim3 grid = blocks256(a.n), block(256);
+  switch (a.kind) {
+    case DMF_OPT_ADAM: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_ADAM>, grid, block, 0, st, a); break;
+    case DMF_OPT_ADAMW: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_ADAMW>, grid, block, 0, st, a); break;
+    case DMF_OPT_SGD: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_SGD>, grid, block, 0, st, a); break;
+    case DMF_OPT_RMSPROP: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_RMSPROP>, grid, block, 0, st, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

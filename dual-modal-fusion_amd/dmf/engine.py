@@ -202,12 +202,19 @@ class _PlanEngine:
         the whole batch: `step` / `load_plan` take GLOBAL batches, the same on every rank, of which rank r trains on its
         contiguous rows (`_rank_shard`, `_load_global_plan`), and a captured graph's steps read plan[cursor]."""
 
-    def __init__(self, net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha):
-        if optimizer not in ('ADAM', 'SGD', 'RMSprop'):
-            raise lib.DmfError('optimizer %r is not one of ADAM, SGD, RMSprop' % (optimizer,))
-        if scaler is not None and optimizer != 'ADAM':
-            raise lib.DmfError('%s with a loss scaler: the loss-scaler step is ADAM' % optimizer)
+    def __init__(self, net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha, weight_decay=0.0,
+                 clip_grad_norm=None):
+        if optimizer not in ('ADAM', 'ADAMW', 'SGD', 'RMSprop'):
+            raise lib.DmfError('optimizer %r is not one of ADAM, ADAMW, SGD, RMSprop' % (optimizer,))
+        if scaler is not None and optimizer not in ('ADAM', 'ADAMW'):
+            raise lib.DmfError('%s with a loss scaler: the loss-scaler step is ADAM or ADAMW' % optimizer)
         self.optim, self.momentum, self.alpha = optimizer, float(momentum), float(alpha)
+        # weight decay (L2; decoupled with ADAMW) and gradient-norm clipping: the one-launch step dmf_optim_step (DESIGN.md §14)
+        self.weight_decay, self.clip_grad_norm = float(weight_decay or 0.0), float(clip_grad_norm or 0.0)
+        if not (np.isfinite(self.weight_decay) and self.weight_decay >= 0.0):
+            raise lib.DmfError('weight_decay %r is not a finite number >= 0' % (weight_decay,))
+        if not (np.isfinite(self.clip_grad_norm) and self.clip_grad_norm >= 0.0):
+            raise lib.DmfError('clip_grad_norm %r is not a finite number >= 0 (None or 0: off)' % (clip_grad_norm,))
         self.lr, self.b1, self.b2, self.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         self.net, self.scene, self.scaler = net, scene, scaler
         self.shape = net.shape
@@ -228,13 +235,22 @@ class _PlanEngine:
         self.dev_cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self.step_count = self.host_cursor = self.plan_steps = 0
         self.plan_xy = self.plan_labels = self.loss_hist = None
+        self.norm_hist = None            # pre-clip gradient norms of the plan's steps (clip_grad_norm), sized like loss_hist
+        self.norm = torch.zeros(1, device=dev)       # ... and of the last eager step
         self.graph, self.graph_steps, self.graph_hparams = None, 0, None
         self.comm = None                 # the one-shot xgmi exchange (TrainEngine only)
         self._rccl_graph = True          # False once RCCL refused to be captured (run_plan), or set by a caller
         self._force_collective = False   # tests only: see _single()
 
     def _hparams(self):
-        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha) + (self.scaler.hparams() if self.scaler is not None else ())
+        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha, self.weight_decay, self.clip_grad_norm) + (
+            self.scaler.hparams() if self.scaler is not None else ())
+
+    def _regularised(self):
+        """Weight decay, AdamW or gradient-norm clipping is active: every step form updates by dmf_optim_step (`_update`), so no
+        fused reduce + ADAM launch, no native launch loop and no xgmi exchange.  ADAMW with weight_decay 0 is ADAM's
+        arithmetic, but still this route: only dmf_optim_step knows the kind."""
+        return self.weight_decay != 0.0 or self.clip_grad_norm != 0.0 or self.optim == 'ADAMW'
 
     def _check_labels(self, lab):                    # lab on the host, or on the device: its two extremes are then read back
         K = self.net.arch['K']
@@ -263,10 +279,17 @@ class _PlanEngine:
           everything else               dmf_grad_reduce -> all-reduce(sum) where the step has a collective -> the mean loss
                                         into loss_hist[cursor] -> dmf_unscale_adam (the check sees the SUM, so every rank
                                         takes the same skip decision) / dmf_sgd_step / dmf_rmsprop_step / dmf_adam_step
+          weight decay, ADAMW or        ALL of the cases above: dmf_grad_reduce -> all-reduce(sum) where the step has a
+          clip_grad_norm active         collective -> the mean loss into loss_hist[cursor] -> dmf_optim_step (unscale and
+                                        check with a scaler, the norm of the whole gradient and its clipping, weight decay,
+                                        the optimiser, the scaler's update: one launch; the pre-clip norm into
+                                        norm_hist[cursor], or into self.norm for an eager step)
         sum_scale scales the all-reduced gradient: 1/world where the loss is a per-rank mean, 1 where the loss kernel
         already divided by the global batch.  dev_step: the device step counter, or None for the host count.  loss /
         loss_hist: where the step's mean loss (this rank's) is recorded; None where the loss kernel records it itself.
         SGD and RMSprop keep their one state vector in m (momentum buffer / running mean of squares)."""
+        if self._regularised():
+            return self._update_regularised(rows, dev_step, cursor, sum_scale, loss, loss_hist)
         sc, hp = self.scaler, (self.lr, self.b1, self.b2, self.eps)
         fused = sc is None and self.optim == 'ADAM'
         if fused and self._single():
@@ -296,6 +319,20 @@ class _PlanEngine:
             else:
                 lib.adam_step(self.theta, self.grad, self.m, self.v, *hp, self.step_count, grad_scale=sum_scale,
                               adam_step_dev=dev_step, cursor_dev=cursor)
+
+    def _update_regularised(self, rows, dev_step, cursor, sum_scale, loss, loss_hist):
+        """`_update` with weight decay, ADAMW or clip_grad_norm active (its docstring's last row)."""
+        sc = self.scaler
+        lib.grad_reduce(self.shape, rows, self.ws, self.grad)
+        if not self._single():
+            self._all_reduce_grad()
+        if loss_hist is not None:
+            loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
+        lib.optim_step(self.optim, self.theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2,
+                       1e-8 if self.optim == 'RMSprop' else self.eps, self.momentum, self.alpha, self.weight_decay,
+                       self.clip_grad_norm, step=self.step_count, grad_scale=sum_scale, step_dev=dev_step, cursor_dev=cursor,
+                       scaler_state=sc.state if sc is not None else None, scaler_hparams=sc.hparams() if sc is not None else None,
+                       norm_hist=self.norm_hist if cursor is not None else self.norm)
 
     # ------------------------------------------------------------------ the unit-gradient step on global batches
     def _unit_step(self, inp, rows, loss_launch, dev_step, cursor, loss=None, loss_hist=None):
@@ -367,8 +404,10 @@ class _PlanEngine:
             for name, t in plan.items():
                 setattr(self, name, t)
             self.loss_hist = torch.empty(max(capacity, 1), device=self.scene.device)
+            self.norm_hist = torch.empty_like(self.loss_hist)
             self.graph = None
         self.loss_hist.zero_()
+        self.norm_hist.zero_()
         self.dev_cursor.zero_()
         self.host_cursor, self.plan_steps = 0, n
         self._seed_dev_step()
@@ -416,7 +455,8 @@ class _PlanEngine:
         """Save everything a step changes (weights, optimiser and scaler state, device step count and cursor, loss history,
         host step count and cursor) and put it back on leaving, also when the body raises.  Yields the restore function
         for a body that needs the state back early."""
-        tensors = [t for t in (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist) if t is not None]
+        tensors = [t for t in (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist, self.norm_hist, self.norm)
+                   if t is not None]
         if self.scaler is not None:
             tensors.append(self.scaler.state)
         saved = [t.clone() for t in tensors]
@@ -501,22 +541,32 @@ class _PlanEngine:
         """Per-step mean loss of the plan steps run so far (one D2H copy)."""
         return self.loss_hist[:int(self.dev_cursor.item())].cpu()
 
+    def grad_norms(self):
+        """Per-step gradient norm BEFORE clipping — what `clip_grad_norm_` returns — of the plan steps run so far (one D2H
+        copy).  Zeros without clip_grad_norm; a step the loss scaler skipped has a non-finite entry."""
+        return self.norm_hist[:int(self.dev_cursor.item())].cpu()
+
 
 class TrainEngine(_PlanEngine):
     """The single-stage train step on a resident scene: the fused step, or with a `criterion` the unit-gradient step around
     dmf_ce_loss (_PlanEngine: what each takes).  `self.fused`, set once by the constructor, says which."""
 
     def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
-                 optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None):
+                 optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None, weight_decay=0.0, clip_grad_norm=None):
         """optimizer: 'ADAM', or the reference's other two (utils/utils.py:13-16) — 'SGD' (`momentum`) and 'RMSprop'
-        (`alpha`, eps 1e-8).  The launches after the backward: _PlanEngine._update.
+        (`alpha`, eps 1e-8) —, or 'ADAMW'.  weight_decay (torch's `weight_decay=`; decoupled with ADAMW) and clip_grad_norm
+        (`clip_grad_norm_(params, max_norm)` between backward and step; None or 0: off) update by dmf_optim_step, without the
+        xgmi exchange.  The launches after the backward: _PlanEngine._update.
         criterion: None = the plain cross-entropy fused into the patch kernel (two launches per step).  A spec of `Criterion`
         (class weights, label smoothing, focal term) trains by the unit-gradient step instead (no xgmi exchange)."""
-        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
+        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha, weight_decay, clip_grad_norm)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
         if optimizer != 'ADAM' and comm is not None:
             raise lib.DmfError('%s: single GPU or RCCL data parallel (the fused xgmi exchange is ADAM)' % optimizer)
+        if self._regularised() and comm is not None:
+            raise lib.DmfError('weight_decay / clip_grad_norm: single GPU or a process group (the norm is taken after the '
+                               'all-reduce; the fused xgmi exchange does not leave the flat gradient)')
         dev = scene.device
         if self.theta.device != dev:
             raise lib.DmfError('net and scene must be on the same device')
@@ -533,6 +583,7 @@ class TrainEngine(_PlanEngine):
             raise lib.DmfError('xgmi communicator does not match this engine (world / capacity)')
         self.plan_pack = self.win = None
         self.short_xy = self.short_labels = self.short_hist = None       # load_block: the epochs' short last batches
+        self.short_norm = None
         self.criterion = None
         self.fused = criterion is None
         if not self.fused:
@@ -573,7 +624,7 @@ class TrainEngine(_PlanEngine):
     def _counts_on_device(self):
         """As _PlanEngine's, and: the xgmi exchange numbers its rounds by the device step count, and SGD's first step is told
         by it."""
-        return self.comm is not None or self.scaler is not None or self.optim != 'ADAM'
+        return self.comm is not None or self.scaler is not None or self.optim not in ('ADAM', 'ADAMW')
 
     def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
         dev_step = self._count_step(dev_step)
@@ -619,7 +670,7 @@ class TrainEngine(_PlanEngine):
         if self.world != 1:
             raise lib.DmfError('load_block: one GPU only (the ranks of a data-parallel run check their exchange every epoch)')
         xy, lab = self._host_ints(xy_all, 'xy_all').reshape(-1, 2), self._host_ints(labels_all, 'labels_all').reshape(-1)
-        self.short_xy = self.short_labels = self.short_hist = None
+        self.short_xy = self.short_labels = self.short_hist = self.short_norm = None
         if short_xy is not None:
             sxy, slab = self._host_ints(short_xy, 'short_xy'), self._host_ints(short_labels, 'short_labels')
             if sxy.dim() != 3 or sxy.shape[2] != 2 or tuple(slab.shape) != tuple(sxy.shape[:2]) or not 0 < sxy.shape[1] <= self.B:
@@ -631,6 +682,7 @@ class TrainEngine(_PlanEngine):
             dev = self.scene.device
             self.short_xy, self.short_labels = sxy.to(dev), slab.to(dev)
             self.short_hist = torch.zeros(sxy.shape[0], device=dev)
+            self.short_norm = torch.zeros(sxy.shape[0], device=dev)
         return n
 
     def step_short(self, e):
@@ -639,12 +691,17 @@ class TrainEngine(_PlanEngine):
         xy = self.short_xy[e]
         self.step(xy, self.short_labels[e], check=False)
         self.short_hist[e:e + 1].copy_(self.loss[:xy.shape[0]].mean().reshape(1))
+        self.short_norm[e:e + 1].copy_(self.norm)
         self._seed_dev_step()
 
     def block_losses(self):
         """(per-step mean losses of the plan steps run so far, the short batches' mean losses or None), on the host: the
         block's two device-to-host copies."""
         return self.loss_hist[:self.host_cursor].cpu(), None if self.short_hist is None else self.short_hist.cpu()
+
+    def block_grad_norms(self):
+        """block_losses' counterpart for the pre-clip gradient norms (clip_grad_norm): (plan steps, short batches or None)."""
+        return self.norm_hist[:self.host_cursor].cpu(), None if self.short_norm is None else self.short_norm.cpu()
 
     def _plan_launch(self):
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy, B=self.B, cursor=self.dev_cursor)
@@ -674,7 +731,8 @@ class TrainEngine(_PlanEngine):
     def _native_loop_ok(self):
         """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler,
         the fused cross-entropy."""
-        return self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.fused
+        return (self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.fused
+                and not self._regularised())
 
     def _graphable(self):
         """Can a step be captured in a hipGraph?  One GPU: yes.  The one-shot exchange: yes (it is part of the reduce launch).
@@ -682,7 +740,7 @@ class TrainEngine(_PlanEngine):
         all_reduce of 32 KB per ~16-us step would otherwise bound the step by the host (DMF_RCCL_GRAPH=0 switches this off)."""
         if self._single() or self.comm is not None:
             return True
-        if self.scaler is not None or self.optim != 'ADAM':
+        if self.scaler is not None or self.optim != 'ADAM' or self._regularised():
             return False
         return self._rccl_capturable()
 
@@ -948,10 +1006,10 @@ class QuaTrainEngine(_PlanEngine):
     single-GPU one.  The update after the backward (optimiser, loss scaler, all-reduce): _PlanEngine._update."""
 
     def __init__(self, net, scene, bs, dqtl, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, scaler=None,
-                 optimizer='ADAM', momentum=0.0, alpha=0.99):
+                 optimizer='ADAM', momentum=0.0, alpha=0.99, weight_decay=0.0, clip_grad_norm=None):
         if not net.arch.get('single_input'):
             raise lib.DmfError('stage 2 needs the single-input net (cfg["gmf"]["single_input"] = 1)')
-        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha)
+        super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha, weight_decay, clip_grad_norm)
         self.bs = int(bs)
         self.unit = lib.unit_supported(self.shape)
         if scaler is not None and not self.unit:

@@ -75,6 +75,8 @@ def _load():
         'dmf_adam_step': (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, vp, vp, vp]),
         'dmf_sgd_step': (i32, [vp, vp, vp, i64, f32, f32, i32, f32, vp, vp, vp]),
         'dmf_rmsprop_step': (i32, [vp, vp, vp, i64, f32, f32, f32, f32, vp, vp]),
+        'dmf_optim_step': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, vp, vp, f32, f32, i32,
+                                 i32, vp, vp]),
         'dmf_grad_reduce_adam': (i32, [SP, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp]),
         'dmf_forward_ce': (i32, [SP, IP, vp, vp, vp, vp, vp, vp, vp]),
         'dmf_train_plan_steps': (i32, [SP, IP, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
@@ -301,6 +303,24 @@ def sgd_step(theta, grad, buf, lr, momentum, step, grad_scale=1.0, step_dev=None
 def rmsprop_step(theta, grad, sq, lr, alpha, eps=1e-8, grad_scale=1.0, cursor_dev=None):
     check(_lib.dmf_rmsprop_step(_ptr(theta), _ptr(grad), _ptr(sq), theta.numel(), lr, alpha, eps, grad_scale, _ptr(cursor_dev),
                                 _stream()))
+
+
+OPTIM_KINDS = {'ADAM': 0, 'ADAMW': 1, 'SGD': 2, 'RMSprop': 3}          # DMF_OPT_* (include/dmf.h)
+
+
+def optim_step(kind, theta, grad, m, v, lr, b1=0.9, b2=0.999, eps=1e-8, momentum=0.0, alpha=0.99, weight_decay=0.0,
+               max_norm=None, step=0, grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None, scaler_hparams=None,
+               unscaled=False, norm_hist=None):
+    """One optimiser step with weight decay, AdamW and gradient-norm clipping on the flat gradient (dmf_optim_step).  kind: a
+    key of OPTIM_KINDS; max_norm None or 0: no clipping; scaler_hparams (growth_factor, backoff_factor, growth_interval) go with
+    scaler_state; norm_hist[cursor] gets the pre-clip norm of a clipped step."""
+    if kind not in OPTIM_KINDS:
+        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
+    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
+    check(_lib.dmf_optim_step(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], lr, b1, b2, eps,
+                              momentum, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
+                              _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
+                              _ptr(norm_hist), _stream()))
 
 
 def grad_reduce_adam(shape, B, ws, theta, m, v, grad, lr, b1, b2, eps, step, adam_step_dev=None, cursor_dev=None,

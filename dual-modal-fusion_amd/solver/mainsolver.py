@@ -20,6 +20,10 @@ defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gi
 loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
 `dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
 then steps eagerly from Python —, no xgmi exchange, the engine shards the batches).  Keys that are all neutral change nothing.
+`schedule.weight_decay`, `schedule.optimizer: ADAMW` and `schedule.clip_grad_norm` (all optional): torch's
+`weight_decay=`, `torch.optim.AdamW` and `clip_grad_norm_(params, max_norm)` between backward and step on both paths; the fast
+path then updates by `dmf_optim_step` on the flat gradient (no native launch loop — set `steps_per_graph` > 0, the default -1
+then steps eagerly from Python —, no xgmi exchange).  Neutral values (`weight_decay: 0`, `clip_grad_norm: null` or 0) change nothing.
 `train.epoch_block: E` (default 1): `train()` chooses once between two loops that keep ONE epoch ledger (`_record_epoch`,
 `_save_current`).  `_train_epochs` is the loop described above.  It is not "a block of one": toStageSolver (its validation is read
 back per batch), data-parallel runs (the ranks check their exchange every epoch) and the drop-in path have no block form; the
@@ -48,7 +52,7 @@ from PIL import Image
 from tqdm import tqdm
 
 from solver.basesolver import BaseSolver
-from utils.utils import criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
+from utils.utils import clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
 
 
 def block_length(epoch, epoch_block, save_every, epochs):
@@ -127,8 +131,8 @@ class Solver(BaseSolver):
         """The configured optimiser (ADAM, SGD or RMSprop) with its own state keys, from the engine's flat state vectors
         (checkpoint interchange with the reference's save_checkpoint / load_checkpoint, utils/utils.py:82-102)."""
         eng = self.engine
-        group = {'lr': eng.lr}
-        if eng.optim == 'ADAM':
+        group = {'lr': eng.lr, 'weight_decay': eng.weight_decay}
+        if eng.optim in ('ADAM', 'ADAMW'):
             group['betas'] = (eng.b1, eng.b2)
         elif eng.optim == 'SGD':
             group['momentum'] = eng.momentum
@@ -217,11 +221,11 @@ class Solver(BaseSolver):
             save_checkpoint(self.cur_model, opt, self.cfg['RESULT_output'] + str(self.time) + '_curweights.pth')
 
     def _loss_scaler(self, hp):
-        """gmf.half: 1 on the fast path -> the device loss scaler with GradScaler's defaults; its step is ADAM."""
+        """gmf.half: 1 on the fast path -> the device loss scaler with GradScaler's defaults; its step is ADAM (or ADAMW)."""
         if not self.half:
             return None
-        if hp['optimizer'] != 'ADAM':
-            raise ValueError('gmf.half: 1 trains with the loss scaler, whose step is ADAM; schedule.optimizer is %s'
+        if hp['optimizer'] not in ('ADAM', 'ADAMW'):
+            raise ValueError('gmf.half: 1 trains with the loss scaler, whose step is ADAM or ADAMW; schedule.optimizer is %s'
                              % hp['optimizer'])
         from dmf.engine import LossScaler
         return LossScaler(self.DEVICE)
@@ -234,7 +238,8 @@ class Solver(BaseSolver):
             raise ValueError('batchsize %d is not divisible by the %d ranks' % (self.cfg['batchsize'], self.world))
         self.engine = self._train_engine(self.cfg['batchsize'] // self.world, dict(
             lr=hp['lr'], betas=hp['betas'], eps=hp['eps'], process_group=self.process_group, scaler=self._loss_scaler(hp),
-            optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99)))
+            optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99),
+            weight_decay=hp.get('weight_decay', 0.0), clip_grad_norm=hp.get('clip_grad_norm')))
         self.eval_engine = self._eval_engine()
 
     def _set_epoch_hparams(self, epoch):
@@ -373,8 +378,10 @@ class Solver(BaseSolver):
 
     def _train_engine(self, batch, kw):
         from dmf.engine import TrainEngine
-        # (the one-shot exchange carries neither the scaler nor the unit-gradient step of a criterion)
-        comm = self.comm if kw['optimizer'] == 'ADAM' and kw['scaler'] is None and self.criterion is None else None
+        # (the one-shot exchange carries neither the scaler, nor the unit-gradient step of a criterion, nor the step with weight
+        # decay or gradient-norm clipping, whose norm is taken from the all-reduced flat gradient)
+        plain = kw['optimizer'] == 'ADAM' and not kw['weight_decay'] and not kw['clip_grad_norm']
+        comm = self.comm if plain and kw['scaler'] is None and self.criterion is None else None
         if self.criterion is not None:
             kw = dict(kw, criterion=self.criterion)
         return TrainEngine(self.cur_model, self.scene, batch, comm=comm, **kw)
@@ -408,12 +415,15 @@ class Solver(BaseSolver):
     def _train_epoch_dropin(self):
         loader = self._bar(self.train_loader)
         losses = []
+        max_norm = clip_grad_norm_of(self.cfg['schedule'])           # schedule.clip_grad_norm (None: the reference's loop)
         for data1, data2, target, _, _ in loader:
             data1, data2, target = data1.to(self.DEVICE), data2.to(self.DEVICE), target.to(self.DEVICE)
             self.optimizer.zero_grad()
             output = self.cur_model(data1, data2)
             loss = self.loss(output, target.long())
             loss.backward()
+            if max_norm:
+                torch.nn.utils.clip_grad_norm_(self.cur_model.parameters(), max_norm)
             self.optimizer.step()
             losses.append(loss.item())
             if not self.cfg['nohup']:

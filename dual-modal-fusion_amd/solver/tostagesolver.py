@@ -49,6 +49,7 @@ import torch
 from function.function import data_padding, data_show, split_data_old
 from solver.mainsolver import Solver
 from train.dataset import dataset_qua_dqtl
+from utils.utils import clip_grad_norm_of
 
 
 class toStageSolver(Solver):
@@ -132,6 +133,7 @@ class toStageSolver(Solver):
     def _train_epoch_dropin(self):
         loader = self._bar(self.train_loader)
         losses = []
+        max_norm = clip_grad_norm_of(self.cfg['schedule'])           # schedule.clip_grad_norm (None: the reference's loop)
         for data1, data2, data3, data4, target, _, _ in loader:
             data = torch.concat([data1, data2, data3, data4]).to(self.DEVICE)            # tostagesolver.py:270-272
             target = target.to(self.DEVICE)
@@ -140,6 +142,8 @@ class toStageSolver(Solver):
             output = self.cur_model(data)
             loss = self.loss(output, bs, target, self.cfg)
             loss.backward()
+            if max_norm:
+                torch.nn.utils.clip_grad_norm_(self.cur_model.parameters(), max_norm)
             self.optimizer.step()
             losses.append(loss.item())
             if not self.cfg['nohup']:

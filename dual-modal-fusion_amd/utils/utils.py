@@ -5,7 +5,8 @@ The three factories return the torch objects the reference builds from the same 
 scheduler kinds keep the reference's constants.  Here they are lookup tables of small constructors rather than
 if-chains.  They serve the drop-in path (reference-style loop -> `model.gmfnet.Net` -> autograd); the resident-scene
 fast path (dmf/engine.py) applies the same ADAM update inside `dmf_grad_reduce_adam` and takes only the hyper-parameters
-from here (`adam_hparams`, `epoch_hparams`: whatever scheduler kind is configured).  Checkpoints keep the reference's layout (:82-111): `{'state_dict', 'optimizer'}`.
+from here (`adam_hparams`, `epoch_hparams`: whatever scheduler kind is configured).  This project's own optional keys on top of
+the reference's: the criterion keys (`criterion_spec`), and `weight_decay`, `optimizer: ADAMW`, `clip_grad_norm` (`optim_hparams`).  Checkpoints keep the reference's layout (:82-111): `{'state_dict', 'optimizer'}`.
 """
 import os
 import random
@@ -17,10 +18,38 @@ from torch.optim import lr_scheduler as _sched
 
 _ADAM_DEFAULTS = ((0.9, 0.999), 1e-8)          # betas, eps of torch.optim.Adam — the reference passes lr only (:12)
 
+
+def weight_decay_of(s):
+    """schedule.weight_decay (NEW, optional): torch's `weight_decay=` — L2 for ADAM, SGD and RMSprop, decoupled for ADAMW,
+    which must state it.  Absent, null and 0 are neutral."""
+    if s['optimizer'] == 'ADAMW' and s.get('weight_decay') is None:
+        raise ValueError('schedule.optimizer: ADAMW needs schedule.weight_decay stated (torch.optim.AdamW(params, lr, weight_decay))')
+    wd = float(s.get('weight_decay') or 0.0)
+    if not (np.isfinite(wd) and wd >= 0.0):
+        raise ValueError('schedule.weight_decay %r is not a finite number >= 0' % (s.get('weight_decay'),))
+    return wd
+
+
+def clip_grad_norm_of(s):
+    """schedule.clip_grad_norm (NEW, optional): max_norm of `torch.nn.utils.clip_grad_norm_(params, max_norm)` between backward
+    and step, or None: absent, null and 0 switch it off."""
+    c = float(s.get('clip_grad_norm') or 0.0)
+    if not (np.isfinite(c) and c >= 0.0):
+        raise ValueError('schedule.clip_grad_norm %r is not a finite number > 0 (null or 0: off)' % (s.get('clip_grad_norm'),))
+    return c or None
+
+
+# (a neutral weight_decay is not passed on: the reference's own constructor calls stay as they are)
+def _wd(s):
+    wd = weight_decay_of(s)
+    return {'weight_decay': wd} if wd else {}
+
+
 _OPTIMIZERS = {
-    'ADAM': lambda s, params: torch.optim.Adam(params, lr=s['lr']),
-    'SGD': lambda s, params: torch.optim.SGD(params, lr=s['lr'], momentum=s['momentum']),
-    'RMSprop': lambda s, params: torch.optim.RMSprop(params, lr=s['lr'], alpha=s['alpha']),
+    'ADAM': lambda s, params: torch.optim.Adam(params, lr=s['lr'], **_wd(s)),
+    'ADAMW': lambda s, params: torch.optim.AdamW(params, lr=s['lr'], weight_decay=weight_decay_of(s)),
+    'SGD': lambda s, params: torch.optim.SGD(params, lr=s['lr'], momentum=s['momentum'], **_wd(s)),
+    'RMSprop': lambda s, params: torch.optim.RMSprop(params, lr=s['lr'], alpha=s['alpha'], **_wd(s)),
 }
 
 
@@ -70,6 +99,9 @@ def _pick(table, key, what):
 
 
 def make_optimizer(cfg, params):
+    """The torch optimiser of cfg['schedule'] (optimizer, lr, momentum / alpha, weight_decay).  schedule.clip_grad_norm is no
+    part of it: the train loops call `clip_grad_norm_` (clip_grad_norm_of), the fast path clips inside dmf_optim_step."""
+    clip_grad_norm_of(cfg['schedule'])
     return _pick(_OPTIMIZERS, cfg['schedule']['optimizer'], 'optimizer')(cfg['schedule'], params)
 
 
@@ -173,11 +205,18 @@ def make_scheduler(optimizer, cfg):
 
 def optim_hparams(cfg):
     """What the resident-scene engine needs to reproduce make_optimizer(cfg, ...): kind + the constructor arguments the
-    reference passes (ADAM: lr; SGD: lr, momentum; RMSprop: lr, alpha — utils/utils.py:10-16), torch defaults otherwise."""
+    reference passes (ADAM: lr; SGD: lr, momentum; RMSprop: lr, alpha — utils/utils.py:10-16), torch defaults otherwise; and
+    this project's own keys where cfg['schedule'] states them: ADAMW, `weight_decay` (0.0 = none) and `clip_grad_norm` (None =
+    off).  A schedule without the keys gives the dict it always gave; read them with .get(key)."""
     s = cfg['schedule']
     kind = s['optimizer']
     _pick(_OPTIMIZERS, kind, 'optimizer')
     out = {'optimizer': kind, 'lr': float(s['lr']), 'betas': _ADAM_DEFAULTS[0], 'eps': _ADAM_DEFAULTS[1]}
+    wd, clip = weight_decay_of(s), clip_grad_norm_of(s)
+    if 'weight_decay' in s:
+        out['weight_decay'] = wd
+    if 'clip_grad_norm' in s:
+        out['clip_grad_norm'] = clip
     if kind == 'SGD':
         out['momentum'] = float(s['momentum'])
     if kind == 'RMSprop':
@@ -242,7 +281,7 @@ def export_optimizer(cfg, params, flat_params, offsets, m, v, step_count, group=
     engine's flat state vectors — so that `<time>_curweights.pth` holds what the reference's `save_checkpoint(model,
     optimizer)` stores (utils/utils.py:82-88) and `load_checkpoint` (:91-102) can feed it to `make_optimizer(cfg)` again.
     Per optimiser kind (torch's own state keys):
-      ADAM     m -> exp_avg, v -> exp_avg_sq, step
+      ADAM     m -> exp_avg, v -> exp_avg_sq, step    (ADAMW: the same keys in a torch.optim.AdamW)
       SGD      m -> momentum_buffer (only when momentum != 0 and a step has been taken, as torch creates it)
       RMSprop  m -> square_avg, step
     params: `model.parameters()` — the order the reference hands to make_optimizer, which is the order a state_dict numbers
@@ -259,7 +298,7 @@ def export_optimizer(cfg, params, flat_params, offsets, m, v, step_count, group=
         seg_m = m[offsets[i]:offsets[i] + n].view(p.shape).clone()
         if step_count <= 0:                       # torch creates an optimiser's state on its first step
             continue
-        if kind == 'ADAM':
+        if kind in ('ADAM', 'ADAMW'):
             opt.state[p] = {'step': torch.tensor(float(step_count)), 'exp_avg': seg_m,
                             'exp_avg_sq': v[offsets[i]:offsets[i] + n].view(p.shape).clone()}
         elif kind == 'SGD':

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 304   /* 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 305   /* 0.3.5: dmf_optim_step (weight decay, AdamW and gradient-norm clipping on the flat gradient); 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -208,7 +208,7 @@ int32_t dmf_backward_dlogits(const dmf_shape* shape, const dmf_input* in, const 
 int32_t dmf_grad_reduce(const dmf_shape* shape, int32_t B, const void* workspace, float* grad, void* stream);
 
 /* Replaces `self.optimizer.step()` for torch.optim.Adam(lr) defaults (utils/utils.py:10-12;
- * betas 0.9/0.999, eps 1e-8, no weight decay).  step = 1-based step count.  grad_scale multiplies grad
+ * betas 0.9/0.999, eps 1e-8, no weight decay: with one, or AdamW, or a clipped gradient norm, dmf_optim_step).  step = 1-based step count.  grad_scale multiplies grad
  * first (1/world_size after an all-reduce(sum)). */
 int32_t dmf_adam_step(float* theta, const float* grad, float* m, float* v, int64_t n,
                       float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale,
@@ -224,6 +224,41 @@ int32_t dmf_sgd_step(float* theta, const float* grad, float* momentum_buf, int64
                      int32_t step, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, void* stream);
 int32_t dmf_rmsprop_step(float* theta, const float* grad, float* square_avg, int64_t n, float lr, float alpha, float eps,
                          float grad_scale, int32_t* cursor_dev, void* stream);
+
+/* ---- weight decay, AdamW and gradient-norm clipping: ONE launch on the flat gradient of dmf_grad_reduce (after
+ * the all-reduce when data parallel) that does what a torch user writes between backward() and the end of step():
+ *   [scaler.unscale_(opt)]  torch.nn.utils.clip_grad_norm_(params, max_norm)  [scaler.step(opt); scaler.update()] / opt.step()
+ * for opt = torch.optim.Adam / AdamW / SGD / RMSprop(..., weight_decay=).  Per element, in this order:
+ *   1. g = grad[i] * grad_scale; with a scaler state and unscaled == 0: g = grad[i] * (grad_scale / state[0]), the product
+ *      dmf_unscale_adam forms.  grad is only read.
+ *   2. with a scaler state, any non-finite g skips the WHOLE step as dmf_unscale_adam does: theta, m, v stay, scale *= backoff,
+ *      tracker = 0, skipped steps += 1, *step_dev -= 1; the cursor still advances (and a clipped step still records its norm,
+ *      which then is inf or NaN).
+ *   3. max_norm > 0: S = sum_i (double)g^2 in a fixed order, norm = (float)sqrt(S), coef = min(1, max_norm / (norm + 1e-6f)),
+ *      g *= coef (a NaN norm gives NaN, as torch's clamp does); norm_hist (may be NULL) gets norm_hist[*cursor_dev] = norm, the
+ *      PRE-clip norm that clip_grad_norm_ returns (norm_hist[0] without a cursor).  max_norm <= 0: no clipping, norm_hist is
+ *      not written.
+ *   4. weight decay: DMF_OPT_ADAM, _SGD, _RMSPROP  g += weight_decay * theta   (torch's `weight_decay=`: L2, before anything else)
+ *                    DMF_OPT_ADAMW                 theta *= 1 - lr * weight_decay   (decoupled)
+ *   5. the update of the kind by the arithmetic of dmf_adam_step (m, v), dmf_sgd_step (m = momentum buffer, may be NULL when
+ *      momentum == 0; v unused) or dmf_rmsprop_step (m = square_avg, `eps`; v unused); the step count (bias corrections, SGD's
+ *      first step) is *step_dev when given, else `step`.
+ *   6. scaler growth as in dmf_unscale_adam; *cursor_dev += 1 (may be NULL).
+ * Every workgroup forms S and the skip decision itself from the whole gradient, in the same order, and then updates its own
+ * 256 elements: the same coef bits everywhere, no second launch and no grid barrier.  Without a scaler state growth_factor,
+ * backoff_factor, growth_interval and unscaled must be 0; with one, step_dev is required.  n == 0 is a no-op.
+ * Fails on: NULL theta / grad, NULL m or v where the kind needs it, n < 0, an unknown kind, a negative or non-finite
+ * weight_decay, a non-finite max_norm, scaler hyper-parameters without a scaler state. */
+#define DMF_OPT_ADAM    0
+#define DMF_OPT_ADAMW   1
+#define DMF_OPT_SGD     2
+#define DMF_OPT_RMSPROP 3
+int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind,
+                       float lr, float beta1, float beta2, float eps, float momentum, float alpha,
+                       float weight_decay, float max_norm, int32_t step, float grad_scale,
+                       int32_t* step_dev, int32_t* cursor_dev,
+                       float* scaler_state, float growth_factor, float backoff_factor, int32_t growth_interval,
+                       int32_t unscaled, float* norm_hist, void* stream);
 
 /* dmf_grad_reduce + dmf_adam_step in one launch (single-GPU step). grad may be NULL. */
 int32_t dmf_grad_reduce_adam(const dmf_shape* shape, int32_t B, const void* workspace,

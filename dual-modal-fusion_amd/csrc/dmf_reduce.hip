@@ -137,18 +137,24 @@ struct FcTile {
 
 // (adam_update's arithmetic, stated again on purpose: through a shared helper the reduce kernel gets another register
 // allocation and six more instructions)
-__device__ __forceinline__ void adam_apply(const ReduceArgs& a, int64_t p, float g, float th0, float m_0, float v_0, const float* bcs) {
+struct ReduceTail { float* scaler; float* grad; float lr, b1, b2, eps; };   // the scalars of the tail, fetched at kernel entry
+__device__ __forceinline__ void adam_apply(const ReduceTail& a, float* theta, float* m, float* v, int64_t p, float g, float th0,
+                                           float m_0, float v_0, const float* bcs) {
   if (a.scaler != nullptr) {                         // unscale_ + the found_inf check of GradScaler, in the reduce
     g *= 1.f / a.scaler[0];
     if (!isfinite(g)) a.scaler[2] = 1.f;             // (every writer stores the same value)
   }
   if (a.grad != nullptr) a.grad[p] = g;
-  if (a.theta != nullptr) {
-    const float mn = m_0 + (g - m_0) * (1.f - a.b1);
-    const float vn = v_0 * a.b2 + (1.f - a.b2) * g * g;
-    a.m[p] = mn;
-    a.v[p] = vn;
-    a.theta[p] = th0 - (a.lr / bcs[0]) * (mn / (sqrtf(vn) / bcs[1] + a.eps));
+  if (theta != nullptr) {
+    // The fused and unfused steps are WRITTEN OUT (and contraction is off): left to the compiler, which products it fuses into
+    // the following addition changes with the code around this function — m's update came out as multiply + add once the
+    // constants were fetched early, one ulp away from every earlier build.  These are the forms the kernel has always had.
+#pragma clang fp contract(off)
+    const float mn = fmaf(g - m_0, 1.f - a.b1, m_0);
+    const float vn = v_0 * a.b2 + ((1.f - a.b2) * g) * g;
+    m[p] = mn;
+    v[p] = vn;
+    theta[p] = fmaf(-(a.lr / bcs[0]), mn / (sqrtf(vn) / bcs[1] + a.eps), th0);
   }
 }
 
@@ -171,14 +177,15 @@ __device__ unsigned long long* g_rstamps = nullptr;
 #endif
 
 // 320 threads: waves 0-3 reduce, wave 4 only forms ADAM's bias corrections (beside the other waves' gradient loads).
-// The first nine arguments are everything a block needs to find its role and ISSUE its gradient loads; they are plain scalars
-// in front of the argument struct so that the compiler's kernarg preload (-mllvm -amdgpu-kernarg-preload-count, build.py) puts
-// them into scalar registers at wave launch: a kernel argument fetched by the wave itself arrives ~1.0 K cycles after wave
-// entry (stamps), and every load of this kernel was waiting behind that.  w0 = nFc1 | t1n << 16, w1 = nFc2 | t2n << 16,
-// w2 = nConv | nAttn << 16 (blocks per kind, tiles per row).
-__global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ dh,
-                                                          const float* __restrict__ z, const float* __restrict__ dl,
-                                                          const float* __restrict__ h, int w0, int w1, int w2, int B, const ReduceArgs a) {
+// The first ten arguments (14 dwords) are everything a block needs to find its role, ISSUE its gradient loads and ISSUE the
+// loads of the ADAM state of the parameters it owns; they are plain scalars in front of the argument struct so that the
+// compiler's kernarg preload (-mllvm -amdgpu-kernarg-preload-count, build.py) puts them into scalar registers at wave launch:
+// a kernel argument fetched by the wave itself arrives ~1.0 K cycles after wave entry (stamps), and a load that waits for it
+// starts its own cold round trip only then.  The slab rows and head vectors are addressed from the ONE workspace pointer
+// (their offsets follow from w3, w4 and B: reduce_words_unpack, dmf_shapes.h), which leaves room for theta / m / v.
+// w0 = nFc1 | t1n << 16, w1 = nFc2 | t2n << 16, w2 = nConv | nAttn << 16 (blocks per kind, tiles per row).
+__global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restrict__ ws, float* theta, float* m, float* v, int w0, int w1,
+                                                          int w2, int w3, int w4, int B, const ReduceArgs a) {
   __shared__ float vbuf[4][256];        // tile partials of the four waves / [16 chunks][64] attention-slab partials / [4][16] piece partials
   __shared__ float bbuf[4][16];         // bias partials of the four waves
   __shared__ float bcs[2];
@@ -190,6 +197,12 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   const int nFc1 = w0 & 0xffff, t1n = w0 >> 16, nFc2 = w1 & 0xffff, t2n = w1 >> 16, nConv = w2 & 0xffff, nAttn = w2 >> 16;
   const int nTotal = nFc1 + nFc2 + nConv + nAttn + 1;
   const int nblk = B < MAX_BLOCKS ? B : MAX_BLOCKS;  // slab rows: the patch kernel's grid
+  const ReduceGeom G = reduce_words_unpack(w3, w4, B);
+  const float* __restrict__ slab = ws;
+  const float* __restrict__ z = ws + G.z;
+  const float* __restrict__ h = ws + G.h;
+  const float* __restrict__ dh = ws + G.dh;
+  const float* __restrict__ dl = ws + G.dl;
   if (blk == nTotal - 1) {                           // bookkeeping block
     const int cur = a.cursor_dev != nullptr ? *a.cursor_dev : 0;
     if (a.loss != nullptr && a.loss_hist != nullptr) {
@@ -226,7 +239,7 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
     const int mt = (int)((float)sub / (float)tn + 0.01f);            // (exact for the few hundred tiles there are)
     m0 = 8 * mt; n0 = 8 * (sub - mt * tn);
     if (tid < 256) {
-      sb = kind == 0 ? ft.init(dh, m0, a.H, z, n0, B) : ft.init(dl, m0, a.K, h, n0, B);
+      sb = kind == 0 ? ft.init(dh, m0, G.H, z, n0, B) : ft.init(dl, m0, G.K, h, n0, B);
       ft.issue(sb);
     }
   } else if (kind == 2 && tid < 256) {
@@ -236,40 +249,62 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
     for (int i = 0; i < 4; ++i)                          // (unconditional, clamped row; masked where they are summed)
       cv[i] = *reinterpret_cast<const float4*>(csrc + (size_t)min((4 * i + wv) * 16 + r16, nblk - 1) * 16);
   }
-  __builtin_amdgcn_sched_barrier(0);                 // (nothing that waits for these loads may move up here)
-  RSTAMP(2);
-  // ---- which parameter(s) this thread finishes (p, own; p2, own2: the bias of a first-column tile), and their ADAM state
+  // ---- which parameter(s) this thread finishes (p, own; p2, own2: the bias of a first-column tile) — from the preloaded words
+  // alone — and their ADAM state, requested in the same batch as the gradients: UNCONDITIONAL loads from a clamped index
+  // (element 0 for a lane that owns nothing; the workspace stands in for a missing theta), masked where they are used
   int64_t p = 0, p2 = 0;
   bool own = false, own2 = false;
   if (kind == 0) {
     const int j = m0 + ((tid >> 3) & 7), i = n0 + (tid & 7);
-    own = tid < 64 && j < a.H && i < a.F2;
-    p = a.oFc1w + (int64_t)j * a.F2 + i;
-    own2 = n0 == 0 && tid < 8 && m0 + tid < a.H;
-    p2 = a.oFc1b + m0 + tid;
+    own = tid < 64 && j < G.H && i < G.F2;
+    p = G.oFc1w + (int64_t)j * G.F2 + i;
+    own2 = n0 == 0 && tid < 8 && m0 + tid < G.H;
+    p2 = G.oFc1b + m0 + tid;
   } else if (kind == 1) {
     const int k = m0 + ((tid >> 3) & 7), j = n0 + (tid & 7);
-    own = tid < 64 && k < a.K && j < a.H;
-    p = a.oFc2w + (int64_t)k * a.H + j;
-    own2 = n0 == 0 && tid < 8 && m0 + tid < a.K;
-    p2 = a.oFc2b + m0 + tid;
+    own = tid < 64 && k < G.K && j < G.H;
+    p = G.oFc2w + (int64_t)k * G.H + j;
+    own2 = n0 == 0 && tid < 8 && m0 + tid < G.K;
+    p2 = G.oFc2b + m0 + tid;
   } else if (kind == 2) {
     p = (int64_t)16 * sub + tid;
-    own = tid < 16 && p < a.NCONV;
-  } else {
-    p = a.oAttn + (int64_t)64 * sub + tid;
-    own = tid < 64 && 64 * sub + tid < a.ASLAB;
+    own = tid < 16 && p < G.NCONV;
   }
   RSTAMP(1);
-  float th0 = 0.f, m_0 = 0.f, v_0 = 0.f, th2 = 0.f, m_2 = 0.f, v_2 = 0.f;
-  if (a.theta != nullptr) {
-    if (own) { th0 = a.theta[p]; m_0 = a.m[p]; v_0 = a.v[p]; }
-    if (own2) { th2 = a.theta[p2]; m_2 = a.m[p2]; v_2 = a.v[p2]; }
+  float th0, m_0, v_0, th2 = 0.f, m_2 = 0.f, v_2 = 0.f;
+  {
+    const bool adam = theta != nullptr;
+    const float* tb = adam ? theta : ws;
+    const float* mb = adam ? m : ws;
+    const float* vb = adam ? v : ws;
+    const int64_t q = (adam && own && kind < 3) ? p : 0;
+    th0 = tb[q]; m_0 = mb[q]; v_0 = vb[q];
+    if (kind < 2) {                                  // (scalar condition)
+      const int64_t q2 = (adam && own2) ? p2 : 0;
+      th2 = tb[q2]; m_2 = mb[q2]; v_2 = vb[q2];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);                 // (nothing that waits for these loads may move up here)
+  RSTAMP(2);
+#ifndef DMF_REDUCE_TAIL_EARLY
+#define DMF_REDUCE_TAIL_EARLY 1
+#endif
+  // the tail's scalars (exchange on / off, scaler, gradient pointer, ADAM's constants) live in the argument struct: read where
+  // they are used they are four DEPENDENT kernarg fetches behind the barrier; fetched here they arrive under the gradient loads
+  const int world = a.x.world;
+  const ReduceTail tl = {a.scaler, a.grad, a.lr, a.b1, a.b2, a.eps};
+#if DMF_REDUCE_TAIL_EARLY
+  asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.lr), "s"(tl.b1), "s"(tl.b2), "s"(tl.eps));
+#endif
+  if (kind == 3) {                                   // attention slabs: the block's role needs the argument struct
+    p = a.oAttn + (int64_t)64 * sub + tid;
+    own = tid < 64 && 64 * sub + tid < a.ASLAB;
+    if (theta != nullptr && own) { th0 = theta[p]; m_0 = m[p]; v_0 = v[p]; }
   }
   float* part = &vbuf[0][0];
   if (tid >= 256) {
     // bias corrections (lanes 0 / 1 of wave 4: beta1 / beta2 side by side), b^step by repeated squaring in double
-    if (a.theta != nullptr && tid < 258) {
+    if (theta != nullptr && tid < 258) {
       float bc = tid == 256 ? a.bc1 : a.bc2_sqrt;
       if (a.step_dev != nullptr) {
         const double pw = powi_double((double)(tid == 256 ? a.b1 : a.b2), *a.step_dev);
@@ -348,13 +383,13 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
       g = tree16(t);
     }
   }
-  if (a.x.world > 1) {                               // (the owning lanes exchange; no barriers inside)
+  if (world > 1) {                               // (the owning lanes exchange; no barriers inside)
     const int seq = *a.step_dev + a.seq_bias;
     g = xgmi_exchange(a.x, 0, seq, p, own, g) * a.grad_scale;
     if (kind < 2 && n0 == 0) g2 = xgmi_exchange(a.x, 0, seq, p2, own2, g2) * a.grad_scale;
   }
-  if (own) adam_apply(a, p, g, th0, m_0, v_0, bcs);
-  if (own2) adam_apply(a, p2, g2, th2, m_2, v_2, bcs);
+  if (own) adam_apply(tl, theta, m, v, p, g, th0, m_0, v_0, bcs);
+  if (own2) adam_apply(tl, theta, m, v, p2, g2, th2, m_2, v_2, bcs);
   RSTAMP(5);
   RSTAMP_DUMP();
 }
@@ -613,10 +648,14 @@ hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const
     *refusal = "grad_reduce: too many blocks of one kind";
     return hipErrorInvalidValue;
   }
-  const WsLayout w = make_ws(L, B);
+  int w3 = 0, w4 = 0;
+  if (!reduce_words_pack(L, B, &w3, &w4)) {
+    *refusal = "grad_reduce: the layout does not fit the packed launch words";
+    return hipErrorInvalidValue;
+  }
   const int grid = nFc1 + nFc2 + nConv + nAttn + 1;   // + the bookkeeping block
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3(grid), dim3(320), 0, st, ws + w.slab, ws + w.dh, ws + w.z, ws + w.dl, ws + w.h,
-                     nFc1 | (t1n << 16), nFc2 | (t2n << 16), nConv | (nAttn << 16), B, a);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16), nFc2 | (t2n << 16),
+                     nConv | (nAttn << 16), w3, w4, B, a);
   return hipGetLastError();
 }
 

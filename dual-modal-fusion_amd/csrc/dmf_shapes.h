@@ -98,4 +98,37 @@ inline WsLayout make_ws(const Layout& L, int B) {
   return w;
 }
 
+// What a block of the reduce launch needs to find the parameters it owns and the head vectors it reads, in TWO 32-bit words
+// (they travel as leading kernel arguments, which are in scalar registers at wave entry: dmf_reduce.hip):
+//   w3 = H | 2F << 8 | K << 16,  w4 = NCONV.
+// Everything else follows from the flat layout (make_layout: fc1.weight starts where the conv parameters end) and from
+// make_ws.  reduce_words_pack refuses a layout the words cannot hold or reproduce.
+struct ReduceGeom {
+  int H, F2, K, NCONV;
+  int64_t oFc1w, oFc1b, oFc2w, oFc2b;      // flat parameter offsets
+  int64_t z, h, dh, dl;                    // workspace offsets (the slab rows start the workspace)
+};
+DMF_HD inline ReduceGeom reduce_words_unpack(int w3, int w4, int B) {
+  ReduceGeom g{};
+  g.H = w3 & 0xff; g.F2 = (w3 >> 8) & 0xff; g.K = (w3 >> 16) & 0xff; g.NCONV = w4;
+  g.oFc1w = g.NCONV;
+  g.oFc1b = g.oFc1w + g.H * g.F2;
+  g.oFc2w = g.oFc1b + g.H;
+  g.oFc2b = g.oFc2w + g.K * g.H;
+  g.z = (int64_t)MAX_BLOCKS * ((g.NCONV + 31) & ~31);
+  g.h = g.z + (int64_t)B * g.F2;
+  g.dh = g.h + (int64_t)B * g.H;
+  g.dl = g.dh + (int64_t)B * g.H;
+  return g;
+}
+inline bool reduce_words_pack(const Layout& L, int B, int* w3, int* w4) {
+  if (L.H < 0 || L.H > 0xff || L.F2 < 0 || L.F2 > 0xff || L.K < 0 || L.K > 0xff || L.NCONV < 0) return false;
+  *w3 = L.H | (L.F2 << 8) | (L.K << 16);
+  *w4 = L.NCONV;
+  const ReduceGeom g = reduce_words_unpack(*w3, *w4, B);
+  const WsLayout w = make_ws(L, B);
+  return g.oFc1w == L.off[8] && g.oFc1b == L.off[9] && g.oFc2w == L.off[10] && g.oFc2b == L.off[11] && w.slab == 0 &&
+         g.z == w.z && g.h == w.h && g.dh == w.dh && g.dl == w.dl;
+}
+
 }  // namespace dmf

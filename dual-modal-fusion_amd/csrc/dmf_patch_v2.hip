@@ -53,7 +53,7 @@ namespace dmf {
 // registers (no wait, no store, no branch inside the phases) and lane 0 dumps them right before the wave ends.
 #ifdef DMF_STAMPS
 __device__ unsigned long long* g_v2stamps = nullptr;     // [block][16 waves][16 stamps]
-#define VSTAMP_DECL unsigned long long vst_[14] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}
+#define VSTAMP_DECL unsigned long long vst_[16] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}
 // (the stamp WAITS for its own result: s_memtime returns like a scalar load, and a compiler that believes the value is there at
 // once may spill it and reuse the register pair — the result, landing late, then overwrites whatever lives there.  Found as a
 // memory fault of the 4-band instance of this diagnostic build, where 14 live stamps exhaust the scalar registers.)
@@ -61,7 +61,7 @@ __device__ unsigned long long* g_v2stamps = nullptr;     // [block][16 waves][16
 #define VSTAMP_W(i) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(vst_[i])); } while (0)
 #define VSTAMP_RT(i) do { asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(vst_[i])); } while (0)
 #define VSTAMP_DUMP() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); if (lane == 0 && g_v2stamps != nullptr) { \
-    _Pragma("unroll") for (int i_ = 0; i_ < 14; ++i_) g_v2stamps[((size_t)blockIdx.x * 16 + wave) * 16 + i_] = vst_[i_]; } } while (0)
+    _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) g_v2stamps[((size_t)blockIdx.x * 16 + wave) * 16 + i_] = vst_[i_]; } } while (0)
 #else
 #define VSTAMP_DECL do { } while (0)
 #define VSTAMP(i) do { } while (0)
@@ -71,6 +71,8 @@ __device__ unsigned long long* g_v2stamps = nullptr;     // [block][16 waves][16
 #endif
 
 typedef const int32_t __attribute__((address_space(4))) cint;
+typedef float __attribute__((address_space(1))) gfloat;
+typedef int32_t __attribute__((address_space(1))) gint;
 
 // LDS-array cycles of one ds_read_b128 x-row read per wave, summed over the conv waves, for a window image
 // [row][RS] = [row][P pixels x CS | row padding]: the 16 lanes of a service group hold different patch rows, and up to two
@@ -273,6 +275,12 @@ __device__ __forceinline__ float lane_below(float v) {
   if constexpr (ROWDPP) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xF, 0xF, true));   // row_shl:1
   else return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));                    // wave_shl:1
 }
+// Where 16-byte chunk c (of 16) of row i of the transposed fc1.weight image [2F][H = 64] sits inside the row, in floats: the
+// chunks are rotated by i mod 4.  The dz phase reads the image with 4 lanes per row, 64 bytes apart, and rows are 256 bytes
+// apart: unrotated, the 16 lanes of a ds_read_b128 service group (4 rows x 4 lanes) share 4 of the 16 chunk positions — a
+// 4-way bank conflict on every one of its 4 reads, 5 waves at once, right behind barrier 2; rotated, they take 16 different
+// ones.  (i mod 4 is the vector component for the head wave, which writes the image: four per-lane offsets in all.)
+__device__ __forceinline__ int w1t_chunk(int i, int c) { return ((c + (i & 3)) & 15) << 2; }
 __device__ __forceinline__ float quad_sum(float v) {     // over the 4 lanes of a quad, result in each of them
   v = DMF_DPP_ADD(v, 0xB1);     // quad_perm [1,0,3,2]
   v = DMF_DPP_ADD(v, 0x4E);     // quad_perm [2,3,0,1]
@@ -641,13 +649,14 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 dhv = *reinterpret_cast<const float4*>(sDh + 16 * m + 4 * q);
-        const float4 wv = *reinterpret_cast<const float4*>(smem + V::oW1T + i * H + 16 * m + 4 * q);
+        const float4 wv = *reinterpret_cast<const float4*>(smem + V::oW1T + i * H + w1t_chunk(i, 4 * m + q));
         d = fmaf(wv.x, dhv.x, fmaf(wv.y, dhv.y, fmaf(wv.z, dhv.z, fmaf(wv.w, dhv.w, d))));
       }
       d = quad_sum(d);
       if (m == 0) sDz[i] = d;
     }
     LDS_BARRIER();                                       // barrier 3: dz complete
+    VSTAMP(14);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int t = tid_ + i * V::NT;
@@ -665,7 +674,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
           const float4 o = *reinterpret_cast<const float4*>(slab);
           v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
         }
-__builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain stores here: 16.80 vs 16.98 us per step)
+        __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain stores here: 16.80 vs 16.98 us per step)
         __builtin_nontemporal_store(v.y, slab + 1);
         __builtin_nontemporal_store(v.z, slab + 2);
         __builtin_nontemporal_store(v.w, slab + 3);
@@ -1117,6 +1126,8 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
     float4 w1r[F2 / 4];                // fc1.weight row `lane`, in registers for fc1 (loaded behind the first gather issue)
     float bh = 0.f, bk = 0.f;
     VSTAMP(1);
+    constexpr bool EXITP = (MODE == MODE_TRAIN || MODE == MODE_BWD);      // the passes with the dz phase and the scaled copy-out
+    gint* adam_p = nullptr;
 
     int it = 0;
     for (int b = blockIdx.x; b < B; b += gridDim.x, ++it) {
@@ -1147,6 +1158,23 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
         label = ((cint*)a.labels)[boff + b];
         label = label < 0 ? 0 : (label >= K ? K - 1 : label);
       }
+      // The loss scaler's value by a SCALAR load, here, where the wave waits for barrier W anyway.  Read as a vector load
+      // inside the `lane < K` block of the softmax its result register stayed "pending" on the merged path, and every
+      // later write to that register — store addresses of the exit among them — got an s_waitcnt vmcnt(0), which by then
+      // waited for the wave's own stores.  (The scaler state is written by other launches only.)
+      float sv = 1.f;
+      if (MODE == MODE_TRAIN && a.scaler != nullptr) sv = ((cfloat*)a.scaler)[0];
+      // What the exit needs of the argument block beyond the words fetched at kernel entry (loss scale, the dl workspace and
+      // the step count's pointer) is fetched here too, with the labels pointer — not between the stores of the exit, where
+      // each fetch was followed by its wait.  (The empty asm is what makes them be here.)
+      float ls_arg = 0.f;
+      gfloat* ws_dl_arg = (gfloat*)a.ws_dl;             // (global pointers by type: an asm operand forgets where it came from)
+      if constexpr (EXITP) {
+        ls_arg = a.loss_scale;
+        gint* adam_arg = (gint*)a.adam_step;
+        asm volatile("" : "+s"(ls_arg), "+s"(ws_dl_arg), "+s"(adam_arg));
+        adam_p = adam_arg;
+      }
       if (MODE == MODE_BWD) dlx = lane < K ? a.dlogits[(size_t)b * K + lane] : 0.f;
       __syncthreads();                                   // barrier W: window complete (this wave's pieces included)
       VSTAMP(4);
@@ -1173,10 +1201,10 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
         if constexpr (TR && !UNIT) {
 #pragma unroll
           for (int q = 0; q < F2 / 4; ++q) {
-            sW1T[(4 * q) * H + lane] = w1r[q].x;
-            sW1T[(4 * q + 1) * H + lane] = w1r[q].y;
-            sW1T[(4 * q + 2) * H + lane] = w1r[q].z;
-            sW1T[(4 * q + 3) * H + lane] = w1r[q].w;
+            sW1T[(4 * q) * H + w1t_chunk(4 * q, lane >> 2) + (lane & 3)] = w1r[q].x;
+            sW1T[(4 * q + 1) * H + w1t_chunk(4 * q + 1, lane >> 2) + (lane & 3)] = w1r[q].y;
+            sW1T[(4 * q + 2) * H + w1t_chunk(4 * q + 2, lane >> 2) + (lane & 3)] = w1r[q].z;
+            sW1T[(4 * q + 3) * H + w1t_chunk(4 * q + 3, lane >> 2) + (lane & 3)] = w1r[q].w;
           }
         }
       }
@@ -1242,7 +1270,7 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
         if (MODE == MODE_TRAIN) {
           const float e = lane < K ? __expf(lg - mx) : 0.f;
           const float se = wave_sum_dpp(e);
-          const float ls = a.loss_scale * (a.scaler != nullptr ? a.scaler[0] : 1.f);
+          const float ls = ls_arg * sv;
           dl = lane < K ? (e / se - (lane == label ? 1.f : 0.f)) * ls : 0.f;
           const float lgt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lg), __builtin_amdgcn_readfirstlane(label)));
           loss_b = (mx + __logf(se)) - lgt;
@@ -1272,6 +1300,7 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
       if constexpr (TR) LDS_BARRIER();                   // barrier 2: dh and the unit gradients complete
       VSTAMP(8);
       if constexpr (TR) scale_and_store(it, b);
+      VSTAMP(15);
       // this patch's head vectors for the gradient reduce
       if ((MODE != MODE_BWD || a.logits != nullptr) && lane < K) a.logits[(size_t)b * K + lane] = lg;
       if (a.pred != nullptr && lane == 0) a.pred[b] = pred_b;
@@ -1293,7 +1322,7 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
         a.ws_h[hv] = h;
         if constexpr (!UNIT) {
           a.ws_dh[hv] = dh;
-          a.ws_dl[hv] = dl;
+          ws_dl_arg[hv] = dl;
         }
         if (lane < F2) a.ws_z[hv] = zo0;
         if (F2 > 64 && 64 + lane < F2) a.ws_z[hv_index(b, 64 + lane, B)] = zo1;
@@ -1302,7 +1331,10 @@ __builtin_nontemporal_store(v.x, slab);       // (nt beats sc1 / sc0 sc1 / plain
     }
     // the device-side ADAM step count advances once per launch — here, at the very end of one wave's work: in front of the
     // coordinate request (where it used to be) its null test made every wave wait for a kernel argument that is not preloaded
-    if ((MODE == MODE_TRAIN || UNIT || DENSE) && a.adam_step != nullptr && blockIdx.x == 0 && lane == 0) *a.adam_step += 1;
+    // (train pass: the block index first — the other workgroups test nothing else; the pointer is the word fetched above)
+    if constexpr (EXITP) {
+      if (MODE == MODE_TRAIN && blockIdx.x == 0 && lane == 0 && adam_p != nullptr) *adam_p += 1;
+    } else if ((UNIT || DENSE) && a.adam_step != nullptr && blockIdx.x == 0 && lane == 0) *a.adam_step += 1;
   }
   VSTAMP_W(10);
   VSTAMP_RT(13);

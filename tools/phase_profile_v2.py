@@ -20,6 +20,10 @@ from function.function import data_padding, data_padding_aux
 from model.gmfnet import Net
 
 CONV = ['entry', 'prologue', 'gather issued', 'aux done', 'barrierW', 'barrier1', 'spec dW', 'sums', 'barrier2', 'slab adds', 'end', 'barrier0']
+# (stamps 12, 13 are the real-time pair; 14: behind barrier 3, every wave; 15: head wave, behind its share of the copy-out = in
+# front of its first store.  'slab adds' (9) is behind the wave's last store)
+COLS = list(range(12)) + [14, 15]
+NAMES = CONV + ['barrier3', 'head stores']
 
 
 def main():
@@ -59,12 +63,12 @@ def main():
     t0[t0 == 0] = np.nan
     first = np.nanmin(t0, axis=1)                      # first wave entry per workgroup
     print('cycles since the workgroup\'s first wave entered the kernel (median over %d workgroups)' % nblk)
-    print('wave ' + ' '.join('%13s' % n for n in CONV))
+    print('wave ' + ' '.join('%13s' % n for n in NAMES))
     for w in range(16):
         if not np.isfinite(t0[:, w]).any():
             continue
         row = []
-        for i in range(12):
+        for i in COLS:
             v = s[:, w, i]
             ok = v > 0
             row.append(np.median(v[ok] - first[ok]) if ok.any() else float('nan'))

@@ -53,6 +53,19 @@ __device__ __forceinline__ size_t qua_row(const QuaArgs& a, int st, int g) {
 __device__ __forceinline__ float xlogx(float y) { return y > 0.f ? y * logf(y) : 0.f; }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
+// d/dy of w * exp(-|c / y|), the beta term's derivative at one probability y (w = beta / (bs K), c = A3 or B3):
+// w e^{-|u|} |u| / y with u = c / y.  It tends to 0 as y -> 0, and that limit is taken wherever the exponential has
+// underflowed (u is then huge or infinite and y * y may be 0: the plain expression would be 0 * inf or 0 / 0) and at
+// y == 0, like y log y.  Where y * y itself underflows under a live exponential (|c| < ~1e-20) the same value is formed
+// without the square.  One function for both forms of the kernel: their rows stay bit-identical.
+__device__ __forceinline__ float beta_dprob(float w, float c, float y) {
+  if (!(y > 0.f)) return 0.f;
+  const float u = c / y, e = expf(-fabsf(u));
+  if (!(e > 0.f)) return 0.f;
+  const float y2 = y * y;
+  return y2 > 0.f ? w * sgn(u) * e * c / y2 : w * (fabsf(u) * e / y);
+}
+
 // The batch is walked in tiles of TS samples whose 4*TS softmax rows live in LDS (sP[stream][sample][k]); within a
 // tile all 1024 threads work: one softmax row each, then thread <-> (sample, quarter) for the sums and
 // thread <-> (sample, stream) for the gradient rows.  A batch that fits one tile (bs <= TS, e.g. 256 x 12 logits)
@@ -229,12 +242,12 @@ __global__ __launch_bounds__(QT) void qua_loss_kernel(const QuaArgs a, const int
         if (st == 0) {
           const float lg1 = (pk > 0.f) ? px[k] + 1.f : 0.f;
           float d = inv_n * (cA1 * (lg1 - qe[k]) + cA2 * (lg1 - lr) + cA3 * (lg1 - ls)) - inv_n * cB1 * qk / (pk + a.eps) + dz;
-          if (a.beta != 0.f && pk > 0.f) { const float u = A3 / pk; d += a.beta * inv_nk * sgn(u) * expf(-fabsf(u)) * A3 / (pk * pk); }
+          if (a.beta != 0.f) d += beta_dprob(a.beta * inv_nk, A3, pk);
           return d;
         }
         const float lg1 = (qk > 0.f) ? qx[k] + 1.f : 0.f;
         float d = inv_n * (cB1 * (lg1 - pe[k]) + cB2 * (lg1 - lr) + cB3 * (lg1 - ls)) - inv_n * cA1 * pk / (qk + a.eps) + dz;
-        if (a.beta != 0.f && qk > 0.f) { const float u = B3 / qk; d += a.beta * inv_nk * sgn(u) * expf(-fabsf(u)) * B3 / (qk * qk); }
+        if (a.beta != 0.f) d += beta_dprob(a.beta * inv_nk, B3, qk);
         return d;
       };
       const float* y = sP + ((size_t)st * TS + i) * K;
@@ -408,13 +421,13 @@ __global__ __launch_bounds__(256) void qua_e3_kernel(const QuaArgs a, const int 
     {
       const float lg1 = (pk > 0.f) ? r.lx[0] + 1.f : 0.f;
       float v = inv_n * (cA1 * (lg1 - r.le[1]) + cA2 * (lg1 - lr) + cA3 * (lg1 - ls)) - inv_n * cB1 * qk / (pk + a.eps) + dz;
-      if (a.beta != 0.f && pk > 0.f) { const float u = sc.A3 / pk; v += a.beta * inv_nk * sgn(u) * expf(-fabsf(u)) * sc.A3 / (pk * pk); }
+      if (a.beta != 0.f) v += beta_dprob(a.beta * inv_nk, sc.A3, pk);
       d[0] = v;
     }
     {
       const float lg1 = (qk > 0.f) ? r.lx[1] + 1.f : 0.f;
       float v = inv_n * (cB1 * (lg1 - r.le[0]) + cB2 * (lg1 - lr) + cB3 * (lg1 - ls)) - inv_n * cA1 * pk / (qk + a.eps) + dz;
-      if (a.beta != 0.f && qk > 0.f) { const float u = sc.B3 / qk; v += a.beta * inv_nk * sgn(u) * expf(-fabsf(u)) * sc.B3 / (qk * qk); }
+      if (a.beta != 0.f) v += beta_dprob(a.beta * inv_nk, sc.B3, qk);
       d[1] = v;
     }
     d[2] = -inv_n * (cA2 * pk + cB2 * qk) / (rk + a.eps);

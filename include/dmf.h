@@ -287,7 +287,12 @@ typedef struct dmf_qua_params { float alpha, beta, gamma, epsilon, tao; } dmf_qu
  * train/loss_function.py:57-76).  logits [4*bs, K]; labels [bs] int32 (the reference passes float class ids);
  * cursor (may be NULL) as in dmf_input: labels[(*cursor)*bs + i], loss_hist[*cursor].  loss [1] and loss_hist may be
  * NULL; dlogits [4*bs, K] may be NULL (loss only: the validation loop, tostagesolver.py:293-295) and is multiplied
- * by grad_scale. */
+ * by grad_scale.
+ * Limits, where a float32 probability y is 0 or so small that a term of the formula underflows (a logit some 50 or more
+ * below its row's maximum): y log y and its derivative count as 0 at y == 0; exp(-|c / y|) of the beta term and its
+ * derivative exp(-|c / y|) |c| / y^2 count as 0 wherever the exponential has underflowed (both tend to 0 with y, although
+ * y * y reaches 0 first and the plain quotient would be 0 / 0).  With these a row with such a class gives a finite loss and
+ * finite dlogits: the values of the formula in exact arithmetic, to within float32 rounding. */
 int32_t dmf_qua_loss(const float* logits, int32_t bs, int32_t K, const int32_t* labels, const int32_t* cursor,
                      const dmf_qua_params* params, float grad_scale, float* loss, float* loss_hist, float* dlogits,
                      void* stream);

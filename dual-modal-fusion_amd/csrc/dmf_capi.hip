@@ -108,6 +108,16 @@ static void host_bias_corrections(float b1, float b2, int32_t step, float* bc1, 
   *bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
 }
 
+// dmf_adam_step, dmf_sgd_step, dmf_rmsprop_step and dmf_unscale_adam are optim_step_kernel with neutral keys (weight decay 0,
+// max_norm 0): what they share of its arguments.  (The kernel writes *step_dev only where a scaler step is skipped.)
+static OptimArgs plain_step(int kind, float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float grad_scale,
+                            int32_t step, const int32_t* step_dev, int32_t* cursor_dev) {
+  OptimArgs a{};
+  a.theta = theta; a.grad = grad; a.m = m; a.v = v; a.n = n; a.kind = kind; a.lr = lr; a.grad_scale = grad_scale;
+  a.step = step; a.step_dev = const_cast<int32_t*>(step_dev); a.cursor_dev = cursor_dev;
+  return a;
+}
+
 extern "C" {
 
 int32_t dmf_version(void) { return DMF_VERSION; }
@@ -280,9 +290,12 @@ int32_t dmf_unscale_adam(float* theta, float* grad, float* m, float* v, int64_t 
     return fail("%s", "unscale_adam: bad n / growth_interval / factors");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (!unscaled && check(launch_unscale_check(grad, n, grad_scale, scaler_state, st), "unscale launch")) return 1;
-  return check(launch_unscale_adam(theta, grad, m, v, n, lr, beta1, beta2, eps, scaler_state, growth_factor, backoff_factor,
-                                   growth_interval, adam_step_dev, cursor_dev, st),
-               "scaled adam launch");
+  // grad is unscaled in memory by now and found_inf is in state[2]: the kernel takes it as it is and closes the scaler's step
+  OptimArgs a = plain_step(DMF_OPT_ADAM, theta, grad, m, v, n, lr, 1.f, 0, adam_step_dev, cursor_dev);
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  a.state = scaler_state; a.growth = growth_factor; a.backoff = backoff_factor; a.interval = growth_interval;
+  a.unscaled = 1; a.checked = 1;
+  return check(launch_optim_step(a, st), "scaled adam launch");
 }
 
 int32_t dmf_half_supported(const dmf_shape* s) {
@@ -533,28 +546,28 @@ int32_t dmf_adam_step(float* theta, const float* grad, float* m, float* v, int64
                       int32_t* cursor_dev, void* stream) {
   if (theta == nullptr || grad == nullptr || m == nullptr || v == nullptr) return fail("%s", "null argument");
   if (n <= 0 || (step < 1 && adam_step_dev == nullptr)) return fail("%s", "n and step must be positive");
-  float bc1, bc2s;                                     // (step < 1: the kernel takes the device step count instead)
-  host_bias_corrections(beta1, beta2, step < 1 ? 1 : step, &bc1, &bc2s);
-  return check(launch_adam(theta, grad, m, v, n, lr, beta1, beta2, eps, bc1, bc2s, grad_scale, adam_step_dev, cursor_dev,
-                           static_cast<hipStream_t>(stream)),
-               "adam launch");
+  OptimArgs a = plain_step(DMF_OPT_ADAM, theta, grad, m, v, n, lr, grad_scale, step, adam_step_dev, cursor_dev);
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  if (adam_step_dev == nullptr) host_bias_corrections(beta1, beta2, step, &a.bc1, &a.bc2_sqrt);   // (else: the kernel, from the device count)
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "adam launch");
 }
 
 int32_t dmf_sgd_step(float* theta, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
                      int32_t step, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, void* stream) {
   if (theta == nullptr || grad == nullptr || (momentum != 0.f && momentum_buf == nullptr)) return fail("%s", "null argument");
   if (n <= 0 || (step < 1 && step_dev == nullptr)) return fail("%s", "n and step must be positive");
-  return check(launch_sgd(theta, grad, momentum_buf, n, lr, momentum, grad_scale, step_dev, step, cursor_dev,
-                          static_cast<hipStream_t>(stream)),
-               "sgd launch");
+  OptimArgs a = plain_step(DMF_OPT_SGD, theta, grad, momentum_buf, nullptr, n, lr, grad_scale, step, step_dev, cursor_dev);
+  a.momentum = momentum;
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "sgd launch");
 }
 
 int32_t dmf_rmsprop_step(float* theta, const float* grad, float* square_avg, int64_t n, float lr, float alpha, float eps,
                          float grad_scale, int32_t* cursor_dev, void* stream) {
   if (theta == nullptr || grad == nullptr || square_avg == nullptr) return fail("%s", "null argument");
   if (n <= 0) return fail("%s", "n must be positive");
-  return check(launch_rmsprop(theta, grad, square_avg, n, lr, alpha, eps, grad_scale, cursor_dev, static_cast<hipStream_t>(stream)),
-               "rmsprop launch");
+  OptimArgs a = plain_step(DMF_OPT_RMSPROP, theta, grad, square_avg, nullptr, n, lr, grad_scale, 0, nullptr, cursor_dev);
+  a.alpha = alpha; a.eps = eps;
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "rmsprop launch");
 }
 
 int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,

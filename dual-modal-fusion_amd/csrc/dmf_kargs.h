@@ -122,17 +122,10 @@ struct ReduceArgs {
 // dmf_reduce.hip.  launch_grad_reduce carves the head vectors and conv slabs out of the workspace `ws` itself; a geometry
 // its block packing cannot hold is refused with hipErrorInvalidValue and *refusal set to the reason (else null).
 hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal);
-hipError_t launch_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                       float bc1, float bc2_sqrt, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, hipStream_t st);
-hipError_t launch_sgd(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum, float grad_scale,
-                      const int32_t* step_dev, int32_t step, int32_t* cursor_dev, hipStream_t st);
-hipError_t launch_rmsprop(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha, float eps,
-                          float grad_scale, int32_t* cursor_dev, hipStream_t st);
-hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st);
-hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2,
-                               float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
-                               int32_t* cursor_dev, hipStream_t st);
-// dmf_optim_step: weight decay / AdamW / gradient-norm clipping on the flat gradient, one launch (optim_step_kernel)
+// The optimiser step on the flat gradient, one launch (optim_step_kernel): dmf_optim_step with weight decay / AdamW /
+// gradient-norm clipping, and with neutral keys dmf_adam_step, dmf_sgd_step, dmf_rmsprop_step and dmf_unscale_adam.
+// launch_optim_step and launch_unscale_check are the only flat-gradient optimiser launchers (launch_adam, launch_sgd,
+// launch_rmsprop and launch_unscale_adam are gone with their kernels).
 struct OptimArgs {
   float* theta; const float* grad; float* m; float* v; int64_t n;
   int kind;                           // DMF_OPT_*
@@ -141,7 +134,10 @@ struct OptimArgs {
   float* state;                       // nullable loss-scaler state
   float growth, backoff; int interval, unscaled;
   float* norm_hist;                   // nullable: norm_hist[*cursor_dev] = the pre-clip norm
+  float bc1, bc2_sqrt;                // ADAM's bias corrections formed on the host; bc1 == 0: form them on the device from the step
+  int checked;                        // found_inf of this step is already in state[2] (needs state): it alone decides the skip
 };
+hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st);
 hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st);
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
 // the validation sum of an epoch and what its end decides (dmf_valid_accum, dmf_keep_best): one workgroup each

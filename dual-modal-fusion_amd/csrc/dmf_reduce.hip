@@ -1,6 +1,8 @@
 // dmf_reduce.hip — the batch-level launches behind the patch and attention kernels: the slab / outer-product gradient
-// reduction with its fused Adam (grad_reduce_kernel), the stand-alone optimiser kernels (Adam, SGD, RMSprop), the loss-scaler
-// pair, the one-launch step with weight decay and gradient-norm clipping (optim_step_kernel) and the small xgmi all-reduce.  dmf_capi.hip validates and calls the launch_* functions at the end of this file.
+// reduction with its fused Adam (grad_reduce_kernel), the ONE optimiser kernel on a flat gradient (optim_step_kernel: Adam, AdamW,
+// SGD, RMSprop, with or without weight decay, gradient-norm clipping and the loss scaler's step end; every dmf_*_step entry
+// point and dmf_unscale_adam launch it), the loss scaler's unscale + check (unscale_check_kernel) and the small xgmi
+// all-reduce.  dmf_capi.hip validates and calls the launch_* functions at the end of this file.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -30,7 +32,10 @@ __device__ __forceinline__ void adam_update(float* theta, float* m, float* v, in
   theta[p] -= (lr / bc1) * (mn / denom);
 }
 
-// the bodies of sgd_kernel and rmsprop_kernel below, for dmf_optim_step (those kernels keep their own statement)
+// ------------------------------------------------------------------------------ the reference's other two optimisers
+// torch.optim.SGD(lr, momentum) (dampening 0, no Nesterov): buf = g on the first step, else m buf + g; p -= lr buf.
+// torch.optim.RMSprop(lr, alpha) (eps 1e-8, momentum 0, not centred): sq = alpha sq + (1 - alpha) g g;
+// p -= lr g / (sqrt(sq) + eps).   (utils/utils.py:13-16)
 __device__ __forceinline__ void sgd_update(float* theta, float* buf, int64_t p, float g, float lr, float momentum, int st) {
   float b = g;
   if (momentum != 0.f) { b = st <= 1 ? g : momentum * buf[p] + g; buf[p] = b; }
@@ -394,44 +399,6 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   RSTAMP_DUMP();
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* theta, const float* grad, float* m, float* v, int64_t n,
-                                                   float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                   float grad_scale, const int32_t* step_dev, int32_t* cursor_dev) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (step_dev != nullptr) bias_corrections(*step_dev, b1, b2, bc1, bc2_sqrt);
-  if (p < n) adam_update(theta, m, v, p, grad[p] * grad_scale, lr, b1, b2, eps, bc1, bc2_sqrt);
-  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
-}
-
-// ------------------------------------------------------------------------------ the reference's other two optimisers
-// torch.optim.SGD(lr, momentum) (dampening 0, no Nesterov, no weight decay): buf = g on the first step, else m buf + g;
-// p -= lr buf.  torch.optim.RMSprop(lr, alpha) (eps 1e-8, momentum 0, not centred): sq = alpha sq + (1 - alpha) g g;
-// p -= lr g / (sqrt(sq) + eps).   (utils/utils.py:13-16)
-__global__ __launch_bounds__(256) void sgd_kernel(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum,
-                                                  float grad_scale, const int32_t* step_dev, int32_t step, int32_t* cursor_dev) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int st = step_dev != nullptr ? *step_dev : step;
-  if (p < n) {
-    const float g = grad[p] * grad_scale;
-    float b = g;
-    if (momentum != 0.f) { b = st <= 1 ? g : momentum * buf[p] + g; buf[p] = b; }
-    theta[p] -= lr * b;
-  }
-  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
-}
-
-__global__ __launch_bounds__(256) void rmsprop_kernel(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha,
-                                                      float eps, float grad_scale, int32_t* cursor_dev) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) {
-    const float g = grad[p] * grad_scale;
-    const float s = alpha * sq[p] + (1.f - alpha) * g * g;
-    sq[p] = s;
-    theta[p] -= lr * (g / (sqrtf(s) + eps));
-  }
-  if (cursor_dev != nullptr && p == 0) *cursor_dev += 1;
-}
-
 // ------------------------------------------------------------------------------ dynamic loss scaling (GradScaler's role)
 // state: [0] scale  [1] growth tracker  [2] found_inf  [3] skipped steps  [4] ticket (int bits)
 __global__ __launch_bounds__(256) void unscale_check_kernel(float* grad, int64_t n, float grad_scale, float* state) {
@@ -442,53 +409,27 @@ __global__ __launch_bounds__(256) void unscale_check_kernel(float* grad, int64_t
   if (!isfinite(g)) state[2] = 1.f;                 // (every writer stores the same value)
 }
 
-__global__ __launch_bounds__(256) void scaled_adam_kernel(float* theta, const float* grad, float* m, float* v, int64_t n,
-                                                          float lr, float b1, float b2, float eps, float* state,
-                                                          float growth, float backoff, int interval,
-                                                          int32_t* step_dev, int32_t* cursor_dev) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool skip = state[2] != 0.f;
-  if (!skip && p < n) {
-    float bc1, bc2s;
-    bias_corrections(*step_dev, b1, b2, bc1, bc2s);
-    adam_update(theta, m, v, p, grad[p], lr, b1, b2, eps, bc1, bc2s);
-  }
-  // the last block to get here has seen every other block read found_inf and the step count: it closes the step
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    int* ticket = reinterpret_cast<int*>(state + 4);
-    if (atomicAdd(ticket, 1) == (int)gridDim.x - 1) {
-      *ticket = 0;
-      if (skip) {
-        state[0] *= backoff; state[1] = 0.f; state[3] += 1.f;
-        *step_dev -= 1;                               // a skipped step does not count for the bias corrections
-      } else {
-        const float t = state[1] + 1.f;
-        if (t >= (float)interval) { state[0] *= growth; state[1] = 0.f; }
-        else state[1] = t;
-      }
-      state[2] = 0.f;
-      if (cursor_dev != nullptr) *cursor_dev += 1;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------ weight decay, AdamW, gradient-norm clipping
-// dmf_optim_step (include/dmf.h states the six steps).  A grid like adam_kernel's, but EVERY block first walks the whole
-// gradient — lane t takes g[t], g[t + 256], ... in index order into one double, the 256 doubles meet in a fixed LDS tree — so
-// every block holds the same norm bits and the same skip decision and then updates its own 256 elements: no second launch,
-// no grid barrier, no atomics on data.  (double)g * (double)g is exact, so an fma and a multiply-add give the same sum.  The
-// values a block needs from what the step's end changes (scale, step count) are read before its ticket; the last block to
-// take a ticket closes the step as scaled_adam_kernel does.  Without a scaler state nothing is read that the end changes
-// (block 0 alone reads and advances the cursor), and there is no ticket.
+// optim_step_kernel is the only statement of an optimiser step on a flat gradient: dmf_optim_step (include/dmf.h states the six
+// steps) and, with neutral keys, dmf_adam_step, dmf_sgd_step, dmf_rmsprop_step and dmf_unscale_adam.  One block per 256
+// elements.  With a scaler state or clipping EVERY block first walks the whole gradient — lane t takes g[t], g[t + 256], ... in
+// index order into one double, the 256 doubles meet in a fixed LDS tree — so every block holds the same norm bits and the same
+// skip decision and then updates its own 256 elements: no second launch, no grid barrier, no atomics on data.
+// (double)g * (double)g is exact, so an fma and a multiply-add give the same sum.  The values a block needs from what the
+// step's end changes (scale, step count, found_inf) are read before its ticket; the last block to take a ticket closes the
+// step.  Without a scaler state nothing is read that the end changes (block 0 alone reads and advances the cursor), and there
+// is no ticket; without clipping either there is no norm pass: the plain update of the kind.
+// a.checked (dmf_unscale_adam alone): found_inf of this step is in state[2] already — unscale_check_kernel or the reduce launch
+// put it there — so state[2] decides the skip and the gradient is not walked a second time.  a.bc1 != 0 (dmf_adam_step without
+// a device step count): ADAM's bias corrections as the host formed them.
 __device__ __forceinline__ float scaled_grad(const float* __restrict__ grad, int64_t i, float gs) {
 #pragma clang fp contract(off)           // g is a float of its own, as torch's unscale_ / clip_grad_norm_ leave one in memory
   return grad[i] * gs;
 }
 
 // One instance per kind: with the kind a run-time branch the compiler merges the three updates' last subtraction into one
-// unfused `theta - x`, and ADAM's theta then is an ulp away from adam_kernel's and scaled_adam_kernel's fused form.
+// unfused `theta - x`, and ADAM's theta then is an ulp away from the fused form it has always had
+// (tests/golden/g11_optim_entry_bits.json holds the bits of every entry point).
 template <int KIND>
 __global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
   __shared__ double part[256];
@@ -497,9 +438,9 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
   const int st = a.step_dev != nullptr ? *a.step_dev : a.step;
   const float gs = (a.state != nullptr && !a.unscaled) ? a.grad_scale / a.state[0] : a.grad_scale;
   const bool clip = a.max_norm > 0.f;
-  bool skip = false;
+  bool skip = a.checked && a.state[2] != 0.f;          // (read, like the scale and the step count, before the ticket)
   float norm = 0.f, coef = 1.f;
-  if (a.state != nullptr || clip) {
+  if ((a.state != nullptr && !a.checked) || clip) {
     double s = 0.0;
     int bad = 0;
     // 16 loads in flight per lane (unconditional, from a clamped index, masked where they are summed: a load under a lane
@@ -521,7 +462,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
       }
     }
     part[t] = s;
-    skip = __syncthreads_or(bad) != 0 && a.state != nullptr;
+    if (__syncthreads_or(bad) != 0 && a.state != nullptr && !a.checked) skip = true;
     for (int w = 128; w > 0; w >>= 1) {
       if (t < w) part[t] += part[t + w];
       __syncthreads();
@@ -546,8 +487,8 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
     if (KIND == DMF_OPT_SGD) sgd_update(a.theta, a.m, p, g, a.lr, a.momentum, st);
     else if (KIND == DMF_OPT_RMSPROP) rmsprop_update(a.theta, a.m, p, g, a.lr, a.alpha, a.eps);
     else {
-      float bc1, bc2s;
-      bias_corrections(st, a.b1, a.b2, bc1, bc2s);
+      float bc1 = a.bc1, bc2s = a.bc2_sqrt;
+      if (bc1 == 0.f) bias_corrections(st, a.b1, a.b2, bc1, bc2s);
       adam_update(a.theta, a.m, a.v, p, g, a.lr, a.b1, a.b2, a.eps, bc1, bc2s);
     }
   }
@@ -661,42 +602,14 @@ hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const
 
 static dim3 blocks256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
-hipError_t launch_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                       float bc1, float bc2_sqrt, float grad_scale, const int32_t* step_dev, int32_t* cursor_dev, hipStream_t st) {
-  hipLaunchKernelGGL(adam_kernel, blocks256(n), dim3(256), 0, st, theta, grad, m, v, n, lr, b1, b2, eps, bc1, bc2_sqrt,
-                     grad_scale, step_dev, cursor_dev);
-  return hipGetLastError();
-}
-
-hipError_t launch_sgd(float* theta, const float* grad, float* buf, int64_t n, float lr, float momentum, float grad_scale,
-                      const int32_t* step_dev, int32_t step, int32_t* cursor_dev, hipStream_t st) {
-  hipLaunchKernelGGL(sgd_kernel, blocks256(n), dim3(256), 0, st, theta, grad, buf, n, lr, momentum, grad_scale, step_dev, step,
-                     cursor_dev);
-  return hipGetLastError();
-}
-
-hipError_t launch_rmsprop(float* theta, const float* grad, float* sq, int64_t n, float lr, float alpha, float eps,
-                          float grad_scale, int32_t* cursor_dev, hipStream_t st) {
-  hipLaunchKernelGGL(rmsprop_kernel, blocks256(n), dim3(256), 0, st, theta, grad, sq, n, lr, alpha, eps, grad_scale, cursor_dev);
-  return hipGetLastError();
-}
-
-// the two launches of dmf_unscale_adam: unscale + found_inf check (skipped when the reduce has done it), then the Adam step
-// that closes the scaler's step
+// the first launch of dmf_unscale_adam(unscaled = 0): unscale + found_inf check; launch_optim_step (checked) follows
 hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st) {
   hipLaunchKernelGGL(unscale_check_kernel, blocks256(n), dim3(256), 0, st, grad, n, grad_scale, state);
   return hipGetLastError();
 }
 
-hipError_t launch_unscale_adam(float* theta, const float* grad, float* m, float* v, int64_t n, float lr, float b1, float b2,
-                               float eps, float* state, float growth, float backoff, int interval, int32_t* step_dev,
-                               int32_t* cursor_dev, hipStream_t st) {
-  hipLaunchKernelGGL(scaled_adam_kernel, blocks256(n), dim3(256), 0, st, theta, grad, m, v, n, lr, b1, b2, eps, state, growth,
-                     backoff, interval, step_dev, cursor_dev);
-  return hipGetLastError();
-}
-
 hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st) {
+  if (a.checked && a.state == nullptr) return hipErrorInvalidValue;
   const dim3 grid = blocks256(a.n), block(256);
   switch (a.kind) {
     case DMF_OPT_ADAM: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_ADAM>, grid, block, 0, st, a); break;

@@ -118,6 +118,14 @@ static OptimArgs plain_step(int kind, float* theta, const float* grad, float* m,
   return a;
 }
 
+// the schedule of a *_sched entry point (`entry`) -> the kernels' words; a NULL schedule or table and rows < 1 are refused
+static int fill_sched(const char* entry, const dmf_hp_schedule* sc, HpSched& hp) {
+  if (sc == nullptr || sc->table == nullptr) return fail("%s: null schedule or table", entry);
+  if (sc->rows < 1) return fail("%s: a schedule needs rows >= 1", entry);
+  hp.table = sc->table; hp.row_dev = sc->row_dev; hp.rows = sc->rows;
+  return 0;
+}
+
 extern "C" {
 
 int32_t dmf_version(void) { return DMF_VERSION; }
@@ -381,6 +389,7 @@ struct ReduceOpts {
   const dmf_xgmi_comm* comm = nullptr;         // exchange the gradient with the peer ranks before Adam
   float grad_scale = 1.f;
   float* scaler = nullptr;                     // loss-scaler state: unscale and check the sum
+  const dmf_hp_schedule* sched = nullptr;      // the fused Adam takes lr, b1, b2 from its row (the *_sched entry points)
 };
 
 static int run_reduce(const dmf_shape* s, int32_t B, const void* workspace, const ReduceOpts& o, void* stream) {
@@ -398,7 +407,8 @@ static int run_reduce(const dmf_shape* s, int32_t B, const void* workspace, cons
   a.lr = o.lr; a.b1 = o.b1; a.b2 = o.b2; a.eps = o.eps;
   if (o.theta != nullptr) {
     if (o.m == nullptr || o.v == nullptr || (o.step < 1 && o.step_dev == nullptr)) return fail("%s", "Adam needs m, v and step >= 1");
-    if (o.step_dev == nullptr) host_bias_corrections(o.b1, o.b2, o.step, &a.bc1, &a.bc2_sqrt);
+    // (with a schedule the row's betas are on the device: the kernel forms the corrections)
+    if (o.sched == nullptr && o.step_dev == nullptr) host_bias_corrections(o.b1, o.b2, o.step, &a.bc1, &a.bc2_sqrt);
   }
   a.step_dev = o.step_dev; a.cursor_dev = o.cursor_dev; a.loss = o.loss; a.loss_hist = o.loss_hist;
   a.grad_scale = o.grad_scale;
@@ -408,8 +418,11 @@ static int run_reduce(const dmf_shape* s, int32_t B, const void* workspace, cons
     if (fill_xgmi(o.comm, a.x)) return 1;
     a.seq_bias = o.comm->seq_bias;
   }
+  HpSched hp{};
+  if (o.sched != nullptr && fill_sched("grad_reduce_adam_sched", o.sched, hp)) return 1;
   const char* refusal = nullptr;
-  const hipError_t e = launch_grad_reduce(a, L, B, ws, static_cast<hipStream_t>(stream), &refusal);
+  const hipError_t e = launch_grad_reduce(a, L, B, ws, static_cast<hipStream_t>(stream), &refusal, o.sched != nullptr ? &hp : nullptr,
+                                          o.step);
   return refusal != nullptr ? fail("%s", refusal) : check(e, "grad_reduce launch");
 }
 
@@ -450,17 +463,29 @@ int32_t dmf_grad_reduce_adam(const dmf_shape* s, int32_t B, const void* workspac
   return run_reduce(s, B, workspace, o, stream);
 }
 
-int32_t dmf_train_plan_steps(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w, const int32_t* labels,
-                             float loss_scale, float* logits, float* loss, void* workspace, float* m, float* v, float lr,
-                             float beta1, float beta2, float eps, int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist,
-                             int32_t n_steps, void* stream) {
+int32_t dmf_grad_reduce_adam_sched(const dmf_shape* s, int32_t B, const void* workspace, float* theta, float* m, float* v,
+                                   float* grad, const dmf_hp_schedule* sched, float eps, int32_t step,
+                                   const int32_t* adam_step_dev, int32_t* cursor_dev, const float* loss, float* loss_hist,
+                                   void* stream) {
+  if (theta == nullptr) return fail("%s", "null theta");
+  HpSched hp{};
+  if (fill_sched("grad_reduce_adam_sched", sched, hp)) return 1;
+  ReduceOpts o = adam_opts(theta, m, v, 0.f, 0.f, 0.f, eps, step, adam_step_dev, cursor_dev, loss, loss_hist);
+  o.grad = grad; o.sched = sched;
+  return run_reduce(s, B, workspace, o, stream);
+}
+
+// dmf_train_plan_steps and its schedule form: `adam` holds the launch arguments or the schedule
+static int plan_steps(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w, const int32_t* labels,
+                      float loss_scale, float* logits, float* loss, void* workspace, const ReduceOpts& adam, int32_t n_steps,
+                      void* stream) {
   if (s == nullptr || in == nullptr || theta == nullptr || labels == nullptr || logits == nullptr || loss == nullptr ||
-      adam_step_dev == nullptr || cursor_dev == nullptr)
+      adam.step_dev == nullptr || adam.cursor_dev == nullptr)
     return fail("%s", "null argument (dmf_train_plan_steps needs the device step count and cursor)");
   if (in->mode != 1 || in->cursor != nullptr) return fail("%s", "dmf_train_plan_steps: gather mode, no plan cursor (the batches are consecutive)");
   if (s->attention) return fail("%s", "dmf_train_plan_steps: late-fusion network only");
   if (n_steps < 0 || in->B <= 0) return fail("%s", "dmf_train_plan_steps: negative step count or empty batch");
-  const ReduceOpts adam = adam_opts(theta, m, v, lr, beta1, beta2, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist);
+  int32_t* adam_step_dev = const_cast<int32_t*>(adam.step_dev);
   dmf_input ik = *in;
   for (int32_t k = 0; k < n_steps; ++k) {
     ik.xy = in->xy + (size_t)2 * in->B * k;
@@ -470,6 +495,25 @@ int32_t dmf_train_plan_steps(const dmf_shape* s, const dmf_input* in, float* the
     if (run_reduce(s, in->B, workspace, adam, stream)) return 1;
   }
   return 0;
+}
+
+int32_t dmf_train_plan_steps(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w, const int32_t* labels,
+                             float loss_scale, float* logits, float* loss, void* workspace, float* m, float* v, float lr,
+                             float beta1, float beta2, float eps, int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist,
+                             int32_t n_steps, void* stream) {
+  return plan_steps(s, in, theta, pool_w, labels, loss_scale, logits, loss, workspace,
+                    adam_opts(theta, m, v, lr, beta1, beta2, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist), n_steps, stream);
+}
+
+int32_t dmf_train_plan_steps_sched(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w,
+                                   const int32_t* labels, float loss_scale, float* logits, float* loss, void* workspace, float* m,
+                                   float* v, const dmf_hp_schedule* sched, float eps, int32_t* adam_step_dev, int32_t* cursor_dev,
+                                   float* loss_hist, int32_t n_steps, void* stream) {
+  HpSched hp{};
+  if (fill_sched("dmf_train_plan_steps_sched", sched, hp)) return 1;
+  ReduceOpts adam = adam_opts(theta, m, v, 0.f, 0.f, 0.f, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist);
+  adam.sched = sched;
+  return plan_steps(s, in, theta, pool_w, labels, loss_scale, logits, loss, workspace, adam, n_steps, stream);
 }
 
 int32_t dmf_grad_reduce_xgmi_adam(const dmf_shape* s, int32_t B, const void* workspace, float* theta, float* m,
@@ -570,16 +614,19 @@ int32_t dmf_rmsprop_step(float* theta, const float* grad, float* square_avg, int
   return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "rmsprop launch");
 }
 
-int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
-                       float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
-                       float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
-                       float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist, void* stream) {
+// dmf_optim_step and dmf_optim_step_sched: with a schedule lr, beta1, beta2 and momentum are unused (the row holds them), and
+// SGD needs its momentum buffer whatever the row says
+static int optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
+                      float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
+                      float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
+                      float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist,
+                      const dmf_hp_schedule* sched, void* stream) {
   if (theta == nullptr || grad == nullptr) return fail("%s", "optim_step: null theta or grad");
   if (kind != DMF_OPT_ADAM && kind != DMF_OPT_ADAMW && kind != DMF_OPT_SGD && kind != DMF_OPT_RMSPROP)
     return fail("%s", "optim_step: unknown kind (DMF_OPT_ADAM, _ADAMW, _SGD, _RMSPROP)");
   const bool adam = kind == DMF_OPT_ADAM || kind == DMF_OPT_ADAMW;
   if ((adam && (m == nullptr || v == nullptr)) || (kind == DMF_OPT_RMSPROP && m == nullptr) ||
-      (kind == DMF_OPT_SGD && momentum != 0.f && m == nullptr))
+      (kind == DMF_OPT_SGD && (momentum != 0.f || sched != nullptr) && m == nullptr))
     return fail("%s", "optim_step: null m or v (ADAM / ADAMW need both, RMSprop m, SGD m when momentum != 0)");
   if (n < 0) return fail("%s", "optim_step: negative n");
   if (!(weight_decay >= 0.f) || !isfinite(weight_decay)) return fail("%s", "optim_step: weight_decay must be finite and >= 0");
@@ -596,7 +643,28 @@ int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int6
   if (n == 0) return 0;
   OptimArgs a{theta, grad, m, v, n, kind, lr, beta1, beta2, eps, momentum, alpha, weight_decay, max_norm, grad_scale,
               step, step_dev, cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled != 0, norm_hist};
-  return check(launch_optim_step(a, static_cast<hipStream_t>(stream)), "optim_step launch");
+  HpSched hp{};
+  if (sched != nullptr && fill_sched("optim_step_sched", sched, hp)) return 1;
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream), sched != nullptr ? &hp : nullptr), "optim_step launch");
+}
+
+int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
+                       float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
+                       float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
+                       float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist, void* stream) {
+  return optim_step(theta, grad, m, v, n, kind, lr, beta1, beta2, eps, momentum, alpha, weight_decay, max_norm, step, grad_scale,
+                    step_dev, cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled, norm_hist, nullptr,
+                    stream);
+}
+
+int32_t dmf_optim_step_sched(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind,
+                             const dmf_hp_schedule* sched, float eps, float alpha, float weight_decay, float max_norm, int32_t step,
+                             float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
+                             float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist, void* stream) {
+  HpSched hp{};
+  if (fill_sched("optim_step_sched", sched, hp)) return 1;
+  return optim_step(theta, grad, m, v, n, kind, 0.f, 0.f, 0.f, eps, 0.f, alpha, weight_decay, max_norm, step, grad_scale, step_dev,
+                    cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled, norm_hist, sched, stream);
 }
 
 int32_t dmf_qua_loss_ranks(const float* gathered, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,

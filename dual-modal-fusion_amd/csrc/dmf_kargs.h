@@ -105,6 +105,11 @@ int attn_shape_supported(const dmf_shape& s);
 //   fc1.weight   : grad = sum_b dh[b][j] * z[b][i]      fc1.bias: sum_b dh[b][j]
 //   fc2.weight   : grad = sum_b dl[b][k] * h[b][j]      fc2.bias: sum_b dl[b][k]
 // (the conv slabs and head vectors z / h / dh / dl reach the kernel as leading scalar arguments: launch_grad_reduce)
+// The device-resident schedule of the *_sched entry points (include/dmf.h: dmf_hp_schedule): table [rows][4] of
+// (lr, beta1, beta2, momentum); the row of a step is *row_dev, or with row_dev == nullptr the 1-based step count - 1, clamped
+// to [0, rows - 1].  The words follow ReduceArgs / OptimArgs in argument structs that only the schedule instances of the two
+// kernels take: the default instances keep their kernel arguments byte for byte.
+struct HpSched { const float* table; const int32_t* row_dev; int32_t rows; };
 struct ReduceArgs {
   int B, NCONV, F2, H, K;
   int64_t oFc1w, oFc1b, oFc2w, oFc2b;
@@ -119,9 +124,13 @@ struct ReduceArgs {
   float grad_scale; int seq_bias;
   float* scaler;                      // loss-scaler state (dmf_grad_reduce_scaled): grad <- sum / scaler[0], non-finite -> scaler[2]
 };
+// ... of grad_reduce_kernel<true>: the schedule, and the host step count (used when step_dev == nullptr)
+struct ReduceSchedArgs : ReduceArgs { HpSched hp; int32_t step; };
 // dmf_reduce.hip.  launch_grad_reduce carves the head vectors and conv slabs out of the workspace `ws` itself; a geometry
 // its block packing cannot hold is refused with hipErrorInvalidValue and *refusal set to the reason (else null).
-hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal);
+// hp != nullptr launches the schedule instance, which also takes the host step count `step`.
+hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal,
+                              const HpSched* hp = nullptr, int32_t step = 0);
 // The optimiser step on the flat gradient, one launch (optim_step_kernel): dmf_optim_step with weight decay / AdamW /
 // gradient-norm clipping, and with neutral keys dmf_adam_step, dmf_sgd_step, dmf_rmsprop_step and dmf_unscale_adam.
 // launch_optim_step and launch_unscale_check are the only flat-gradient optimiser launchers (launch_adam, launch_sgd,
@@ -137,8 +146,9 @@ struct OptimArgs {
   float bc1, bc2_sqrt;                // ADAM's bias corrections formed on the host; bc1 == 0: form them on the device from the step
   int checked;                        // found_inf of this step is already in state[2] (needs state): it alone decides the skip
 };
+struct OptimSchedArgs : OptimArgs { HpSched hp; };   // ... of optim_step_kernel<KIND, true>: lr, betas / momentum from the step's row
 hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st);
-hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st);
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp = nullptr);   // hp: the schedule instance
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
 // the validation sum of an epoch and what its end decides (dmf_valid_accum, dmf_keep_best): one workgroup each
 hipError_t launch_valid_accum(const float* loss, int n, double* acc, hipStream_t st);

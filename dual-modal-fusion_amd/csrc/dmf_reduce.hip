@@ -7,6 +7,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dmf_kargs.h"
 #include "dmf_lanes.h"
 #include "dmf_xgmi.h"
@@ -181,6 +183,9 @@ __device__ unsigned long long* g_rstamps = nullptr;
 #define RSTAMP_DUMP() do { } while (0)
 #endif
 
+typedef const int32_t __attribute__((address_space(4)))* const_i32;   // memory that no launch writes while it is read
+typedef const float __attribute__((address_space(4)))* const_f32;
+
 // 320 threads: waves 0-3 reduce, wave 4 only forms ADAM's bias corrections (beside the other waves' gradient loads).
 // The first ten arguments (14 dwords) are everything a block needs to find its role, ISSUE its gradient loads and ISSUE the
 // loads of the ADAM state of the parameters it owns; they are plain scalars in front of the argument struct so that the
@@ -189,8 +194,13 @@ __device__ unsigned long long* g_rstamps = nullptr;
 // starts its own cold round trip only then.  The slab rows and head vectors are addressed from the ONE workspace pointer
 // (their offsets follow from w3, w4 and B: reduce_words_unpack, dmf_shapes.h), which leaves room for theta / m / v.
 // w0 = nFc1 | t1n << 16, w1 = nFc2 | t2n << 16, w2 = nConv | nAttn << 16 (blocks per kind, tiles per row).
+// SCHED (the second instance): lr, beta1 and beta2 come from the row of a.hp that belongs to this step instead of
+// the launch arguments; the row index and the 16-byte row are fetched where the tail's other scalars are, and wave 4 forms
+// b^step from the row's betas.  Nothing else differs, and the default instance takes the arguments it has always taken.
+template <bool SCHED>
 __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restrict__ ws, float* theta, float* m, float* v, int w0, int w1,
-                                                          int w2, int w3, int w4, int B, const ReduceArgs a) {
+                                                          int w2, int w3, int w4, int B,
+                                                          const std::conditional_t<SCHED, ReduceSchedArgs, ReduceArgs> a) {
   __shared__ float vbuf[4][256];        // tile partials of the four waves / [16 chunks][64] attention-slab partials / [4][16] piece partials
   __shared__ float bbuf[4][16];         // bias partials of the four waves
   __shared__ float bcs[2];
@@ -297,10 +307,27 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   // the tail's scalars (exchange on / off, scaler, gradient pointer, ADAM's constants) live in the argument struct: read where
   // they are used they are four DEPENDENT kernarg fetches behind the barrier; fetched here they arrive under the gradient loads
   const int world = a.x.world;
-  const ReduceTail tl = {a.scaler, a.grad, a.lr, a.b1, a.b2, a.eps};
+  ReduceTail tl = {a.scaler, a.grad, a.lr, a.b1, a.b2, a.eps};
+  int hp_st = 0;
 #if DMF_REDUCE_TAIL_EARLY
-  asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.lr), "s"(tl.b1), "s"(tl.b2), "s"(tl.eps));
+  if (!SCHED) asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.lr), "s"(tl.b1), "s"(tl.b2), "s"(tl.eps));
 #endif
+  if constexpr (SCHED) {
+    // the step's row (uniform addresses: step count and row index -> 16 bytes of the table), requested here, behind the first
+    // batch of gradient and state loads; wave 4 and the tail wait for it where they use it
+    const int32_t* sd = a.step_dev;
+    const int32_t* rd = a.hp.row_dev;
+    const float* tb = a.hp.table;
+    const int rows = a.hp.rows;
+    asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.eps), "s"(sd), "s"(rd), "s"(tb), "s"(rows));
+    // (this launch writes none of the three: read through the constant address space they are scalar loads, which do not
+    // queue behind the gradient loads as vector loads would)
+    hp_st = sd != nullptr ? *(const_i32)sd : a.step;
+    int row = rd != nullptr ? *(const_i32)rd : hp_st - 1;
+    row = row < 0 ? 0 : (row > rows - 1 ? rows - 1 : row);
+    const const_f32 hr = (const_f32)tb + (size_t)row * 4;
+    tl.lr = hr[0]; tl.b1 = hr[1]; tl.b2 = hr[2];
+  }
   if (kind == 3) {                                   // attention slabs: the block's role needs the argument struct
     p = a.oAttn + (int64_t)64 * sub + tid;
     own = tid < 64 && 64 * sub + tid < a.ASLAB;
@@ -311,7 +338,10 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
     // bias corrections (lanes 0 / 1 of wave 4: beta1 / beta2 side by side), b^step by repeated squaring in double
     if (theta != nullptr && tid < 258) {
       float bc = tid == 256 ? a.bc1 : a.bc2_sqrt;
-      if (a.step_dev != nullptr) {
+      if (SCHED) {                                     // (the host does not know the row's betas: always formed here)
+        const double pw = powi_double((double)(tid == 256 ? tl.b1 : tl.b2), hp_st);
+        bc = tid == 256 ? (float)(1.0 - pw) : (float)sqrt(1.0 - pw);
+      } else if (a.step_dev != nullptr) {
         const double pw = powi_double((double)(tid == 256 ? a.b1 : a.b2), *a.step_dev);
         bc = tid == 256 ? (float)(1.0 - pw) : (float)sqrt(1.0 - pw);
       }
@@ -430,12 +460,25 @@ __device__ __forceinline__ float scaled_grad(const float* __restrict__ grad, int
 // One instance per kind: with the kind a run-time branch the compiler merges the three updates' last subtraction into one
 // unfused `theta - x`, and ADAM's theta then is an ulp away from the fused form it has always had
 // (tests/golden/g11_optim_entry_bits.json holds the bits of every entry point).
-template <int KIND>
-__global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
+// SCHED (the *_sched entry points): lr and, by kind, beta1 / beta2 or momentum come from the step's row of a.hp,
+// read at entry beside the step count (and so, like it, before the ticket); everything below runs on them as on the launch
+// arguments.  A step the scaler skips takes its count back: with hp.row_dev == nullptr the next step reads the same row again.
+template <int KIND, bool SCHED>
+__global__ __launch_bounds__(256) void optim_step_kernel(const std::conditional_t<SCHED, OptimSchedArgs, OptimArgs> a) {
   __shared__ double part[256];
   const int t = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * 256 + t;
   const int st = a.step_dev != nullptr ? *a.step_dev : a.step;
+  float lr = a.lr, b1 = a.b1, b2 = a.b2, momentum = a.momentum;
+  if constexpr (SCHED) {
+    int row = a.hp.row_dev != nullptr ? *a.hp.row_dev : st - 1;
+    row = row < 0 ? 0 : (row > a.hp.rows - 1 ? a.hp.rows - 1 : row);
+    const float* hr = a.hp.table + (size_t)row * 4;
+    const float r0 = hr[0], r1 = hr[1], r2 = hr[2], r3 = hr[3];
+    lr = r0;
+    if (KIND == DMF_OPT_ADAM || KIND == DMF_OPT_ADAMW) { b1 = r1; b2 = r2; }
+    if (KIND == DMF_OPT_SGD) momentum = r3;
+  }
   const float gs = (a.state != nullptr && !a.unscaled) ? a.grad_scale / a.state[0] : a.grad_scale;
   const bool clip = a.max_norm > 0.f;
   bool skip = a.checked && a.state[2] != 0.f;          // (read, like the scale and the step count, before the ticket)
@@ -480,16 +523,16 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimArgs a) {
       if (clip) g *= coef;
       if (a.weight_decay != 0.f) {
         const float th = a.theta[p];
-        if (KIND == DMF_OPT_ADAMW) a.theta[p] = th * (float)(1.0 - (double)a.lr * (double)a.weight_decay);
+        if (KIND == DMF_OPT_ADAMW) a.theta[p] = th * (float)(1.0 - (double)lr * (double)a.weight_decay);
         else g += a.weight_decay * th;
       }
     }
-    if (KIND == DMF_OPT_SGD) sgd_update(a.theta, a.m, p, g, a.lr, a.momentum, st);
-    else if (KIND == DMF_OPT_RMSPROP) rmsprop_update(a.theta, a.m, p, g, a.lr, a.alpha, a.eps);
+    if (KIND == DMF_OPT_SGD) sgd_update(a.theta, a.m, p, g, lr, momentum, st);
+    else if (KIND == DMF_OPT_RMSPROP) rmsprop_update(a.theta, a.m, p, g, lr, a.alpha, a.eps);
     else {
       float bc1 = a.bc1, bc2s = a.bc2_sqrt;
-      if (bc1 == 0.f) bias_corrections(st, a.b1, a.b2, bc1, bc2s);
-      adam_update(a.theta, a.m, a.v, p, g, a.lr, a.b1, a.b2, a.eps, bc1, bc2s);
+      if (bc1 == 0.f) bias_corrections(st, b1, b2, bc1, bc2s);
+      adam_update(a.theta, a.m, a.v, p, g, lr, b1, b2, a.eps, bc1, bc2s);
     }
   }
   bool closer = blockIdx.x == 0 && t == 0;
@@ -576,7 +619,8 @@ __global__ __launch_bounds__(1024) void keep_best_kernel(double* acc, double* be
 // ------------------------------------------------------------------------------ launchers
 // Blocks per kind, tiles per row, packed for the kernel's preloaded scalars.  A geometry the packing cannot hold is refused:
 // hipErrorInvalidValue, and *refusal names the reason.
-hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal) {
+hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal,
+                              const HpSched* hp, int32_t step) {
   *refusal = nullptr;
   if (L.H % 8 != 0 || L.F2 % 8 != 0) {
     *refusal = "grad_reduce: hidden width and 2 x gmf.width must be multiples of 8";
@@ -595,8 +639,15 @@ hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const
     return hipErrorInvalidValue;
   }
   const int grid = nFc1 + nFc2 + nConv + nAttn + 1;   // + the bookkeeping block
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16), nFc2 | (t2n << 16),
-                     nConv | (nAttn << 16), w3, w4, B, a);
+  if (hp != nullptr) {
+    ReduceSchedArgs as{};
+    static_cast<ReduceArgs&>(as) = a;
+    as.hp = *hp; as.step = step;
+    hipLaunchKernelGGL(grad_reduce_kernel<true>, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16),
+                       nFc2 | (t2n << 16), nConv | (nAttn << 16), w3, w4, B, as);
+  } else
+    hipLaunchKernelGGL(grad_reduce_kernel<false>, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16), nFc2 | (t2n << 16),
+                       nConv | (nAttn << 16), w3, w4, B, a);
   return hipGetLastError();
 }
 
@@ -608,16 +659,25 @@ hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float*
   return hipGetLastError();
 }
 
-hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st) {
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp) {
   if (a.checked && a.state == nullptr) return hipErrorInvalidValue;
   const dim3 grid = blocks256(a.n), block(256);
+  OptimSchedArgs as{};
+  if (hp != nullptr) {
+    static_cast<OptimArgs&>(as) = a;
+    as.hp = *hp;
+  }
+#define DMF_OPTIM_LAUNCH(K) \
+  if (hp != nullptr) hipLaunchKernelGGL((optim_step_kernel<K, true>), grid, block, 0, st, as); \
+  else hipLaunchKernelGGL((optim_step_kernel<K, false>), grid, block, 0, st, a)
   switch (a.kind) {
-    case DMF_OPT_ADAM: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_ADAM>, grid, block, 0, st, a); break;
-    case DMF_OPT_ADAMW: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_ADAMW>, grid, block, 0, st, a); break;
-    case DMF_OPT_SGD: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_SGD>, grid, block, 0, st, a); break;
-    case DMF_OPT_RMSPROP: hipLaunchKernelGGL(optim_step_kernel<DMF_OPT_RMSPROP>, grid, block, 0, st, a); break;
+    case DMF_OPT_ADAM: DMF_OPTIM_LAUNCH(DMF_OPT_ADAM); break;
+    case DMF_OPT_ADAMW: DMF_OPTIM_LAUNCH(DMF_OPT_ADAMW); break;
+    case DMF_OPT_SGD: DMF_OPTIM_LAUNCH(DMF_OPT_SGD); break;
+    case DMF_OPT_RMSPROP: DMF_OPTIM_LAUNCH(DMF_OPT_RMSPROP); break;
     default: return hipErrorInvalidValue;
   }
+#undef DMF_OPTIM_LAUNCH
   return hipGetLastError();
 }
 

@@ -241,8 +241,57 @@ class _PlanEngine:
         self.comm = None                 # the one-shot xgmi exchange (TrainEngine only)
         self._rccl_graph = True          # False once RCCL refused to be captured (run_plan), or set by a caller
         self._force_collective = False   # tests only: see _single()
+        # the device-resident schedule (set_schedule): the HpSchedule the *_sched entry points take, its table and row index
+        self.sched = self.hp_table = self.hp_row = self.hp_unit = None
+
+    # ------------------------------------------------------------------ lr, betas and momentum from a table on the device
+    def set_schedule(self, table, unit='epoch'):
+        """Take lr, beta1, beta2 and momentum of every step from a table on the device instead of the launch arguments
+        (DESIGN.md §15): every step form — the fused step, the native loop, the scaler, SGD and RMSprop forms, the regularised
+        step, the unit-gradient step, `step_short` and plain eager `step` — then updates by the `_sched` entry points, and a
+        captured graph or the native loop follows a scheduler without a re-capture (`_hparams`).
+        table: host float32 [rows, 4], a row = (lr, beta1, beta2, momentum); checked here: finite, lr >= 0, betas and momentum
+        in [0, 1).  unit 'epoch': the row is the device int that `set_epoch(e)` fills; unit 'step': the row is the 1-based count
+        of optimiser steps taken - 1 (a step the loss scaler skips does not count).  Rows past the table's end read its last row.
+        The step count then lives on the device for every optimiser (`_counts_on_device`).  eps, alpha, weight_decay and
+        clip_grad_norm stay the engine's attributes.  `self.lr`, `self.b1`, `self.b2` and `self.momentum` are no longer read by
+        a step; the solvers keep them at the current row for the checkpoint.
+        Data parallel: the one-shot xGMI launch has no schedule form, so an engine that was given a communicator lets go of it
+        and takes the collective route (dmf_grad_reduce -> all-reduce -> dmf_optim_step_sched), as the regularised step does."""
+        if unit not in ('epoch', 'step'):
+            raise lib.DmfError('schedule unit %r is neither epoch nor step' % (unit,))
+        t = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+        if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1:
+            raise lib.DmfError('a schedule table is [rows >= 1, 4] (lr, beta1, beta2, momentum), got shape %s' % (t.shape,))
+        if not np.isfinite(t).all():
+            raise lib.DmfError('schedule table: non-finite value in row %d' % int(np.argwhere(~np.isfinite(t))[0][0]))
+        if (t[:, 0] < 0).any():
+            raise lib.DmfError('schedule table: negative lr in row %d' % int(np.argwhere(t[:, 0] < 0)[0][0]))
+        bad = (t[:, 1:] < 0) | (t[:, 1:] >= 1)
+        if bad.any():
+            raise lib.DmfError('schedule table: beta1, beta2 and momentum must lie in [0, 1) (row %d)' % int(np.argwhere(bad)[0][0]))
+        dev = self.scene.device
+        if not self._counts_on_device():             # from here on the device counts the steps: hand it the host's count
+            self.dev_step.fill_(self.step_count)
+        self.hp_table = torch.from_numpy(t.copy()).to(dev)
+        self.hp_row = torch.zeros(1, dtype=torch.int32, device=dev) if unit == 'epoch' else None
+        self.hp_unit = unit
+        self.sched = lib.hp_schedule(self.hp_table, self.hp_row)
+        self.comm = None
+        self.graph = None
+
+    def set_epoch(self, e):
+        """Unit 'epoch': the steps from here on read row e of the table (a stream-ordered device fill, no synchronisation; never
+        called inside a capture).  Unit 'step', or no schedule: nothing to do."""
+        if self.hp_row is not None:
+            self.hp_row.fill_(int(e))
 
     def _hparams(self):
+        """What a captured graph bakes in as launch arguments.  With a schedule lr, the betas and momentum are not among them:
+        the graph survives every change of them."""
+        if self.sched is not None:
+            return ('sched', self.eps, self.alpha, self.weight_decay, self.clip_grad_norm) + (
+                self.scaler.hparams() if self.scaler is not None else ())
         return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha, self.weight_decay, self.clip_grad_norm) + (
             self.scaler.hparams() if self.scaler is not None else ())
 
@@ -261,8 +310,9 @@ class _PlanEngine:
     def _counts_on_device(self):
         """Is the device step counter the true step count?  Then eager steps advance it too, and load_plan leaves it alone;
         otherwise eager steps use the host count `step_count` and load_plan copies it into the counter.  With a loss
-        scaler it is: a skipped step takes its count back on the device."""
-        return self.scaler is not None
+        scaler it is: a skipped step takes its count back on the device.  With a schedule it is: unit 'step' finds its row
+        by it."""
+        return self.scaler is not None or self.sched is not None
 
     def _count_step(self, dev_step):
         """Count one step on the host; returns the device step counter the step's launches take (None: the host count).
@@ -284,6 +334,9 @@ class _PlanEngine:
                                         check with a scaler, the norm of the whole gradient and its clipping, weight decay,
                                         the optimiser, the scaler's update: one launch; the pre-clip norm into
                                         norm_hist[cursor], or into self.norm for an eager step)
+          a schedule (set_schedule)     the same reduce launch per case, and the `_sched` twin of the optimiser launch:
+                                        dmf_grad_reduce_adam_sched for the fused case, dmf_optim_step_sched for every other
+                                        (`_update_sched`; the xGMI case takes the collective route)
         sum_scale scales the all-reduced gradient: 1/world where the loss is a per-rank mean, 1 where the loss kernel
         already divided by the global batch.  dev_step: the device step counter, or None for the host count.  loss /
         loss_hist: where the step's mean loss (this rank's) is recorded; None where the loss kernel records it itself.
@@ -292,6 +345,8 @@ class _PlanEngine:
             return self._update_regularised(rows, dev_step, cursor, sum_scale, loss, loss_hist)
         sc, hp = self.scaler, (self.lr, self.b1, self.b2, self.eps)
         fused = sc is None and self.optim == 'ADAM'
+        if self.sched is not None:
+            return self._update_sched(rows, dev_step, cursor, sum_scale, loss, loss_hist, fused)
         if fused and self._single():
             lib.grad_reduce_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count,
                                  adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
@@ -322,17 +377,45 @@ class _PlanEngine:
 
     def _update_regularised(self, rows, dev_step, cursor, sum_scale, loss, loss_hist):
         """`_update` with weight decay, ADAMW or clip_grad_norm active (its docstring's last row)."""
-        sc = self.scaler
         lib.grad_reduce(self.shape, rows, self.ws, self.grad)
         if not self._single():
             self._all_reduce_grad()
         if loss_hist is not None:
             loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
-        lib.optim_step(self.optim, self.theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2,
-                       1e-8 if self.optim == 'RMSprop' else self.eps, self.momentum, self.alpha, self.weight_decay,
-                       self.clip_grad_norm, step=self.step_count, grad_scale=sum_scale, step_dev=dev_step, cursor_dev=cursor,
-                       scaler_state=sc.state if sc is not None else None, scaler_hparams=sc.hparams() if sc is not None else None,
-                       norm_hist=self.norm_hist if cursor is not None else self.norm)
+        self._optim_step(dev_step, cursor, sum_scale, norm_hist=self.norm_hist if cursor is not None else self.norm)
+
+    def _optim_step(self, dev_step, cursor, sum_scale, unscaled=False, norm_hist=None):
+        """dmf_optim_step on self.grad with the engine's optimiser, keys and scaler — dmf_optim_step_sched with a schedule."""
+        sc = self.scaler
+        keys = dict(eps=1e-8 if self.optim == 'RMSprop' else self.eps, alpha=self.alpha, weight_decay=self.weight_decay,
+                    max_norm=self.clip_grad_norm, step=self.step_count, grad_scale=sum_scale, step_dev=dev_step, cursor_dev=cursor,
+                    scaler_state=sc.state if sc is not None else None, scaler_hparams=sc.hparams() if sc is not None else None,
+                    unscaled=unscaled, norm_hist=norm_hist)
+        if self.sched is not None:
+            lib.optim_step_sched(self.optim, self.theta, self.grad, self.m, self.v, self.sched, **keys)
+        else:
+            lib.optim_step(self.optim, self.theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, momentum=self.momentum, **keys)
+
+    def _update_sched(self, rows, dev_step, cursor, sum_scale, loss, loss_hist, fused):
+        """`_update` with a schedule and without weight decay, ADAMW or clipping: the same reduce launch per case, so the gradient
+        and the recorded loss keep their bits, and the optimiser's arithmetic from the step's row — fused ADAM on one GPU by
+        dmf_grad_reduce_adam_sched, everything else by dmf_optim_step_sched with neutral keys (the kernel behind
+        dmf_unscale_adam, dmf_sgd_step, dmf_rmsprop_step and dmf_adam_step)."""
+        sc = self.scaler
+        if fused and self._single():
+            lib.grad_reduce_adam_sched(self.shape, rows, self.ws, self.theta, self.m, self.v, None, self.sched, self.eps,
+                                       self.step_count, adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+        elif sc is not None and self._single():
+            lib.grad_reduce_scaled(self.shape, rows, self.ws, self.grad, sc.state, cursor_dev=cursor, loss=loss,
+                                   loss_hist=loss_hist)
+            self._optim_step(dev_step, None, 1.0, unscaled=True)
+        else:
+            lib.grad_reduce(self.shape, rows, self.ws, self.grad)
+            if not self._single():
+                self._all_reduce_grad()
+            if loss_hist is not None:
+                loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
+            self._optim_step(dev_step, cursor, sum_scale)
 
     # ------------------------------------------------------------------ the unit-gradient step on global batches
     def _unit_step(self, inp, rows, loss_launch, dev_step, cursor, loss=None, loss_hist=None):
@@ -437,7 +520,8 @@ class _PlanEngine:
         done = 0
         if steps_per_graph > 0 and self._graphable():
             # lr, betas and eps are launch arguments baked into the captured graph (reference: `scheduler.step()` changes
-            # the optimiser's lr every epoch, mainsolver.py:60): a change invalidates the graph
+            # the optimiser's lr every epoch, mainsolver.py:60): a change invalidates the graph — unless a schedule on the
+            # device holds them (set_schedule)
             if self.graph is None or self.graph_steps != steps_per_graph or self.graph_hparams != self._hparams():
                 self._capture_for_replay(steps_per_graph)
             while self.graph is not None and steps - done >= steps_per_graph:
@@ -624,7 +708,7 @@ class TrainEngine(_PlanEngine):
     def _counts_on_device(self):
         """As _PlanEngine's, and: the xgmi exchange numbers its rounds by the device step count, and SGD's first step is told
         by it."""
-        return self.comm is not None or self.scaler is not None or self.optim not in ('ADAM', 'ADAMW')
+        return super()._counts_on_device() or self.comm is not None or self.optim not in ('ADAM', 'ADAMW')
 
     def _launch(self, inp, labels, dev_step, dev_cursor, loss_hist=None):
         dev_step = self._count_step(dev_step)
@@ -721,9 +805,15 @@ class TrainEngine(_PlanEngine):
         # no graph): for a short run the fixed cost is one kernel launch instead of a window copy + a graph launch
         k0 = self.host_cursor
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy[k0 * self.B:(k0 + steps) * self.B], B=self.B)
-        lib.train_plan_steps(self.shape, inp, self.theta, self.net.pool_w, self.plan_labels[k0 * self.B:(k0 + steps) * self.B],
-                             1.0 / self.B, self.logits, self.loss, self.ws, self.m, self.v, self.lr, self.b1, self.b2, self.eps,
-                             self.dev_step, self.dev_cursor, self.loss_hist, steps)
+        labels = self.plan_labels[k0 * self.B:(k0 + steps) * self.B]
+        if self.sched is not None:
+            lib.train_plan_steps_sched(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
+                                       self.ws, self.m, self.v, self.sched, self.eps, self.dev_step, self.dev_cursor,
+                                       self.loss_hist, steps)
+        else:
+            lib.train_plan_steps(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss, self.ws,
+                                 self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.dev_step, self.dev_cursor,
+                                 self.loss_hist, steps)
         self.step_count += steps
         self.host_cursor += steps
         return steps

@@ -34,6 +34,11 @@ class CeParams(C.Structure):
     _fields_ = [('kind', C.c_int32), ('label_smoothing', C.c_float), ('gamma', C.c_float)]
 
 
+class HpSchedule(C.Structure):
+    """dmf_hp_schedule: table [rows][4] fp32 on the device, row_dev a device int32 (unit `epoch`) or NULL (unit `step`)."""
+    _fields_ = [('table', C.c_void_p), ('rows', C.c_int32), ('row_dev', C.c_void_p)]
+
+
 class Input(C.Structure):
     _fields_ = [('mode', C.c_int32), ('B', C.c_int32), ('a', C.c_void_p), ('b', C.c_void_p), ('sceneA', C.c_void_p),
                 ('sceneB', C.c_void_p), ('xy', C.c_void_p), ('Wp', C.c_int32), ('WpB', C.c_int32), ('cursor', C.c_void_p),
@@ -46,7 +51,7 @@ def _load():
                        '(hipcc --offload-arch=gfx950); there is no CPU fallback for the product path')
     lib = C.CDLL(LIB_PATH)
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    SP, IP = C.POINTER(Shape), C.POINTER(Input)
+    SP, IP, HP = C.POINTER(Shape), C.POINTER(Input), C.POINTER(HpSchedule)
     protos = {
         'dmf_version': (i32, []),
         'dmf_last_error': (C.c_char_p, []),
@@ -80,6 +85,9 @@ def _load():
         'dmf_grad_reduce_adam': (i32, [SP, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp]),
         'dmf_forward_ce': (i32, [SP, IP, vp, vp, vp, vp, vp, vp, vp]),
         'dmf_train_plan_steps': (i32, [SP, IP, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
+        'dmf_optim_step_sched': (i32, [vp, vp, vp, vp, i64, i32, HP, f32, f32, f32, f32, i32, f32, vp, vp, vp, f32, f32, i32, i32, vp, vp]),
+        'dmf_grad_reduce_adam_sched': (i32, [SP, i32, vp, vp, vp, vp, vp, HP, f32, i32, vp, vp, vp, vp, vp]),
+        'dmf_train_plan_steps_sched': (i32, [SP, IP, vp, vp, vp, f32, vp, vp, vp, vp, vp, HP, f32, vp, vp, vp, i32, vp]),
         'dmf_xgmi_sizes': (i32, [i64, i32, C.POINTER(i64), C.POINTER(i64)]),
         'dmf_xgmi_alloc': (i32, [i64, C.POINTER(vp)]),
         'dmf_xgmi_free': (i32, [vp]),
@@ -321,6 +329,49 @@ def optim_step(kind, theta, grad, m, v, lr, b1=0.9, b2=0.999, eps=1e-8, momentum
                               momentum, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
                               _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
                               _ptr(norm_hist), _stream()))
+
+
+def hp_schedule(table, row_dev=None):
+    """-> HpSchedule of a device table [rows, 4] float32 (lr, beta1, beta2, momentum per row) and the device row index
+    (int32 [1]: unit `epoch`; None: unit `step`, row = step count - 1).  The caller keeps both tensors alive."""
+    _dev(table, torch.float32, 'schedule table')
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1:
+        raise DmfError('a schedule table is [rows >= 1, 4]: lr, beta1, beta2, momentum')
+    if row_dev is not None:
+        _dev(row_dev, torch.int32, 'schedule row index')
+    return HpSchedule(table=table.data_ptr(), rows=table.shape[0], row_dev=None if row_dev is None else row_dev.data_ptr())
+
+
+def _sched_ref(sched):
+    return None if sched is None else C.byref(sched)
+
+
+def optim_step_sched(kind, theta, grad, m, v, sched, eps=1e-8, alpha=0.99, weight_decay=0.0, max_norm=None, step=0,
+                     grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None, scaler_hparams=None, unscaled=False,
+                     norm_hist=None):
+    """optim_step with lr, betas and momentum from the step's row of `sched` (an HpSchedule; dmf_optim_step_sched)."""
+    if kind not in OPTIM_KINDS:
+        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
+    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
+    check(_lib.dmf_optim_step_sched(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], _sched_ref(sched),
+                                    eps, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
+                                    _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
+                                    _ptr(norm_hist), _stream()))
+
+
+def grad_reduce_adam_sched(shape, B, ws, theta, m, v, grad, sched, eps, step, adam_step_dev=None, cursor_dev=None, loss=None,
+                           loss_hist=None):
+    """grad_reduce_adam with lr and the betas from the step's row of `sched` (dmf_grad_reduce_adam_sched)."""
+    check(_lib.dmf_grad_reduce_adam_sched(C.byref(shape), B, _ptr(ws), _ptr(theta), _ptr(m), _ptr(v), _ptr(grad), _sched_ref(sched),
+                                          eps, step, _ptr(adam_step_dev), _ptr(cursor_dev), _ptr(loss), _ptr(loss_hist), _stream()))
+
+
+def train_plan_steps_sched(shape, inp, theta, pool_w, labels, loss_scale, logits, loss, ws, m, v, sched, eps, adam_step_dev,
+                           cursor_dev, loss_hist, n_steps):
+    """train_plan_steps with lr and the betas from the steps' rows of `sched` (dmf_train_plan_steps_sched)."""
+    check(_lib.dmf_train_plan_steps_sched(C.byref(shape), C.byref(inp), _ptr(theta), _ptr(pool_w), _ptr(labels), loss_scale,
+                                          _ptr(logits), _ptr(loss), _ptr(ws), _ptr(m), _ptr(v), _sched_ref(sched), eps,
+                                          _ptr(adam_step_dev), _ptr(cursor_dev), _ptr(loss_hist), n_steps, _stream()))
 
 
 def grad_reduce_adam(shape, B, ws, theta, m, v, grad, lr, b1, b2, eps, step, adam_step_dev=None, cursor_dev=None,

@@ -19,7 +19,8 @@ defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gi
 `schedule.focal_gamma` (all optional): the criterion becomes `nn.CrossEntropyLoss(weight=, label_smoothing=)` or the focal
 loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
 `dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
-then steps eagerly from Python —, no xgmi exchange, the engine shards the batches).  Keys that are all neutral change nothing.
+then steps eagerly from Python; with a scheduler add `device_schedule: 1`, or the graph is re-captured every epoch —, no xgmi
+exchange, the engine shards the batches).  Keys that are all neutral change nothing.
 `schedule.weight_decay`, `schedule.optimizer: ADAMW` and `schedule.clip_grad_norm` (all optional): torch's
 `weight_decay=`, `torch.optim.AdamW` and `clip_grad_norm_(params, max_norm)` between backward and step on both paths; the fast
 path then updates by `dmf_optim_step` on the flat gradient (no native launch loop — set `steps_per_graph` > 0, the default -1
@@ -32,7 +33,13 @@ epochs (`block_length`), inside which the host only enqueues (`_enqueue_block`) 
 ledger entries, same files, same RNG stream.  One difference: `<t>_weights.pth` appears at the end of the block in which the
 best epoch lies, not at that epoch (an interrupted run loses at most one block; a completed one leaves the same file).  With a
 scheduler and `steps_per_graph` > 0 the engine re-captures its graph whenever lr changes, and a capture synchronises (as with
-E = 1); the library's launch loop and a constant lr have no sync.
+E = 1) — unless `schedule.device_schedule: 1` keeps the schedule on the device, which has no sync; nor have the library's launch
+loop and a constant lr.
+`schedule.device_schedule: 1` (default 0) on the fast path: lr, betas and momentum of every epoch live in a table on
+the device and the optimiser kernels read their row themselves (`_set_device_schedule`), so ONE captured graph serves the whole
+run, whatever the scheduler.  `schedule.scheduler_unit: step` (default epoch): `scheduler.step()` after every optimiser step
+instead of once per epoch, on the drop-in path by one branch in the loop, on the fast path by a table row per step (it requires
+device_schedule: 1).
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -52,7 +59,8 @@ from PIL import Image
 from tqdm import tqdm
 
 from solver.basesolver import BaseSolver
-from utils.utils import clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams, make_optimizer, make_scheduler, save_checkpoint
+from utils.utils import (clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
+                         make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
 
 def block_length(epoch, epoch_block, save_every, epochs):
@@ -67,6 +75,7 @@ class Solver(BaseSolver):
     drop-in path `_train_epoch_dropin`, `_valid_pass`, `_predict_dropin`, `_test_whole_split`."""
     engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
     epoch_blocks = True                                  # `train.epoch_block` > 1 has a block form for this stage
+    device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
     def __init__(self, cfg):
         keys = criterion_keys(cfg)
@@ -75,6 +84,10 @@ class Solver(BaseSolver):
                              % (keys[0], type(self).__name__, cfg['schedule']['loss']))
         self.cfg, self.rank, self.world = cfg, 0, 1
         self._epoch_block()                            # (a stage without a block form refuses the key before anything is read)
+        # schedule.device_schedule / schedule.scheduler_unit (utils.schedule_keys; `step` on the fast path needs the device table)
+        self.device_schedule, self.scheduler_unit = schedule_keys(
+            cfg, fast=bool(cfg.get('fast_path', 1)) and str(cfg.get('device', '')).startswith('cuda'))
+        self._step_groups = None                       # unit step on the fast path: the parameter group of every step of the run
         super().__init__(cfg)
         self.criterion = None                          # criterion_spec of the cfg, made by dataloader() (None: plain cross-entropy)
         self.train_labels = None
@@ -163,6 +176,9 @@ class Solver(BaseSolver):
             self.loss = self.loss.to(self.DEVICE)             # (the class weights are a buffer of the module)
         if self.fast:
             self._make_engines()
+        elif self.scheduler_unit == 'step' and self.scheduler is not None:
+            # stepped after every optimiser step: the scheduler spans epochs x batches steps (OneCycleLR's total_steps)
+            self.scheduler = make_scheduler(self.optimizer, self.cfg, total=self.EPOCH * len(self.train_loader))
         self.step_losses, self.val_history, self.best_loss = [], [], float('inf')
         self.best_epoch = 0 if self.cfg['train']['save_best'] else None
         if self.fast and E > 1:
@@ -241,10 +257,38 @@ class Solver(BaseSolver):
             optimizer=hp['optimizer'], momentum=hp.get('momentum', 0.0), alpha=hp.get('alpha', 0.99),
             weight_decay=hp.get('weight_decay', 0.0), clip_grad_norm=hp.get('clip_grad_norm')))
         self.eval_engine = self._eval_engine()
+        self._set_device_schedule()
+
+    def _steps_per_epoch(self):
+        """Optimiser steps of one epoch on the fast path: the full batches, and the short last one where `_rank_batches` keeps it
+        (it needs a pixel for every rank)."""
+        n_full, rest = divmod(len(self.train_index_loader.dataset), self.cfg['batchsize'])
+        return n_full + (1 if rest >= self.world else 0)
+
+    def _set_device_schedule(self):
+        """schedule.device_schedule: 1 — the run's table of (lr, beta1, beta2, momentum) goes to the device once
+        (utils.schedule_table -> engine.set_schedule); it is rebuilt from cfg by every train().  Unit epoch: one row per epoch,
+        `_set_epoch_hparams` points the engine at the epoch's.  Unit step: one row per optimiser step of the run (the short
+        last batch counts), found by the engine's own step count — a resumed engine indexes by the count it was given."""
+        self._step_groups = None
+        if not self.device_schedule:
+            return
+        unit = self.scheduler_unit
+        rows = self.EPOCH * (self._steps_per_epoch() if unit == 'step' else 1)
+        if unit == 'step':
+            self._step_groups = schedule_groups(self.cfg, max(rows, 1), unit)
+        self.engine.set_schedule(schedule_table(self.cfg, max(rows, 1), unit), unit)
 
     def _set_epoch_hparams(self, epoch):
+        """The engine's host-side lr, betas and momentum of this epoch: launch arguments of its steps, or with
+        device_schedule: 1 only what the checkpoint's parameter group is written from (unit step: the row of the epoch's last
+        step), while the steps read the table — the row that `set_epoch` fills in, without a synchronisation."""
         eng = self.engine
         hp = epoch_hparams(self.cfg, epoch)                   # lr (and, under OneCycleLR, beta1 / momentum) of this epoch
+        if self._step_groups is not None:
+            hp = self._step_groups[min((epoch + 1) * self._steps_per_epoch(), len(self._step_groups)) - 1]
+        if self.device_schedule:
+            eng.set_epoch(epoch)
         eng.lr = float(hp['lr'])
         if 'betas' in hp:
             eng.b1, eng.b2 = float(hp['betas'][0]), float(hp['betas'][1])
@@ -298,8 +342,10 @@ class Solver(BaseSolver):
     def _enqueue_block(self, first_epoch, n_epochs):
         """Enqueue epochs [first_epoch, first_epoch + n_epochs): per epoch the plan steps, the short last batch, the validation
         launches in today's batches of `color_batchsize` rows (with class weights the batching is part of the number) and
-        dmf_keep_best.  NO host synchronisation: the uploads come first, on an idle device, and nothing is read back.  (A
-        captured graph that has to be re-captured, `steps_per_graph` > 0 with a changing lr, synchronises inside the engine.)"""
+        dmf_keep_best.  NO host synchronisation: the uploads come first, on an idle device, and nothing is read back.  (With
+        `steps_per_graph` > 0 and a scheduler the engine re-captures its graph when lr changes, and a capture synchronises —
+        unless `schedule.device_schedule: 1` keeps lr on the device: then the graph captured in the first block is replayed to
+        the end, `set_epoch` is a device fill, and a scheduler from graphs does not synchronise inside a block either.)"""
         from dmf import lib
         eng, blk, B, save_best = self.engine, self._block, self.cfg['batchsize'], self.cfg['train']['save_best']
         # the RNG draws of these epochs in today's order: the train loader's two, then the validation loader's base seed
@@ -416,6 +462,7 @@ class Solver(BaseSolver):
         loader = self._bar(self.train_loader)
         losses = []
         max_norm = clip_grad_norm_of(self.cfg['schedule'])           # schedule.clip_grad_norm (None: the reference's loop)
+        per_step = self.scheduler_unit == 'step' and self.scheduler is not None
         for data1, data2, target, _, _ in loader:
             data1, data2, target = data1.to(self.DEVICE), data2.to(self.DEVICE), target.to(self.DEVICE)
             self.optimizer.zero_grad()
@@ -425,10 +472,12 @@ class Solver(BaseSolver):
             if max_norm:
                 torch.nn.utils.clip_grad_norm_(self.cur_model.parameters(), max_norm)
             self.optimizer.step()
+            if per_step:
+                self.scheduler.step()                                # schedule.scheduler_unit: step
             losses.append(loss.item())
             if not self.cfg['nohup']:
                 loader.set_postfix(ls=losses[-1], ep=self.epoch, tm=self.time, m='train', d=self.cfg['device'])
-        if self.cfg['schedule']['if_scheduler']:
+        if self.cfg['schedule']['if_scheduler'] and not per_step:
             self.scheduler.step()
         return losses
 

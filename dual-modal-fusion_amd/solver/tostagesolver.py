@@ -134,6 +134,7 @@ class toStageSolver(Solver):
         loader = self._bar(self.train_loader)
         losses = []
         max_norm = clip_grad_norm_of(self.cfg['schedule'])           # schedule.clip_grad_norm (None: the reference's loop)
+        per_step = self.scheduler_unit == 'step' and self.scheduler is not None
         for data1, data2, data3, data4, target, _, _ in loader:
             data = torch.concat([data1, data2, data3, data4]).to(self.DEVICE)            # tostagesolver.py:270-272
             target = target.to(self.DEVICE)
@@ -145,10 +146,12 @@ class toStageSolver(Solver):
             if max_norm:
                 torch.nn.utils.clip_grad_norm_(self.cur_model.parameters(), max_norm)
             self.optimizer.step()
+            if per_step:
+                self.scheduler.step()                                # schedule.scheduler_unit: step
             losses.append(loss.item())
             if not self.cfg['nohup']:
                 loader.set_postfix(loss=losses[-1], epoch=self.epoch, time=self.time, mode='train')
-        if self.cfg['schedule']['if_scheduler']:
+        if self.cfg['schedule']['if_scheduler'] and not per_step:
             self.scheduler.step()
         return losses
 

@@ -196,11 +196,34 @@ def make_loss(loss_type, cfg, train_labels=None):
     return make()
 
 
-def make_scheduler(optimizer, cfg):
+def make_scheduler(optimizer, cfg, total=None):
+    """total: the number of scheduler steps of the run where that is not cfg['epoch'] (`scheduler_unit: step`: epochs x steps
+    per epoch) — OneCycleLR's total_steps."""
     s = cfg['schedule']
     if not s['if_scheduler']:
         return None
-    return _pick(_SCHEDULERS, s['scheduler'], 'scheduler')(optimizer, s, cfg)
+    return _pick(_SCHEDULERS, s['scheduler'], 'scheduler')(optimizer, s, cfg if total is None else dict(cfg, epoch=int(total)))
+
+
+SCHEDULER_UNITS = ('epoch', 'step')
+
+
+def schedule_keys(cfg, fast=False):
+    """(device_schedule, scheduler_unit) of cfg['schedule'] (both NEW, optional; defaults 0 and epoch).
+    device_schedule: 1 — the fast path keeps lr, betas and momentum of the whole run in a table on the device
+    (`schedule_table`, dmf.engine set_schedule): a captured graph and the library's launch loop follow the scheduler without a
+    re-capture.  scheduler_unit: step — `scheduler.step()` after every optimiser step (torch's OneCycleLR / CyclicLR / warm-up
+    usage) instead of once per epoch; on the fast path (`fast`) only the device table can change lr inside a graph or the
+    launch loop, so it requires device_schedule: 1."""
+    s = cfg['schedule']
+    dev = bool(int(s.get('device_schedule', 0) or 0))
+    unit = s.get('scheduler_unit') or 'epoch'
+    if unit not in SCHEDULER_UNITS:
+        raise ValueError('schedule.scheduler_unit %r is not one of %s' % (unit, ', '.join(SCHEDULER_UNITS)))
+    if unit == 'step' and fast and not dev:
+        raise ValueError('schedule.scheduler_unit: step on the fast path requires schedule.device_schedule: 1 (lr is a launch '
+                         'argument there and cannot change inside a captured graph or the launch loop); set it, or fast_path: 0')
+    return dev, unit
 
 
 def optim_hparams(cfg):
@@ -239,11 +262,11 @@ class _Schedule:
     same class and defaults) and its parameter group is read after every `scheduler.step()` — exactly the sequence the
     reference sees (mainsolver.py:60: one step per epoch).  OneCycleLR also cycles ADAM's beta1; that comes along."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, total=None):
         self.cfg = cfg
         self.param = torch.nn.Parameter(torch.zeros(1))
         self.opt = make_optimizer(cfg, [self.param])
-        self.sched = make_scheduler(self.opt, cfg)
+        self.sched = make_scheduler(self.opt, cfg, total)
         self.seq = [self._group()]
 
     def _group(self):
@@ -269,6 +292,31 @@ def epoch_hparams(cfg, epoch):
     if sch is None or sch.cfg is not cfg:
         sch = _SCHEDULES[key] = _Schedule(cfg)
     return sch.at(epoch)
+
+
+def schedule_groups(cfg, rows, unit='epoch'):
+    """The optimiser parameter groups (lr, betas, momentum ... as torch holds them) of `rows` consecutive scheduler steps:
+    group i is in force after i calls of `scheduler.step()` — epoch i with unit 'epoch' (`epoch_hparams(cfg, i)`), optimiser
+    step i + 1 with unit 'step', where the scheduler is built for `rows` steps in all (make_scheduler's `total`).
+    schedule.if_scheduler: 0 gives one group."""
+    if unit not in SCHEDULER_UNITS:
+        raise ValueError('scheduler unit %r is not one of %s' % (unit, ', '.join(SCHEDULER_UNITS)))
+    if rows < 1:
+        raise ValueError('a schedule needs at least one row, got %d' % rows)
+    sch = _Schedule(cfg, int(rows) if unit == 'step' else None)
+    return [dict(sch.at(i)) for i in range(int(rows) if sch.sched is not None else 1)]
+
+
+def schedule_table(cfg, rows, unit='epoch'):
+    """float32 [rows, 4], row = (lr, beta1, beta2, momentum) of schedule_groups(cfg, rows, unit): the table that
+    dmf.engine's set_schedule uploads.  A value the optimiser kind does not have is torch's ADAM default for the betas and 0
+    for momentum; the kernels do not read it.  Every value is the float32 that the launch argument of the same step would be."""
+    groups = schedule_groups(cfg, rows, unit)
+    out = np.empty((len(groups), 4), dtype=np.float32)
+    for i, g in enumerate(groups):
+        b1, b2 = g.get('betas', _ADAM_DEFAULTS[0])
+        out[i] = (g['lr'], b1, b2, g.get('momentum', 0.0) or 0.0)
+    return out
 
 
 def epoch_lr(cfg, epoch):

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 305   /* 0.3.5: dmf_optim_step (weight decay, AdamW and gradient-norm clipping on the flat gradient); 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 306   /* 0.3.6: dmf_hp_schedule and the *_sched entry points (lr, betas, momentum from a device table); 0.3.5: dmf_optim_step (weight decay, AdamW and gradient-norm clipping on the flat gradient); 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -278,6 +278,41 @@ int32_t dmf_train_plan_steps(const dmf_shape* shape, const dmf_input* in, float*
                              const int32_t* labels, float loss_scale, float* logits, float* loss, void* workspace,
                              float* m, float* v, float lr, float beta1, float beta2, float eps,
                              int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist, int32_t n_steps, void* stream);
+
+/* ---- a device-resident schedule of the step's hyper-parameters ------------------------------------
+ * table [rows][4] fp32 on the device, row = (lr, beta1, beta2, momentum): the optimiser kernels read the row of their step
+ * themselves, so a captured hipGraph or the launch loop of dmf_train_plan_steps follows a learning-rate scheduler without new
+ * launch arguments.  The row of a step:
+ *   row_dev != NULL  (unit `epoch`)  row = *row_dev, a device int32 that the host sets between epochs by a stream-ordered
+ *                                    fill (never inside a captured graph);
+ *   row_dev == NULL  (unit `step`)   row = st - 1, st the 1-based optimiser step count the kernel already has (*step_dev /
+ *                                    *adam_step_dev when given, else the `step` argument).  The forward launch has advanced
+ *                                    the device count before the update launch reads it.  A step that the loss scaler skips
+ *                                    takes its count back (dmf_optim_step, 2.), so the next step reads the SAME row again:
+ *                                    the schedule counts optimiser steps taken, as torch's scheduler.step() after a skipped
+ *                                    GradScaler step is usually guarded to do.
+ * In both units the row is clamped to [0, rows - 1].  lr always comes from the row; beta1 and beta2 for DMF_OPT_ADAM / _ADAMW
+ * (bias corrections from the row's betas and st, always formed on the device; AdamW's 1 - lr * weight_decay from the row's
+ * lr); momentum for DMF_OPT_SGD.  eps, alpha, weight_decay and max_norm stay launch arguments.  The table is only read.
+ * Each *_sched entry point is its twin with (lr, beta1, beta2[, momentum]) replaced by the schedule, does the same arithmetic
+ * on the same fp32 values, and fails on: a NULL schedule or table, rows < 1, and everything its twin fails on;
+ * dmf_optim_step_sched also on DMF_OPT_SGD without m (the host cannot see the row's momentum). */
+typedef struct dmf_hp_schedule { const float* table; int32_t rows; const int32_t* row_dev; } dmf_hp_schedule;
+int32_t dmf_optim_step_sched(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind,
+                             const dmf_hp_schedule* sched, float eps, float alpha,
+                             float weight_decay, float max_norm, int32_t step, float grad_scale,
+                             int32_t* step_dev, int32_t* cursor_dev,
+                             float* scaler_state, float growth_factor, float backoff_factor, int32_t growth_interval,
+                             int32_t unscaled, float* norm_hist, void* stream);
+int32_t dmf_grad_reduce_adam_sched(const dmf_shape* shape, int32_t B, const void* workspace,
+                                   float* theta, float* m, float* v, float* grad,
+                                   const dmf_hp_schedule* sched, float eps, int32_t step,
+                                   const int32_t* adam_step_dev, int32_t* cursor_dev,
+                                   const float* loss, float* loss_hist, void* stream);
+int32_t dmf_train_plan_steps_sched(const dmf_shape* shape, const dmf_input* in, float* theta, const float* pool_w,
+                                   const int32_t* labels, float loss_scale, float* logits, float* loss, void* workspace,
+                                   float* m, float* v, const dmf_hp_schedule* sched, float eps,
+                                   int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist, int32_t n_steps, void* stream);
 
 /* ---- stage 2 of the two-stage path (solver/tostagesolver.py:259-346) ---------------------------------------
  * The stage-2 net takes ONE input, the four streams (ms, pan, ms_gan, pan_gan) stacked on the batch axis

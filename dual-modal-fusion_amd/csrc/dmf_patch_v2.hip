@@ -227,6 +227,11 @@ __device__ __forceinline__ f4v hidden_read4(unsigned addr, int off) {      // (1
 }
 __device__ __forceinline__ void hidden_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 #define HIDDEN_USE(v) asm volatile("" : "+v"(v))
+// End of one column of a column-pipelined loop (see the primary branch): an accumulator named here has taken the column's
+// contribution at this point of the program.  Without it the vectoriser pairs the FMA chains of DIFFERENT columns into
+// packed instructions and emits them behind the last column — all of a column's row arithmetic leaves the loop it was
+// written into, and every row register stays live to the end.  No instruction; the values stay where they are.
+#define COLUMN_DONE(v) asm volatile("" : "+v"(v) :: "memory")
 
 __device__ __forceinline__ float wave_max_dpp(float v) {  // all 64 lanes, result in every lane
 #define DMF_DPP_MAX(v, CTRL) fmaxf((v), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (v)), __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, false)))
@@ -297,30 +302,90 @@ struct ConvRows { float y1u[P], y1d[P], gq[P]; };
 
 struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 
+// The row arithmetic comes in per-column steps, so that a caller can run one column at a time between other work (the
+// primary branch interleaves them with its window reads, see the kernel); conv_row_fwd / conv_row_bwd below run the same
+// steps phase by phase.  Every accumulator (z, dw[k], db) takes its contributions in column order in either form.
+//   conv_fwd_shift(c): y1u[c] / y1d[c], the two lane shifts of y1[c]
+//   conv_fwd_out(c)  : output column c — needs the shifts of columns c-1 .. c+1
+//   conv_fwd_col(c)  : the shifts of column c, then output column c-1 (the last output column is left to the caller)
+template <int P, bool RD>
+__device__ __forceinline__ void conv_fwd_shift(const float (&y1c)[P], ConvRows<P>& t, int c) {
+  t.y1u[c] = lane_above<RD>(y1c[c]); t.y1d[c] = lane_below<RD>(y1c[c]);
+}
+template <int P>
+__device__ __forceinline__ void conv_fwd_out(const float (&y1c)[P], const float (&w)[9], float bias, const float (&pw)[P],
+                                             ConvRows<P>& t, float& z, int c, float* y2) {
+  float y = bias;
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const int cc = c + v - 1;
+    if (cc >= 0 && cc < P) {
+      y = fmaf(w[v], t.y1u[cc], y);
+      y = fmaf(w[3 + v], y1c[cc], y);
+      y = fmaf(w[6 + v], t.y1d[cc], y);
+    }
+  }
+  t.gq[c] = y > 0.f ? pw[c] : 0.f;
+  z = fmaf(t.gq[c], y, z);
+  if (y2 != nullptr) y2[c] = fmaxf(y, 0.f);           // (token mode: the feature map itself)
+}
+template <int P, bool RD>
+__device__ __forceinline__ void conv_fwd_col(const float (&y1c)[P], const float (&w)[9], float bias, const float (&pw)[P],
+                                             ConvRows<P>& t, float& z, int c, float* y2) {
+  conv_fwd_shift<P, RD>(y1c, t, c);
+  if (c > 0) conv_fwd_out<P>(y1c, w, bias, pw, t, z, c - 1, y2);
+}
+
 // hook(c) runs after output column c: the aux branch issues the rest of the window gather from there (see the kernel)
 template <int P, bool RD, class Hook = NoHook>
 __device__ __forceinline__ void conv_row_fwd(const float (&y1c)[P], const float (&w)[9], float bias, const float (&pw)[P],
                                              ConvRows<P>& t, float& z, Hook&& hook = Hook(), float* y2 = nullptr) {
 #pragma unroll
-  for (int c = 0; c < P; ++c) { t.y1u[c] = lane_above<RD>(y1c[c]); t.y1d[c] = lane_below<RD>(y1c[c]); }
+  for (int c = 0; c < P; ++c) conv_fwd_shift<P, RD>(y1c, t, c);
   z = 0.f;
 #pragma unroll
   for (int c = 0; c < P; ++c) {
-    float y = bias;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      const int cc = c + v - 1;
-      if (cc >= 0 && cc < P) {
-        y = fmaf(w[v], t.y1u[cc], y);
-        y = fmaf(w[3 + v], y1c[cc], y);
-        y = fmaf(w[6 + v], t.y1d[cc], y);
-      }
-    }
-    t.gq[c] = y > 0.f ? pw[c] : 0.f;
-    z = fmaf(t.gq[c], y, z);
-    if (y2 != nullptr) y2[c] = fmaxf(y, 0.f);           // (token mode: the feature map itself)
+    conv_fwd_out<P>(y1c, w, bias, pw, t, z, c, y2);
     hook(c);
   }
+}
+
+// Backward steps.  dY1(r,c) = [y1 > 0] * sum_{u,v} W[u][v] * dY2(r-u+1, c-v+1): u = 0 pairs with the row below, u = 2 with
+// the row above.
+//   conv_bwd_shift(c): gu[c] / gd[c], the two lane shifts of the gated pooling weight gq[c]
+//   conv_bwd_acc(c)  : the contributions of output column c to dw[9] and db
+//   conv_bwd_dy(c)   : dy[c] — needs the shifts of columns c-1 .. c+1
+template <int P, bool RD>
+__device__ __forceinline__ void conv_bwd_shift(const ConvRows<P>& t, float (&gu)[P], float (&gd)[P], int c) {
+  gu[c] = lane_above<RD>(t.gq[c]); gd[c] = lane_below<RD>(t.gq[c]);
+}
+template <int P>
+__device__ __forceinline__ void conv_bwd_acc(const float (&y1c)[P], const ConvRows<P>& t, float (&dw)[9], float& db, int c) {
+  db += t.gq[c];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const int cc = c + v - 1;
+    if (cc >= 0 && cc < P) {
+      dw[v] = fmaf(t.gq[c], t.y1u[cc], dw[v]);
+      dw[3 + v] = fmaf(t.gq[c], y1c[cc], dw[3 + v]);
+      dw[6 + v] = fmaf(t.gq[c], t.y1d[cc], dw[6 + v]);
+    }
+  }
+}
+template <int P>
+__device__ __forceinline__ float conv_bwd_dy(const float (&y1c)[P], const float (&w)[9], const ConvRows<P>& t,
+                                             const float (&gu)[P], const float (&gd)[P], int c) {
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const int cc = c - v + 1;
+    if (cc >= 0 && cc < P) {
+      s = fmaf(w[v], gd[cc], s);
+      s = fmaf(w[3 + v], t.gq[cc], s);
+      s = fmaf(w[6 + v], gu[cc], s);
+    }
+  }
+  return y1c[c] > 0.f ? s : 0.f;
 }
 
 template <int P, bool RD>
@@ -330,36 +395,12 @@ __device__ __forceinline__ void conv_row_bwd(const float (&y1c)[P], const float 
   for (int k = 0; k < 9; ++k) dw[k] = 0.f;
   db = 0.f;
 #pragma unroll
-  for (int c = 0; c < P; ++c) {
-    db += t.gq[c];
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      const int cc = c + v - 1;
-      if (cc >= 0 && cc < P) {
-        dw[v] = fmaf(t.gq[c], t.y1u[cc], dw[v]);
-        dw[3 + v] = fmaf(t.gq[c], y1c[cc], dw[3 + v]);
-        dw[6 + v] = fmaf(t.gq[c], t.y1d[cc], dw[6 + v]);
-      }
-    }
-  }
-  // dY1(r,c) = [y1 > 0] * sum_{u,v} W[u][v] * dY2(r-u+1, c-v+1): u = 0 pairs with the row below, u = 2 with the row above
+  for (int c = 0; c < P; ++c) conv_bwd_acc<P>(y1c, t, dw, db, c);
   float gu[P], gd[P];
 #pragma unroll
-  for (int c = 0; c < P; ++c) { gu[c] = lane_above<RD>(t.gq[c]); gd[c] = lane_below<RD>(t.gq[c]); }
+  for (int c = 0; c < P; ++c) conv_bwd_shift<P, RD>(t, gu, gd, c);
 #pragma unroll
-  for (int c = 0; c < P; ++c) {
-    float s = 0.f;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      const int cc = c - v + 1;
-      if (cc >= 0 && cc < P) {
-        s = fmaf(w[v], gd[cc], s);
-        s = fmaf(w[3 + v], t.gq[cc], s);
-        s = fmaf(w[6 + v], gu[cc], s);
-      }
-    }
-    dy[c] = y1c[c] > 0.f ? s : 0.f;
-  }
+  for (int c = 0; c < P; ++c) dy[c] = conv_bwd_dy<P>(y1c, w, t, gu, gd, c);
 }
 
 template <int P, bool TR, bool RD, class Hook = NoHook>
@@ -968,60 +1009,67 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
         if (4 * q + 2 < P) pw[4 * q + 2] = v.z;
         if (4 * q + 3 < P) pw[4 * q + 3] = v.w;
       }
-      float y1a[P];
-      if constexpr (HF) {   // spec_a on fp16 operands: two bands per word, v_dot2_f32_f16 (exact products, fp32 accumulate)
-        h2 w1h[Cg / 2];
+      // spec_a and spat_a forward, one window column at a time.  The two have opposite bottlenecks — spec_a waits for its
+      // window reads (QC ds_read_b128 per column and lane, the LDS pipeline's busiest stretch), the depthwise rows are pure
+      // vector work — so a lane finishes spec_a of column c, requesting piece q of column c + 1 as soon as piece q of
+      // column c is consumed, and then runs the conv step that the new y1[c] makes possible (output column c - 1) while
+      // those reads are in flight.  The sched_barrier per column bounds the reads the scheduler keeps in flight (registers:
+      // one column; two columns ahead do not fit the 224-band instance), COLUMN_DONE keeps a column's arithmetic inside its
+      // column.  (profiles/column_pipeline.md)
+      using XV = std::conditional_t<HF, float2, float4>;   // one 16-byte (fp16: 8-byte) piece of a window column
+      XV xw[QC];                                           // one column of pieces: piece q of the next column is requested into the slot piece q just left
+      auto request = [&](int c, int q) { xw[q] = *reinterpret_cast<const XV*>(xr + c * V::CS + (HF ? 2 : 4) * q); };
+      auto request_first = [&]() {
 #pragma unroll
-        for (int q = 0; q < QC; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(sTh + Sh::oA1w + f * Cg + 4 * q);
+        for (int q = 0; q < QC; ++q) request(0, q);
+      };
+      float y1a[P];
+      float za = 0.f, dwa[9], dba = 0.f;
+      ConvRows<P> ta;
+      float y2a[P];
+      const float bias2a = act ? b2a : -1e30f;
+      const float b1 = sTh[Sh::oA1b + f];
+      h2 w1h[HF ? Cg / 2 : 1];                             // fp16 operands: two bands per word, v_dot2_f32_f16 (exact products, fp32 accumulate)
+      v2f w1p[HF ? 1 : Cg / 2];                            // fp32: even / odd bands of the group in the two halves of a packed accumulator
+#pragma unroll
+      for (int q = 0; q < QC; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(sTh + Sh::oA1w + f * Cg + 4 * q);
+        if constexpr (HF) {
           w1h[2 * q] = (h2){(_Float16)v.x, (_Float16)v.y};
           w1h[2 * q + 1] = (h2){(_Float16)v.z, (_Float16)v.w};
-        }
-        const float b1 = sTh[Sh::oA1b + f];
-        float ap[P];
-#pragma unroll
-        for (int c = 0; c < P; ++c) ap[c] = b1;
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-          if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int q = 0; q < QC; ++q) {
-            const float2 xv = *reinterpret_cast<const float2*>(xr + c * V::CS + 2 * q);
-            ap[c] = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xv.x), w1h[2 * q], ap[c], false);
-            ap[c] = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xv.y), w1h[2 * q + 1], ap[c], false);
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < P; ++c) y1a[c] = relu_lim(ap[c], lim);
-      } else {   // spec_a: even / odd bands of the group in the two halves of a packed accumulator
-        v2f w1p[Cg / 2];
-#pragma unroll
-        for (int q = 0; q < QC; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(sTh + Sh::oA1w + f * Cg + 4 * q);
+        } else {
           w1p[2 * q] = (v2f){v.x, v.y};
           w1p[2 * q + 1] = (v2f){v.z, v.w};
         }
-        const float b1 = sTh[Sh::oA1b + f];
-        v2f ap[P];
+      }
+      request_first();
 #pragma unroll
-        for (int c = 0; c < P; ++c) ap[c] = (v2f){b1, 0.f};
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-          if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);   // bounds the window reads the scheduler keeps in flight (registers)
+      for (int c = 0; c < P; ++c) {
+        __builtin_amdgcn_sched_barrier(0);
+        const XV* xc = xw;
+        if constexpr (HF) {
+          float ap = b1;
 #pragma unroll
           for (int q = 0; q < QC; ++q) {
-            const float4 xv = *reinterpret_cast<const float4*>(xr + c * V::CS + 4 * q);
-            ap[c] = pk_fma(w1p[2 * q], (v2f){xv.x, xv.y}, ap[c]);
-            ap[c] = pk_fma(w1p[2 * q + 1], (v2f){xv.z, xv.w}, ap[c]);
+            ap = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xc[q].x), w1h[2 * q], ap, false);
+            ap = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xc[q].y), w1h[2 * q + 1], ap, false);
+            if (c + 1 < P) request(c + 1, q);
           }
-        }
+          y1a[c] = relu_lim(ap, lim);
+        } else {
+          v2f ap = (v2f){b1, 0.f};
 #pragma unroll
-        for (int c = 0; c < P; ++c) y1a[c] = relu_lim(ap[c].x + ap[c].y, lim);
+          for (int q = 0; q < QC; ++q) {
+            ap = pk_fma(w1p[2 * q], (v2f){xc[q].x, xc[q].y}, ap);
+            ap = pk_fma(w1p[2 * q + 1], (v2f){xc[q].z, xc[q].w}, ap);
+            if (c + 1 < P) request(c + 1, q);
+          }
+          y1a[c] = relu_lim(ap.x + ap.y, lim);
+        }
+        conv_fwd_col<P, V::ROWDPP>(y1a, w2a, bias2a, pw, ta, za, c, TOK ? y2a : nullptr);
+        COLUMN_DONE(za);
       }
-      float za, dwa[9], dba = 0.f, dya[P];
-      ConvRows<P> ta;
-      float y2a[P];
-      conv_row_fwd<P, V::ROWDPP>(y1a, w2a, act ? b2a : -1e30f, pw, ta, za, NoHook(), TOK ? y2a : nullptr);
+      conv_fwd_out<P>(y1a, w2a, bias2a, pw, ta, za, P - 1, TOK ? y2a : nullptr);
       if constexpr (TOK) {   // both feature-map rows -> the bf16 staging [map][token = pixel][channel]
         if (act) {
           unsigned short* sTok = reinterpret_cast<unsigned short*>(smem + V::oW2);
@@ -1052,54 +1100,119 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       VSTAMP(5);
       if constexpr (TOK) { token_out(b); continue; }
       if constexpr (!TR) continue;
-      // spat_a's unit backward runs BEHIND barrier 1: the head starts a conv backward earlier, and its chain of LDS round
-      // trips (fc1 -> fc2 -> softmax -> dh) begins while the conv waves execute pure vector work instead of queueing behind
-      // their window reads
-      conv_row_bwd<P, V::ROWDPP>(y1a, w2a, ta, dwa, dba, dya);
-
-      // ------------------------------------------------------------------ unit gradients of spec_a from the still-resident window
+      // spat_a's unit backward runs BEHIND barrier 1, not in front of it: the head wave starts its chain of LDS round trips
+      // (fc1 -> fc2 -> softmax -> dh) a whole conv backward earlier.  It used to start against conv waves that did pure vector
+      // work first; now they request their first window column at once and run the conv backward step of a column UNDER its
+      // reads, so the head's reads share the LDS pipeline with theirs from the start (its chain measures 0.18 K cycles longer,
+      // 5.3 -> 5.5 K; the phase as a whole is 0.3 K shorter and now ends with the head, profiles/column_pipeline.md).
+      // The unit gradient of spec_a needs the window a second time, and dY1 of a column needs nothing from LDS: the same
+      // column pipeline as the forward.  The reads of column c + 1 are in flight — they do not depend on dy — while the conv
+      // backward step of column c runs, then come the weight-gradient FMAs of that column.  dwa / dba are summed over the quad
+      // as soon as their chains end, under the reads of the last columns.  Not for 16-row instances (one 16-byte read per
+      // column: nothing to overlap, and with all of y1 / y1u / y1d / gq live through the loop the allocator spills in the aux
+      // phase): they keep the phase-by-phase form in the else branch.
+      constexpr bool PIPE_BWD = !V::ROWDPP;
       float acc[Cg], db1 = 0.f;
-      if constexpr (HF) {   // fp16 window x fp32 gradient, fp32 accumulate (v_fma_mix_f32)
+      if constexpr (PIPE_BWD) {
+        float gu[P], gd[P];
+        v2f gp[HF ? 1 : Cg / 2];
 #pragma unroll
-        for (int j = 0; j < Cg; ++j) acc[j] = 0.f;
+        for (int j = 0; j < Cg; ++j) acc[j] = 0.f;        // (HF accumulates here, fp32 in gp)
+#pragma unroll
+        for (int j = 0; j < (HF ? 0 : Cg / 2); ++j) gp[j] = (v2f){0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dwa[k] = 0.f;
+        dba = 0.f;
+        request_first();
+        conv_bwd_shift<P, V::ROWDPP>(ta, gu, gd, 0);
 #pragma unroll
         for (int c = 0; c < P; ++c) {
-          if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);
-          db1 += dya[c];
-#pragma unroll
-          for (int q = 0; q < QC; ++q) {
-            const float2 xv = *reinterpret_cast<const float2*>(xr + c * V::CS + 2 * q);
-            acc[4 * q] = fma_mix_lo(xv.x, dya[c], acc[4 * q]);
-            acc[4 * q + 1] = fma_mix_hi(xv.x, dya[c], acc[4 * q + 1]);
-            acc[4 * q + 2] = fma_mix_lo(xv.y, dya[c], acc[4 * q + 2]);
-            acc[4 * q + 3] = fma_mix_hi(xv.y, dya[c], acc[4 * q + 3]);
+          __builtin_amdgcn_sched_barrier(0);
+          if (c + 1 < P) conv_bwd_shift<P, V::ROWDPP>(ta, gu, gd, c + 1);
+          const float dy = conv_bwd_dy<P>(y1a, w2a, ta, gu, gd, c);
+          conv_bwd_acc<P>(y1a, ta, dwa, dba, c);
+          if (c == P - 2) {         // the v = 2 taps end with output column P - 2
+            dwa[2] = quad_sum(dwa[2]); dwa[5] = quad_sum(dwa[5]); dwa[8] = quad_sum(dwa[8]);
           }
+          if (c == P - 1) {
+            dwa[0] = quad_sum(dwa[0]); dwa[1] = quad_sum(dwa[1]); dwa[3] = quad_sum(dwa[3]);
+            dwa[4] = quad_sum(dwa[4]); dwa[6] = quad_sum(dwa[6]); dwa[7] = quad_sum(dwa[7]);
+            dba = quad_sum(dba);
+          }
+          db1 += dy;
+          const XV* xc = xw;
+          if constexpr (HF) {   // fp16 window x fp32 gradient, fp32 accumulate (v_fma_mix_f32)
+#pragma unroll
+            for (int q = 0; q < QC; ++q) {
+              acc[4 * q] = fma_mix_lo(xc[q].x, dy, acc[4 * q]);
+              acc[4 * q + 1] = fma_mix_hi(xc[q].x, dy, acc[4 * q + 1]);
+              acc[4 * q + 2] = fma_mix_lo(xc[q].y, dy, acc[4 * q + 2]);
+              acc[4 * q + 3] = fma_mix_hi(xc[q].y, dy, acc[4 * q + 3]);
+              if (c + 1 < P) request(c + 1, q);
+            }
+          } else {
+            const v2f d2 = (v2f){dy, dy};
+#pragma unroll
+            for (int q = 0; q < QC; ++q) {
+              gp[2 * q] = pk_fma(d2, (v2f){xc[q].x, xc[q].y}, gp[2 * q]);
+              gp[2 * q + 1] = pk_fma(d2, (v2f){xc[q].z, xc[q].w}, gp[2 * q + 1]);
+              if (c + 1 < P) request(c + 1, q);
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 9; ++k) COLUMN_DONE(dwa[k]);
+          COLUMN_DONE(dba);
+        }
+        if constexpr (!HF) {
+#pragma unroll
+          for (int j = 0; j < Cg / 2; ++j) { acc[2 * j] = gp[j].x; acc[2 * j + 1] = gp[j].y; }
         }
       } else {
-        v2f gp[Cg / 2];
+        float dya[P];
+        conv_row_bwd<P, V::ROWDPP>(y1a, w2a, ta, dwa, dba, dya);
+        // unit gradients of spec_a from the still-resident window
+        if constexpr (HF) {   // fp16 window x fp32 gradient, fp32 accumulate (v_fma_mix_f32)
 #pragma unroll
-        for (int j = 0; j < Cg / 2; ++j) gp[j] = (v2f){0.f, 0.f};
+          for (int j = 0; j < Cg; ++j) acc[j] = 0.f;
 #pragma unroll
-        for (int c = 0; c < P; ++c) {
-          if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);
-          db1 += dya[c];
-          const v2f d2 = (v2f){dya[c], dya[c]};
+          for (int c = 0; c < P; ++c) {
+            if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);
+            db1 += dya[c];
 #pragma unroll
-          for (int q = 0; q < QC; ++q) {
-            const float4 xv = *reinterpret_cast<const float4*>(xr + c * V::CS + 4 * q);
-            gp[2 * q] = pk_fma(d2, (v2f){xv.x, xv.y}, gp[2 * q]);
-            gp[2 * q + 1] = pk_fma(d2, (v2f){xv.z, xv.w}, gp[2 * q + 1]);
+            for (int q = 0; q < QC; ++q) {
+              const float2 xv = *reinterpret_cast<const float2*>(xr + c * V::CS + 2 * q);
+              acc[4 * q] = fma_mix_lo(xv.x, dya[c], acc[4 * q]);
+              acc[4 * q + 1] = fma_mix_hi(xv.x, dya[c], acc[4 * q + 1]);
+              acc[4 * q + 2] = fma_mix_lo(xv.y, dya[c], acc[4 * q + 2]);
+              acc[4 * q + 3] = fma_mix_hi(xv.y, dya[c], acc[4 * q + 3]);
+            }
           }
+        } else {
+          v2f gp[Cg / 2];
+#pragma unroll
+          for (int j = 0; j < Cg / 2; ++j) gp[j] = (v2f){0.f, 0.f};
+#pragma unroll
+          for (int c = 0; c < P; ++c) {
+            if (c % 3 == 0 && c > 0) __builtin_amdgcn_sched_barrier(0);
+            db1 += dya[c];
+            const v2f d2 = (v2f){dya[c], dya[c]};
+#pragma unroll
+            for (int q = 0; q < QC; ++q) {
+              const float4 xv = *reinterpret_cast<const float4*>(xr + c * V::CS + 4 * q);
+              gp[2 * q] = pk_fma(d2, (v2f){xv.x, xv.y}, gp[2 * q]);
+              gp[2 * q + 1] = pk_fma(d2, (v2f){xv.z, xv.w}, gp[2 * q + 1]);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < Cg / 2; ++j) { acc[2 * j] = gp[j].x; acc[2 * j + 1] = gp[j].y; }
         }
 #pragma unroll
-        for (int j = 0; j < Cg / 2; ++j) { acc[2 * j] = gp[j].x; acc[2 * j + 1] = gp[j].y; }
+        for (int k = 0; k < 9; ++k) dwa[k] = quad_sum(dwa[k]);
+        dba = quad_sum(dba);
       }
       VSTAMP(6);
 #pragma unroll
       for (int j = 0; j < Cg; ++j) acc[j] = quad_sum(acc[j]);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) dwa[k] = quad_sum(dwa[k]);
-      dba = quad_sum(dba);
       db1 = quad_sum(db1);
       if (lead) {   // the primary branch's unit gradients -> this quad's slab copy
         float* so = sl + Sh::oA1w + f * Cg;

@@ -2,8 +2,13 @@
 //
 // Replaces (reference): `output = self.cur_model(data1, data2)`, `loss = self.loss(output, target.long())`,
 // `loss.backward()` — solver/mainsolver.py:52-54 — and the eval forward + argmax (mainsolver.py:109,139,169-170).
-// Arithmetic: oracle/gmfnet_ref.py.  The ONLY patch kernel since round 3 (round 1's generic kernel, which also took band
-// groups that are not whole 16-byte chunks — 200 bands at gmf.width 32 — was retired with that shape).
+// Arithmetic: oracle/gmfnet_ref.py.  The only patch kernel: every compiled shape is a row of the instance table at the end
+// of this file, and band groups must be whole 16-byte chunks (200 bands at gmf.width 32 has no instance).
+//
+// The file, top to bottom: V2<> (compile-time geometry and the LDS map of an instance), the lane helpers and the
+// per-column depthwise-conv steps, dma_piece (LDS-DMA), patch_v2_kernel (one body for every mode), unit_backward_kernel
+// (second half of the unit-gradient step), the launchers and the instance table.  The kernel's code object reacts to
+// edits that look neutral: tools/isa_diff.py compares two trees kernel by kernel (profiles/say_once.md).
 //
 // Measured facts this design is built on (tools/valu_rate.hip, tools/phase_profile_v2.py on MI355X):
 //   * A SIMD issues one vector instruction per ~3.2 (v_fmac) to ~4.9 (DPP, packed) cycles however many waves it hosts,
@@ -292,6 +297,12 @@ __device__ __forceinline__ float quad_sum(float v) {     // over the 4 lanes of 
   return v;
 }
 
+// the label as the head wave takes it: clamped into [0, K)
+__device__ __forceinline__ int clamp_label(int label, int K) { return label < 0 ? 0 : (label >= K ? K - 1 : label); }
+// the value the wave-uniform lane l holds of v, in every lane.  (A macro: as a function the train instances compile to
+// other code — profiles/say_once.md.)
+#define DMF_LANE_VALUE(v, l) __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, (v)), __builtin_amdgcn_readfirstlane(l)))
+
 // Depthwise 3x3 (zero pad 1) + ReLU + anchor pooling of one channel row, and — TRAIN — its backward for a UNIT
 // gradient on the pooled scalar: dY2 = [y2 > 0] * pool.  A lane holds row r of its channel; rows r-1 / r+1 are the
 // neighbouring lanes.  Padding lanes carry y1 = 0 and a closed gate, which is exactly the zero padding.
@@ -414,17 +425,17 @@ __device__ __forceinline__ void conv_row(const float (&y1c)[P], const float (&w)
 // One piece of LDS-DMA: lane l reads BYTES (4 or 16) bytes at base + soff + voff into lds + BYTES l (lanes with voff < 0 are
 // masked off).  BUFFER form (buffer_load_dword[x4] ... lds): see the header comment.  (Device pass only: the buffer-resource
 // type does not exist in the host pass, which needs nothing but the kernel's stub.)
+#define DMF_DMA_RSRC(base) __builtin_amdgcn_make_buffer_rsrc((void*)(base), 0, 0x7FFFFFFF, 0x00020000)
 template <int BYTES>
 __device__ __forceinline__ void dma_piece(const float* base, int soff, int voff, float* lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = DMF_DMA_RSRC(base);
   if (voff >= 0) {
     if constexpr (BYTES == 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
     else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds, 4, voff, soff, 0, 0);
   }
 #endif
 }
-__device__ __forceinline__ void gather_piece(const float* base, int soff, int voff, float* lds) { dma_piece<16>(base, soff, voff, lds); }
 
 // Channel (dz index) of every slab element, 8 bits each, one word per 16-byte slab piece: a compile-time table in the code
 // object's constant data, staged into LDS with the other patch-invariant tables (forming it in the kernel cost every
@@ -437,17 +448,7 @@ struct DzixTable {
     for (int t = 0; t < Sh::SLAB / 4; ++t) {
       int w = 0;
       for (int e = 0; e < 4; ++e) {
-        const int p = 4 * t + e;
-        int ix = 0;
-        if (p < Sh::oA1b) ix = p / Sh::Cg;
-        else if (p < Sh::oA2w) ix = p - Sh::oA1b;
-        else if (p < Sh::oA2b) ix = (p - Sh::oA2w) / 9;
-        else if (p < Sh::oB1w) ix = p - Sh::oA2b;
-        else if (p < Sh::oB1b) ix = Sh::F + (p - Sh::oB1w) / Sh::TB;
-        else if (p < Sh::oB2w) ix = Sh::F + p - Sh::oB1b;
-        else if (p < Sh::oB2b) ix = Sh::F + (p - Sh::oB2w) / 9;
-        else if (p < Sh::NCONV) ix = Sh::F + p - Sh::oB2b;
-        w |= ix << (8 * e);
+        w |= Sh::slab_channel(4 * t + e, 0) << (8 * e);
       }
       v[t] = w;
     }
@@ -506,10 +507,10 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
   const int boff = (a.in.cursor != nullptr) ? ((cint*)a.in.cursor)[0] * B : 0;     // epoch-plan offset of this batch
   // first patch's coordinates: requested before anything else (kernarg -> coordinates -> gather is the kernel's longest
   // dependent chain of memory round trips; the table staging below runs under it)
+  // (a macro: as a lambda the same two loads compile to other code in every gather instance — profiles/say_once.md)
   int xn = 0, yn = 0;
-  if (INMODE == 1 && (int)blockIdx.x < B) {
-    xn = ((cint*)a.in.xy)[2 * (size_t)(boff + blockIdx.x)]; yn = ((cint*)a.in.xy)[2 * (size_t)(boff + blockIdx.x) + 1];
-  }
+#define DMF_REQUEST_XY(bi) { xn = ((cint*)a.in.xy)[2 * (size_t)(boff + bi)]; yn = ((cint*)a.in.xy)[2 * (size_t)(boff + bi) + 1]; }
+  if (INMODE == 1 && (int)blockIdx.x < B) DMF_REQUEST_XY(blockIdx.x)
   if constexpr (TR) {   // the slab rows' padding beyond the last parameter is copied out too: keep it zero
     if (tid < Sh::SLAB - Sh::NCONV) {                   // (< 32 elements)
 #pragma unroll
@@ -539,9 +540,6 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       }
     }
   }
-  // (inline asm: the compiler must not count this against later loads — it orders visible LDS accesses behind the staging
-  // pieces with counted waits of its own)
-#define DMF_STAGE_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
   static_assert(Sh::NCONV % 4 == 0, "conv parameters in whole 16-byte pieces");
   // This wave's share of the gather: pieces p = wave + k NW of the window image.  Lane l of piece p holds image floats
   // n = 256 p + 4 l .. + 3 = pixel n / CS, bands n % CS ..; its scene offset is ((row Wp + col) C + band) floats.
@@ -562,7 +560,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       // image except in the last piece.
       const int D4 = (a.in.Wp * V::CW - V::RS) * 4;
 #if defined(__HIP_DEVICE_COMPILE__)
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7FFFFFFF, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrc = DMF_DMA_RSRC(base);
       int w_ = wave;
       asm volatile("" : "+s"(w_));                           // (formed here, per call: hoisted, 11 pieces' scalars are spilled)
 #pragma unroll
@@ -599,7 +597,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
         if (pr >= P || pc >= P || band >= V::CW) off = -1;
       }
       if (p >= V::NPIECE) off = -1;
-      gather_piece(base, 0, off, smem + V::oX + (p < V::NPIECE ? p : 0) * 256);
+      dma_piece<16>(base, 0, off, smem + V::oX + (p < V::NPIECE ? p : 0) * 256);
     }
   };
 
@@ -641,6 +639,14 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
   constexpr int NI = (Sh::SLAB / 4 + V::NT - 1) / V::NT;   // 16-byte slab pieces per thread
   // (channel (dz index) of each slab element: the staged DzixTable in LDS — kept in registers across the patch loop it is
   // spilled to scratch, and scratch lines are written back at kernel end)
+  // float4 v = the sum of the quad copies of 16-byte slab piece t.  (A macro: written as a lambda or a function, with the
+  // same statements in the same order, 38 instances compile to other code — profiles/say_once.md.)
+#define DMF_QUAD_COPY_SUM(v, t)                                                                   \
+  float4 v = *reinterpret_cast<const float4*>(sSlab + 4 * (t));                                   \
+  _Pragma("unroll") for (int c_ = 1; c_ < V::NCOPY; ++c_) {                                       \
+    const float4 u_ = *reinterpret_cast<const float4*>(sSlab + c_ * Sh::SLAB + 4 * (t));          \
+    v.x += u_.x; v.y += u_.y; v.z += u_.z; v.w += u_.w;                                           \
+  }
   auto scale_and_store = [&](int it, int b) {
     int tid_ = tid;
     OPAQUE(tid_);            // (addresses formed here, not carried — spilled — across the patch loop)
@@ -649,12 +655,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       for (int i = 0; i < NI; ++i) {
         const int t = tid_ + i * V::NT;
         if (t < Sh::SLAB / 4) {
-          float4 v = *reinterpret_cast<const float4*>(sSlab + 4 * t);
-#pragma unroll
-          for (int c = 1; c < V::NCOPY; ++c) {
-            const float4 u = *reinterpret_cast<const float4*>(sSlab + c * Sh::SLAB + 4 * t);
-            v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-          }
+          DMF_QUAD_COPY_SUM(v, t);
           float* __restrict__ slab = a.slab + slab_index(blockIdx.x, 4 * t, gridDim.x);
           if (it > 0) {
             const float4 o = *reinterpret_cast<const float4*>(slab);
@@ -671,12 +672,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       for (int i = 0; i < NI; ++i) {
         const int t = tid_ + i * V::NT;
         if (t < Sh::SLAB / 4) {
-          float4 v = *reinterpret_cast<const float4*>(sSlab + 4 * t);
-#pragma unroll
-          for (int c = 1; c < V::NCOPY; ++c) {
-            const float4 u = *reinterpret_cast<const float4*>(sSlab + c * Sh::SLAB + 4 * t);
-            v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-          }
+          DMF_QUAD_COPY_SUM(v, t);
           *reinterpret_cast<float4*>(a.slab + (size_t)b * Sh::SLAB + 4 * t) = v;
         }
       }
@@ -702,12 +698,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
     for (int i = 0; i < NI; ++i) {
       const int t = tid_ + i * V::NT;
       if (t < Sh::SLAB / 4) {
-        float4 v = *reinterpret_cast<const float4*>(sSlab + 4 * t);
-#pragma unroll
-        for (int c = 1; c < V::NCOPY; ++c) {
-          const float4 u = *reinterpret_cast<const float4*>(sSlab + c * Sh::SLAB + 4 * t);
-          v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-        }
+        DMF_QUAD_COPY_SUM(v, t);
         const int dx = reinterpret_cast<const int*>(smem + V::oDzix)[t];
         v.x *= sDz[dx & 255]; v.y *= sDz[(dx >> 8) & 255]; v.z *= sDz[(dx >> 16) & 255]; v.w *= sDz[(dx >> 24) & 255];
         float* __restrict__ slab = a.slab + slab_index(blockIdx.x, 4 * t, gridDim.x);      // (piece-major: dmf_shapes.h)
@@ -817,12 +808,12 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
             // wait here for an LDS-DMA aux image too, which depends on the coordinates: the barrier stood at ~3.4 K cycles.
             VSTAMP(11);
             wait_older_than_gather(std::integral_constant<int, NV4 + NR1>());
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            LDS_BARRIER();
           }
         }
         {   // the next patch's coordinates, a whole patch ahead of their use
           const int bn = b + (int)gridDim.x < B ? b + (int)gridDim.x : b;
-          xn = ((cint*)a.in.xy)[2 * (size_t)(boff + bn)]; yn = ((cint*)a.in.xy)[2 * (size_t)(boff + bn) + 1];
+          DMF_REQUEST_XY(bn)
         }
       } else {
         // materialised band-major patches (the reference dataloader's tensors; test / drop-in path)
@@ -843,7 +834,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 #pragma unroll
             for (int k = 0; k < C2; ++k) ax[c * C2 + k] = srcB[k * P2 + rc * P + c];
         }
-        if (it == 0) { DMF_STAGE_WAIT(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }   // barrier X
+        if (it == 0) { DMF_STAGE_WAIT(); LDS_BARRIER(); }   // barrier X
         const float* __restrict__ srcA = a.in.a + (size_t)(boff + b) * Sh::C * P2;
         for (int e = tid; e < Sh::C * P2; e += V::NB * 64) {
           const int cb = e / P2, pix = e - cb * P2;
@@ -902,23 +893,26 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
           if constexpr ((V::NC4 & (V::NC4 - 1)) == 0) return (j + rc) & (V::NC4 - 1);
           else { int pc = j + rc; pc -= pc >= V::NC4 ? V::NC4 : 0; return pc; }
         };
+        // STMT for every float x of this lane's S image rows, with its output column col and its tap of lift_b.  (A macro: as a
+        // lambda over a lambda the S = 4 instances compile to other code, five with more registers — profiles/say_once.md.)
+#define DMF_FOR_EACH_AUX_TAP(STMT)                                                         \
+        _Pragma("unroll") for (int j = 0; j < V::NC4; ++j) {                               \
+          const float* ap = auxr + 4 * chunk_of(j);                                        \
+          _Pragma("unroll") for (int u = 0; u < Sh::S; ++u) {                              \
+            const float4 a4 = *reinterpret_cast<const float4*>(ap + u * V::RL);            \
+            const float av[4] = {a4.x, a4.y, a4.z, a4.w};                                  \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                \
+              const int m = 4 * j + e, cp = m / C2, k = m % C2;                            \
+              const int col = cp / Sh::S, tap = (k * Sh::S + u) * Sh::S + cp % Sh::S;      \
+              const float x = av[e];                                                       \
+              STMT;                                                                        \
+            }                                                                              \
+          }                                                                                \
+        }
         if constexpr (V::SX) {
 #pragma unroll
           for (int c = 0; c < P; ++c) y1b[c] = bl;
-#pragma unroll
-          for (int j = 0; j < V::NC4; ++j) {
-            const float* ap = auxr + 4 * chunk_of(j);
-#pragma unroll
-            for (int u = 0; u < Sh::S; ++u) {
-              const float4 a4 = *reinterpret_cast<const float4*>(ap + u * V::RL);
-              const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const int m = 4 * j + e, cp = m / C2, k = m % C2;
-                y1b[cp / Sh::S] = fmaf(wl[(k * Sh::S + u) * Sh::S + cp % Sh::S], av[e], y1b[cp / Sh::S]);
-              }
-            }
-          }
+          DMF_FOR_EACH_AUX_TAP(y1b[col] = fmaf(wl[tap], x, y1b[col]))
 #pragma unroll
           for (int c = 0; c < P; ++c) y1b[c] = relu_lim(y1b[c], lim);
         } else {
@@ -948,20 +942,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 #pragma unroll
           for (int c = 0; c < P; ++c) dbl += dyb[c];
           if constexpr (V::SX) {
-#pragma unroll
-            for (int j = 0; j < V::NC4; ++j) {
-              const float* ap = auxr + 4 * chunk_of(j);
-#pragma unroll
-              for (int u = 0; u < Sh::S; ++u) {
-                const float4 a4 = *reinterpret_cast<const float4*>(ap + u * V::RL);
-                const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  const int m = 4 * j + e, cp = m / C2, k = m % C2, t = (k * Sh::S + u) * Sh::S + cp % Sh::S;
-                  dwl[t] = fmaf(dyb[cp / Sh::S], av[e], dwl[t]);
-                }
-              }
-            }
+            DMF_FOR_EACH_AUX_TAP(dwl[tap] = fmaf(dyb[col], x, dwl[tap]))
           } else {
 #pragma unroll
             for (int c = 0; c < P; ++c)
@@ -1112,6 +1093,17 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
       // column: nothing to overlap, and with all of y1 / y1u / y1d / gq live through the loop the allocator spills in the aux
       // phase): they keep the phase-by-phase form in the else branch.
       constexpr bool PIPE_BWD = !V::ROWDPP;
+      // spec_a's unit weight gradient, piece q of a window column x the column's dy: fp16 window x fp32 gradient with fp32
+      // accumulation (v_fma_mix_f32) into acc, or packed fp32 FMAs (d2 = dy twice) into gp.  (Macros: as one function for both
+      // loops the 16-row instances compile to other code — profiles/say_once.md.)
+#define DMF_WGRAD_PIECE_HALF(xv_, dy_, q_)                                                  \
+      acc[4 * q_] = fma_mix_lo(xv_.x, dy_, acc[4 * q_]);                                    \
+      acc[4 * q_ + 1] = fma_mix_hi(xv_.x, dy_, acc[4 * q_ + 1]);                            \
+      acc[4 * q_ + 2] = fma_mix_lo(xv_.y, dy_, acc[4 * q_ + 2]);                            \
+      acc[4 * q_ + 3] = fma_mix_hi(xv_.y, dy_, acc[4 * q_ + 3])
+#define DMF_WGRAD_PIECE_FLOAT(xv_, d2_, q_)                                                 \
+      gp[2 * q_] = pk_fma(d2_, (v2f){xv_.x, xv_.y}, gp[2 * q_]);                            \
+      gp[2 * q_ + 1] = pk_fma(d2_, (v2f){xv_.z, xv_.w}, gp[2 * q_ + 1])
       float acc[Cg], db1 = 0.f;
       if constexpr (PIPE_BWD) {
         float gu[P], gd[P];
@@ -1144,18 +1136,14 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
           if constexpr (HF) {   // fp16 window x fp32 gradient, fp32 accumulate (v_fma_mix_f32)
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
-              acc[4 * q] = fma_mix_lo(xc[q].x, dy, acc[4 * q]);
-              acc[4 * q + 1] = fma_mix_hi(xc[q].x, dy, acc[4 * q + 1]);
-              acc[4 * q + 2] = fma_mix_lo(xc[q].y, dy, acc[4 * q + 2]);
-              acc[4 * q + 3] = fma_mix_hi(xc[q].y, dy, acc[4 * q + 3]);
+              DMF_WGRAD_PIECE_HALF(xc[q], dy, q);
               if (c + 1 < P) request(c + 1, q);
             }
           } else {
             const v2f d2 = (v2f){dy, dy};
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
-              gp[2 * q] = pk_fma(d2, (v2f){xc[q].x, xc[q].y}, gp[2 * q]);
-              gp[2 * q + 1] = pk_fma(d2, (v2f){xc[q].z, xc[q].w}, gp[2 * q + 1]);
+              DMF_WGRAD_PIECE_FLOAT(xc[q], d2, q);
               if (c + 1 < P) request(c + 1, q);
             }
           }
@@ -1181,10 +1169,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
               const float2 xv = *reinterpret_cast<const float2*>(xr + c * V::CS + 2 * q);
-              acc[4 * q] = fma_mix_lo(xv.x, dya[c], acc[4 * q]);
-              acc[4 * q + 1] = fma_mix_hi(xv.x, dya[c], acc[4 * q + 1]);
-              acc[4 * q + 2] = fma_mix_lo(xv.y, dya[c], acc[4 * q + 2]);
-              acc[4 * q + 3] = fma_mix_hi(xv.y, dya[c], acc[4 * q + 3]);
+              DMF_WGRAD_PIECE_HALF(xv, dya[c], q);
             }
           }
         } else {
@@ -1199,8 +1184,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
               const float4 xv = *reinterpret_cast<const float4*>(xr + c * V::CS + 4 * q);
-              gp[2 * q] = pk_fma(d2, (v2f){xv.x, xv.y}, gp[2 * q]);
-              gp[2 * q + 1] = pk_fma(d2, (v2f){xv.z, xv.w}, gp[2 * q + 1]);
+              DMF_WGRAD_PIECE_FLOAT(xv, d2, q);
             }
           }
 #pragma unroll
@@ -1255,21 +1239,20 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
           __syncthreads();                               // (every patch: the aux image is complete, see the conv waves)
         } else if (it == 0) {
           wait_older_than_gather(std::integral_constant<int, 0>());
-          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // barrier X (first patch): staged tables complete
+          LDS_BARRIER();    // barrier X (first patch): staged tables complete
         }
         issue_gather(x, y, V::K0, V::NK);                // ... and the rest (nothing else to do until barrier 1)
         __builtin_amdgcn_sched_barrier(0);
-        const int bn = b + (int)gridDim.x < B ? b + (int)gridDim.x : b;
-        xn = ((cint*)a.in.xy)[2 * (size_t)(boff + bn)]; yn = ((cint*)a.in.xy)[2 * (size_t)(boff + bn) + 1];
+        const int bn = b + (int)gridDim.x < B ? b + (int)gridDim.x : b;      // the next patch's coordinates, see the conv waves
+        DMF_REQUEST_XY(bn)
       } else {
-        if (it == 0) { DMF_STAGE_WAIT(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }      // barrier X
+        if (it == 0) { DMF_STAGE_WAIT(); LDS_BARRIER(); }      // barrier X
         if constexpr (V::SX) __syncthreads();            // (the conv waves' aux image, see there)
       }
       int label = 0;
       float dlx = 0.f;
       if (MODE == MODE_TRAIN) {
-        label = ((cint*)a.labels)[boff + b];
-        label = label < 0 ? 0 : (label >= K ? K - 1 : label);
+        label = clamp_label(((cint*)a.labels)[boff + b], K);
       }
       // The loss scaler's value by a SCALAR load, here, where the wave waits for barrier W anyway.  Read as a vector load
       // inside the `lane < K` block of the softmax its result register stayed "pending" on the merged path, and every
@@ -1385,7 +1368,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
           const float se = wave_sum_dpp(e);
           const float ls = ls_arg * sv;
           dl = lane < K ? (e / se - (lane == label ? 1.f : 0.f)) * ls : 0.f;
-          const float lgt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lg), __builtin_amdgcn_readfirstlane(label)));
+          const float lgt = DMF_LANE_VALUE(lg, label);
           loss_b = (mx + __logf(se)) - lgt;
         } else {
           dl = dlx;
@@ -1421,11 +1404,10 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
         // evaluation with labels (dmf_forward_ce: the validation pass, mainsolver.py:62-76): the per-patch cross-entropy, by the
         // training kernel's own formula
         if (a.labels != nullptr && a.loss != nullptr) {
-          int label = ((cint*)a.labels)[boff + b];
-          label = label < 0 ? 0 : (label >= K ? K - 1 : label);
+          const int label = clamp_label(((cint*)a.labels)[boff + b], K);
           const float e = lane < K ? __expf(lg - mx) : 0.f;
           const float se = wave_sum_dpp(e);
-          const float lgt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lg), __builtin_amdgcn_readfirstlane(label)));
+          const float lgt = DMF_LANE_VALUE(lg, label);
           if (lane == 0) a.loss[b] = (mx + __logf(se)) - lgt;
         }
       }
@@ -1463,7 +1445,7 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
 // fc gradients of the reduce kernel as usual.
 template <class Sh>
 __global__ __launch_bounds__(256) void unit_backward_kernel(const UnitBwdArgs a) {
-  constexpr int F = Sh::F, F2 = Sh::F2, H = Sh::H, Cg = Sh::Cg;
+  constexpr int F2 = Sh::F2, H = Sh::H;
   constexpr int W1S = F2 + 1;                       // column reads of fc1.weight: odd stride
   constexpr int NE = (Sh::SLAB + 255) / 256;        // slab elements per thread
   __shared__ float sW1[H * W1S];
@@ -1477,19 +1459,7 @@ __global__ __launch_bounds__(256) void unit_backward_kernel(const UnitBwdArgs a)
   for (int i = tid; i < K * H; i += 256) sW2[(i / H) * (H + 1) + (i % H)] = a.theta[Sh::oFc2w + i];
   int ix[NE];                                       // dz index of this thread's slab elements
 #pragma unroll
-  for (int e = 0; e < NE; ++e) {
-    const int p = tid + 256 * e;
-    int v = F2;                                     // padding: multiplies with sDz[.][F2] = 0
-    if (p < Sh::oA1b) v = p / Cg;
-    else if (p < Sh::oA2w) v = p - Sh::oA1b;
-    else if (p < Sh::oA2b) v = (p - Sh::oA2w) / 9;
-    else if (p < Sh::oB1w) v = p - Sh::oA2b;
-    else if (p < Sh::oB1b) v = F + (p - Sh::oB1w) / Sh::TB;
-    else if (p < Sh::oB2w) v = F + p - Sh::oB1b;
-    else if (p < Sh::oB2b) v = F + (p - Sh::oB2w) / 9;
-    else if (p < Sh::NCONV) v = F + p - Sh::oB2b;
-    ix[e] = v;
-  }
+  for (int e = 0; e < NE; ++e) ix[e] = Sh::slab_channel(tid + 256 * e, F2);     // padding: multiplies with sDz[.][F2] = 0
   float acc[NE];
 #pragma unroll
   for (int e = 0; e < NE; ++e) acc[e] = 0.f;
@@ -1543,35 +1513,44 @@ __global__ __launch_bounds__(256) void unit_backward_kernel(const UnitBwdArgs a)
 }
 
 // ---------------------------------------------------------------------------------------- launch
+constexpr int LDS_MAX = 160 * 1024;      // LDS of one CU: a workgroup may ask for all of it (one workgroup per CU)
+
 template <class Sh, int MODE, int INMODE, bool HF>
 static hipError_t launch_v2_inst(const KArgs& a, int grid, int bytes, hipStream_t st) {
   static LdsAttrOnce once;
-  hipError_t e = once.set(reinterpret_cast<const void*>(&patch_v2_kernel<Sh, MODE, INMODE, HF>), 160 * 1024);
+  hipError_t e = once.set(reinterpret_cast<const void*>(&patch_v2_kernel<Sh, MODE, INMODE, HF>), LDS_MAX);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((patch_v2_kernel<Sh, MODE, INMODE, HF>), dim3(grid), dim3(V2<Sh>::NT), bytes, st, a.in.xy, a.in.cursor, a.in.B,
                      a.theta, a.pool, a.in.sceneA, a.in.sceneB, a.in.Wp, a);
   return hipGetLastError();
 }
 
-template <class Sh, bool HF>
-static hipError_t launch_v2(int mode, const KArgs& a, hipStream_t st) {
+// one workgroup per patch up to one per CU; the INMODE instance is picked by dmf_input.mode (1: gather from the scenes)
+template <class Sh, int MODE, bool HF>
+static hipError_t launch_v2_mode(const KArgs& a, int bytes, hipStream_t st) {
   const int grid = a.in.B < MAX_BLOCKS ? a.in.B : MAX_BLOCKS;
   if (grid <= 0) return hipSuccess;
+  if (bytes > LDS_MAX) return hipErrorInvalidValue;
+  return a.in.mode == 1 ? launch_v2_inst<Sh, MODE, 1, HF>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE, 0, HF>(a, grid, bytes, st);
+}
+
+template <class Sh, bool HF>
+static hipError_t launch_v2(int mode, const KArgs& a, hipStream_t st) {
   const int bytes = mode == MODE_FWD ? V2<Sh, false, HF>::lds_bytes(a.K) : V2<Sh, true, HF>::lds_bytes(a.K);
-  if (bytes > 160 * 1024) return hipErrorInvalidValue;
-  const bool gather = a.in.mode == 1;
   switch (mode) {
-    case MODE_FWD:
-      return gather ? launch_v2_inst<Sh, MODE_FWD, 1, HF>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_FWD, 0, HF>(a, grid, bytes, st);
-    case MODE_TRAIN:
-      return gather ? launch_v2_inst<Sh, MODE_TRAIN, 1, HF>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_TRAIN, 0, HF>(a, grid, bytes, st);
-    case MODE_BWD:
-      return gather ? launch_v2_inst<Sh, MODE_BWD, 1, HF>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_BWD, 0, HF>(a, grid, bytes, st);
-    case MODE_UNIT:
-      return gather ? launch_v2_inst<Sh, MODE_UNIT, 1, HF>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_UNIT, 0, HF>(a, grid, bytes, st);
-    default:
-      return hipErrorInvalidValue;
+    case MODE_FWD: return launch_v2_mode<Sh, MODE_FWD, HF>(a, bytes, st);
+    case MODE_TRAIN: return launch_v2_mode<Sh, MODE_TRAIN, HF>(a, bytes, st);
+    case MODE_BWD: return launch_v2_mode<Sh, MODE_BWD, HF>(a, bytes, st);
+    case MODE_UNIT: return launch_v2_mode<Sh, MODE_UNIT, HF>(a, bytes, st);
+    default: return a.in.B <= 0 ? hipSuccess : hipErrorInvalidValue;
   }
+}
+
+template <class Sh>
+static hipError_t launch_v2_attn(int mode, const KArgs& a, hipStream_t st) {
+  if (mode == MODE_TOKENS)      // + the bf16 token staging
+    return launch_v2_mode<Sh, MODE_TOKENS, false>(a, (V2<Sh, false, false>::FIXED + 2 * 128 * 72 / 2) * 4, st);
+  return launch_v2_mode<Sh, MODE_DENSE, false>(a, V2<Sh, true, false>::lds_bytes(a.K), st);
 }
 
 // Compiled instances: ONE table.  X(C, C2, P, S, F, G, H) — every row gets forward / train / backward-from-dlogits /
@@ -1607,6 +1586,11 @@ static hipError_t launch_v2(int mode, const KArgs& a, hipStream_t st) {
   X(224, 3, 11, 1, 32, 8, 64)                                                                                 \
   X(8, 1, 5, 1, 40, 2, 64)                                                                                    \
   X(4, 1, 16, 1, 40, 1, 64)
+// One table row as a statement: the site's ROW with the row's shape as Sh
+#define SHAPE_ROW(C, C2, P, S, F, G, H) { using Sh = Shape<C, C2, P, S, F, G, H>; ROW }
+#define STR2(x) #x
+#define STR(x) STR2(x)
+#define SHAPE_NAME(C, C2, P, S, F, G, H) " " STR(C) "/" STR(C2) "/" STR(P) "/" STR(S) "/" STR(F) "/" STR(G)
 
 template <class Sh>
 static bool v2_matches(const dmf_shape& s) {
@@ -1617,98 +1601,70 @@ static bool v2_matches(const dmf_shape& s) {
 template <class Sh, bool HF = false>
 static bool v2_fits(const dmf_shape& s) {
   static_assert(V2<Sh, true, HF>::OK, "shape outside the v2 kernel's geometry");
-  return v2_matches<Sh>(s) && V2<Sh, true, HF>::lds_bytes(s.K) <= 160 * 1024;
-}
-
-template <class Sh>
-static hipError_t launch_v2_attn(int mode, const KArgs& a, hipStream_t st) {
-  const int grid = a.in.B < MAX_BLOCKS ? a.in.B : MAX_BLOCKS;
-  if (grid <= 0) return hipSuccess;
-  const bool gather = a.in.mode == 1;
-  if (mode == MODE_TOKENS) {
-    const int bytes = (V2<Sh, false, false>::FIXED + 2 * 128 * 72 / 2) * 4;      // + the bf16 token staging
-    if (bytes > 160 * 1024) return hipErrorInvalidValue;
-    return gather ? launch_v2_inst<Sh, MODE_TOKENS, 1, false>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_TOKENS, 0, false>(a, grid, bytes, st);
-  }
-  const int bytes = V2<Sh, true, false>::lds_bytes(a.K);
-  if (bytes > 160 * 1024) return hipErrorInvalidValue;
-  return gather ? launch_v2_inst<Sh, MODE_DENSE, 1, false>(a, grid, bytes, st) : launch_v2_inst<Sh, MODE_DENSE, 0, false>(a, grid, bytes, st);
+  return v2_matches<Sh>(s) && V2<Sh, true, HF>::lds_bytes(s.K) <= LDS_MAX;
 }
 
 int patch_v2_supported(const dmf_shape& s, int mode, int half) {
   if (mode == MODE_TOKENS || mode == MODE_DENSE) {       // launches of the attention network (shape->attention is set)
     if (half || s.K < 1 || s.K > KMAX) return 0;
-#define X(C, C2, P, S, F, G, H) if (v2_fits<Shape<C, C2, P, S, F, G, H>>(s)) return 1;
-    DMF_V2_ATTN_SHAPES(X)
-#undef X
+#define ROW if (v2_fits<Sh>(s)) return 1;
+    DMF_V2_ATTN_SHAPES(SHAPE_ROW)
+#undef ROW
     return 0;
   }
   if (mode != MODE_FWD && mode != MODE_TRAIN && mode != MODE_BWD && mode != MODE_UNIT) return 0;
   if (s.K < 1 || s.K > KMAX || s.attention) return 0;
   if (half) {
-#define X(C, C2, P, S, F, G, H) if (v2_fits<Shape<C, C2, P, S, F, G, H>, true>(s)) return 1;
-    DMF_V2_HALF_SHAPES(X)
-#undef X
+#define ROW if (v2_fits<Sh, true>(s)) return 1;
+    DMF_V2_HALF_SHAPES(SHAPE_ROW)
+#undef ROW
     return 0;
   }
-#define X(C, C2, P, S, F, G, H) if (v2_fits<Shape<C, C2, P, S, F, G, H>>(s)) return 1;
-  DMF_V2_SHAPES(X)
-#undef X
+#define ROW if (v2_fits<Sh>(s)) return 1;
+  DMF_V2_SHAPES(SHAPE_ROW)
+#undef ROW
   return 0;
 }
 
 // "C/C2/P/S/F/G" of every row, for error messages
-const char* patch_v2_shape_list() {
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define X(C, C2, P, S, F, G, H) " " STR(C) "/" STR(C2) "/" STR(P) "/" STR(S) "/" STR(F) "/" STR(G)
-  return DMF_V2_SHAPES(X);
-#undef X
-#undef STR
-#undef STR2
-}
+const char* patch_v2_shape_list() { return DMF_V2_SHAPES(SHAPE_NAME); }
+const char* patch_v2_half_shape_list() { return DMF_V2_HALF_SHAPES(SHAPE_NAME); }
 
 hipError_t patch_v2_dispatch(const dmf_shape& s, int mode, const KArgs& a, hipStream_t st) {
   if (mode == MODE_TOKENS || mode == MODE_DENSE) {
-#define X(C, C2, P, S, F, G, H) if (v2_matches<Shape<C, C2, P, S, F, G, H>>(s)) return launch_v2_attn<Shape<C, C2, P, S, F, G, H>>(mode, a, st);
-    DMF_V2_ATTN_SHAPES(X)
-#undef X
+#define ROW if (v2_matches<Sh>(s)) return launch_v2_attn<Sh>(mode, a, st);
+    DMF_V2_ATTN_SHAPES(SHAPE_ROW)
+#undef ROW
     return hipErrorInvalidValue;
   }
   if (a.in.half) {
-#define X(C, C2, P, S, F, G, H) if (v2_matches<Shape<C, C2, P, S, F, G, H>>(s)) return launch_v2<Shape<C, C2, P, S, F, G, H>, true>(mode, a, st);
-    DMF_V2_HALF_SHAPES(X)
-#undef X
+#define ROW if (v2_matches<Sh>(s)) return launch_v2<Sh, true>(mode, a, st);
+    DMF_V2_HALF_SHAPES(SHAPE_ROW)
+#undef ROW
     return hipErrorInvalidValue;
   }
-#define X(C, C2, P, S, F, G, H) if (v2_matches<Shape<C, C2, P, S, F, G, H>>(s)) return launch_v2<Shape<C, C2, P, S, F, G, H>, false>(mode, a, st);
-  DMF_V2_SHAPES(X)
-#undef X
+#define ROW if (v2_matches<Sh>(s)) return launch_v2<Sh, false>(mode, a, st);
+  DMF_V2_SHAPES(SHAPE_ROW)
+#undef ROW
   return hipErrorInvalidValue;
-}
-
-const char* patch_v2_half_shape_list() {
-#define STR2(x) #x
-#define STR(x) STR2(x)
-#define X(C, C2, P, S, F, G, H) " " STR(C) "/" STR(C2) "/" STR(P) "/" STR(S) "/" STR(F) "/" STR(G)
-  return DMF_V2_HALF_SHAPES(X);
-#undef X
-#undef STR
-#undef STR2
 }
 
 hipError_t patch_v2_unit_backward(const dmf_shape& s, const UnitBwdArgs& a, hipStream_t st) {
   const int grid = a.B < MAX_BLOCKS ? a.B : MAX_BLOCKS;
   if (grid <= 0) return hipSuccess;
-#define X(C, C2, P, S, F, G, H)                                                                              \
-  if (v2_matches<Shape<C, C2, P, S, F, G, H>>(s)) {                                                          \
-    hipLaunchKernelGGL((unit_backward_kernel<Shape<C, C2, P, S, F, G, H>>), dim3(grid), dim3(256), 0, st, a); \
-    return hipGetLastError();                                                                                \
+#define ROW                                                                              \
+  if (v2_matches<Sh>(s)) {                                                               \
+    hipLaunchKernelGGL((unit_backward_kernel<Sh>), dim3(grid), dim3(256), 0, st, a);     \
+    return hipGetLastError();                                                            \
   }
-  DMF_V2_SHAPES(X)
-#undef X
+  DMF_V2_SHAPES(SHAPE_ROW)
+#undef ROW
   return hipErrorInvalidValue;
 }
+#undef SHAPE_NAME
+#undef STR
+#undef STR2
+#undef SHAPE_ROW
 
 #ifdef DMF_STAMPS
 hipError_t set_v2_stamps(unsigned long long* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_v2stamps), &p, sizeof(p)); }

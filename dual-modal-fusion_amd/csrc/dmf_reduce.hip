@@ -301,17 +301,12 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   }
   __builtin_amdgcn_sched_barrier(0);                 // (nothing that waits for these loads may move up here)
   RSTAMP(2);
-#ifndef DMF_REDUCE_TAIL_EARLY
-#define DMF_REDUCE_TAIL_EARLY 1
-#endif
   // the tail's scalars (exchange on / off, scaler, gradient pointer, ADAM's constants) live in the argument struct: read where
   // they are used they are four DEPENDENT kernarg fetches behind the barrier; fetched here they arrive under the gradient loads
   const int world = a.x.world;
   ReduceTail tl = {a.scaler, a.grad, a.lr, a.b1, a.b2, a.eps};
   int hp_st = 0;
-#if DMF_REDUCE_TAIL_EARLY
   if (!SCHED) asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.lr), "s"(tl.b1), "s"(tl.b2), "s"(tl.eps));
-#endif
   if constexpr (SCHED) {
     // the step's row (uniform addresses: step count and row index -> 16 bytes of the table), requested here, behind the first
     // batch of gradient and state loads; wave 4 and the tail wait for it where they use it

@@ -33,6 +33,19 @@ struct Shape {
   static constexpr int oFc1b = oFc1w + H * F2;
   static constexpr int oFc2w = oFc1b + H;   // [K, H], K is a run-time value
   static constexpr int SLAB = (NCONV + 31) & ~31;   // slab row pitch (floats)
+  // feature channel (index into the 2F pooled scalars: primary branch f, aux branch F + f) that conv parameter p belongs
+  // to; `pad` for the row padding beyond NCONV
+  static constexpr int slab_channel(int p, int pad) {
+    if (p < oA1b) return p / Cg;
+    if (p < oA2w) return p - oA1b;
+    if (p < oA2b) return (p - oA2w) / 9;
+    if (p < oB1w) return p - oA2b;
+    if (p < oB1b) return F + (p - oB1w) / TB;
+    if (p < oB2w) return F + p - oB1b;
+    if (p < oB2b) return F + (p - oB2w) / 9;
+    if (p < NCONV) return F + p - oB2b;
+    return pad;
+  }
 
   static_assert(C % G == 0 && F % G == 0, "groups must divide C and F");
   static_assert(Cg % 4 == 0, "bands per group: whole 16-byte chunks");

@@ -23,7 +23,8 @@ Guards, asserted by `case` on the oracle alone (a case that misses one gets anot
   4. gradient signal   every parameter tensor has max |grad| >= 1e-4: 10 x the absolute term of the gradient tolerance.
                        Two tensors cannot: the query and key projections of the attention net reach the loss only through a
                        softmax that is nearly flat on this recipe, max |grad| 9e-6 .. 1e-4 over 22 seeds and four batches; they
-                       keep the floor tests/test_gpu_parity.py::test_attention_train_grads gives them, 1e-6.
+                       keep the floor tests/test_gpu_parity.py::test_attention_train_grads gives them, 1e-6.  tests/attn_cases.py
+                       is where those two tensors are held to more than a floor, on a recipe with sharp heads.
   5. open or shut      no fc1 pre-activation lies within 1e-5 of zero, the absolute tolerance of h: a kernel whose h is within
                        tolerance may open a ReLU gate the oracle has shut, and dh of that unit, 1 / B of a whole gradient term
                        (5e-5 at B = 513), then goes with it.  Found on the GPU: hsi7 and hsi224p9 at 513 with seed 5 hold one

@@ -497,7 +497,8 @@ def test_attention_forward(name, B):
 def test_attention_train_grads(name, B):
     """Fused fwd + CE + bwd of the attention network (token kernel, attention fwd+bwd kernel, dense conv backward,
     gradient reduce) against torch autograd through the oracle (bf16 forward operands, straight-through roundings).
-    Tolerance: logits as in test_attention_forward; gradients 2e-5 absolute + 2e-3 relative.  Looser than the fp32
+    Tolerance: logits as in test_attention_forward; gradients 2e-5 absolute + 2e-3 relative, the absolute term of the four
+    attention tensors min(2e-5, 1e-3 of the tensor's maximum).  Looser than the fp32
     network's 1e-4 because a bf16 operand on a rounding boundary may round the other way between the two forward
     passes (accumulation order), which moves the forward value by one bf16 ulp of one operand."""
     from dmf import lib
@@ -527,7 +528,10 @@ def test_attention_train_grads(name, B):
         got = grad[off[i]:off[i] + p.numel()].view(p.shape).cpu()
         err = (got - want).abs().max().item()
         worst = max(worst, err / (want.abs().max().item() + 1e-12))
-        assert_close(got, want, 2e-5, 2e-3, 'grad %s[%s,B=%d]' % (k, name, B))
+        # attention tensors: the absolute term is at most 1e-3 of the tensor's maximum (tests/attn_cases.py), so that attn_wq and
+        # attn_wk, 9e-6 .. 1e-4 on this flat-softmax recipe, are held to more than a floor
+        atol = min(2e-5, 1e-3 * want.abs().max().item()) if k.startswith('attn_') else 2e-5
+        assert_close(got, want, atol, 2e-3, 'grad %s[%s,B=%d]' % (k, name, B))
         if k.startswith('attn_'):
             assert want.abs().max().item() > 1e-6, 'attention gradient vanishes: the test would prove nothing'
     print('attention train %s B=%d: worst relative-to-max gradient error %.2e' % (name, B, worst))

@@ -33,6 +33,8 @@
 //   aux      lift_b + spat_b forward AND backward for a UNIT upstream gradient, under the gather (tables and aux rows through
 //            LDS reads the compiler cannot see; see hidden_read)
 //   barrier W  window complete
+//   head tables  first patch, head wave: its fc1 row into registers, then the fc2 image and the row-block fc1 image of the dz
+//            phase by LDS-DMA straight from theta — issued and not waited for (V2::W1B; profiles/spec_group.md)
 //   primary  spec_a (packed FMAs, weights in registers, x from the group's LDS slice), spat_a forward
 //   barrier 1  pooled features complete -> the head wave runs fc1 / fc2 / softmax-CE / dh while the conv waves do spat_a's
 //            unit backward and form the unit spec_a weight gradient from the still-resident window
@@ -172,8 +174,17 @@ struct V2 {
   static constexpr int oX = 0;
   static constexpr int oTh = oX + XF;                 // conv part of theta, parameter order
   static constexpr int oPool = oTh + Sh::SLAB;        // pooling profile [P][RSP]
-  static constexpr int oW1T = oPool + P * RSP;        // fc1.weight transposed [2F][H]  (training: dz on the conv waves)
-  static constexpr int oZ = oW1T + (TR ? F2 * H : 0); // pooled features [ZS]; eval: two buffers (it runs ahead of the head)
+  // fc1.weight for the dz phase (training: dz on all waves), [H / 4 row blocks][W1B]: block jc holds, for feature i, the 16
+  // bytes fc1.weight[4 jc .. 4 jc + 3][i] — what a dz lane multiplies with four consecutive dh — in 16-byte slot
+  // w1_slot(i, jc).  It is staged by 4-byte LDS-DMA whose 64 lanes fetch 16 consecutive floats of 4 rows of fc1.weight: a few
+  // cache lines per piece (the row-per-feature image [2F][H] of the same size, which it replaces, needs 64 lines for every
+  // 256 bytes: profiles/spec_group.md).  The slots of a block are rotated by 4 (jc / 4): the 16 lanes of a ds_read_b128 service
+  // group in the dz phase read 4 features x 4 blocks that lie 4 blocks = a multiple of 256 bytes apart, and the rotation
+  // puts them on 16 different bank quads.
+  static constexpr int W1B = 4 * F2;
+  static constexpr int w1_slot(int i, int jc) { return (i + 4 * (jc >> 2)) % F2; }
+  static constexpr int oW1T = oPool + P * RSP;
+  static constexpr int oZ = oW1T + (TR ? (H / 4) * W1B : 0);   // pooled features [ZS]; eval: two buffers (it runs ahead of the head)
   static constexpr int NZB = TR ? 1 : 2;
   static constexpr int oZP = oZ + NZB * ZS;           // per conv wave: the quad partials of its channels' pooled features [NB][ZPW]
   static constexpr int ZPW = ((2 * CPW * NQ + 15) / 16) * 16;
@@ -285,12 +296,6 @@ __device__ __forceinline__ float lane_below(float v) {
   if constexpr (ROWDPP) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xF, 0xF, true));   // row_shl:1
   else return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));                    // wave_shl:1
 }
-// Where 16-byte chunk c (of 16) of row i of the transposed fc1.weight image [2F][H = 64] sits inside the row, in floats: the
-// chunks are rotated by i mod 4.  The dz phase reads the image with 4 lanes per row, 64 bytes apart, and rows are 256 bytes
-// apart: unrotated, the 16 lanes of a ds_read_b128 service group (4 rows x 4 lanes) share 4 of the 16 chunk positions — a
-// 4-way bank conflict on every one of its 4 reads, 5 waves at once, right behind barrier 2; rotated, they take 16 different
-// ones.  (i mod 4 is the vector component for the head wave, which writes the image: four per-lane offsets in all.)
-__device__ __forceinline__ int w1t_chunk(int i, int c) { return ((c + (i & 3)) & 15) << 2; }
 __device__ __forceinline__ float quad_sum(float v) {     // over the 4 lanes of a quad, result in each of them
   v = DMF_DPP_ADD(v, 0xB1);     // quad_perm [1,0,3,2]
   v = DMF_DPP_ADD(v, 0x4E);     // quad_perm [2,3,0,1]
@@ -682,11 +687,13 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
     float* sDz = smem + V::oDz;
     for (int t = tid_; t < 4 * F2; t += V::NT) {         // (whole quads: NT and 4 F2 are multiples of 4)
       const int i = t >> 2, m = t & 3;
+      int sl = i + 4 * m;                                // V::w1_slot(i, 4 m + q), the same for the lane's four blocks
+      sl -= sl >= F2 ? F2 : 0;
       float d = 0.f;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 dhv = *reinterpret_cast<const float4*>(sDh + 16 * m + 4 * q);
-        const float4 wv = *reinterpret_cast<const float4*>(smem + V::oW1T + i * H + w1t_chunk(i, 4 * m + q));
+        const float4 wv = *reinterpret_cast<const float4*>(smem + V::oW1T + (4 * m + q) * V::W1B + 4 * sl);      // fc1.weight[16 m + 4 q ..][i]
         d = fmaf(wv.x, dhv.x, fmaf(wv.y, dhv.y, fmaf(wv.z, dhv.z, fmaf(wv.w, dhv.w, d))));
       }
       d = quad_sum(d);
@@ -1281,28 +1288,59 @@ __global__ __launch_bounds__(V2<Sh>::NT) void patch_v2_kernel(const int32_t* xy_
         for (int q = 0; q < F2 / 4; ++q) w1r[q] = *reinterpret_cast<const float4*>(th + Sh::oFc1w + lane * F2 + 4 * q);
         bh = th[Sh::oFc1b + lane];
         bk = lane < K ? th[Sh::oFc2w + K * H + lane] : 0.f;
-        for (int i0 = 0; i0 < K4 / 4; i0 += 4) {
-          float4 v[4];
+        // The two LDS images come by LDS-DMA straight from theta as it lies, behind the register loads above (fc1 needs those
+        // first): no register round trip and no LDS store on this wave, whose vector and LDS instructions at priority 3 come
+        // out of the slots of its SIMD's two conv waves.  Nothing waits here: this wave's first LDS read behind barrier 1
+        // is ordered behind its outstanding DMA by the compiler, and the other waves read the fc1 image behind barrier 2.
+        // The zero rows K .. K4 - 1 of the fc2 image are plain stores, in FRONT of the first piece (behind one they would wait
+        // for it): dh multiplies them with dl = 0, so they have to be zero.
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int idx = (i0 + u) * 64 + lane, k = idx >> 4;
-            v[u] = (i0 + u < K4 / 4 && k < K) ? *reinterpret_cast<const float4*>(th + Sh::oFc2w + 4 * idx) : make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int idx = (i0 + u) * 64 + lane, k = idx >> 4, c4 = idx & 15;
-            if (i0 + u < K4 / 4) *reinterpret_cast<float4*>(sW2 + k * V::W2S + 4 * c4) = v[u];
+        for (int u = 0; u < 3; ++u)
+          if (K + u < K4) sW2[(K + u) * V::W2S + lane] = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef __attribute__((address_space(3))) void* lds_ptr;
+        int l_ = lane;
+        OPAQUE(l_);
+        {   // fc2.weight [K][H] -> [K4][W2S]: 16-byte piece p of the image holds its chunks 64 p .. 64 p + 63, chunk n = row
+            // k = n / CPR, 16-byte column c4 = n % CPR; the padding column and whatever lies behind row K - 1 are masked lanes.
+            // (k, c4) are carried from piece to piece: 64 chunks further on is DK rows and DC columns.
+          constexpr int CPR = V::W2S / 4, DK = 64 / CPR, DC = 64 % CPR;
+          const __amdgpu_buffer_rsrc_t rsrc = DMF_DMA_RSRC(th + Sh::oFc2w);
+          int k = l_ / CPR, c4 = l_ - k * CPR;
+          unsigned dst = lds_addr(sW2);
+          for (int p = 0; p * 64 < K * CPR; ++p) {
+            if (k < K && c4 < H / 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)dst, 16, (k * H + 4 * c4) * 4, 0, 0, 0);
+            c4 += DC; k += DK;
+            if (c4 >= CPR) { c4 -= CPR; k += 1; }
+            dst += 1024;
           }
         }
         if constexpr (TR && !UNIT) {
+          // fc1.weight [H][2F] -> row blocks [H / 4][W1B] (see V2::W1B), 4-byte pieces: piece (jc, t) is floats 64 t .. 64 t + 63
+          // of block jc, i.e. slots 16 t .. 16 t + 15, and the lane at float l of the piece fetches fc1.weight[4 jc + (l & 3)][i]
+          // for the feature i whose slot that is: i = 16 t + (l >> 2) - 4 (jc / 4), + 2F where that is negative — which
+          // happens in a block's first piece only.  So: one per-lane offset for all later pieces (the piece's own part goes
+          // into its scalar offset) and one per jc / 4 for the first pieces; slots behind 2F - 1 are masked lanes.  (The
+          // image's LDS address is formed here, per piece: hoisted out of the patch loop, the addresses of all pieces are
+          // spilled to vector lanes and every piece fetches its own with a vector instruction.)
+          static_assert(H == 64 && F2 >= 16, "four groups of four row blocks; only a block's first piece wraps");
+          constexpr int NPB = (4 * F2 + 63) / 64;          // pieces per row block
+          const __amdgpu_buffer_rsrc_t rsrc = DMF_DMA_RSRC(th + Sh::oFc1w);
+          const int vo = ((l_ & 3) * F2 + (l_ >> 2)) * 4;
+          int vo0[4];
 #pragma unroll
-          for (int q = 0; q < F2 / 4; ++q) {
-            sW1T[(4 * q) * H + w1t_chunk(4 * q, lane >> 2) + (lane & 3)] = w1r[q].x;
-            sW1T[(4 * q + 1) * H + w1t_chunk(4 * q + 1, lane >> 2) + (lane & 3)] = w1r[q].y;
-            sW1T[(4 * q + 2) * H + w1t_chunk(4 * q + 2, lane >> 2) + (lane & 3)] = w1r[q].z;
-            sW1T[(4 * q + 3) * H + w1t_chunk(4 * q + 3, lane >> 2) + (lane & 3)] = w1r[q].w;
-          }
+          for (int m = 0; m < 4; ++m) vo0[m] = vo + ((l_ >> 2) < 4 * m ? F2 - 4 * m : -4 * m) * 4;
+          unsigned dst = lds_addr(sW1T);
+          asm volatile("" : "+s"(dst));
+#pragma unroll
+          for (int jc = 0; jc < H / 4; ++jc)
+#pragma unroll
+            for (int t = 0; t < NPB; ++t)
+              if (16 * t + 16 <= F2 || 16 * t + (l_ >> 2) < F2)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst + (jc * V::W1B + 64 * t) * 4), 4, t == 0 ? vo0[jc >> 2] : vo,
+                                                         (4 * jc * F2 + (t == 0 ? 0 : 16 * t - 4 * (jc >> 2))) * 4, 0, 0);
         }
+#endif
       }
       LDS_BARRIER();                                     // barrier 1: pooled features complete
       VSTAMP(5);

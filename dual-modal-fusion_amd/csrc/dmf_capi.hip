@@ -126,6 +126,20 @@ static int fill_sched(const char* entry, const dmf_hp_schedule* sc, HpSched& hp)
   return 0;
 }
 
+// the averaged copy of an *_avg entry point (`entry`) -> the kernels' words; refused: a NULL struct or vector, an unknown
+// kind, an EMA weight outside (0, 1], start < 1, reserved != 0, and avg [n] overlapping theta [n]
+static int fill_avg(const char* entry, const dmf_weight_avg* w, const float* theta, int64_t n, AvgArgs& av) {
+  if (w == nullptr || w->avg == nullptr) return fail("%s: null dmf_weight_avg or avg", entry);
+  if (w->kind != DMF_AVG_EMA && w->kind != DMF_AVG_MEAN) return fail("%s: unknown averaging kind (DMF_AVG_EMA, DMF_AVG_MEAN)", entry);
+  if (w->kind == DMF_AVG_EMA && !(isfinite(w->weight) && w->weight > 0.f && w->weight <= 1.f))
+    return fail("%s: the EMA weight (1 - decay) must lie in (0, 1]", entry);
+  if (w->start < 1) return fail("%s: the first averaged step must be >= 1", entry);
+  if (w->reserved != 0) return fail("%s: dmf_weight_avg.reserved must be 0", entry);
+  if (theta != nullptr && n > 0 && w->avg < theta + n && theta < w->avg + n) return fail("%s: avg overlaps theta", entry);
+  av.avg = w->avg; av.kind = w->kind; av.w = w->weight; av.start = w->start;
+  return 0;
+}
+
 extern "C" {
 
 int32_t dmf_version(void) { return DMF_VERSION; }
@@ -390,6 +404,7 @@ struct ReduceOpts {
   float grad_scale = 1.f;
   float* scaler = nullptr;                     // loss-scaler state: unscale and check the sum
   const dmf_hp_schedule* sched = nullptr;      // the fused Adam takes lr, b1, b2 from its row (the *_sched entry points)
+  const dmf_weight_avg* avg = nullptr;         // the fused Adam keeps the averaged copy (the *_avg entry points)
 };
 
 static int run_reduce(const dmf_shape* s, int32_t B, const void* workspace, const ReduceOpts& o, void* stream) {
@@ -420,9 +435,14 @@ static int run_reduce(const dmf_shape* s, int32_t B, const void* workspace, cons
   }
   HpSched hp{};
   if (o.sched != nullptr && fill_sched("grad_reduce_adam_sched", o.sched, hp)) return 1;
+  AvgArgs av{};
+  if (o.avg != nullptr) {
+    if (o.theta == nullptr || o.comm != nullptr) return fail("%s", "grad_reduce_adam_avg: needs theta, and has no xgmi form");
+    if (fill_avg("grad_reduce_adam_avg", o.avg, o.theta, L.n_params, av)) return 1;
+  }
   const char* refusal = nullptr;
   const hipError_t e = launch_grad_reduce(a, L, B, ws, static_cast<hipStream_t>(stream), &refusal, o.sched != nullptr ? &hp : nullptr,
-                                          o.step);
+                                          o.step, o.avg != nullptr ? &av : nullptr);
   return refusal != nullptr ? fail("%s", refusal) : check(e, "grad_reduce launch");
 }
 
@@ -475,6 +495,18 @@ int32_t dmf_grad_reduce_adam_sched(const dmf_shape* s, int32_t B, const void* wo
   return run_reduce(s, B, workspace, o, stream);
 }
 
+int32_t dmf_grad_reduce_adam_avg(const dmf_shape* s, int32_t B, const void* workspace, float* theta, float* m, float* v,
+                                 float* grad, float lr, float beta1, float beta2, float eps, int32_t step,
+                                 const int32_t* adam_step_dev, int32_t* cursor_dev, const float* loss, float* loss_hist,
+                                 const dmf_hp_schedule* sched, const dmf_weight_avg* avg, void* stream) {
+  if (theta == nullptr) return fail("%s", "null theta");
+  if (avg == nullptr) return fail("%s", "grad_reduce_adam_avg: null dmf_weight_avg or avg");
+  ReduceOpts o = sched != nullptr ? adam_opts(theta, m, v, 0.f, 0.f, 0.f, eps, step, adam_step_dev, cursor_dev, loss, loss_hist)
+                                  : adam_opts(theta, m, v, lr, beta1, beta2, eps, step, adam_step_dev, cursor_dev, loss, loss_hist);
+  o.grad = grad; o.sched = sched; o.avg = avg;
+  return run_reduce(s, B, workspace, o, stream);
+}
+
 // dmf_train_plan_steps and its schedule form: `adam` holds the launch arguments or the schedule
 static int plan_steps(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w, const int32_t* labels,
                       float loss_scale, float* logits, float* loss, void* workspace, const ReduceOpts& adam, int32_t n_steps,
@@ -513,6 +545,20 @@ int32_t dmf_train_plan_steps_sched(const dmf_shape* s, const dmf_input* in, floa
   if (fill_sched("dmf_train_plan_steps_sched", sched, hp)) return 1;
   ReduceOpts adam = adam_opts(theta, m, v, 0.f, 0.f, 0.f, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist);
   adam.sched = sched;
+  return plan_steps(s, in, theta, pool_w, labels, loss_scale, logits, loss, workspace, adam, n_steps, stream);
+}
+
+int32_t dmf_train_plan_steps_avg(const dmf_shape* s, const dmf_input* in, float* theta, const float* pool_w, const int32_t* labels,
+                                 float loss_scale, float* logits, float* loss, void* workspace, float* m, float* v, float lr,
+                                 float beta1, float beta2, float eps, int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist,
+                                 const dmf_hp_schedule* sched, const dmf_weight_avg* avg, int32_t n_steps, void* stream) {
+  HpSched hp{};
+  AvgArgs av{};
+  if (sched != nullptr && fill_sched("dmf_train_plan_steps_avg", sched, hp)) return 1;
+  if (fill_avg("dmf_train_plan_steps_avg", avg, theta, s != nullptr ? layout_of(*s).n_params : 0, av)) return 1;   // (before any launch)
+  ReduceOpts adam = sched != nullptr ? adam_opts(theta, m, v, 0.f, 0.f, 0.f, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist)
+                                     : adam_opts(theta, m, v, lr, beta1, beta2, eps, 0, adam_step_dev, cursor_dev, loss, loss_hist);
+  adam.sched = sched; adam.avg = avg;
   return plan_steps(s, in, theta, pool_w, labels, loss_scale, logits, loss, workspace, adam, n_steps, stream);
 }
 
@@ -620,7 +666,7 @@ static int optim_step(float* theta, const float* grad, float* m, float* v, int64
                       float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
                       float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
                       float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist,
-                      const dmf_hp_schedule* sched, void* stream) {
+                      const dmf_hp_schedule* sched, void* stream, const dmf_weight_avg* avg = nullptr, bool averaging = false) {
   if (theta == nullptr || grad == nullptr) return fail("%s", "optim_step: null theta or grad");
   if (kind != DMF_OPT_ADAM && kind != DMF_OPT_ADAMW && kind != DMF_OPT_SGD && kind != DMF_OPT_RMSPROP)
     return fail("%s", "optim_step: unknown kind (DMF_OPT_ADAM, _ADAMW, _SGD, _RMSPROP)");
@@ -640,12 +686,15 @@ static int optim_step(float* theta, const float* grad, float* m, float* v, int64
     if (growth_interval < 1 || !(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f))
       return fail("%s", "optim_step: bad growth_interval / factors");
   }
+  AvgArgs av{};
+  if (averaging && fill_avg("optim_step_avg", avg, theta, n, av)) return 1;
   if (n == 0) return 0;
   OptimArgs a{theta, grad, m, v, n, kind, lr, beta1, beta2, eps, momentum, alpha, weight_decay, max_norm, grad_scale,
               step, step_dev, cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled != 0, norm_hist};
   HpSched hp{};
   if (sched != nullptr && fill_sched("optim_step_sched", sched, hp)) return 1;
-  return check(launch_optim_step(a, static_cast<hipStream_t>(stream), sched != nullptr ? &hp : nullptr), "optim_step launch");
+  return check(launch_optim_step(a, static_cast<hipStream_t>(stream), sched != nullptr ? &hp : nullptr, averaging ? &av : nullptr),
+               "optim_step launch");
 }
 
 int32_t dmf_optim_step(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
@@ -665,6 +714,32 @@ int32_t dmf_optim_step_sched(float* theta, const float* grad, float* m, float* v
   if (fill_sched("optim_step_sched", sched, hp)) return 1;
   return optim_step(theta, grad, m, v, n, kind, 0.f, 0.f, 0.f, eps, 0.f, alpha, weight_decay, max_norm, step, grad_scale, step_dev,
                     cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled, norm_hist, sched, stream);
+}
+
+int32_t dmf_optim_step_avg(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind, float lr, float beta1,
+                           float beta2, float eps, float momentum, float alpha, float weight_decay, float max_norm, int32_t step,
+                           float grad_scale, int32_t* step_dev, int32_t* cursor_dev, float* scaler_state, float growth_factor,
+                           float backoff_factor, int32_t growth_interval, int32_t unscaled, float* norm_hist,
+                           const dmf_hp_schedule* sched, const dmf_weight_avg* avg, void* stream) {
+  HpSched hp{};
+  if (sched != nullptr) {
+    if (fill_sched("optim_step_avg", sched, hp)) return 1;
+    lr = beta1 = beta2 = momentum = 0.f;
+  }
+  return optim_step(theta, grad, m, v, n, kind, lr, beta1, beta2, eps, momentum, alpha, weight_decay, max_norm, step, grad_scale,
+                    step_dev, cursor_dev, scaler_state, growth_factor, backoff_factor, growth_interval, unscaled, norm_hist, sched,
+                    stream, avg, true);
+}
+
+int32_t dmf_weight_average(const dmf_weight_avg* avg, const float* theta, int64_t n, int32_t step, const int32_t* step_dev,
+                           void* stream) {
+  if (theta == nullptr) return fail("%s", "weight_average: null theta");
+  if (n < 0) return fail("%s", "weight_average: negative n");
+  if (step < 1 && step_dev == nullptr) return fail("%s", "weight_average: step must be positive (or step_dev given)");
+  AvgArgs av{};
+  if (fill_avg("weight_average", avg, theta, n, av)) return 1;
+  if (n == 0) return 0;
+  return check(launch_weight_average(av, theta, n, step, step_dev, static_cast<hipStream_t>(stream)), "weight_average launch");
 }
 
 int32_t dmf_qua_loss_ranks(const float* gathered, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K,

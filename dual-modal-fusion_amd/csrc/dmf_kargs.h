@@ -110,6 +110,10 @@ int attn_shape_supported(const dmf_shape& s);
 // to [0, rows - 1].  The words follow ReduceArgs / OptimArgs in argument structs that only the schedule instances of the two
 // kernels take: the default instances keep their kernel arguments byte for byte.
 struct HpSched { const float* table; const int32_t* row_dev; int32_t rows; };
+// The averaged copy of the weights of the *_avg entry points (include/dmf.h: dmf_weight_avg): avg [n] beside
+// theta, kind DMF_AVG_*, w = float32(1 - decay) for DMF_AVG_EMA, start = the first averaged optimiser step (1-based).  The words
+// follow the schedule's in argument structs that only the averaging instances take (which read the schedule when SCHED).
+struct AvgArgs { float* avg; int32_t kind; float w; int32_t start; };
 struct ReduceArgs {
   int B, NCONV, F2, H, K;
   int64_t oFc1w, oFc1b, oFc2w, oFc2b;
@@ -126,11 +130,14 @@ struct ReduceArgs {
 };
 // ... of grad_reduce_kernel<true>: the schedule, and the host step count (used when step_dev == nullptr)
 struct ReduceSchedArgs : ReduceArgs { HpSched hp; int32_t step; };
+// ... of grad_reduce_kernel<SCHED, true>: hp is read by the <true, true> instance alone, step by both
+struct ReduceAvgArgs : ReduceSchedArgs { AvgArgs av; };
 // dmf_reduce.hip.  launch_grad_reduce carves the head vectors and conv slabs out of the workspace `ws` itself; a geometry
 // its block packing cannot hold is refused with hipErrorInvalidValue and *refusal set to the reason (else null).
-// hp != nullptr launches the schedule instance, which also takes the host step count `step`.
+// hp != nullptr launches the schedule instance, which also takes the host step count `step`; av != nullptr the averaging
+// instance (with or without a schedule; not with the xgmi exchange).
 hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal,
-                              const HpSched* hp = nullptr, int32_t step = 0);
+                              const HpSched* hp = nullptr, int32_t step = 0, const AvgArgs* av = nullptr);
 // The optimiser step on the flat gradient, one launch (optim_step_kernel): dmf_optim_step with weight decay / AdamW /
 // gradient-norm clipping, and with neutral keys dmf_adam_step, dmf_sgd_step, dmf_rmsprop_step and dmf_unscale_adam.
 // launch_optim_step and launch_unscale_check are the only flat-gradient optimiser launchers (launch_adam, launch_sgd,
@@ -148,7 +155,12 @@ struct OptimArgs {
 };
 struct OptimSchedArgs : OptimArgs { HpSched hp; };   // ... of optim_step_kernel<KIND, true>: lr, betas / momentum from the step's row
 hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float* state, hipStream_t st);
-hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp = nullptr);   // hp: the schedule instance
+struct OptimAvgArgs : OptimSchedArgs { AvgArgs av; };  // ... of optim_step_kernel<KIND, SCHED, true> (hp read when SCHED)
+// hp: the schedule instance; av: the averaging instance
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp = nullptr, const AvgArgs* av = nullptr);
+// avg <- the averaging rule on theta [n], stand-alone (weight_average_kernel); the step count is *step_dev when given, else step
+hipError_t launch_weight_average(const AvgArgs& av, const float* theta, int64_t n, int32_t step, const int32_t* step_dev,
+                                 hipStream_t st);
 hipError_t launch_xgmi_allreduce(const XgmiDev& x, float* buf, int64_t n, int seq, hipStream_t st);
 // the validation sum of an epoch and what its end decides (dmf_valid_accum, dmf_keep_best): one workgroup each
 hipError_t launch_valid_accum(const float* loss, int n, double* acc, hipStream_t st);

@@ -50,6 +50,32 @@ __device__ __forceinline__ void rmsprop_update(float* theta, float* sq, int64_t 
   theta[p] -= lr * (g / (sqrtf(s) + eps));
 }
 
+// ------------------------------------------------------------------------------ the averaged copy of the weights
+// torch.optim.swa_utils.AveragedModel on the flat vector: st = the 1-based count of the optimiser step just taken;
+// st <= start copies theta through (st == start is AveragedModel's first update_parameters), later steps lerp towards it
+// with w = 1 - decay (DMF_AVG_EMA, formed by the host) or 1 / (n + 1), n = st - start (DMF_AVG_MEAN: torch's
+// 1 / (num_averaged + 1)).  lerp is torch's, its fused steps written out (contraction off) as adam_apply's are.
+__device__ __forceinline__ float avg_lerp(float a, float b, float w) {
+#pragma clang fp contract(off)
+  const float d = b - a;
+  return fabsf(w) < 0.5f ? fmaf(w, d, a) : fmaf(-(1.f - w), d, b);
+}
+
+__device__ __forceinline__ float avg_rule(int kind, float w_ema, int start, int st, float avg_old, float th_new) {
+  if (st <= start) return th_new;
+  const float w = kind == DMF_AVG_MEAN ? 1.f / (float)(st - start + 1) : w_ema;
+  return avg_lerp(avg_old, th_new, w);
+}
+
+// The stand-alone form (dmf_weight_average): the routes without a fused form, and what the fused forms are compared against.
+__global__ __launch_bounds__(256) void weight_average_kernel(const AvgArgs av, const float* __restrict__ theta, int64_t n, int step,
+                                                             const int32_t* step_dev) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int st = step_dev != nullptr ? *step_dev : step;
+  if (p >= n) return;
+  av.avg[p] = avg_rule(av.kind, av.w, av.start, st, av.avg[p], theta[p]);
+}
+
 // ---- the reduce launch.  What bounds it (tools/reduce_phase_profile.py, stamps of round 3): ONE CU takes in only ~15 bytes
 // per clock from the Infinity Cache (about 64 lines in flight x ~550 cycles), and the 2.2 MB the patch kernel left behind are
 // nowhere else.  The first forms (16 or 64 parameters per block, 64-byte pieces of 7-KB rows, 64 KB fetched per block) spent
@@ -145,8 +171,9 @@ struct FcTile {
 // (adam_update's arithmetic, stated again on purpose: through a shared helper the reduce kernel gets another register
 // allocation and six more instructions)
 struct ReduceTail { float* scaler; float* grad; float lr, b1, b2, eps; };   // the scalars of the tail, fetched at kernel entry
-__device__ __forceinline__ void adam_apply(const ReduceTail& a, float* theta, float* m, float* v, int64_t p, float g, float th0,
-                                           float m_0, float v_0, const float* bcs) {
+// Returns the theta it stored (th0 without one): the averaging instances go on from it without reading it back.
+__device__ __forceinline__ float adam_apply(const ReduceTail& a, float* theta, float* m, float* v, int64_t p, float g, float th0,
+                                            float m_0, float v_0, const float* bcs) {
   if (a.scaler != nullptr) {                         // unscale_ + the found_inf check of GradScaler, in the reduce
     g *= 1.f / a.scaler[0];
     if (!isfinite(g)) a.scaler[2] = 1.f;             // (every writer stores the same value)
@@ -161,8 +188,10 @@ __device__ __forceinline__ void adam_apply(const ReduceTail& a, float* theta, fl
     const float vn = v_0 * a.b2 + ((1.f - a.b2) * g) * g;
     m[p] = mn;
     v[p] = vn;
-    theta[p] = fmaf(-(a.lr / bcs[0]), mn / (sqrtf(vn) / bcs[1] + a.eps), th0);
+    th0 = fmaf(-(a.lr / bcs[0]), mn / (sqrtf(vn) / bcs[1] + a.eps), th0);
+    theta[p] = th0;
   }
+  return th0;
 }
 
 // Diagnostic build only (-DDMF_STAMPS, tools/reduce_phase_profile.py): clock stamps of every wave of the reduce launch in
@@ -197,10 +226,14 @@ typedef const float __attribute__((address_space(4)))* const_f32;
 // SCHED (the second instance): lr, beta1 and beta2 come from the row of a.hp that belongs to this step instead of
 // the launch arguments; the row index and the 16-byte row are fetched where the tail's other scalars are, and wave 4 forms
 // b^step from the row's betas.  Nothing else differs, and the default instance takes the arguments it has always taken.
-template <bool SCHED>
+// AVG (the third and fourth instances): every lane that owns a parameter also keeps its element of a.av.avg by
+// avg_rule, from the theta it has just written.  The avg pointer and words are fetched where the tail's scalars are, the element
+// is requested right behind them (unconditional, clamped index, like the state loads), and the step count is the one the
+// SCHED instance reads.  AVG takes ReduceAvgArgs with or without SCHED; there is no AVG form of the xgmi exchange.
+template <bool SCHED, bool AVG>
 __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restrict__ ws, float* theta, float* m, float* v, int w0, int w1,
                                                           int w2, int w3, int w4, int B,
-                                                          const std::conditional_t<SCHED, ReduceSchedArgs, ReduceArgs> a) {
+                                                          const std::conditional_t<AVG, ReduceAvgArgs, std::conditional_t<SCHED, ReduceSchedArgs, ReduceArgs>> a) {
   __shared__ float vbuf[4][256];        // tile partials of the four waves / [16 chunks][64] attention-slab partials / [4][16] piece partials
   __shared__ float bbuf[4][16];         // bias partials of the four waves
   __shared__ float bcs[2];
@@ -306,7 +339,20 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   const int world = a.x.world;
   ReduceTail tl = {a.scaler, a.grad, a.lr, a.b1, a.b2, a.eps};
   int hp_st = 0;
+  // the averaged copy: its pointer and words in the same fetch (a second one behind it is a second wait for the argument struct)
+  float* avp = nullptr;
+  int av_kind = 0, av_start = 0;
+  float av_w = 0.f, av0 = 0.f, av2 = 0.f;
+  if constexpr (AVG) {
+    avp = a.av.avg; av_kind = a.av.kind; av_w = a.av.w; av_start = a.av.start;
+    asm volatile("" ::"s"(avp), "s"(av_kind), "s"(av_w), "s"(av_start), "s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.eps));
+  }
   if (!SCHED) asm volatile("" ::"s"(world), "s"(tl.scaler), "s"(tl.grad), "s"(tl.lr), "s"(tl.b1), "s"(tl.b2), "s"(tl.eps));
+  if constexpr (AVG) {                               // ... and the owned elements requested at once
+    const bool adam = theta != nullptr;
+    av0 = avp[(adam && own && kind < 3) ? p : 0];
+    if (kind < 2) av2 = avp[(adam && own2) ? p2 : 0];
+  }
   if constexpr (SCHED) {
     // the step's row (uniform addresses: step count and row index -> 16 bytes of the table), requested here, behind the first
     // batch of gradient and state loads; wave 4 and the tail wait for it where they use it
@@ -326,7 +372,16 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
   if (kind == 3) {                                   // attention slabs: the block's role needs the argument struct
     p = a.oAttn + (int64_t)64 * sub + tid;
     own = tid < 64 && 64 * sub + tid < a.ASLAB;
-    if (theta != nullptr && own) { th0 = theta[p]; m_0 = m[p]; v_0 = v[p]; }
+    if (theta != nullptr && own) {
+      th0 = theta[p]; m_0 = m[p]; v_0 = v[p];
+      if constexpr (AVG) av0 = avp[p];
+    }
+  }
+  if constexpr (AVG && !SCHED) {
+    // the step count (the schedule instance has it): requested behind the attention block's words — a scalar wait cannot tell
+    // loads apart, and in front of them every wave waited there for this dependent fetch — and used in the tail
+    const int32_t* sd = a.step_dev;
+    hp_st = sd != nullptr ? *(const_i32)sd : a.step;
   }
   float* part = &vbuf[0][0];
   if (tid >= 256) {
@@ -418,8 +473,14 @@ __global__ __launch_bounds__(320) void grad_reduce_kernel(const float* __restric
     g = xgmi_exchange(a.x, 0, seq, p, own, g) * a.grad_scale;
     if (kind < 2 && n0 == 0) g2 = xgmi_exchange(a.x, 0, seq, p2, own2, g2) * a.grad_scale;
   }
-  if (own) adam_apply(tl, theta, m, v, p, g, th0, m_0, v_0, bcs);
-  if (own2) adam_apply(tl, theta, m, v, p2, g2, th2, m_2, v_2, bcs);
+  if (own) th0 = adam_apply(tl, theta, m, v, p, g, th0, m_0, v_0, bcs);
+  if (own2) th2 = adam_apply(tl, theta, m, v, p2, g2, th2, m_2, v_2, bcs);
+  if constexpr (AVG) {                               // (th0, th2: what adam_apply has just stored)
+    if (theta != nullptr) {
+      if (own) avp[p] = avg_rule(av_kind, av_w, av_start, hp_st, av0, th0);
+      if (own2) avp[p2] = avg_rule(av_kind, av_w, av_start, hp_st, av2, th2);
+    }
+  }
   RSTAMP(5);
   RSTAMP_DUMP();
 }
@@ -458,13 +519,18 @@ __device__ __forceinline__ float scaled_grad(const float* __restrict__ grad, int
 // SCHED (the *_sched entry points): lr and, by kind, beta1 / beta2 or momentum come from the step's row of a.hp,
 // read at entry beside the step count (and so, like it, before the ticket); everything below runs on them as on the launch
 // arguments.  A step the scaler skips takes its count back: with hp.row_dev == nullptr the next step reads the same row again.
-template <int KIND, bool SCHED>
-__global__ __launch_bounds__(256) void optim_step_kernel(const std::conditional_t<SCHED, OptimSchedArgs, OptimArgs> a) {
+// AVG (the *_avg entry points): a lane that has updated theta[p] also keeps a.av.avg[p] by avg_rule, with the step
+// count read at entry; a step the scaler skips leaves avg alone and, its count taken back, does not count for the mean.
+template <int KIND, bool SCHED, bool AVG>
+__global__ __launch_bounds__(256) void optim_step_kernel(
+    const std::conditional_t<AVG, OptimAvgArgs, std::conditional_t<SCHED, OptimSchedArgs, OptimArgs>> a) {
   __shared__ double part[256];
   const int t = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * 256 + t;
   const int st = a.step_dev != nullptr ? *a.step_dev : a.step;
   float lr = a.lr, b1 = a.b1, b2 = a.b2, momentum = a.momentum;
+  float av_old = 0.f;                                  // the element of avg, requested at entry (unconditional, clamped index)
+  if constexpr (AVG) av_old = a.av.avg[p < a.n ? p : a.n - 1];
   if constexpr (SCHED) {
     int row = a.hp.row_dev != nullptr ? *a.hp.row_dev : st - 1;
     row = row < 0 ? 0 : (row > a.hp.rows - 1 ? a.hp.rows - 1 : row);
@@ -529,6 +595,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const std::conditional_
       if (bc1 == 0.f) bias_corrections(st, b1, b2, bc1, bc2s);
       adam_update(a.theta, a.m, a.v, p, g, lr, b1, b2, a.eps, bc1, bc2s);
     }
+    if constexpr (AVG) a.av.avg[p] = avg_rule(a.av.kind, a.av.w, a.av.start, st, av_old, a.theta[p]);
   }
   bool closer = blockIdx.x == 0 && t == 0;
   if (a.state != nullptr) {
@@ -615,8 +682,12 @@ __global__ __launch_bounds__(1024) void keep_best_kernel(double* acc, double* be
 // Blocks per kind, tiles per row, packed for the kernel's preloaded scalars.  A geometry the packing cannot hold is refused:
 // hipErrorInvalidValue, and *refusal names the reason.
 hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const float* ws, hipStream_t st, const char** refusal,
-                              const HpSched* hp, int32_t step) {
+                              const HpSched* hp, int32_t step, const AvgArgs* av) {
   *refusal = nullptr;
+  if (av != nullptr && a.x.world > 1) {
+    *refusal = "grad_reduce: the xgmi exchange has no averaging form";
+    return hipErrorInvalidValue;
+  }
   if (L.H % 8 != 0 || L.F2 % 8 != 0) {
     *refusal = "grad_reduce: hidden width and 2 x gmf.width must be multiples of 8";
     return hipErrorInvalidValue;
@@ -634,14 +705,25 @@ hipError_t launch_grad_reduce(const ReduceArgs& a, const Layout& L, int B, const
     return hipErrorInvalidValue;
   }
   const int grid = nFc1 + nFc2 + nConv + nAttn + 1;   // + the bookkeeping block
-  if (hp != nullptr) {
+  if (av != nullptr) {
+    ReduceAvgArgs aa{};
+    static_cast<ReduceArgs&>(aa) = a;
+    if (hp != nullptr) aa.hp = *hp;
+    aa.step = step; aa.av = *av;
+    if (hp != nullptr)
+      hipLaunchKernelGGL((grad_reduce_kernel<true, true>), dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16),
+                         nFc2 | (t2n << 16), nConv | (nAttn << 16), w3, w4, B, aa);
+    else
+      hipLaunchKernelGGL((grad_reduce_kernel<false, true>), dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16),
+                         nFc2 | (t2n << 16), nConv | (nAttn << 16), w3, w4, B, aa);
+  } else if (hp != nullptr) {
     ReduceSchedArgs as{};
     static_cast<ReduceArgs&>(as) = a;
     as.hp = *hp; as.step = step;
-    hipLaunchKernelGGL(grad_reduce_kernel<true>, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16),
+    hipLaunchKernelGGL((grad_reduce_kernel<true, false>), dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16),
                        nFc2 | (t2n << 16), nConv | (nAttn << 16), w3, w4, B, as);
   } else
-    hipLaunchKernelGGL(grad_reduce_kernel<false>, dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16), nFc2 | (t2n << 16),
+    hipLaunchKernelGGL((grad_reduce_kernel<false, false>), dim3(grid), dim3(320), 0, st, ws, a.theta, a.m, a.v, nFc1 | (t1n << 16), nFc2 | (t2n << 16),
                        nConv | (nAttn << 16), w3, w4, B, a);
   return hipGetLastError();
 }
@@ -654,17 +736,19 @@ hipError_t launch_unscale_check(float* grad, int64_t n, float grad_scale, float*
   return hipGetLastError();
 }
 
-hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp) {
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* hp, const AvgArgs* av) {
   if (a.checked && a.state == nullptr) return hipErrorInvalidValue;
   const dim3 grid = blocks256(a.n), block(256);
-  OptimSchedArgs as{};
-  if (hp != nullptr) {
-    static_cast<OptimArgs&>(as) = a;
-    as.hp = *hp;
-  }
+  OptimAvgArgs aa{};
+  if (hp != nullptr || av != nullptr) static_cast<OptimArgs&>(aa) = a;
+  if (hp != nullptr) aa.hp = *hp;
+  if (av != nullptr) aa.av = *av;
+  const OptimSchedArgs& as = aa;
 #define DMF_OPTIM_LAUNCH(K) \
-  if (hp != nullptr) hipLaunchKernelGGL((optim_step_kernel<K, true>), grid, block, 0, st, as); \
-  else hipLaunchKernelGGL((optim_step_kernel<K, false>), grid, block, 0, st, a)
+  if (av != nullptr && hp != nullptr) hipLaunchKernelGGL((optim_step_kernel<K, true, true>), grid, block, 0, st, aa); \
+  else if (av != nullptr) hipLaunchKernelGGL((optim_step_kernel<K, false, true>), grid, block, 0, st, aa); \
+  else if (hp != nullptr) hipLaunchKernelGGL((optim_step_kernel<K, true, false>), grid, block, 0, st, as); \
+  else hipLaunchKernelGGL((optim_step_kernel<K, false, false>), grid, block, 0, st, a)
   switch (a.kind) {
     case DMF_OPT_ADAM: DMF_OPTIM_LAUNCH(DMF_OPT_ADAM); break;
     case DMF_OPT_ADAMW: DMF_OPTIM_LAUNCH(DMF_OPT_ADAMW); break;
@@ -673,6 +757,12 @@ hipError_t launch_optim_step(const OptimArgs& a, hipStream_t st, const HpSched* 
     default: return hipErrorInvalidValue;
   }
 #undef DMF_OPTIM_LAUNCH
+  return hipGetLastError();
+}
+
+hipError_t launch_weight_average(const AvgArgs& av, const float* theta, int64_t n, int32_t step, const int32_t* step_dev,
+                                 hipStream_t st) {
+  hipLaunchKernelGGL(weight_average_kernel, blocks256(n), dim3(256), 0, st, av, theta, n, step, step_dev);
   return hipGetLastError();
 }
 

@@ -243,6 +243,8 @@ class _PlanEngine:
         self._force_collective = False   # tests only: see _single()
         # the device-resident schedule (set_schedule): the HpSchedule the *_sched entry points take, its table and row index
         self.sched = self.hp_table = self.hp_row = self.hp_unit = None
+        # the averaged copy of the weights (set_averaging): the vector, the WeightAvg the *_avg entry points take, (kind, decay, start)
+        self.avg = self.wavg = self.avg_spec = None
 
     # ------------------------------------------------------------------ lr, betas and momentum from a table on the device
     def set_schedule(self, table, unit='epoch'):
@@ -280,6 +282,34 @@ class _PlanEngine:
         self.comm = None
         self.graph = None
 
+    # ------------------------------------------------------------------ an averaged copy of the weights, kept by the update
+    def set_averaging(self, kind, decay=0.999, start_step=1):
+        """Keep `self.avg`, torch's `AveragedModel` of the weights, updated by every optimiser step (DESIGN.md §16): kind 'ema'
+        (`get_ema_multi_avg_fn(decay)`) or 'mean' (the default equal average, `decay` unused); start_step >= 1 is the first
+        averaged optimiser step (AveragedModel's first `update_parameters`), until which avg is a copy of theta.  avg starts
+        as a copy of theta.  Every step form then updates by the `_avg` entry points (`_update`): the fused ADAM step and the
+        native loop inside the reduce + ADAM launch, every other optimiser launch inside dmf_optim_step_avg; the reduce launch in
+        front of it is the one it was, so gradients and recorded losses keep their bits.  The xGMI exchange keeps its launch and
+        is followed by dmf_weight_average.  The step count then lives on the device for every optimiser (`_counts_on_device`): a
+        step the loss scaler skips does not count.  Averaging is local to a rank."""
+        if kind not in lib.AVG_KINDS:
+            raise lib.DmfError('averaging kind %r is not one of %s' % (kind, sorted(lib.AVG_KINDS)))
+        decay, start_step = float(decay), int(start_step)
+        if kind == 'ema' and not 0.0 <= decay < 1.0:
+            raise lib.DmfError('averaging decay %r is not in [0, 1)' % (decay,))
+        if start_step < 1:
+            raise lib.DmfError('averaging start_step %d: the first averaged step is at least 1' % start_step)
+        if not self._counts_on_device():             # from here on the device counts the steps: hand it the host's count
+            self.dev_step.fill_(self.step_count)
+        self.avg = self.theta.clone()
+        self.avg_spec = (kind, decay, start_step)
+        self.wavg = lib.weight_avg(self.avg, kind, decay, start_step)
+        self.graph = None
+
+    def averaged_parameters(self):
+        """The averaged flat vector (None without set_averaging): a live device tensor, valid weights at every moment."""
+        return self.avg
+
     def set_epoch(self, e):
         """Unit 'epoch': the steps from here on read row e of the table (a stream-ordered device fill, no synchronisation; never
         called inside a capture).  Unit 'step', or no schedule: nothing to do."""
@@ -289,11 +319,14 @@ class _PlanEngine:
     def _hparams(self):
         """What a captured graph bakes in as launch arguments.  With a schedule lr, the betas and momentum are not among them:
         the graph survives every change of them."""
+        avg = ()
+        if self.wavg is not None:                    # kind, the float32 weight and the first averaged step are launch arguments
+            avg = ('avg', self.wavg.kind, self.wavg.weight, self.wavg.start)
         if self.sched is not None:
             return ('sched', self.eps, self.alpha, self.weight_decay, self.clip_grad_norm) + (
-                self.scaler.hparams() if self.scaler is not None else ())
+                self.scaler.hparams() if self.scaler is not None else ()) + avg
         return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha, self.weight_decay, self.clip_grad_norm) + (
-            self.scaler.hparams() if self.scaler is not None else ())
+            self.scaler.hparams() if self.scaler is not None else ()) + avg
 
     def _regularised(self):
         """Weight decay, AdamW or gradient-norm clipping is active: every step form updates by dmf_optim_step (`_update`), so no
@@ -311,8 +344,8 @@ class _PlanEngine:
         """Is the device step counter the true step count?  Then eager steps advance it too, and load_plan leaves it alone;
         otherwise eager steps use the host count `step_count` and load_plan copies it into the counter.  With a loss
         scaler it is: a skipped step takes its count back on the device.  With a schedule it is: unit 'step' finds its row
-        by it."""
-        return self.scaler is not None or self.sched is not None
+        by it.  With averaging it is: the rule reads it."""
+        return self.scaler is not None or self.sched is not None or self.wavg is not None
 
     def _count_step(self, dev_step):
         """Count one step on the host; returns the device step counter the step's launches take (None: the host count).
@@ -337,6 +370,10 @@ class _PlanEngine:
           a schedule (set_schedule)     the same reduce launch per case, and the `_sched` twin of the optimiser launch:
                                         dmf_grad_reduce_adam_sched for the fused case, dmf_optim_step_sched for every other
                                         (`_update_sched`; the xGMI case takes the collective route)
+          averaging (set_averaging)     the same reduce launch per case again, and the `_avg` form of the optimiser launch, with
+                                        the schedule if there is one: dmf_grad_reduce_adam_avg for the fused case,
+                                        dmf_optim_step_avg for every other (`_optim_step`); the xGMI case keeps its launch
+                                        and is followed by dmf_weight_average
         sum_scale scales the all-reduced gradient: 1/world where the loss is a per-rank mean, 1 where the loss kernel
         already divided by the global batch.  dev_step: the device step counter, or None for the host count.  loss /
         loss_hist: where the step's mean loss (this rank's) is recorded; None where the loss kernel records it itself.
@@ -348,22 +385,33 @@ class _PlanEngine:
         if self.sched is not None:
             return self._update_sched(rows, dev_step, cursor, sum_scale, loss, loss_hist, fused)
         if fused and self._single():
-            lib.grad_reduce_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count,
-                                 adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+            if self.wavg is not None:
+                lib.grad_reduce_adam_avg(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count, self.wavg,
+                                         adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+            else:
+                lib.grad_reduce_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count,
+                                     adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
         elif fused and self.comm is not None:
             lib.grad_reduce_xgmi_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, self.comm.c, *hp, sum_scale,
                                       dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+            if self.wavg is not None:
+                lib.weight_average(self.wavg, self.theta, self.step_count, step_dev=dev_step)
         elif sc is not None and self._single():
             lib.grad_reduce_scaled(self.shape, rows, self.ws, self.grad, sc.state, cursor_dev=cursor, loss=loss,
                                    loss_hist=loss_hist)
-            lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step, unscaled=True)
+            if self.wavg is not None:
+                self._optim_step(dev_step, None, 1.0, unscaled=True)
+            else:
+                lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step, unscaled=True)
         else:
             lib.grad_reduce(self.shape, rows, self.ws, self.grad)
             if not self._single():
                 self._all_reduce_grad()
             if loss_hist is not None:
                 loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
-            if sc is not None:
+            if self.wavg is not None:
+                self._optim_step(dev_step, cursor, sum_scale)
+            elif sc is not None:
                 lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step,
                                  grad_scale=sum_scale, cursor_dev=cursor)
             elif self.optim == 'SGD':
@@ -385,13 +433,17 @@ class _PlanEngine:
         self._optim_step(dev_step, cursor, sum_scale, norm_hist=self.norm_hist if cursor is not None else self.norm)
 
     def _optim_step(self, dev_step, cursor, sum_scale, unscaled=False, norm_hist=None):
-        """dmf_optim_step on self.grad with the engine's optimiser, keys and scaler — dmf_optim_step_sched with a schedule."""
+        """dmf_optim_step on self.grad with the engine's optimiser, keys and scaler — dmf_optim_step_sched with a schedule,
+        dmf_optim_step_avg (which takes the schedule, if any) with averaging."""
         sc = self.scaler
         keys = dict(eps=1e-8 if self.optim == 'RMSprop' else self.eps, alpha=self.alpha, weight_decay=self.weight_decay,
                     max_norm=self.clip_grad_norm, step=self.step_count, grad_scale=sum_scale, step_dev=dev_step, cursor_dev=cursor,
                     scaler_state=sc.state if sc is not None else None, scaler_hparams=sc.hparams() if sc is not None else None,
                     unscaled=unscaled, norm_hist=norm_hist)
-        if self.sched is not None:
+        if self.wavg is not None:
+            lib.optim_step_avg(self.optim, self.theta, self.grad, self.m, self.v, self.wavg, sched=self.sched, lr=self.lr, b1=self.b1,
+                               b2=self.b2, momentum=self.momentum, **keys)
+        elif self.sched is not None:
             lib.optim_step_sched(self.optim, self.theta, self.grad, self.m, self.v, self.sched, **keys)
         else:
             lib.optim_step(self.optim, self.theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, momentum=self.momentum, **keys)
@@ -402,7 +454,11 @@ class _PlanEngine:
         dmf_grad_reduce_adam_sched, everything else by dmf_optim_step_sched with neutral keys (the kernel behind
         dmf_unscale_adam, dmf_sgd_step, dmf_rmsprop_step and dmf_adam_step)."""
         sc = self.scaler
-        if fused and self._single():
+        if fused and self._single() and self.wavg is not None:
+            lib.grad_reduce_adam_avg(self.shape, rows, self.ws, self.theta, self.m, self.v, None, 0.0, 0.0, 0.0, self.eps,
+                                     self.step_count, self.wavg, sched=self.sched, adam_step_dev=dev_step, cursor_dev=cursor,
+                                     loss=loss, loss_hist=loss_hist)
+        elif fused and self._single():
             lib.grad_reduce_adam_sched(self.shape, rows, self.ws, self.theta, self.m, self.v, None, self.sched, self.eps,
                                        self.step_count, adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
         elif sc is not None and self._single():
@@ -539,8 +595,8 @@ class _PlanEngine:
         """Save everything a step changes (weights, optimiser and scaler state, device step count and cursor, loss history,
         host step count and cursor) and put it back on leaving, also when the body raises.  Yields the restore function
         for a body that needs the state back early."""
-        tensors = [t for t in (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist, self.norm_hist, self.norm)
-                   if t is not None]
+        tensors = [t for t in (self.theta, self.m, self.v, self.dev_step, self.dev_cursor, self.loss_hist, self.norm_hist, self.norm,
+                               self.avg) if t is not None]
         if self.scaler is not None:
             tensors.append(self.scaler.state)
         saved = [t.clone() for t in tensors]
@@ -806,7 +862,11 @@ class TrainEngine(_PlanEngine):
         k0 = self.host_cursor
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy[k0 * self.B:(k0 + steps) * self.B], B=self.B)
         labels = self.plan_labels[k0 * self.B:(k0 + steps) * self.B]
-        if self.sched is not None:
+        if self.wavg is not None:
+            lib.train_plan_steps_avg(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
+                                     self.ws, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.dev_step, self.dev_cursor,
+                                     self.loss_hist, self.sched, self.wavg, steps)
+        elif self.sched is not None:
             lib.train_plan_steps_sched(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
                                        self.ws, self.m, self.v, self.sched, self.eps, self.dev_step, self.dev_cursor,
                                        self.loss_hist, steps)
@@ -966,6 +1026,20 @@ class EvalEngine(_ShardedEval):
             self.attn_ws = torch.empty(lib.attn_workspace_bytes(self.shape, self.B), dtype=torch.uint8, device=dev)
         self.ce = torch.zeros(self.B, device=dev)
         self._no_ce = False
+        self._theta = None
+
+    def use_parameters(self, flat=None):
+        """Evaluate the flat vector `flat` (float32 on the scene's device, the net's layout — a train engine's
+        `averaged_parameters()`) instead of the net's own parameters; None: the net's again.  The tensor is read at every call."""
+        if flat is not None:
+            lib._dev(flat, torch.float32, 'parameters')
+            if flat.numel() != self.net.flat_parameters().numel() or flat.device != self.scene.device:
+                raise lib.DmfError('use_parameters: a flat vector of the net\'s %d parameters on the scene\'s device'
+                                   % self.net.flat_parameters().numel())
+        self._theta = flat
+
+    def _params(self):
+        return self._theta if self._theta is not None else self.net.flat_parameters()
 
     def predict(self, xy):
         """xy [n,2] int32 device -> (logits [n,K], pred [n]) views valid until the next call."""
@@ -973,9 +1047,9 @@ class EvalEngine(_ShardedEval):
         self._check_batch(n)
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         if self.shape.attention:
-            lib.forward_attn(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, self.attn_ws, self.logits, self.pred)
+            lib.forward_attn(self.shape, inp, self._params(), self.net.pool_w, self.attn_ws, self.logits, self.pred)
         else:
-            lib.forward(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, self.logits, self.pred)
+            lib.forward(self.shape, inp, self._params(), self.net.pool_w, self.logits, self.pred)
         return self.logits[:n], self.pred[:n]
 
     def _patch_losses(self, xy, labels):
@@ -994,7 +1068,7 @@ class EvalEngine(_ShardedEval):
             return False
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         try:
-            lib.forward_ce(self.shape, inp, self.net.flat_parameters(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
+            lib.forward_ce(self.shape, inp, self._params(), self.net.pool_w, labels, self.logits, self.ce, self.pred)
         except lib.DmfError:
             self._no_ce = True
             return False

@@ -39,6 +39,11 @@ class HpSchedule(C.Structure):
     _fields_ = [('table', C.c_void_p), ('rows', C.c_int32), ('row_dev', C.c_void_p)]
 
 
+class WeightAvg(C.Structure):
+    """dmf_weight_avg: avg [n] fp32 on the device, kind DMF_AVG_*, weight = float32(1 - decay) (EMA), start = first averaged step."""
+    _fields_ = [('avg', C.c_void_p), ('kind', C.c_int32), ('weight', C.c_float), ('start', C.c_int32), ('reserved', C.c_int32)]
+
+
 class Input(C.Structure):
     _fields_ = [('mode', C.c_int32), ('B', C.c_int32), ('a', C.c_void_p), ('b', C.c_void_p), ('sceneA', C.c_void_p),
                 ('sceneB', C.c_void_p), ('xy', C.c_void_p), ('Wp', C.c_int32), ('WpB', C.c_int32), ('cursor', C.c_void_p),
@@ -51,7 +56,7 @@ def _load():
                        '(hipcc --offload-arch=gfx950); there is no CPU fallback for the product path')
     lib = C.CDLL(LIB_PATH)
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    SP, IP, HP = C.POINTER(Shape), C.POINTER(Input), C.POINTER(HpSchedule)
+    SP, IP, HP, AP = C.POINTER(Shape), C.POINTER(Input), C.POINTER(HpSchedule), C.POINTER(WeightAvg)
     protos = {
         'dmf_version': (i32, []),
         'dmf_last_error': (C.c_char_p, []),
@@ -88,6 +93,12 @@ def _load():
         'dmf_optim_step_sched': (i32, [vp, vp, vp, vp, i64, i32, HP, f32, f32, f32, f32, i32, f32, vp, vp, vp, f32, f32, i32, i32, vp, vp]),
         'dmf_grad_reduce_adam_sched': (i32, [SP, i32, vp, vp, vp, vp, vp, HP, f32, i32, vp, vp, vp, vp, vp]),
         'dmf_train_plan_steps_sched': (i32, [SP, IP, vp, vp, vp, f32, vp, vp, vp, vp, vp, HP, f32, vp, vp, vp, i32, vp]),
+        'dmf_weight_average': (i32, [AP, vp, i64, i32, vp, vp]),
+        'dmf_optim_step_avg': (i32, [vp, vp, vp, vp, i64, i32, f32, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, vp, vp, f32, f32,
+                                     i32, i32, vp, HP, AP, vp]),
+        'dmf_grad_reduce_adam_avg': (i32, [SP, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, vp, HP, AP, vp]),
+        'dmf_train_plan_steps_avg': (i32, [SP, IP, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp, vp, HP, AP, i32,
+                                           vp]),
         'dmf_xgmi_sizes': (i32, [i64, i32, C.POINTER(i64), C.POINTER(i64)]),
         'dmf_xgmi_alloc': (i32, [i64, C.POINTER(vp)]),
         'dmf_xgmi_free': (i32, [vp]),
@@ -372,6 +383,56 @@ def train_plan_steps_sched(shape, inp, theta, pool_w, labels, loss_scale, logits
     check(_lib.dmf_train_plan_steps_sched(C.byref(shape), C.byref(inp), _ptr(theta), _ptr(pool_w), _ptr(labels), loss_scale,
                                           _ptr(logits), _ptr(loss), _ptr(ws), _ptr(m), _ptr(v), _sched_ref(sched), eps,
                                           _ptr(adam_step_dev), _ptr(cursor_dev), _ptr(loss_hist), n_steps, _stream()))
+
+
+AVG_KINDS = {'ema': 0, 'mean': 1}           # DMF_AVG_* (include/dmf.h)
+
+
+def weight_avg(avg, kind, decay=0.999, start=1):
+    """-> WeightAvg of a device vector `avg` (float32, theta's layout): kind a key of AVG_KINDS, weight the float32 of
+    1 - decay formed in double (EMA), start the first averaged optimiser step (1-based).  The caller keeps `avg` alive."""
+    if kind not in AVG_KINDS:
+        raise DmfError('averaging kind %r is not one of %s' % (kind, sorted(AVG_KINDS)))
+    _dev(avg, torch.float32, 'avg')
+    return WeightAvg(avg=avg.data_ptr(), kind=AVG_KINDS[kind], weight=1.0 - float(decay), start=int(start), reserved=0)
+
+
+def _avg_ref(avg):
+    return None if avg is None else C.byref(avg)
+
+
+def weight_average(avg, theta, step=0, step_dev=None):
+    """The averaging rule alone on theta (dmf_weight_average); avg: a WeightAvg."""
+    check(_lib.dmf_weight_average(_avg_ref(avg), _ptr(theta), theta.numel(), step, _ptr(step_dev), _stream()))
+
+
+def optim_step_avg(kind, theta, grad, m, v, avg, sched=None, lr=0.0, b1=0.9, b2=0.999, eps=1e-8, momentum=0.0, alpha=0.99,
+                   weight_decay=0.0, max_norm=None, step=0, grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None,
+                   scaler_hparams=None, unscaled=False, norm_hist=None):
+    """optim_step (sched None) or optim_step_sched that also keeps the averaged copy `avg` (a WeightAvg; dmf_optim_step_avg)."""
+    if kind not in OPTIM_KINDS:
+        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
+    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
+    check(_lib.dmf_optim_step_avg(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], lr, b1, b2, eps,
+                                  momentum, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
+                                  _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
+                                  _ptr(norm_hist), _sched_ref(sched), _avg_ref(avg), _stream()))
+
+
+def grad_reduce_adam_avg(shape, B, ws, theta, m, v, grad, lr, b1, b2, eps, step, avg, sched=None, adam_step_dev=None,
+                         cursor_dev=None, loss=None, loss_hist=None):
+    """grad_reduce_adam (sched None) or grad_reduce_adam_sched that also keeps `avg` (dmf_grad_reduce_adam_avg)."""
+    check(_lib.dmf_grad_reduce_adam_avg(C.byref(shape), B, _ptr(ws), _ptr(theta), _ptr(m), _ptr(v), _ptr(grad), lr, b1, b2, eps,
+                                        step, _ptr(adam_step_dev), _ptr(cursor_dev), _ptr(loss), _ptr(loss_hist),
+                                        _sched_ref(sched), _avg_ref(avg), _stream()))
+
+
+def train_plan_steps_avg(shape, inp, theta, pool_w, labels, loss_scale, logits, loss, ws, m, v, lr, b1, b2, eps, adam_step_dev,
+                         cursor_dev, loss_hist, sched, avg, n_steps):
+    """train_plan_steps / _sched whose steps also keep `avg` (dmf_train_plan_steps_avg)."""
+    check(_lib.dmf_train_plan_steps_avg(C.byref(shape), C.byref(inp), _ptr(theta), _ptr(pool_w), _ptr(labels), loss_scale,
+                                        _ptr(logits), _ptr(loss), _ptr(ws), _ptr(m), _ptr(v), lr, b1, b2, eps, _ptr(adam_step_dev),
+                                        _ptr(cursor_dev), _ptr(loss_hist), _sched_ref(sched), _avg_ref(avg), n_steps, _stream()))
 
 
 def grad_reduce_adam(shape, B, ws, theta, m, v, grad, lr, b1, b2, eps, step, adam_step_dev=None, cursor_dev=None,

@@ -40,6 +40,12 @@ the device and the optimiser kernels read their row themselves (`_set_device_sch
 run, whatever the scheduler.  `schedule.scheduler_unit: step` (default epoch): `scheduler.step()` after every optimiser step
 instead of once per epoch, on the drop-in path by one branch in the loop, on the fast path by a table row per step (it requires
 device_schedule: 1).
+`schedule.weight_average: ema | mean` (default none) with `average_decay` and `average_start` (epochs): an averaged
+copy of the weights, torch's `AveragedModel`, updated after every optimiser step — on the fast path inside the update launch
+(`engine.set_averaging`), on the drop-in path by `_foreach_lerp_` in the loop (`_average_dropin`).  Validation then evaluates
+the averaged weights (`_on_average`), `<t>_weights.pth` holds those of the best epoch (in an epoch block dmf_keep_best is handed
+them), so test() / color() classify with them; `<t>_curweights.pth` keeps the raw weights and the optimiser and gains the key
+`averaged`, which test() loads with `save_best: 0`.  toStageSolver refuses the keys.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -48,6 +54,7 @@ Deliberate differences: `test()` evaluates the whole test split when `test.full:
 after the first batch, :142 — that stays the default); the t-SNE plot inside `test()` and the visualisation
 helpers (:110-136,211-441) are out of scope; `nohup: 1` does not crash (reference bug at :76).
 """
+import contextlib
 import importlib
 import itertools
 import time
@@ -59,7 +66,7 @@ from PIL import Image
 from tqdm import tqdm
 
 from solver.basesolver import BaseSolver
-from utils.utils import (clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
+from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
                          make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
 
@@ -75,6 +82,8 @@ class Solver(BaseSolver):
     drop-in path `_train_epoch_dropin`, `_valid_pass`, `_predict_dropin`, `_test_whole_split`."""
     engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
     epoch_blocks = True                                  # `train.epoch_block` > 1 has a block form for this stage
+    weight_averaging = True                              # `schedule.weight_average` is in scope for this stage
+    averaging = None                                     # (the constructor reads it from cfg['schedule'])
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
     def __init__(self, cfg):
@@ -82,6 +91,11 @@ class Solver(BaseSolver):
         if keys and (self.engine_loss != 'Criterion' or cfg['schedule']['loss'] != 'Criterion'):
             raise ValueError('schedule.%s belongs to schedule.loss: Criterion of Solver; %s trains with %s'
                              % (keys[0], type(self).__name__, cfg['schedule']['loss']))
+        self.averaging = averaging_keys(cfg)           # None, or (kind, decay, epochs before the first averaged step)
+        if self.averaging is not None and not self.weight_averaging:
+            raise ValueError('schedule.weight_average, schedule.average_decay and schedule.average_start are out of scope for %s: '
+                             'set weight_average to none' % type(self).__name__)
+        self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken
         self.cfg, self.rank, self.world = cfg, 0, 1
         self._epoch_block()                            # (a stage without a block form refuses the key before anything is read)
         # schedule.device_schedule / schedule.scheduler_unit (utils.schedule_keys; `step` on the fast path needs the device table)
@@ -179,6 +193,8 @@ class Solver(BaseSolver):
         elif self.scheduler_unit == 'step' and self.scheduler is not None:
             # stepped after every optimiser step: the scheduler spans epochs x batches steps (OneCycleLR's total_steps)
             self.scheduler = make_scheduler(self.optimizer, self.cfg, total=self.EPOCH * len(self.train_loader))
+        if self.averaging is not None and not self.fast:       # (the fast path's engine keeps its own: _make_engines)
+            self._avg_flat, self._avg_steps = self.cur_model.flat_parameters().detach().clone(), 0
         self.step_losses, self.val_history, self.best_loss = [], [], float('inf')
         self.best_epoch = 0 if self.cfg['train']['save_best'] else None
         if self.fast and E > 1:
@@ -197,9 +213,11 @@ class Solver(BaseSolver):
             val = None
             if save_best:
                 self.cur_model.eval()
-                val = self._valid_pass(self.best_loss)
+                with self._on_average():
+                    val = self._valid_pass(self.best_loss)
             if self._record_epoch(self.epoch, losses, val) and self.rank == 0:
-                torch.save(self.cur_model.state_dict(), self.cfg['RESULT_output'] + str(self.time) + '_weights.pth')
+                best = self.cur_model.state_dict() if self.averaging is None else self._flat_state_dict(self._averaged())
+                torch.save(best, self.cfg['RESULT_output'] + str(self.time) + '_weights.pth')
             self._save_current(self.epoch + 1)
             if self.world > 1:
                 import torch.distributed as dist
@@ -234,7 +252,47 @@ class Solver(BaseSolver):
         small epoch's 5.6 ms, tools/solver_epoch_profile.sh) and after the last."""
         if self.rank == 0 and (done % self._save_every() == 0 or done == self.EPOCH):
             opt = self._export_optimizer() if self.fast else self.optimizer
-            save_checkpoint(self.cur_model, opt, self.cfg['RESULT_output'] + str(self.time) + '_curweights.pth')
+            extra = {} if self.averaging is None else {'averaged': self._flat_state_dict(self._averaged())}
+            save_checkpoint(self.cur_model, opt, self.cfg['RESULT_output'] + str(self.time) + '_curweights.pth', **extra)
+
+    # ------------------------------------------------------------------ the averaged weights (schedule.weight_average)
+    def _average_start_step(self, steps_per_epoch):
+        """The first averaged optimiser step (1-based): the first step after `average_start` epochs."""
+        return self.averaging[2] * steps_per_epoch + 1
+
+    def _averaged(self):
+        """The averaged flat vector: the engine's, or the drop-in loop's."""
+        return self.engine.averaged_parameters() if self.fast else self._avg_flat
+
+    def _average_dropin(self):
+        """After `optimizer.step()` of the drop-in loop: AveragedModel.update_parameters, on the net's flat vector."""
+        kind, decay, _ = self.averaging
+        self._avg_steps += 1
+        average_update_([self._avg_flat], [self.cur_model.flat_parameters().detach()], kind, decay,
+                        self._average_start_step(len(self.train_loader)), self._avg_steps)
+
+    @contextlib.contextmanager
+    def _on_average(self):
+        """The validation pass inside evaluates the averaged weights: the eval engine is pointed at them; the drop-in path's
+        net holds them for the pass and gets its own back."""
+        if self.averaging is None:
+            yield
+        elif self.fast:
+            self.eval_engine.use_parameters(self._averaged())
+            try:
+                yield
+            finally:
+                self.eval_engine.use_parameters(None)
+        else:
+            flat = self.cur_model.flat_parameters()
+            own = flat.detach().clone()
+            with torch.no_grad():
+                flat.copy_(self._avg_flat)
+            try:
+                yield
+            finally:
+                with torch.no_grad():
+                    flat.copy_(own)
 
     def _loss_scaler(self, hp):
         """gmf.half: 1 on the fast path -> the device loss scaler with GradScaler's defaults; its step is ADAM (or ADAMW)."""
@@ -258,6 +316,8 @@ class Solver(BaseSolver):
             weight_decay=hp.get('weight_decay', 0.0), clip_grad_norm=hp.get('clip_grad_norm')))
         self.eval_engine = self._eval_engine()
         self._set_device_schedule()
+        if self.averaging is not None:
+            self.engine.set_averaging(self.averaging[0], self.averaging[1], self._average_start_step(self._steps_per_epoch()))
 
     def _steps_per_epoch(self):
         """Optimiser steps of one epoch on the fast path: the full batches, and the short last one where `_rank_batches` keeps it
@@ -363,10 +423,12 @@ class Solver(BaseSolver):
             if rest:
                 eng.step_short(e)
             if save_best:
-                with torch.no_grad():
+                with torch.no_grad(), self._on_average():
                     for i in range(0, valid[0].shape[0], vb):
                         self.eval_engine.valid_accum(valid[0][i:i + vb], valid[1][i:i + vb], blk.acc)
-                lib.keep_best(blk.acc, blk.best, blk.best_epoch, first_epoch + e, eng.theta, blk.best_theta, blk.val_hist)
+                # (with averaging the best weights are the averaged ones, as they were validated)
+                lib.keep_best(blk.acc, blk.best, blk.best_epoch, first_epoch + e, eng.theta if self.averaging is None else eng.avg,
+                              blk.best_theta, blk.val_hist)
         blk.enqueued = (first_epoch, n_epochs, n_full)
 
     def _collect_block(self):
@@ -394,9 +456,13 @@ class Solver(BaseSolver):
             self.cur_model.eval()
 
     def _best_state_dict(self):
-        """The state dict of the best epoch: the net's own keys in their order, every parameter a piece of the device's copy
-        of the best flat vector (the net's name / offset table), the buffers as they are."""
-        net, flat = self.cur_model, self._block.best_theta.clone()
+        """The state dict of the best epoch, from the device's copy of the best flat vector."""
+        return self._flat_state_dict(self._block.best_theta)
+
+    def _flat_state_dict(self, flat):
+        """The net's state dict with a copy of the flat vector `flat` for its parameters: the net's own keys in their order,
+        every parameter a piece of the copy (the net's name / offset table), the buffers as they are."""
+        net, flat = self.cur_model, flat.detach().clone()
         start = dict(zip(net._order(), net._offsets))
         now = net.state_dict()
         best = type(now)((k, flat[start[k]:start[k] + v.numel()].view(v.shape) if k in start else v) for k, v in now.items())
@@ -472,6 +538,8 @@ class Solver(BaseSolver):
             if max_norm:
                 torch.nn.utils.clip_grad_norm_(self.cur_model.parameters(), max_norm)
             self.optimizer.step()
+            if self.averaging is not None:
+                self._average_dropin()
             if per_step:
                 self.scheduler.step()                                # schedule.scheduler_unit: step
             losses.append(loss.item())
@@ -518,7 +586,9 @@ class Solver(BaseSolver):
     def _load_weights(self, best):
         path = self.cfg['RESULT_output'] + str(self.time) + ('_weights.pth' if best else '_curweights.pth')
         sd = torch.load(path, map_location=self.DEVICE, weights_only=True)
-        self.cur_model.load_state_dict(sd if best else sd['state_dict'])
+        if not best:                                     # the averaged weights where they are configured and the file has them
+            sd = sd['averaged'] if self.averaging is not None and 'averaged' in sd else sd['state_dict']
+        self.cur_model.load_state_dict(sd)
 
     def _ensure_model(self):
         if self.cur_model is None:

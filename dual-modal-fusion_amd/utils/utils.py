@@ -226,6 +226,41 @@ def schedule_keys(cfg, fast=False):
     return dev, unit
 
 
+AVERAGE_KINDS = ('none', 'ema', 'mean')
+
+
+def averaging_keys(cfg):
+    """schedule.weight_average / average_decay / average_start (all NEW, optional) -> None, or (kind, decay, start_epochs):
+    an averaged copy of the weights in the role of `torch.optim.swa_utils.AveragedModel`, updated after every optimiser step —
+    `ema` with `get_ema_multi_avg_fn(average_decay)` (default 0.999), `mean` with its default equal average —, from the first
+    step after `average_start` epochs (default 0) on, and a copy of the weights until then.  With it validation, the best
+    weights and therefore test() / color() use the averaged weights."""
+    s = cfg['schedule']
+    kind = s.get('weight_average') or 'none'
+    if kind not in AVERAGE_KINDS:
+        raise ValueError('schedule.weight_average %r is not one of %s' % (kind, ', '.join(AVERAGE_KINDS)))
+    if kind == 'none':
+        return None
+    decay = float(s.get('average_decay', 0.999))
+    start = s.get('average_start', 0) or 0
+    if not 0.0 <= decay < 1.0:
+        raise ValueError('schedule.average_decay %r is not in [0, 1)' % (s.get('average_decay'),))
+    if int(start) != start or start < 0:
+        raise ValueError('schedule.average_start %r is not a whole number of epochs >= 0' % (start,))
+    return kind, decay, int(start)
+
+
+def average_update_(avg, params, kind, decay, start_step, step):
+    """`AveragedModel.update_parameters` on lists of tensors, with torch's own ops: `step` is the 1-based count of the optimiser
+    step just taken; step <= start_step copies (step == start_step is AveragedModel's first update), later steps
+    `_foreach_lerp_` with 1 - decay (`get_ema_multi_avg_fn`) or 1 / (num_averaged + 1) (the default equal average)."""
+    with torch.no_grad():
+        if step <= start_step:
+            torch._foreach_copy_(avg, params)
+        else:
+            torch._foreach_lerp_(avg, params, 1.0 - decay if kind == 'ema' else 1.0 / (step - start_step + 1))
+
+
 def optim_hparams(cfg):
     """What the resident-scene engine needs to reproduce make_optimizer(cfg, ...): kind + the constructor arguments the
     reference passes (ADAM: lr; SGD: lr, momentum; RMSprop: lr, alpha — utils/utils.py:10-16), torch defaults otherwise; and
@@ -364,8 +399,8 @@ def _bundle(model, optimizer, **extra):
     return d
 
 
-def save_checkpoint(model, optimizer, filename='my_checkpoint.pth.tar'):
-    torch.save(_bundle(model, optimizer), filename)
+def save_checkpoint(model, optimizer, filename='my_checkpoint.pth.tar', **extra):
+    torch.save(_bundle(model, optimizer, **extra), filename)
 
 
 def save_point_sche(model, optimizer, schedule, filename='my_checkpoint.pth.tar'):

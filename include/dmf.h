@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define DMF_VERSION 306   /* 0.3.6: dmf_hp_schedule and the *_sched entry points (lr, betas, momentum from a device table); 0.3.5: dmf_optim_step (weight decay, AdamW and gradient-norm clipping on the flat gradient); 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
+#define DMF_VERSION 307   /* 0.3.6: dmf_hp_schedule and the *_sched entry points (lr, betas, momentum from a device table); 0.3.5: dmf_optim_step (weight decay, AdamW and gradient-norm clipping on the flat gradient); 0.3.4: dmf_valid_accum, dmf_keep_best (validation sum and best weights stay on the device); 0.3.3: dmf_ce_loss (class weights, label smoothing, focal loss for the unit-gradient step); 0.3.2: dmf_scene_minmax, dmf_scene_prepare (scene preparation on the device); 0.3.1: dmf_qua_loss_ranks (stage-2 loss on the gathered data-parallel batch); 0.3.0 (round 3): dmf_train_plan_steps, dmf_forward_ce, tagged-word exchange (dmf_xgmi_sizes grew), one patch kernel; 0.2.0: dmf_input.half, unit-gradient step, loss scaler, SGD / RMSprop steps */
 #define DMF_KMAX 64       /* max number of logits (Categories_Number, utils/config.py:25) */
 
 /* Network / patch geometry (oracle/gmfnet_ref.py::arch_from_cfg). */
@@ -313,6 +313,51 @@ int32_t dmf_train_plan_steps_sched(const dmf_shape* shape, const dmf_input* in, 
                                    const int32_t* labels, float loss_scale, float* logits, float* loss, void* workspace,
                                    float* m, float* v, const dmf_hp_schedule* sched, float eps,
                                    int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist, int32_t n_steps, void* stream);
+
+/* ---- an averaged copy of the weights, kept by the update launch -------------------------------------
+ * The role of `torch.optim.swa_utils.AveragedModel(model[, multi_avg_fn=get_ema_multi_avg_fn(decay)])` with
+ * `update_parameters(model)` after every optimiser step: avg [n] fp32 on the device, in theta's layout.  With st the 1-based
+ * count of the optimiser step just taken (*step_dev / *adam_step_dev when given, else the `step` argument: the count the
+ * update already reads) and start >= 1 the first averaged step:
+ *   st <= start   avg[i] = theta[i]                        (a copy: avg is a valid weight vector from the first step on;
+ *                                                          st == start is AveragedModel's first update_parameters)
+ *   st >  start   avg[i] = lerp(avg[i], theta[i], w)       n = st - start
+ *                 DMF_AVG_EMA   w = `weight`, the float32 of 1 - decay (formed in double by the caller, as torch forms it)
+ *                 DMF_AVG_MEAN  w = 1.f / (float)(n + 1)   (torch's default equal average)
+ *   lerp(a, b, w) = |w| < 0.5 ? fmaf(w, b - a, a) : fmaf(-(1 - w), b - a, b)      (torch.lerp; nothing else is contracted)
+ * theta is the vector the step has just updated.  A step the loss scaler skips leaves avg untouched and takes its count back,
+ * so n counts optimiser steps taken.  Averaging is local to a rank: every rank holds the same theta after the update.
+ *   dmf_weight_average          the rule alone, one launch over n elements (n == 0: a no-op)
+ *   dmf_optim_step_avg          dmf_optim_step (sched == NULL) or dmf_optim_step_sched (then lr, beta1, beta2 and momentum are
+ *                               ignored) with the rule applied by the lane that updated theta[i]
+ *   dmf_grad_reduce_adam_avg    dmf_grad_reduce_adam / _sched likewise, inside the reduce + Adam launch
+ *   dmf_train_plan_steps_avg    dmf_train_plan_steps / _sched on dmf_grad_reduce_adam_avg
+ * theta, m, v, grad, the loss history and every other output keep the bits of the twin.  Each entry point fails on: a NULL
+ * dmf_weight_avg or avg pointer, an unknown kind, DMF_AVG_EMA with a weight that is not finite or not in (0, 1], start < 1, avg
+ * overlapping theta, and everything its twin fails on.  `reserved` must be 0. */
+#define DMF_AVG_EMA  0
+#define DMF_AVG_MEAN 1
+typedef struct dmf_weight_avg { float* avg; int32_t kind; float weight; int32_t start; int32_t reserved; } dmf_weight_avg;
+int32_t dmf_weight_average(const dmf_weight_avg* avg, const float* theta, int64_t n, int32_t step, const int32_t* step_dev,
+                           void* stream);
+int32_t dmf_optim_step_avg(float* theta, const float* grad, float* m, float* v, int64_t n, int32_t kind,
+                           float lr, float beta1, float beta2, float eps, float momentum, float alpha,
+                           float weight_decay, float max_norm, int32_t step, float grad_scale,
+                           int32_t* step_dev, int32_t* cursor_dev,
+                           float* scaler_state, float growth_factor, float backoff_factor, int32_t growth_interval,
+                           int32_t unscaled, float* norm_hist,
+                           const dmf_hp_schedule* sched /* NULL: the launch arguments */, const dmf_weight_avg* avg, void* stream);
+int32_t dmf_grad_reduce_adam_avg(const dmf_shape* shape, int32_t B, const void* workspace,
+                                 float* theta, float* m, float* v, float* grad,
+                                 float lr, float beta1, float beta2, float eps, int32_t step,
+                                 const int32_t* adam_step_dev, int32_t* cursor_dev,
+                                 const float* loss, float* loss_hist,
+                                 const dmf_hp_schedule* sched, const dmf_weight_avg* avg, void* stream);
+int32_t dmf_train_plan_steps_avg(const dmf_shape* shape, const dmf_input* in, float* theta, const float* pool_w,
+                                 const int32_t* labels, float loss_scale, float* logits, float* loss, void* workspace,
+                                 float* m, float* v, float lr, float beta1, float beta2, float eps,
+                                 int32_t* adam_step_dev, int32_t* cursor_dev, float* loss_hist,
+                                 const dmf_hp_schedule* sched, const dmf_weight_avg* avg, int32_t n_steps, void* stream);
 
 /* ---- stage 2 of the two-stage path (solver/tostagesolver.py:259-346) ---------------------------------------
  * The stage-2 net takes ONE input, the four streams (ms, pan, ms_gan, pan_gan) stacked on the batch axis

@@ -1,7 +1,11 @@
 """Diagnostic: clock stamps of every wave of the gradient-reduce launch (stamps build, never the shipped library), taken
 from the LAST step of a replayed hipGraph at the default bench shape (steady state: alternating with the patch kernel).
 
-    python tools/reduce_phase_profile.py [B]
+    python tools/reduce_phase_profile.py [B] [avg]
+
+`avg`: the engine keeps an averaged copy of the weights (EMA, from step 1), so the launch is the averaging instance
+(DESIGN.md 16).  The last lines give the median over all blocks of every stamp; a run with `avg` and one without are compared
+by hand.
 """
 import ctypes as C
 import os
@@ -40,6 +44,8 @@ def main():
     xy_all = np.stack([rng2.integers(0, 145, n_steps * B), rng2.integers(0, 145, n_steps * B)], 1).astype(np.int32)
     lab_all = rng2.integers(1, 17, n_steps * B).astype(np.int32)
     eng = TrainEngine(net, scene, B, lr=1e-3)
+    if 'avg' in sys.argv[2:]:
+        eng.set_averaging('ema', 0.999, 1)
     eng.load_plan(xy_all, lab_all)
     eng.run_plan(n_steps, 40)
     torch.cuda.synchronize()
@@ -57,6 +63,10 @@ def main():
               + ' | ' + ' '.join('%8.0f' % v for v in w4))
     ends = s[used][:, :, 6]
     print('grid span in cycles: first entry -> last end %.0f; entry spread %.0f' % (ends.max() - first_all, t00[t00 > 0].max() - first_all))
+    # per stamp: the median over the blocks of (the median over a block's waves 0-3) since that block's own entry
+    own = [float(np.median([np.median(s[b, :4, i] - s[b, :4, 0]) for b in used])) for i in (1, 2, 3, 4, 5, 6)]
+    print('median over the blocks, cycles since the block\'s own entry: role known %.0f, kernel arguments %.0f, partials written '
+          '%.0f, behind barrier %.0f, stores issued %.0f, end %.0f' % tuple(own))
     rt = s[used][:, :, 7]
     print('s_memrealtime entry spread: %.2f us' % ((rt[rt > 0].max() - rt[rt > 0].min()) / 100.0))
 

@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "dmf_ce_math.h"
 #include "dmf_kargs.h"
 
 namespace dmf {
@@ -190,6 +191,16 @@ struct AttnTrainLds {
   static_assert(BYTES <= 160 * 1024, "one workgroup per CU");
 };
 
+// LDS of the criterion instance (CRIT): the training kernel's, and behind it what the criterion needs of the batch (sKw below:
+// the class weights w[0..63], 0 for k >= K, and five scalars) — patch invariant, written once per workgroup
+template <class Sh, int E, int NH>
+struct AttnCeLds : AttnTrainLds<Sh, E, NH> {
+  using Base = AttnTrainLds<Sh, E, NH>;
+  static constexpr int fKw = Base::FLOATS, FLOATS = fKw + 80;
+  static constexpr size_t BYTES = (size_t)Base::HALVES * 2 + (size_t)FLOATS * 4;
+  static_assert(BYTES <= 160 * 1024, "one workgroup per CU");
+};
+
 // LDS of the forward-only kernel (TRAIN = false): what inference needs and nothing else — token maps, K as rows, V transposed,
 // one head's Wq / Wk / Wv / Wo, the head's vectors — 77,888 bytes, so that TWO workgroups share a CU (4 waves per SIMD at its
 // ~120 registers) and each covers the other's barrier waits and LDS round trips.  Q needs no image at all: formed as
@@ -211,11 +222,23 @@ struct AttnFwdLds {
   static_assert(2 * BYTES <= 160 * 1024, "two workgroups per CU");
 };
 
+// The criterion instance of the training kernel is selected by TAGGING its shape: a fifth template parameter would rename every
+// instance (the symbol of a kernel spells its template arguments), and tools/isa_diff.py — which gates that the plain instances
+// stay what they were, instruction for instruction — pairs the kernels of two trees by symbol.
+template <class Sh> struct Crit : Sh {};
+template <class Sh> struct is_crit : std::false_type {};
+template <class Sh> struct is_crit<Crit<Sh>> : std::true_type {};
+
 // TRAIN = false: forward only (logits, argmax) — the inference / evaluation kernel of the attention network.
+// CRIT (Sh = Crit<shape>, training only): the criterion of DESIGN.md §12 — class weights, label smoothing, focal term — where the
+// plain instance forms its cross-entropy: wave 0 calls the per-sample arithmetic of ce_loss_kernel (dmf_ce_math.h) on the patch's
+// logits, with the batch's denominator read from a.denom.
 template <class Sh, int E, int NH, bool TRAIN>
 __global__ __launch_bounds__(512) void attn_train_kernel(const AttnTrainArgs a) {
+  constexpr bool CRIT = is_crit<Sh>::value;
+  static_assert(TRAIN || !CRIT, "the criterion belongs to the training kernel");
   using namespace at;
-  using L = typename std::conditional<TRAIN, AttnTrainLds<Sh, E, NH>, AttnFwdLds<Sh, E, NH>>::type;
+  using L = typename std::conditional<TRAIN, std::conditional_t<CRIT, AttnCeLds<Sh, E, NH>, AttnTrainLds<Sh, E, NH>>, AttnFwdLds<Sh, E, NH>>::type;
   constexpr int T = L::T, FP = L::FP, DH = L::DH, FO = L::FO, NT = 512;
   constexpr int VS = L::VS, QS = L::QS, KS = L::KS, WS = L::WS, OS = L::OS;
   constexpr int F = Sh::F, F2 = Sh::F2, H = Sh::H, P2 = Sh::P2;
@@ -258,6 +281,7 @@ __global__ __launch_bounds__(512) void attn_train_kernel(const AttnTrainArgs a) 
 #define sCw AT_F(L::fCw)
 #define sC AT_F(L::fC)
 #define sG AT_F(L::fG)
+#define sKw AT_F(L::fKw)   /* CRIT only: class weights [64]; [64] their sum, [65] grad_scale / D, [66] label row (int), [67] eps, [68] gamma */
 
   const int tid0 = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -266,6 +290,30 @@ __global__ __launch_bounds__(512) void attn_train_kernel(const AttnTrainArgs a) 
   const int K = a.K;
   const float scale = 0.17677669529663687f;          // float32(1/sqrt(32))
   const int boff = a.cursor != nullptr ? a.cursor[0] * a.B : 0;
+  (void)boff;
+  // CRIT: what the criterion needs of the batch is patch invariant and fetched ONCE, here, by wave 0 (which evaluates it): the
+  // class weights (0 past K) and their sum, the float32 factor grad_scale / D of the gradient from the denominator D of the plan
+  // row, and the row of the global batch's labels that is this rank's.  It waits in LDS, not in registers — the kernel has
+  // neither vector nor scalar registers to spare across the patch loop — and is read behind the barriers of the first patch.
+  if constexpr (CRIT) {
+    if (wave == 0) {
+      const int l = tid0 & 63;
+      const float w = l < K ? (a.class_w != nullptr ? a.class_w[l] : 1.f) : 0.f;
+      const float ws = grp_sum<64>(w);
+      sKw[l] = w;
+      const int cur = a.cursor != nullptr ? a.cursor[0] : 0;
+      const double D = a.denom[cur];
+      if (l == 0) {
+        sKw[64] = ws;
+        sKw[65] = a.grad_scale / (float)D;               // (the factor of the product ce_loss_kernel forms: g * (grad_scale / D))
+        *reinterpret_cast<int*>(sKw + 66) = (cur * a.ranks + a.rank) * a.B;
+        // (eps and gamma too: float arithmetic on a kernel argument is vector arithmetic that the compiler forms in front of
+        // the patch loop and then keeps in registers across it)
+        sKw[67] = a.eps;
+        sKw[68] = a.gamma;
+      }
+    }
+  }
 
   for (int i = tid0; i < T; i += NT) sPw[i] = i < P2 ? a.pool[i] : 0.f;
 
@@ -554,7 +602,19 @@ __global__ __launch_bounds__(512) void attn_train_kernel(const AttnTrainArgs a) 
     if (wave == 0) {
       const float lg = lane < K ? sLg[lane] : -INFINITY;
       float dl = 0.f;
-      if (a.labels != nullptr) {
+      if constexpr (CRIT) {
+        // the criterion's gradient of one sample, lane k = class k over the whole wave for every K (dmf_ce_math.h: L = 64 gives
+        // the bits of ce_loss_kernel's 16-lane groups too)
+        const int label = clamp_label(a.labels[(int64_t)*reinterpret_cast<const int*>(sKw + 66) + b], K);
+        CeTerm t;
+        const float eps = sKw[67], gamma = sKw[68];
+        int Kc = K;                                    // (opaque for the same reason: (float)K stays inside this section)
+        asm volatile("" : "+s"(Kc));
+        const float g = ce_grad<64>(lg, sKw[lane], sKw[64], lane, label, Kc, a.kind, eps, gamma, t);
+        dl = lane < K ? g * sKw[65] : 0.f;
+        // (the per-patch VALUE is not formed here: its float64 exp / log / pow cost this kernel 180 bytes of scratch per lane.
+        // dmf_train_attn_fwd_bwd_ce takes it from a value-only ce_loss_kernel launch on the logits stored below)
+      } else if (a.labels != nullptr) {
         int label = a.labels[boff + b];
         label = label < 0 ? 0 : (label >= K ? K - 1 : label);
         float mx = lg;
@@ -912,7 +972,8 @@ hipError_t attn_prep_launch(const float* theta, int64_t oWq, int64_t oWk, int64_
 template <class Sh, bool TRAIN>
 static hipError_t launch_attn_train(const AttnTrainArgs& a, int grid, hipStream_t st) {
   static LdsAttrOnce once;
-  constexpr size_t bytes = std::conditional<TRAIN, AttnTrainLds<Sh, 96, 3>, AttnFwdLds<Sh, 96, 3>>::type::BYTES;
+  constexpr size_t bytes = std::conditional<TRAIN, std::conditional_t<is_crit<Sh>::value, AttnCeLds<Sh, 96, 3>, AttnTrainLds<Sh, 96, 3>>,
+                                            AttnFwdLds<Sh, 96, 3>>::type::BYTES;
   static_assert(bytes <= 160 * 1024, "attention kernel LDS");
   hipError_t e = once.set(reinterpret_cast<const void*>(&attn_train_kernel<Sh, 96, 3, TRAIN>), (int)bytes);
   if (e != hipSuccess) return e;
@@ -923,6 +984,12 @@ static hipError_t launch_attn_train(const AttnTrainArgs& a, int grid, hipStream_
 hipError_t attn_train_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st) {
   if (s.C == 200) return launch_attn_train<ShapeHSI, true>(a, grid, st);
   if (s.C == 8) return launch_attn_train<ShapeTiny1, true>(a, grid, st);
+  return hipErrorInvalidValue;
+}
+
+hipError_t attn_train_ce_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st) {
+  if (s.C == 200) return launch_attn_train<Crit<ShapeHSI>, true>(a, grid, st);
+  if (s.C == 8) return launch_attn_train<Crit<ShapeTiny1>, true>(a, grid, st);
   return hipErrorInvalidValue;
 }
 

@@ -235,6 +235,43 @@ int64_t dmf_attn_train_workspace_bytes(const dmf_shape* s, int32_t B) {
   return attn_ws(*s, B, true, nullptr).bytes;
 }
 
+// The train step of the attention network behind dmf_train_attn_fwd_bwd and dmf_train_attn_fwd_bwd_ce (`entry`), whose own
+// arguments the caller has checked: token kernel, attention fwd+bwd kernel, conv backward.  ce == nullptr: the plain instance
+// with `labels` (this rank's) or `dlogits`; else the criterion instance, `labels` = ce->labels_global.
+static int attn_train_step(const char* entry, const dmf_shape* s, const dmf_input* in, const float* theta, const float* pool_w,
+                           const int32_t* labels, const float* dlogits, float loss_scale, const dmf_ce_fused* ce, float* logits,
+                           float* loss, void* workspace, void* attn_workspace, int32_t* adam_step_dev, hipStream_t st) {
+  AttnWs aw;
+  AttnTrainArgs t{};
+  if (attn_common(entry, s, in, theta, pool_w, attn_workspace, true, logits, st, aw, t)) return 1;
+  const WsLayout w = make_ws(layout_of(*s), in->B);
+  float* ws = static_cast<float*>(workspace);
+  t.labels = labels; t.cursor = in->cursor; t.dlogits = dlogits; t.loss_scale = loss_scale; t.loss = loss;
+  head_ws(ws, w, t);
+  t.dYa = aw.dYa; t.dYb = aw.dYb; t.aslab = ws + w.aslab;
+  const int grid = in->B < MAX_BLOCKS ? in->B : MAX_BLOCKS;          // one slab per workgroup, as the conv kernel
+  if (ce != nullptr) {
+    const dmf_ce_params* p = ce->params;
+    t.class_w = ce->class_w; t.denom = ce->denom; t.ranks = ce->ranks; t.rank = ce->rank; t.kind = p->kind;
+    t.eps = p->kind == 0 ? p->label_smoothing : 0.f; t.gamma = p->kind == 1 ? p->gamma : 0.f; t.grad_scale = ce->grad_scale;
+    t.loss = nullptr;                                  // (the value: the launch behind the conv backward)
+    if (check(attn_train_ce_dispatch(*s, t, grid, st), "attention training kernel launch")) return 1;
+  } else if (check(attn_train_dispatch(*s, t, grid, st), "attention training kernel launch")) {
+    return 1;
+  }
+  KArgs d{};
+  d.in = *in; d.theta = theta; d.pool = pool_w; d.K = s->K;
+  d.slab = ws + w.slab; d.dYa = aw.dYa; d.dYb = aw.dYb; d.adam_step = adam_step_dev;
+  if (check(conv_dispatch(*s, MODE_DENSE, d, st), "dense conv backward launch")) return 1;
+  if (ce == nullptr || loss == nullptr) return 0;
+  // The per-patch value N t_i / D: ce_loss_kernel, value only, on the logits the attention kernel stored — the float64
+  // arithmetic of the value does not fit the attention kernel's registers.  Behind the conv backward, which
+  // the gradient reduce waits for; nothing but the loss history reads `loss`.
+  CeArgs v{logits, labels, in->cursor, ce->class_w, nullptr, loss, nullptr, ce->ranks, ce->rank, in->B, s->K, t.kind, t.eps, t.gamma,
+           ce->grad_scale};
+  return check(launch_ce_loss(v, st), "ce_loss (value) launch");
+}
+
 int32_t dmf_train_attn_fwd_bwd(const dmf_shape* s, const dmf_input* in, const float* theta, const float* pool_w,
                                const int32_t* labels, const float* dlogits, float loss_scale, float* logits, float* loss,
                                void* workspace, void* attn_workspace, int32_t* adam_step_dev, void* stream) {
@@ -243,21 +280,34 @@ int32_t dmf_train_attn_fwd_bwd(const dmf_shape* s, const dmf_input* in, const fl
       attn_workspace == nullptr || logits == nullptr)
     return fail("%s", "null argument");
   if ((labels == nullptr) == (dlogits == nullptr)) return fail("%s", "give exactly one of labels / dlogits");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  AttnWs aw;
-  AttnTrainArgs t{};
-  if (attn_common("dmf_train_attn_fwd_bwd", s, in, theta, pool_w, attn_workspace, true, logits, st, aw, t)) return 1;
-  const WsLayout w = make_ws(layout_of(*s), in->B);
-  float* ws = static_cast<float*>(workspace);
-  t.labels = labels; t.cursor = in->cursor; t.dlogits = dlogits; t.loss_scale = loss_scale; t.loss = loss;
-  head_ws(ws, w, t);
-  t.dYa = aw.dYa; t.dYb = aw.dYb; t.aslab = ws + w.aslab;
-  const int grid = in->B < MAX_BLOCKS ? in->B : MAX_BLOCKS;          // one slab per workgroup, as the conv kernel
-  if (check(attn_train_dispatch(*s, t, grid, st), "attention training kernel launch")) return 1;
-  KArgs d{};
-  d.in = *in; d.theta = theta; d.pool = pool_w; d.K = s->K;
-  d.slab = ws + w.slab; d.dYa = aw.dYa; d.dYb = aw.dYb; d.adam_step = adam_step_dev;
-  return check(conv_dispatch(*s, MODE_DENSE, d, st), "dense conv backward launch");
+  return attn_train_step("dmf_train_attn_fwd_bwd", s, in, theta, pool_w, labels, dlogits, loss_scale, nullptr, logits, loss, workspace,
+                         attn_workspace, adam_step_dev, static_cast<hipStream_t>(stream));
+}
+
+// what dmf_ce_loss and dmf_train_attn_fwd_bwd_ce (`entry`) refuse of a criterion and of the place of a rank in the global batch
+static int check_ce(const char* entry, const dmf_ce_params* prm, int32_t ranks, int32_t rank, int32_t bs_r, int32_t K) {
+  if (ranks < 1 || rank < 0 || rank >= ranks) return fail("%s: ranks must be positive and 0 <= rank < ranks", entry);
+  if (bs_r <= 0 || K < 1 || K > KMAX) return fail("%s: bs must be positive and 1 <= K <= DMF_KMAX", entry);
+  if ((int64_t)ranks * bs_r > INT32_MAX || (int64_t)bs_r * K > INT32_MAX) return fail("%s: the batch is too large", entry);
+  if (prm->kind != 0 && prm->kind != 1) return fail("%s: kind must be 0 (cross-entropy) or 1 (focal)", entry);
+  if (!(prm->label_smoothing >= 0.f && prm->label_smoothing < 1.f)) return fail("%s: label_smoothing must lie in [0, 1)", entry);
+  if (!(prm->gamma == 0.f || (prm->gamma >= 1.f && isfinite(prm->gamma)))) return fail("%s: gamma must be 0 or >= 1", entry);
+  return 0;
+}
+
+int32_t dmf_train_attn_fwd_bwd_ce(const dmf_shape* s, const dmf_input* in, const float* theta, const float* pool_w,
+                                  const dmf_ce_fused* ce, float* logits, float* loss, void* workspace, void* attn_workspace,
+                                  int32_t* adam_step_dev, void* stream) {
+  if (in != nullptr && in->B == 0) return 0;
+  if (s == nullptr || in == nullptr || theta == nullptr || pool_w == nullptr || workspace == nullptr ||
+      attn_workspace == nullptr || logits == nullptr)
+    return fail("%s", "null argument");
+  if (ce == nullptr || ce->params == nullptr || ce->labels_global == nullptr || ce->denom == nullptr)
+    return fail("%s", "dmf_train_attn_fwd_bwd_ce: null dmf_ce_fused, params, labels_global or denom");
+  if (ce->reserved != 0) return fail("%s", "dmf_train_attn_fwd_bwd_ce: dmf_ce_fused.reserved must be 0");
+  if (check_ce("dmf_train_attn_fwd_bwd_ce", ce->params, ce->ranks, ce->rank, in->B, s->K)) return 1;
+  return attn_train_step("dmf_train_attn_fwd_bwd_ce", s, in, theta, pool_w, ce->labels_global, nullptr, 0.f, ce, logits, loss,
+                         workspace, attn_workspace, adam_step_dev, static_cast<hipStream_t>(stream));
 }
 
 int32_t dmf_forward(const dmf_shape* s, const dmf_input* in, const float* theta, const float* pool_w,
@@ -771,15 +821,20 @@ int32_t dmf_ce_loss(const float* logits, int32_t ranks, int32_t rank, int32_t bs
                     const int32_t* cursor, const float* class_w, const dmf_ce_params* prm, float grad_scale,
                     const float* scaler_state, float* loss, float* dlogits, void* stream) {
   if (logits == nullptr || labels_global == nullptr || prm == nullptr) return fail("%s", "null argument");
-  if (ranks < 1 || rank < 0 || rank >= ranks) return fail("%s", "ce_loss: ranks must be positive and 0 <= rank < ranks");
-  if (bs_r <= 0 || K < 1 || K > KMAX) return fail("%s", "ce_loss: bs must be positive and 1 <= K <= DMF_KMAX");
-  if ((int64_t)ranks * bs_r > INT32_MAX || (int64_t)bs_r * K > INT32_MAX) return fail("%s", "ce_loss: the batch is too large");
-  if (prm->kind != 0 && prm->kind != 1) return fail("%s", "ce_loss: kind must be 0 (cross-entropy) or 1 (focal)");
-  if (!(prm->label_smoothing >= 0.f && prm->label_smoothing < 1.f)) return fail("%s", "ce_loss: label_smoothing must lie in [0, 1)");
-  if (!(prm->gamma == 0.f || (prm->gamma >= 1.f && isfinite(prm->gamma)))) return fail("%s", "ce_loss: gamma must be 0 or >= 1");
+  if (check_ce("ce_loss", prm, ranks, rank, bs_r, K)) return 1;
   CeArgs a{logits, labels_global, cursor, class_w, scaler_state, loss, dlogits, ranks, rank, bs_r, K, prm->kind,
            prm->kind == 0 ? prm->label_smoothing : 0.f, prm->kind == 1 ? prm->gamma : 0.f, grad_scale};
   return check(launch_ce_loss(a, static_cast<hipStream_t>(stream)), "ce_loss launch");
+}
+
+int32_t dmf_ce_denominators(const int32_t* labels_global, int32_t N, int32_t rows, int32_t K, const float* class_w, double* denom,
+                            void* stream) {
+  if (labels_global == nullptr || denom == nullptr) return fail("%s", "ce_denominators: null labels or denom");
+  if (N < 1 || rows < 0) return fail("%s", "ce_denominators: N must be positive and rows >= 0");
+  if (K < 1 || K > KMAX) return fail("%s", "ce_denominators: 1 <= K <= DMF_KMAX");
+  if (rows == 0) return 0;
+  return check(launch_ce_denominators(labels_global, N, rows, K, class_w, denom, static_cast<hipStream_t>(stream)),
+               "ce_denominators launch");
 }
 
 int32_t dmf_pair_argmax(const float* logits, int32_t bs, int32_t K, int32_t* pred, void* stream) {

@@ -93,10 +93,19 @@ struct AttnTrainArgs {
   const unsigned short* wprep;          // [NH][WPREP] bf16 weights of every head, already in the LDS layout (attn_prep_kernel)
   int64_t oWq, oWk, oWv, oWo, oFc1w, oFc1b, oFc2w, oFc2b;
   int32_t B, K;
+  // Read by the criterion instances of the training kernel alone (dmf_train_attn_fwd_bwd_ce: class weights, label smoothing or a
+  // focal term where the plain instance forms its cross-entropy); they FOLLOW the words above, whose offsets the plain instances
+  // keep.  `labels` then is the GLOBAL batch's, rank-major (labels[((*cursor) * ranks + rank) * B + b], as CeArgs), and
+  // denom[*cursor] its denominator (dmf_ce_denominators).
+  const float* class_w;                 // [K], nullable = all ones
+  const double* denom;                  // [plan rows]
+  int32_t ranks, rank, kind;
+  float eps, gamma, grad_scale;
 };
 size_t attn_prep_bytes();
 hipError_t attn_prep_launch(const float* theta, int64_t oWq, int64_t oWk, int64_t oWv, int64_t oWo, void* out, hipStream_t st);
 hipError_t attn_train_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st);
+hipError_t attn_train_ce_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st);   // the criterion instances
 hipError_t attn_forward_dispatch(const dmf_shape& s, const AttnTrainArgs& a, int grid, hipStream_t st);
 int attn_shape_supported(const dmf_shape& s);
 
@@ -197,6 +206,8 @@ struct CeArgs {
   float eps, gamma, grad_scale;
 };
 hipError_t launch_ce_loss(const CeArgs& a, hipStream_t st);
+// denom[r] = sum over the N labels of row r of (double)class_w[label] (NULL: ones), the bits ce_loss_kernel forms for that row
+hipError_t launch_ce_denominators(const int32_t* labels, int N, int rows, int K, const float* class_w, double* denom, hipStream_t st);
 
 // scene preparation (dmf_scene.hip)
 struct ScenePrepArgs {

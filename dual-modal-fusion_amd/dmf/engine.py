@@ -530,8 +530,14 @@ class _PlanEngine:
         plan = dict(plan_xy=xy.to(dev).contiguous(), plan_labels=lab.to(dev).contiguous())
         if pack:
             plan['plan_pack'] = torch.cat([plan['plan_xy'].view(cap, 2 * rows), plan['plan_labels'].view(cap, rows)], 1).contiguous()
+        plan.update(self._plan_extras(plan['plan_labels'], rows, cap))
         self._install_plan(n, cap, **plan)
         return n
+
+    def _plan_extras(self, labels, rows, cap):
+        """Further plan tensors (attribute name -> tensor) derived from the uploaded labels [cap * rows]; they are installed
+        with the plan, so a plan of the same shape is copied into the tensors a captured graph reads."""
+        return {}
 
     def _install_plan(self, n, capacity, **plan):
         """Make `plan` (attribute name -> device tensor, `capacity` steps long) the loaded plan of n steps and rewind to its first
@@ -689,16 +695,22 @@ class _PlanEngine:
 
 class TrainEngine(_PlanEngine):
     """The single-stage train step on a resident scene: the fused step, or with a `criterion` the unit-gradient step around
-    dmf_ce_loss (_PlanEngine: what each takes).  `self.fused`, set once by the constructor, says which."""
+    dmf_ce_loss (_PlanEngine: what each takes) — for the attention net the criterion inside the attention kernel, on the
+    unit-gradient step's global batches.  `self.fused`, set once by the constructor, says which (True: no criterion)."""
 
     def __init__(self, net, scene, batch, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, comm=None, scaler=None,
-                 optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None, weight_decay=0.0, clip_grad_norm=None):
+                 optimizer='ADAM', momentum=0.0, alpha=0.99, criterion=None, weight_decay=0.0, clip_grad_norm=None,
+                 criterion_in_kernel=False):
         """optimizer: 'ADAM', or the reference's other two (utils/utils.py:13-16) — 'SGD' (`momentum`) and 'RMSprop'
         (`alpha`, eps 1e-8) —, or 'ADAMW'.  weight_decay (torch's `weight_decay=`; decoupled with ADAMW) and clip_grad_norm
         (`clip_grad_norm_(params, max_norm)` between backward and step; None or 0: off) update by dmf_optim_step, without the
         xgmi exchange.  The launches after the backward: _PlanEngine._update.
         criterion: None = the plain cross-entropy fused into the patch kernel (two launches per step).  A spec of `Criterion`
-        (class weights, label smoothing, focal term) trains by the unit-gradient step instead (no xgmi exchange)."""
+        (class weights, label smoothing, focal term) trains by the unit-gradient step instead (no xgmi exchange).
+        criterion_in_kernel (attention net with a criterion only): True evaluates the criterion inside the attention kernel
+        (dmf_train_attn_fwd_bwd_ce) on the unit-gradient step's global batches: `step` / `load_plan` as there, the
+        launches after the backward as without a criterion.  The default keeps what a caller of this constructor has always got
+        for that net, the refusal (it has no unit-gradient step): whoever catches it to fall back elsewhere still does."""
         super().__init__(net, scene, lr, betas, eps, process_group, scaler, optimizer, momentum, alpha, weight_decay, clip_grad_norm)
         if scaler is not None and (comm is not None or self.shape.attention):
             raise lib.DmfError('loss scaling: late-fusion net, single GPU or RCCL data parallel (not the xgmi exchange)')
@@ -726,18 +738,26 @@ class TrainEngine(_PlanEngine):
         self.short_norm = None
         self.criterion = None
         self.fused = criterion is None
+        self.plan_denom = None                    # attention net with a criterion: the plan rows' denominators (float64)
+        if criterion_in_kernel and (self.fused or not self.shape.attention):
+            raise lib.DmfError('criterion_in_kernel belongs to the attention network with a criterion (the late-fusion net trains '
+                               'a criterion by the unit-gradient step)')
         if not self.fused:
-            if self.shape.attention:
+            if self.shape.attention and not criterion_in_kernel:
                 raise lib.DmfError('a criterion with class weights, label smoothing or a focal term trains by the unit-gradient '
-                                   'step, which the attention network does not have')
-            if not lib.unit_supported(self.shape):
+                                   'step, which the attention network does not have; criterion_in_kernel=True evaluates it '
+                                   'inside the attention kernel instead')
+            if not self.shape.attention and not lib.unit_supported(self.shape):
                 raise lib.DmfError('a criterion with class weights, label smoothing or a focal term needs the unit-gradient '
                                    'kernel (dmf_unit_supported), which this shape does not have')
             if comm is not None:
                 raise lib.DmfError('a criterion with class weights, label smoothing or a focal term: single GPU or a process '
                                    'group (not the xgmi exchange)')
             self.criterion = Criterion(criterion, K, dev)
-            self.dlogits = torch.empty(self.B, K, device=dev)
+            if self.shape.attention:              # the criterion inside the attention kernel (dmf_train_attn_fwd_bwd_ce)
+                self.denom = torch.zeros(1, dtype=torch.float64, device=dev)     # ... of an eager step's batch
+            else:
+                self.dlogits = torch.empty(self.B, K, device=dev)
 
     # ------------------------------------------------------------------ eager step (host-side step count)
     def step(self, xy, labels, check=True):
@@ -770,6 +790,16 @@ class TrainEngine(_PlanEngine):
         dev_step = self._count_step(dev_step)
         sc, nB, cr = self.scaler, inp.B, self.criterion
         loss = self.loss if loss_hist is not None else None
+        if not self.fused and self.shape.attention:
+            # The criterion inside the attention kernel: the step keeps the fused step's launches.  labels: the GLOBAL batch's, and
+            # its denominator — the plan's travel together (plan_denom); an eager batch's is one one-row launch ahead of the step.
+            # The loss kernel's arithmetic has divided by the global batch: the ranks' sum is the gradient.
+            denom = self.plan_denom if dev_cursor is not None else self.denom
+            if dev_cursor is None:
+                lib.ce_denominators(labels[:self.world * nB], self.world * nB, self.shape.K, denom, cr.class_w)
+            lib.train_attn_fwd_bwd_ce(self.shape, inp, self.theta, self.net.pool_w, labels, denom, cr.params, self.world, self.rank,
+                                      self.logits, self.loss, self.ws, self.attn_ws, class_w=cr.class_w, adam_step_dev=dev_step)
+            return self._update(nB, dev_step, dev_cursor, 1.0, loss, loss_hist)
         if not self.fused:                     # labels: the GLOBAL batch's ([world * nB] at row dev_cursor)
             return self._unit_step(inp, nB, lambda: lib.ce_loss(
                 self.logits[:nB], self.world, self.rank, labels, cr.params, class_w=cr.class_w, loss=self.loss,
@@ -791,6 +821,15 @@ class TrainEngine(_PlanEngine):
         if not self.fused:
             return self._load_global_plan(xy_all, labels_all, self.B)
         return self._upload_plan(xy_all, labels_all, self.B, pack=True)
+
+    def _plan_extras(self, labels, rows, cap):
+        """The attention net with a criterion: the denominators travel with the labels — plan_denom [cap] float64, one
+        dmf_ce_denominators launch per plan upload."""
+        if self.fused or not self.shape.attention:
+            return {}
+        denom = torch.empty(cap, dtype=torch.float64, device=self.scene.device)
+        lib.ce_denominators(labels, rows, self.shape.K, denom, self.criterion.class_w)
+        return dict(plan_denom=denom)
 
     # ------------------------------------------------------------------ a block of epochs as one plan (train.epoch_block)
     def _host_ints(self, t, what):

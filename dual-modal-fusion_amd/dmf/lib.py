@@ -34,6 +34,12 @@ class CeParams(C.Structure):
     _fields_ = [('kind', C.c_int32), ('label_smoothing', C.c_float), ('gamma', C.c_float)]
 
 
+class CeFused(C.Structure):
+    """dmf_ce_fused: the criterion of dmf_train_attn_fwd_bwd_ce — labels_global / denom on the device, one row per plan step."""
+    _fields_ = [('params', C.POINTER(CeParams)), ('class_w', C.c_void_p), ('labels_global', C.c_void_p), ('denom', C.c_void_p),
+                ('ranks', C.c_int32), ('rank', C.c_int32), ('grad_scale', C.c_float), ('reserved', C.c_int32)]
+
+
 class HpSchedule(C.Structure):
     """dmf_hp_schedule: table [rows][4] fp32 on the device, row_dev a device int32 (unit `epoch`) or NULL (unit `step`)."""
     _fields_ = [('table', C.c_void_p), ('rows', C.c_int32), ('row_dev', C.c_void_p)]
@@ -111,6 +117,8 @@ def _load():
                                             vp, vp, vp]),
         'dmf_qua_loss': (i32, [vp, i32, i32, vp, vp, C.POINTER(QuaParams), f32, vp, vp, vp, vp]),
         'dmf_ce_loss': (i32, [vp, i32, i32, i32, i32, vp, vp, vp, C.POINTER(CeParams), f32, vp, vp, vp, vp]),
+        'dmf_ce_denominators': (i32, [vp, i32, i32, i32, vp, vp, vp]),
+        'dmf_train_attn_fwd_bwd_ce': (i32, [SP, IP, vp, vp, C.POINTER(CeFused), vp, vp, vp, vp, vp, vp]),
         'dmf_pair_argmax': (i32, [vp, i32, i32, vp, vp]),
         'dmf_band_mean': (i32, [vp, i32, i64, i64, i32, vp, vp]),
         'dmf_confusion_accum': (i32, [vp, vp, i32, i32, vp, vp]),
@@ -599,6 +607,43 @@ def ce_loss(logits, ranks, rank, labels_global, params, class_w=None, loss=None,
             raise DmfError('dlogits must have the shape of logits')
     check(_lib.dmf_ce_loss(_ptr(logits), ranks, rank, bs_r, K, _ptr(labels_global), _ptr(cursor), _ptr(class_w),
                            C.byref(params), grad_scale, _ptr(scaler_state), _ptr(loss), _ptr(dlogits), _stream()))
+
+
+def ce_denominators(labels_global, N, K, denom, class_w=None):
+    """denom[r] <- sum over the N labels of row r of labels_global [rows * N] of (double)class_w[label] (None: ones), the bits of
+    the denominator dmf_ce_loss forms for that row (dmf_ce_denominators); rows = labels_global.numel() // N."""
+    _dev(labels_global, torch.int32, 'labels_global'); _dev(denom, torch.float64, 'denom')
+    if N < 1 or labels_global.numel() % N:
+        raise DmfError('ce_denominators wants rows of %d labels, got %d labels' % (N, labels_global.numel()))
+    rows = labels_global.numel() // N
+    if denom.numel() < rows:
+        raise DmfError('denom must hold one denominator per row (%d), got %d' % (rows, denom.numel()))
+    if class_w is not None:
+        _dev(class_w, torch.float32, 'class_w')
+        if class_w.numel() != K:
+            raise DmfError('class_w must hold one weight per class (%d), got %d' % (K, class_w.numel()))
+    check(_lib.dmf_ce_denominators(_ptr(labels_global), N, rows, K, _ptr(class_w), _ptr(denom), _stream()))
+
+
+def train_attn_fwd_bwd_ce(shape, inp, theta, pool_w, labels_global, denom, params, ranks, rank, logits, loss, ws, attn_ws,
+                          class_w=None, grad_scale=1.0, adam_step_dev=None):
+    """The attention network's train step with the criterion `params` / class_w evaluated inside the attention kernel
+    (dmf_train_attn_fwd_bwd_ce): labels_global [rows, ranks * B] rank-major and denom [rows] (ce_denominators), both read at row
+    *inp.cursor (row 0 without a cursor); loss [B] may be None."""
+    _dev(labels_global, torch.int32, 'labels_global'); _dev(denom, torch.float64, 'denom')
+    if not 0 <= rank < ranks:
+        raise DmfError('train_attn_fwd_bwd_ce: rank %d of %d ranks' % (rank, ranks))
+    if not inp.cursor and (labels_global.numel() < ranks * inp.B or denom.numel() < 1):
+        raise DmfError('train_attn_fwd_bwd_ce wants one label per sample of the global batch and its denominator')
+    if class_w is not None:
+        _dev(class_w, torch.float32, 'class_w')
+        if class_w.numel() != shape.K:
+            raise DmfError('class_w must hold one weight per class (%d), got %d' % (shape.K, class_w.numel()))
+    ce = CeFused(params=C.pointer(params), class_w=None if class_w is None else class_w.data_ptr(),
+                 labels_global=labels_global.data_ptr(), denom=denom.data_ptr(), ranks=ranks, rank=rank, grad_scale=grad_scale,
+                 reserved=0)
+    check(_lib.dmf_train_attn_fwd_bwd_ce(C.byref(shape), C.byref(inp), _ptr(theta), _ptr(pool_w), C.byref(ce), _ptr(logits),
+                                         _ptr(loss), _ptr(ws), _ptr(attn_ws), _ptr(adam_step_dev), _stream()))
 
 
 def pair_argmax(logits, bs, pred):

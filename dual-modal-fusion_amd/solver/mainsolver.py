@@ -20,7 +20,9 @@ defaults) around the ADAM step — the meaning `bench.py --half 1 --scaler 1` gi
 loss on both paths and in the validation pass (utils.make_loss); the fast path then trains by the unit-gradient step around
 `dmf_ce_loss` (TrainEngine(criterion=...), DESIGN §12: no native launch loop — set `steps_per_graph` > 0, the default -1
 then steps eagerly from Python; with a scheduler add `device_schedule: 1`, or the graph is re-captured every epoch —, no xgmi
-exchange, the engine shards the batches).  Keys that are all neutral change nothing.
+exchange, the engine shards the batches).  With `gmf.attention: 1` the same keys train on the fast path too: the attention
+kernel evaluates the criterion itself (`TrainEngine(criterion_in_kernel=True)`, `dmf_train_attn_fwd_bwd_ce`), and what is said
+above about `steps_per_graph`, the scheduler and the sharding holds as it stands.  Keys that are all neutral change nothing.
 `schedule.weight_decay`, `schedule.optimizer: ADAMW` and `schedule.clip_grad_norm` (all optional): torch's
 `weight_decay=`, `torch.optim.AdamW` and `clip_grad_norm_(params, max_norm)` between backward and step on both paths; the fast
 path then updates by `dmf_optim_step` on the flat gradient (no native launch loop — set `steps_per_graph` > 0, the default -1
@@ -496,6 +498,8 @@ class Solver(BaseSolver):
         comm = self.comm if plain and kw['scaler'] is None and self.criterion is None else None
         if self.criterion is not None:
             kw = dict(kw, criterion=self.criterion)
+            if self.cur_model.arch['attention']:           # ... evaluated inside the attention kernel
+                kw['criterion_in_kernel'] = True
         return TrainEngine(self.cur_model, self.scene, batch, comm=comm, **kw)
 
     def _eval_engine(self):

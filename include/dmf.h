@@ -168,6 +168,30 @@ int32_t dmf_ce_loss(const float* logits, int32_t ranks, int32_t rank, int32_t bs
                     const dmf_ce_params* params, float grad_scale, const float* scaler_state,
                     float* loss, float* dlogits, void* stream);
 
+/* The same criterion INSIDE the attention network's train step: the attention kernel evaluates class weights,
+ * label smoothing or the focal term where it otherwise forms the plain cross-entropy, so the step keeps its three launches and
+ * visits the patches once.  Two calls:
+ *   dmf_ce_denominators        denom[r] = sum over the N labels of plan row r of (double)class_w[label] (NULL: ones), r < rows —
+ *                              one 256-thread workgroup per row, in dmf_ce_loss's own summation order: the bits of the D that
+ *                              dmf_ce_loss forms for that row.  Once per plan upload (or per eager batch, rows = 1).
+ *                              Fails for NULL labels or denom, N < 1, rows < 0, K outside 1..DMF_KMAX; rows == 0 is a no-op.
+ *   dmf_train_attn_fwd_bwd_ce  dmf_train_attn_fwd_bwd with the criterion `ce`: labels_global [plan rows][ranks * B] rank-major
+ *                              and denom [plan rows], both indexed by *in->cursor (row 0 without a cursor); rank `rank` trains on
+ *                              its B rows.  logits [B, K] and the gradient are bit for bit what dmf_train_attn_fwd_bwd(labels) ->
+ *                              dmf_ce_loss(grad_scale) -> dmf_train_attn_fwd_bwd(dlogits) leave, and loss [B] (may be NULL) the
+ *                              rows dmf_ce_loss writes: N t_i / D, from a value-only launch of its kernel behind the step's three.
+ *                              Fails where dmf_train_attn_fwd_bwd or dmf_ce_loss fail, for a NULL struct, params, labels_global
+ *                              or denom, and for reserved != 0. */
+typedef struct dmf_ce_fused {
+  const dmf_ce_params* params; const float* class_w; const int32_t* labels_global; const double* denom;
+  int32_t ranks, rank; float grad_scale; int32_t reserved;
+} dmf_ce_fused;
+int32_t dmf_ce_denominators(const int32_t* labels_global, int32_t N, int32_t rows, int32_t K,
+                            const float* class_w /* NULL: ones */, double* denom /* [rows] */, void* stream);
+int32_t dmf_train_attn_fwd_bwd_ce(const dmf_shape* shape, const dmf_input* in, const float* theta, const float* pool_w,
+                                  const dmf_ce_fused* ce, float* logits, float* loss /* nullable */,
+                                  void* workspace, void* attn_workspace, int32_t* adam_step_dev, void* stream);
+
 /* 0 if the fp16-scene kernels (dmf_input.half) exist for this shape. */
 int32_t dmf_half_supported(const dmf_shape* shape);
 

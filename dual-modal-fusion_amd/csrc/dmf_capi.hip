@@ -881,6 +881,49 @@ int32_t dmf_labelmap_write(const int32_t* pred, const int32_t* xy, int32_t B, in
   return check(launch_labelmap(pred, xy, B, W, map, static_cast<hipStream_t>(stream)), "labelmap launch");
 }
 
+int32_t dmf_softmax_stats(const float* logits, int32_t B, int32_t K, const float* inv_temp, const int32_t* xy, int32_t W,
+                          int32_t* pred, float* conf, float* margin, float* entropy, void* stream) {
+  if (logits == nullptr) return fail("%s", "softmax_stats: null logits");
+  if (B < 0) return fail("%s", "softmax_stats: negative B");
+  if (K < 1 || K > KMAX) return fail("%s", "softmax_stats: 1 <= K <= DMF_KMAX");
+  if (xy != nullptr && W < 1) return fail("%s", "softmax_stats: xy needs W >= 1");
+  if (pred == nullptr && conf == nullptr && margin == nullptr && entropy == nullptr)
+    return fail("%s", "softmax_stats: every output is NULL");
+  if (B == 0) return 0;
+  const SoftmaxStatsArgs a{logits, B, K, inv_temp, xy, W, pred, conf, margin, entropy};
+  return check(launch_softmax_stats(a, static_cast<hipStream_t>(stream)), "softmax_stats launch");
+}
+
+int32_t dmf_calib_accum(const float* conf, const int32_t* pred, const int32_t* target, int32_t B, int32_t K, int32_t nbins,
+                        int64_t* hist, void* stream) {
+  if (conf == nullptr || pred == nullptr || target == nullptr || hist == nullptr) return fail("%s", "calib_accum: null argument");
+  if (nbins < 1 || nbins > 1024) return fail("%s", "calib_accum: 1 <= nbins <= 1024");
+  if (B < 0) return fail("%s", "calib_accum: negative B");
+  if (B == 0) return 0;
+  return check(launch_calib_accum(conf, pred, target, B, K, nbins, reinterpret_cast<unsigned long long*>(hist),
+                                  static_cast<hipStream_t>(stream)), "calib_accum launch");
+}
+
+int32_t dmf_temperature_init(double* state, void* stream) {
+  if (state == nullptr) return fail("%s", "temperature_init: null state");
+  return check(launch_temperature_init(state, static_cast<hipStream_t>(stream)), "temperature_init launch");
+}
+
+int64_t dmf_temperature_workspace_bytes(int32_t N) {
+  if (N < 0) return -1;
+  return ((int64_t)N + 255) / 256 * 3 * (int64_t)sizeof(double);
+}
+
+int32_t dmf_temperature_step(const float* logits, const int32_t* labels, int32_t N, int32_t K, double* state, void* workspace,
+                             int32_t update, void* stream) {
+  if (logits == nullptr || labels == nullptr || state == nullptr) return fail("%s", "temperature_step: null logits, labels or state");
+  if (N < 1) return fail("%s", "temperature_step: N must be positive");
+  if (K < 1 || K > KMAX) return fail("%s", "temperature_step: 1 <= K <= DMF_KMAX");
+  if (workspace == nullptr) return fail("%s", "temperature_step: null workspace");
+  return check(launch_temperature_step(logits, labels, N, K, state, static_cast<double*>(workspace), update != 0,
+                                       static_cast<hipStream_t>(stream)), "temperature_step launch");
+}
+
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream) {
   if (pan == nullptr || out == nullptr) return fail("%s", "null argument");
   if (H <= 0 || W <= 0 || pitch < 4 * W) return fail("%s", "bad pan2ms geometry");

@@ -194,6 +194,21 @@ hipError_t launch_band_mean(const float* x, int layout, int64_t n_img, int64_t n
 hipError_t launch_confusion(const int32_t* pred, const int32_t* target, int B, int K, unsigned long long* matrix, hipStream_t st);
 hipError_t launch_labelmap(const int32_t* pred, const int32_t* xy, int B, int W, int32_t* map, hipStream_t st);
 
+// calibrated confidence (dmf_calib.hip)
+struct SoftmaxStatsArgs {
+  const float* logits; int B, K;
+  const float* inv_temp;   // nullable device [1]: beta = 1 / T (NULL: 1)
+  const int32_t* xy; int W;   // nullable [B][2]: row i writes index x * W + y instead of i
+  int32_t* pred; float* conf; float* margin; float* entropy;   // each nullable
+};
+hipError_t launch_softmax_stats(const SoftmaxStatsArgs& a, hipStream_t st);
+hipError_t launch_calib_accum(const float* conf, const int32_t* pred, const int32_t* target, int B, int K, int nbins,
+                              unsigned long long* hist, hipStream_t st);
+hipError_t launch_temperature_init(double* state, hipStream_t st);
+// partial: [(N + 255) / 256][3] doubles (dmf_temperature_workspace_bytes)
+hipError_t launch_temperature_step(const float* logits, const int32_t* labels, int N, int K, double* state, double* partial,
+                                   int update, hipStream_t st);
+
 // per-sample classification losses of the unit-gradient step (dmf_loss.hip)
 struct CeArgs {
   const float* logits;   // [bs_r][K], this rank's rows

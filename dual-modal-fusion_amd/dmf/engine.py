@@ -1139,6 +1139,107 @@ class EvalEngine(_ShardedEval):
     def _chunk_pred(self, xy):
         return self.predict(xy)[1]
 
+    # ------------------------------------------------------------------ calibrated confidence
+    # One device only: the solvers refuse the keys for data-parallel runs.  Everything works on `predict`'s logits, so the
+    # late-fusion and the attention network share it.
+    def _beta(self, inv_temp):
+        """inv_temp (None, a number beta = 1 / T > 0, or a device float32 [1]) -> None or the device float32 [1]."""
+        if inv_temp is None or torch.is_tensor(inv_temp):
+            return inv_temp
+        if not (inv_temp > 0 and np.isfinite(inv_temp)):
+            raise lib.DmfError('inv_temp %r is not a finite number > 0' % (inv_temp,))
+        return torch.tensor([float(inv_temp)], dtype=torch.float32, device=self.scene.device)
+
+    def confidence_maps(self, xy_all, H, W, inv_temp=None):
+        """-> (label map [H, W] int32, planes [3, H, W] float32: confidence, margin, entropy of the softmax at beta = inv_temp)
+        of all given pixels, 0 elsewhere.  `label_map`'s chunks and launches, with one dmf_softmax_stats per chunk in the
+        place of dmf_labelmap_write: the label map is the one `label_map` gives."""
+        dev = self.scene.device
+        beta = self._beta(inv_temp)
+        host, xy_all = self._whole_set(None, xy_all)
+        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
+            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))      # the kernel writes map[x * W + y]
+        label_map = torch.zeros(H, W, dtype=torch.int32, device=dev)
+        planes = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
+        for i in range(0, xy_all.shape[0], self.B):
+            xy = xy_all[i:i + self.B]
+            lib.softmax_stats(self.predict(xy)[0], pred=label_map, conf=planes[0], margin=planes[1], entropy=planes[2],
+                              inv_temp=beta, xy=xy, W=W)
+        return label_map, planes
+
+    def collect_logits(self, xy_all, labels_all=None):
+        """-> the logits of all given pixels in ONE device tensor [N, K] (and their labels as device int32 [N])."""
+        _, *rows = self._whole_set(None, xy_all, *(() if labels_all is None else (labels_all,)))
+        xy_all = rows[0]
+        out = torch.empty(xy_all.shape[0], self.net.arch['K'], device=self.scene.device)
+        for i in range(0, xy_all.shape[0], self.B):
+            out[i:i + self.B].copy_(self.predict(xy_all[i:i + self.B])[0])
+        return out if labels_all is None else (out, rows[1])
+
+    def calibration_of(self, logits, labels, nbins, inv_temp=None, hist=None):
+        """hist [nbins, 3] int64 (+)= the reliability histogram of device logits [n, K] / labels [n] at beta = inv_temp."""
+        n, K = logits.shape
+        dev = self.scene.device
+        if hist is None:
+            hist = torch.zeros(nbins, 3, dtype=torch.int64, device=dev)
+        if n:
+            conf, pred = torch.empty(n, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+            lib.softmax_stats(logits, pred=pred, conf=conf, inv_temp=self._beta(inv_temp))
+            lib.calib_accum(conf, pred, labels, K, hist)
+        return hist
+
+    def calibration(self, xy_all, labels_all, nbins, inv_temp=None):
+        """Reliability histogram hist [nbins, 3] int64 over all given pixels (rows, hits, confidence sum in units of 2^-32 per
+        confidence bin; dmf_softmax_stats + dmf_calib_accum per chunk).  Labels outside [0, K) are skipped."""
+        beta = self._beta(inv_temp)
+        _, xy_all, labels_all = self._whole_set(None, xy_all, labels_all)
+        hist = torch.zeros(nbins, 3, dtype=torch.int64, device=self.scene.device)
+        for i in range(0, xy_all.shape[0], self.B):
+            self.calibration_of(self.predict(xy_all[i:i + self.B])[0], labels_all[i:i + self.B], nbins, beta, hist)
+        return hist
+
+    def _temp_ws(self, n):
+        """The fit's workspace, allocated on first use and grown on demand."""
+        need = lib.temperature_workspace_bytes(n)
+        if getattr(self, '_temp_workspace', None) is None or self._temp_workspace.numel() < need:
+            self._temp_workspace = torch.empty(max(need, 24), dtype=torch.uint8, device=self.scene.device)
+        return self._temp_workspace
+
+    def nll_of(self, logits, labels, inv_temp=None):
+        """-> device float64 [TEMP_DOUBLES]: dmf_temperature_step's evaluation (update = 0) of logits [n, K] / labels [n] at
+        beta = inv_temp; [1] is the NLL summed over the rows."""
+        state = torch.empty(lib.TEMP_DOUBLES, dtype=torch.float64, device=self.scene.device)
+        lib.temperature_init(state)
+        beta = self._beta(inv_temp)
+        if beta is not None:
+            state[0:1].copy_(beta)
+        lib.temperature_step(logits, labels, state, self._temp_ws(logits.shape[0]), update=False)
+        return state
+
+    def fit_temperature_of(self, logits, labels, steps=40):
+        """The temperature fit on device logits [n, K] / labels [n] -> float64 numpy [3, TEMP_DOUBLES], read once: the
+        evaluation at beta = 1, the state after `steps` safeguarded Newton steps, the evaluation at the fitted beta."""
+        if logits.shape[0] < 1:
+            raise lib.DmfError('fit_temperature: no pixels to fit on')
+        ws = self._temp_ws(logits.shape[0])
+        out = torch.empty(3, lib.TEMP_DOUBLES, dtype=torch.float64, device=self.scene.device)
+        at_one, state, at_fit = out[0], out[1], out[2]
+        for s in (at_one, state):
+            lib.temperature_init(s)
+        lib.temperature_step(logits, labels, at_one, ws, update=False)
+        for _ in range(steps):
+            lib.temperature_step(logits, labels, state, ws, update=True)
+        at_fit.copy_(state)
+        lib.temperature_step(logits, labels, at_fit, ws, update=False)
+        return out.cpu().numpy()
+
+    def fit_temperature(self, xy_all, labels_all, steps=40):
+        """Temperature scaling on the given split (the validation split): `steps` steps of dmf_temperature_step enqueued at
+        once -> the state (float64 numpy [TEMP_DOUBLES]: beta, nll, g, h, lo, hi, steps taken, reserved), read once.
+        `last_fit` keeps all three rows of `fit_temperature_of`."""
+        self.last_fit = self.fit_temperature_of(*self.collect_logits(xy_all, labels_all), steps=steps)
+        return self.last_fit[1]
+
 
 # ====================================================================== stage 2 of the two-stage path
 class QuaScene:

@@ -123,6 +123,11 @@ def _load():
         'dmf_band_mean': (i32, [vp, i32, i64, i64, i32, vp, vp]),
         'dmf_confusion_accum': (i32, [vp, vp, i32, i32, vp, vp]),
         'dmf_labelmap_write': (i32, [vp, vp, i32, i32, vp, vp]),
+        'dmf_softmax_stats': (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        'dmf_calib_accum': (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        'dmf_temperature_init': (i32, [vp, vp]),
+        'dmf_temperature_workspace_bytes': (i64, [i32]),
+        'dmf_temperature_step': (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
         'dmf_valid_accum': (i32, [vp, i32, vp, vp]),
         'dmf_keep_best': (i32, [vp, vp, vp, i32, vp, vp, i64, vp, vp]),
         'dmf_pan2ms': (i32, [vp, i32, i32, i32, vp, vp]),
@@ -676,6 +681,75 @@ def confusion_accum(pred, target, K, matrix):
 
 def labelmap_write(pred, xy, W, label_map):
     check(_lib.dmf_labelmap_write(_ptr(pred), _ptr(xy), pred.numel(), W, _ptr(label_map), _stream()))
+
+
+def softmax_stats(logits, pred=None, conf=None, margin=None, entropy=None, inv_temp=None, xy=None, W=0):
+    """Argmax (first maximal index), confidence, margin and entropy of every row of logits [B, K] (dmf_softmax_stats), each
+    output optional.  inv_temp: device float32 [1], beta = 1 / T (None: 1).  Without xy row i writes element i of the
+    outputs; with xy [B, 2] int32 it writes element x * W + y of maps the caller has sized and whose bounds it has checked."""
+    _dev(logits, torch.float32, 'logits')
+    if logits.dim() != 2:
+        raise DmfError('softmax_stats wants logits [B, K]')
+    B, K = logits.shape
+    if inv_temp is not None:
+        _dev(inv_temp, torch.float32, 'inv_temp')
+        if inv_temp.numel() < 1:
+            raise DmfError('inv_temp holds one float')
+    if xy is not None:
+        _dev(xy, torch.int32, 'xy')
+        if xy.dim() != 2 or tuple(xy.shape) != (B, 2):
+            raise DmfError('xy must be [B, 2]')
+    for t, dt, name in ((pred, torch.int32, 'pred'), (conf, torch.float32, 'conf'), (margin, torch.float32, 'margin'),
+                        (entropy, torch.float32, 'entropy')):
+        if t is not None:
+            _dev(t, dt, name)
+            if xy is None and t.numel() < B:
+                raise DmfError('%s must hold one element per row' % name)
+    check(_lib.dmf_softmax_stats(_ptr(logits), B, K, _ptr(inv_temp), _ptr(xy), W, _ptr(pred), _ptr(conf), _ptr(margin),
+                                 _ptr(entropy), _stream()))
+
+
+def calib_accum(conf, pred, target, K, hist):
+    """hist [nbins, 3] int64 += the reliability histogram of conf / pred / target [B] (dmf_calib_accum): rows, hits and the
+    confidence sum in units of 2^-32 per bin; rows whose target lies outside [0, K) are skipped."""
+    _dev(conf, torch.float32, 'conf'); _dev(pred, torch.int32, 'pred'); _dev(target, torch.int32, 'target')
+    _dev(hist, torch.int64, 'hist')
+    if hist.dim() != 2 or hist.shape[1] != 3:
+        raise DmfError('hist must be [nbins, 3]')
+    B = conf.numel()
+    if pred.numel() < B or target.numel() < B:
+        raise DmfError('calib_accum: pred and target must hold one element per confidence')
+    check(_lib.dmf_calib_accum(_ptr(conf), _ptr(pred), _ptr(target), B, K, hist.shape[0], _ptr(hist), _stream()))
+
+
+TEMP_DOUBLES = 8                             # DMF_TEMP_DOUBLES: beta, nll, g, h, lo, hi, steps taken, reserved
+
+
+def temperature_init(state):
+    """state [TEMP_DOUBLES] float64 on the device <- beta = 1 in the bracket [2^-6, 2^6] (dmf_temperature_init)."""
+    _dev(state, torch.float64, 'temperature state')
+    if state.numel() < TEMP_DOUBLES:
+        raise DmfError('temperature state needs %d doubles' % TEMP_DOUBLES)
+    check(_lib.dmf_temperature_init(_ptr(state), _stream()))
+
+
+def temperature_workspace_bytes(N):
+    n = _lib.dmf_temperature_workspace_bytes(N)
+    if n < 0:
+        raise DmfError('dmf_temperature_workspace_bytes failed')
+    return n
+
+
+def temperature_step(logits, labels, state, ws, update=True):
+    """One step of the temperature fit on logits [N, K] / labels [N] int32 (dmf_temperature_step): nll, g and h at state's beta,
+    then with `update` the safeguarded Newton step.  ws: uint8, at least temperature_workspace_bytes(N)."""
+    _dev(logits, torch.float32, 'logits'); _dev(labels, torch.int32, 'labels'); _dev(state, torch.float64, 'temperature state')
+    if logits.dim() != 2 or labels.numel() < logits.shape[0] or state.numel() < TEMP_DOUBLES:
+        raise DmfError('temperature_step wants logits [N, K], one label per row and a state of %d doubles' % TEMP_DOUBLES)
+    N, K = logits.shape
+    if ws is None or ws.numel() * ws.element_size() < temperature_workspace_bytes(N):
+        raise DmfError('temperature_step: the workspace is smaller than temperature_workspace_bytes(%d)' % N)
+    check(_lib.dmf_temperature_step(_ptr(logits), _ptr(labels), N, K, _ptr(state), _ptr(ws), int(bool(update)), _stream()))
 
 
 def valid_accum(loss, n, acc):

@@ -48,6 +48,15 @@ copy of the weights, torch's `AveragedModel`, updated after every optimiser step
 the averaged weights (`_on_average`), `<t>_weights.pth` holds those of the best epoch (in an epoch block dmf_keep_best is handed
 them), so test() / color() classify with them; `<t>_curweights.pth` keeps the raw weights and the optimiser and gains the key
 `averaged`, which test() loads with `save_best: 0`.  toStageSolver refuses the keys.
+`test.calibration: 1`, `test.calibration_bins`, `test.temperature: none | fit | T` and `color.confidence: 1` (all optional, DESIGN
+§17): after the confusion matrix and over the same pixels `test()` fills the reliability histogram, ECE, MCE and the mean NLL
+(`self.calibration`, `<t>_calibration.json`), at the temperature T — a number, or with `fit` the temperature-scaling fit on
+the VALIDATION split (`_temperature_used`, once per trained model) —, and with T != 1 the same block `before` scaling;
+`color()` also writes `<t>_confidence_{1,2}.npy` (float32 [3, H, W]: confidence, margin, entropy; 0 where nothing is coloured)
+and `<t>_conf_{1,2}.png` (8-bit grey, round(255 conf)), composed as the label maps are.  Fast path: dmf_softmax_stats /
+dmf_calib_accum / dmf_temperature_step on the eval engine's logits, the label maps written by dmf_softmax_stats in
+dmf_labelmap_write's place; drop-in path: torch ops in float64; both through utils/calibration.py.  `indicator()` and its export
+are untouched; toStageSolver and data-parallel runs refuse the keys.  Neutral values change nothing.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -59,6 +68,7 @@ helpers (:110-136,211-441) are out of scope; `nohup: 1` does not crash (referenc
 import contextlib
 import importlib
 import itertools
+import json
 import time
 import types
 
@@ -68,6 +78,7 @@ from PIL import Image
 from tqdm import tqdm
 
 from solver.basesolver import BaseSolver
+from utils import calibration as calib
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
                          make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
@@ -85,6 +96,7 @@ class Solver(BaseSolver):
     engine_loss = 'Criterion'                            # the schedule.loss that the fast path's train engine implements
     epoch_blocks = True                                  # `train.epoch_block` > 1 has a block form for this stage
     weight_averaging = True                              # `schedule.weight_average` is in scope for this stage
+    calibrated = True                                    # `test.calibration` / `test.temperature` / `color.confidence` are in scope
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
@@ -97,6 +109,11 @@ class Solver(BaseSolver):
         if self.averaging is not None and not self.weight_averaging:
             raise ValueError('schedule.weight_average, schedule.average_decay and schedule.average_start are out of scope for %s: '
                              'set weight_average to none' % type(self).__name__)
+        self.calib = calib.calibration_keys(cfg)       # test.calibration / calibration_bins / temperature, color.confidence
+        if calib.keys_in_use(self.calib) and not self.calibrated:
+            raise ValueError('%s is out of scope for %s (its prediction is the pair argmax of two streams): leave the key out'
+                             % (calib.keys_in_use(self.calib)[0], type(self).__name__))
+        self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
         self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken
         self.cfg, self.rank, self.world = cfg, 0, 1
         self._epoch_block()                            # (a stage without a block form refuses the key before anything is read)
@@ -141,6 +158,7 @@ class Solver(BaseSolver):
         rank of a data-parallel run, which all draw the same split)."""
         super().dataloader()
         self._valid_dev = None
+        self._temp = None
         if criterion_keys(self.cfg):
             self.train_labels = self.index_dataset.label[np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)]
             self.criterion = criterion_spec(self.cfg, self.train_labels)
@@ -185,6 +203,7 @@ class Solver(BaseSolver):
     def train(self):
         E = self._epoch_block()
         time1 = time.time()
+        self._temp = None                              # (a fitted temperature belongs to the weights it was fitted on)
         if not self.cfg['train']['pretrained']:
             self.init_model()
         self.cur_model = self.model.to(self.DEVICE)
@@ -603,6 +622,7 @@ class Solver(BaseSolver):
 
     def test(self):
         time1 = time.time()
+        self._calibration_scope()
         self._ensure_model()
         self._load_weights(self.cfg['train']['save_best'])
         self.cur_model.eval()
@@ -611,6 +631,9 @@ class Solver(BaseSolver):
             matrix = self._test_matrix_fast(whole) if self.fast else self._test_matrix_dropin(whole)
         self.test_time = time.time() - time1
         self.test_matrix = matrix.astype(np.float64)
+        if self.calib['calibration']:
+            with torch.no_grad():
+                self._calibrate(whole)
         if self.rank == 0:
             self.indicator()
         else:
@@ -620,9 +643,13 @@ class Solver(BaseSolver):
     def _test_matrix_fast(self, whole):
         """The whole split in evaluation chunks of the engine's own size (data parallel: every rank classifies its part of
         the pixels, the matrices are summed), or the first batch alone, which every rank classifies whole."""
+        xy, lab = self._test_pixels(whole)
+        return self.eval_engine.confusion(xy, lab, process_group=self.process_group if whole else None).cpu().numpy()
+
+    def _test_pixels(self, whole):
+        """(xy [n, 2], labels [n]) int32 on the host: the pixels test() classifies on the fast path."""
         parts = [self._xy_labels(b) for b in (self.test_index_loader if whole else itertools.islice(self.test_index_loader, 1))]
-        return self.eval_engine.confusion(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
-                                          process_group=self.process_group if whole else None).cpu().numpy()
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
     def _test_matrix_dropin(self, whole):
         K = self.cfg['Categories_Number']
@@ -632,8 +659,83 @@ class Solver(BaseSolver):
             np.add.at(matrix, (pred.cpu().numpy(), target.long().numpy()), 1)            # test_matrix[pred][target] += 1
         return matrix
 
+    # ------------------------------------------------------------------ calibration (test.calibration, test.temperature)
+    def _calibration_scope(self):
+        """Data-parallel runs refuse the keys (the histogram and the fit are not sharded), as `_epoch_block` refuses its key."""
+        if calib.keys_in_use(self.calib) and self.world > 1:
+            raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out'
+                             % (calib.keys_in_use(self.calib)[0], self.world))
+
+    @staticmethod
+    def _beta(T):
+        """beta = 1 / T as the float32 that the kernels read, on both paths."""
+        return float(np.float32(1.0 / T))
+
+    def _dropin_logits(self, loader):
+        """(logits [n, K] float64, labels [n]) as numpy over the batches of a materialising loader."""
+        out = [(self.cur_model(d1.to(self.DEVICE), d2.to(self.DEVICE)).detach().double().cpu().numpy(), np.asarray(t))
+               for d1, d2, t, _, _ in loader]
+        return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out]).astype(np.int64)
+
+    def _temperature_used(self):
+        """(T, fit block or None) of `test.temperature`, decided once per trained model: a number as it stands, none -> 1, fit ->
+        temperature scaling on the VALIDATION split: 40 safeguarded Newton steps in beta = 1 / T, on the device without a host
+        round trip (EvalEngine.fit_temperature_of) or on the drop-in path the same rule on the host."""
+        if self._temp is None:
+            t = self.calib['temperature']
+            if t != 'fit':
+                self._temp = (1.0 if t is None else t, None)
+            else:
+                with torch.no_grad():
+                    if self.fast:
+                        xy, lab = self._valid_split()
+                        at_one, state, at_fit = self.eval_engine.fit_temperature_of(*self.eval_engine.collect_logits(xy, lab),
+                                                                                    steps=calib.FIT_STEPS)
+                        n, beta, steps, nll1, nllT = int(lab.shape[0]), float(state[0]), int(state[6]), float(at_one[1]), float(at_fit[1])
+                    else:
+                        logits, lab = self._dropin_logits(self.valid_loader)
+                        f = calib.fit_temperature(logits, lab)
+                        n, beta, steps = len(lab), f['beta'], f['steps']
+                        nll1, nllT = calib.nll_terms(logits, lab, 1.0)[0], calib.nll_terms(logits, lab, beta)[0]
+                if n < 1:
+                    raise ValueError('test.temperature: fit needs a validation split')
+                self._temp = (1.0 / beta, dict(n=n, nll_at_1=nll1 / n, nll_at_T=nllT / n, beta=beta, steps=steps))
+        return self._temp
+
+    def _calibration_block(self, logits, labels, T):
+        """The block of utils.calibration.summary at temperature T, from the logits of the test pixels: device tensors on the
+        fast path, numpy on the drop-in path."""
+        bins, beta = self.calib['bins'], self._beta(T)
+        if self.fast:
+            hist = self.eval_engine.calibration_of(logits, labels, bins, beta).cpu().numpy()
+            nll = float(self.eval_engine.nll_of(logits, labels, beta)[1].item()) if logits.shape[0] else 0.0
+        else:
+            K = logits.shape[1]
+            pred, st = calib.softmax_stats(torch.from_numpy(logits), beta)
+            hist = calib.histogram(st[0].numpy(), pred.numpy(), labels, K, bins)
+            nll = calib.nll_terms(logits, labels, beta)[0]
+        return calib.summary(hist, nll, T)
+
+    def _calibrate(self, whole):
+        """`self.calibration` and `<t>_calibration.json` over the pixels of the confusion matrix."""
+        T, fit = self._temperature_used()
+        if self.fast:
+            logits, labels = self.eval_engine.collect_logits(*self._test_pixels(whole))
+        else:
+            logits, labels = self._dropin_logits(self.test_loader if whole else itertools.islice(self.test_loader, 1))
+        block = self._calibration_block(logits, labels, T)
+        if T != 1.0:
+            block['before'] = self._calibration_block(logits, labels, 1.0)
+        if fit is not None:
+            block['fit'] = fit
+        self.calibration = block
+        if self.rank == 0:
+            with open(self.cfg['RESULT_output'] + str(self.time) + '_calibration.json', 'w') as f:
+                json.dump(block, f, indent=1)
+
     # ------------------------------------------------------------------ colour
     def color(self):
+        self._calibration_scope()
         self._ensure_model()
         self._load_weights(True)
         self.cur_model.eval()
@@ -641,17 +743,36 @@ class Solver(BaseSolver):
         H, W = int(size[0]), int(size[1])
         lut = np.asarray(self.cfg['DATA_DICT'][self.cfg['data_city']]['color'], dtype=np.uint8)
         label_map = self._label_map_fast if self.fast else self._label_map_dropin
-        maps = []
+        confident = self.calib['confidence']           # color.confidence: the label maps come with their confidence planes
+        if confident:
+            beta = self._beta(self._temperature_used()[0])
+            conf_map = self._confidence_map_fast if self.fast else self._confidence_map_dropin
+        maps, planes = [], []
         with torch.no_grad():
             for use, loaders in ((self.cfg['color']['supervised'], (self.color_index_loader1, self.color_loader1)),
                                  (self.cfg['color']['unsupervised'], (self.color_index_loader2, self.color_loader2))):
-                maps.append(label_map(loaders, H, W) if use else np.zeros([H, W], dtype=np.int32))
+                if use and confident:
+                    m, p = conf_map(loaders, H, W, beta)
+                    maps.append(m); planes.append(p)
+                else:
+                    maps.append(label_map(loaders, H, W) if use else np.zeros([H, W], dtype=np.int32))
+                    if confident:
+                        planes.append(np.zeros([3, H, W], dtype=np.float32))
         label_np1 = maps[0]
         label_np2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
         self.label_maps = (label_np1, label_np2)
         if self.cfg['color']['supervised'] and self.rank == 0:
             Image.fromarray(lut[label_np1]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_1.png")
             Image.fromarray(lut[label_np2]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_2.png")
+        if confident:
+            # map 2 takes the unsupervised pixel where its label is not 0, as label_np2 does
+            conf2 = np.where(maps[1][None] != 0, planes[1], planes[0]) if self.cfg['color']['unsupervised'] else planes[0]
+            self.confidence_maps = (planes[0], conf2)
+            if self.cfg['color']['supervised'] and self.rank == 0:
+                for k, p in enumerate(self.confidence_maps, 1):
+                    np.save(self.cfg['RESULT_output'] + str(self.time) + '_confidence_%d.npy' % k, p)
+                    grey = np.round(255.0 * p[0].astype(np.float64)).clip(0, 255).astype(np.uint8)
+                    Image.fromarray(grey).save(self.cfg['RESULT_output'] + str(self.time) + '_conf_%d.png' % k)
 
     def _label_map_fast(self, loaders, H, W):
         """All pixels of the index-only loader, in evaluation chunks of the engine's own size."""
@@ -664,6 +785,20 @@ class Solver(BaseSolver):
             pred, _, x, y = self._predict_dropin(batch)
             m[np.asarray(x), np.asarray(y)] = pred.cpu().numpy()
         return m
+
+    def _confidence_map_fast(self, loaders, H, W, beta):
+        """`_label_map_fast` with the confidence planes [3, H, W]: one dmf_softmax_stats per chunk writes all four maps."""
+        m, p = self.eval_engine.confidence_maps(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W, beta)
+        return m.cpu().numpy(), p.cpu().numpy()
+
+    def _confidence_map_dropin(self, loaders, H, W, beta):
+        m, p = np.zeros([H, W], dtype=np.int32), np.zeros([3, H, W], dtype=np.float32)
+        for data1, data2, _, x, y in loaders[1]:
+            logits = self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE))
+            x, y = np.asarray(x), np.asarray(y)
+            m[x, y] = logits.data.max(1)[1].cpu().numpy()                  # (the prediction of `_predict_dropin`)
+            p[:, x, y] = calib.softmax_stats(logits, beta)[1].cpu().numpy().astype(np.float32)
+        return m, p
 
     def run(self):
         while self.time < self.TIME:

@@ -56,6 +56,7 @@ class toStageSolver(Solver):
     engine_loss = 'qua_loss'
     epoch_blocks = False                                 # (its validation is a batch-coupled loss read back per batch)
     weight_averaging = False                             # (schedule.weight_average is out of scope here: refused by name)
+    calibrated = False                                   # (test.calibration, test.temperature, color.confidence: refused by name)
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -477,6 +477,40 @@ int32_t dmf_keep_best(double* acc, double* best, int32_t* best_epoch, int32_t ep
 /* Replaces `label_np[x][y] = pred` (mainsolver.py:171-173,182-183): map [H, W] int32. */
 int32_t dmf_labelmap_write(const int32_t* pred, const int32_t* xy, int32_t B, int32_t W, int32_t* map, void* stream);
 
+/* ---- calibrated confidence: how far a pixel's class can be trusted, from the logits [B, K] that the forward
+ * entry points leave on the device.  New symbols at an unchanged DMF_VERSION: detect them by name.
+ *
+ * Per row, with beta = inv_temp[0] (device; NULL: 1) and m the row maximum: pred = the FIRST maximal index (the rule of the
+ * forward entry points' own pred); t_c = (l_c - m) * beta in fp32, e_c = expf(t_c), Z = sum e_c in a fixed order;
+ * conf = 1 / Z; margin = (1 - e2) / Z with e2 the largest e_c over c != pred (K == 1: 0); entropy = max(0, logf(Z) -
+ * (sum e_c t_c) / Z), a term with e_c == 0 counting as 0.  Each output may be NULL, not all of them.  xy == NULL: row i
+ * writes index i; else xy [B, 2] and row i writes index x * W + y (the addressing of the label-map entry point below, whose
+ * launch this one replaces where the confidence is wanted too).  Finite logits and beta > 0 are the caller's contract.
+ * Fails on NULL logits, B < 0, K outside 1..DMF_KMAX, xy with W < 1, and when every output is NULL; B == 0 is a no-op. */
+int32_t dmf_softmax_stats(const float* logits, int32_t B, int32_t K, const float* inv_temp, const int32_t* xy, int32_t W,
+                          int32_t* pred, float* conf, float* margin, float* entropy, void* stream);
+/* The reliability histogram hist [nbins][3] int64 (the caller zeroes it): a row whose target lies outside [0, K) is skipped,
+ * else b = min(nbins - 1, (int)(conf * (float)nbins)) and hist[b][0] += 1, hist[b][1] += (pred == target),
+ * hist[b][2] += llrint((double)conf * 2^32): integers, so the result is exact and independent of the order.
+ * Fails on a NULL argument, nbins outside 1..1024 and B < 0; B == 0 is a no-op. */
+int32_t dmf_calib_accum(const float* conf, const int32_t* pred, const int32_t* target, int32_t B, int32_t K, int32_t nbins,
+                        int64_t* hist, void* stream);
+/* Temperature scaling (Guo et al. 2017) without a host round trip.  state = DMF_TEMP_DOUBLES doubles on the device:
+ * [0] beta = 1 / T, [1] nll, [2] g = d nll / d beta, [3] h = d2 nll / d beta2 (sums over the rows, at the beta the step
+ * started from), [4] lo, [5] hi, [6] steps taken, [7] reserved.  The init sets beta = 1, lo = 2^-6, hi = 2^6.
+ * A step is two launches: (a) workgroups of 256 rows form, in double, with d_c = l_c - m, Z = sum exp(beta d_c) and
+ * p_c = exp(beta d_c) / Z: nll_i = ln Z - beta d_y, g_i = sum p_c d_c - d_y, h_i = sum p_c d_c^2 - (sum p_c d_c)^2 (a row whose
+ * label lies outside [0, K) adds nothing) and leave their three sums, taken in a fixed tree order, in `workspace`; (b) one
+ * workgroup adds those in index order and stores nll, g, h.  With update != 0 it then takes the safeguarded Newton step:
+ * g > 0 -> hi = beta, else lo = beta; beta <- beta - g / h, or sqrt(lo hi) if h <= 0 or that candidate is not finite or not
+ * strictly inside (lo, hi); steps += 1.  update == 0 only evaluates (the NLL of a split at a given beta).
+ * The workspace query needs N >= 0 (else -1); the step fails on NULL logits, labels, state or workspace, N < 1 and K outside 1..DMF_KMAX. */
+#define DMF_TEMP_DOUBLES 8
+int32_t dmf_temperature_init(double* state, void* stream);
+int64_t dmf_temperature_workspace_bytes(int32_t N);
+int32_t dmf_temperature_step(const float* logits, const int32_t* labels, int32_t N, int32_t K, double* state, void* workspace,
+                             int32_t update, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

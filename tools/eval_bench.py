@@ -3,6 +3,9 @@ and .confusion over all pixels of a synthetic scene, for several evaluation chun
 
     python tools/eval_bench.py [size] [bands] [aux_bands] [width]      default: 512 224 3 32 (BASELINE configs[3] scene)
     python tools/eval_bench.py qua [size]                              stage 2: pair prediction over four 4-band streams, 16x16 patches
+    python tools/eval_bench.py [size ...] --confidence                 EvalEngine.confidence_maps (label map + confidence, margin and
+                                                                       entropy planes) against EvalEngine.label_map, whose
+                                                                       code this feature leaves as it was: five alternated runs each
 """
 import os
 import sys
@@ -48,9 +51,31 @@ def main_qua():
               % (B, n, (t1 - t0) * 1e3, n / (t1 - t0) / 1e6, bool(torch.equal(lm, ref_map))), flush=True)
 
 
+def confidence_runs(ev, xy, size, runs=5):
+    """label_map and confidence_maps over all pixels, alternated `runs` times after one warm-up of each -> two lists of ms."""
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+    timed(lambda: ev.label_map(xy, size, size)); timed(lambda: ev.confidence_maps(xy, size, size))
+    plain, conf = [], []
+    for _ in range(runs):
+        ms, lm = timed(lambda: ev.label_map(xy, size, size))
+        plain.append(ms)
+        ms, (cm, planes) = timed(lambda: ev.confidence_maps(xy, size, size))
+        conf.append(ms)
+        assert torch.equal(lm, cm)
+    return plain, conf
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == 'qua':
         return main_qua()
+    confidence = '--confidence' in sys.argv
+    if confidence:
+        sys.argv.remove('--confidence')
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     C = int(sys.argv[2]) if len(sys.argv) > 2 else 224
     C2 = int(sys.argv[3]) if len(sys.argv) > 3 else 3
@@ -70,6 +95,13 @@ def main():
     n = xy.shape[0]
     bytes_per_patch = 4.0 * (P * P * C + P * P * C2)
     ref_map = None
+    if confidence:
+        for B in (4096, 16384):
+            plain, conf = confidence_runs(EvalEngine(net, scene, B), xy, size)
+            print('chunk %6d, %d pixels, ms per pass: label_map %s (%.2f .. %.2f) | confidence_maps %s (%.2f .. %.2f); label maps identical'
+                  % (B, n, ' '.join('%.2f' % t for t in plain), min(plain), max(plain), ' '.join('%.2f' % t for t in conf),
+                     min(conf), max(conf)), flush=True)
+        return
     for B in (256, 1024, 4096, 16384):
         ev = EvalEngine(net, scene, B)
         ev.label_map(xy[:B * 2], size, size)

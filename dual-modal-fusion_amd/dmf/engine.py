@@ -136,6 +136,72 @@ class Scene:
         cfg = {'patch_size': patch, 'scale': scale}
         return cls(data_padding(primary_raw, cfg, 'ms'), data_padding_aux(aux_raw, cfg), device, half=half)
 
+    def atlas(self, patch, scale, ops):
+        """-> the `AtlasScene` of this scene for patches of `patch` pixels, aux scale `scale` and the variants `ops` (see
+        dmf.augment: a name of augment.OPS or a list of 0..7 that starts with 0).  Two dmf_scene_atlas launches, fp32 or fp16
+        primary scene alike.  This scene's tensors are RELEASED afterwards (A and B become None): the atlas holds the untouched
+        scene in slot 0 and replaces it.  Peak memory is source plus atlas; resident afterwards is len(ops) x the scene, or more
+        for a non-square scene with a transposed op, whose slots are squares of the longer side."""
+        out = AtlasScene(self, patch, scale, ops)
+        self.A = self.B = None
+        return out
+
+
+class AtlasScene(Scene):
+    """A `Scene` whose A and B are scene atlases: the variants `ops` of the padded scenes, stacked along the row
+    axis, slot s = variant ops[s], slot 0 the untouched scene at the origin.  Every engine takes it as it takes a Scene:
+    coordinates that are not mapped keep their meaning, and a patch of variant ops[s] is the ordinary patch at `map_xy(xy, s)`.
+      A [V * R, Wq, C], B [V * S * R, S * Wq, C2];  ops, slot_rows = R, extent = (Hp, Wp), patch, scale."""
+
+    def __init__(self, scene, patch, scale, ops):
+        from . import augment
+        self.ops = augment.ops_of(ops, 'atlas')
+        self.patch, self.scale = int(patch), int(scale)
+        self.half, self.device = scene.half, scene.device
+        Hp, Wp = scene.A.shape[:2]
+        S = self.scale
+        if Hp < self.patch or Wp < self.patch or scene.B.shape[0] < S * Hp or scene.B.shape[1] < S * Wp:
+            raise lib.DmfError('atlas: the aux scene %s does not hold %d x the primary scene %s, or the patch %d does not fit'
+                               % (tuple(scene.B.shape), S, tuple(scene.A.shape), self.patch))
+        self.extent = (Hp, Wp)
+        R, Wq = augment.atlas_geometry(Hp, Wp, self.ops)
+        self.slot_rows = R
+        self._affine = {}                                # (slot, device) -> the constants of map_xy's one-slot form
+        V = len(self.ops)
+        self.A = torch.empty(V * R, Wq, scene.A.shape[2], dtype=scene.A.dtype, device=self.device)
+        self.B = torch.empty(V * S * R, S * Wq, scene.B.shape[2], dtype=scene.B.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            lib.scene_atlas(scene.A, Hp, Wp, self.ops, R, self.A)
+            lib.scene_atlas(scene.B, S * Hp, S * Wp, self.ops, S * R, self.B)       # (the last S - 1 rows / columns: read by no patch)
+
+    def slot_of(self, op):
+        """The slot that holds variant `op`."""
+        if op not in self.ops:
+            raise lib.DmfError('the atlas holds the variants %s, not %d' % (list(self.ops), op))
+        return self.ops.index(op)
+
+    def map_xy(self, xy, slot):
+        """Atlas coordinates of the patches at xy [n, 2] (host numpy, or a device int32 tensor), each taken from `slot` (an array
+        [n] or a scalar): dmf.augment.map_xy with this atlas' geometry."""
+        from . import augment
+        if torch.is_tensor(xy) and xy.is_cuda and isinstance(slot, int):
+            # one slot for a whole device batch (test-time augmentation): the map is (x, y) or (y, x) times a sign plus an
+            # offset, two small launches with the slot's constants kept on the device
+            if slot == 0:
+                return xy                                # the untouched scene at the origin
+            key = (slot, xy.device)
+            if key not in self._affine:
+                k, (h, w), n = self.ops[slot], self.extent, self.patch
+                if k & 4:
+                    h, w = w, h
+                sign = [-1 if k & 2 else 1, -1 if k & 1 else 1]
+                off = [(h - n if k & 2 else 0) + slot * self.slot_rows, w - n if k & 1 else 0]
+                self._affine[key] = (bool(k & 4), torch.tensor(sign, dtype=torch.int32, device=xy.device),
+                                     torch.tensor(off, dtype=torch.int32, device=xy.device))
+            swap, sign, off = self._affine[key]
+            return (xy.flip(1) if swap else xy) * sign + off
+        return augment.map_xy(xy, slot, self.ops, self.extent, self.patch, self.slot_rows)
+
 
 class LossScaler:
     """Device-resident dynamic loss scale — the role of `torch.cuda.amp.GradScaler` (tostagesolver.py:83-84 builds two
@@ -1050,9 +1116,26 @@ class _ShardedEval:
 class EvalEngine(_ShardedEval):
     """Forward + argmax + on-device confusion matrix / label map (mainsolver.py:102-147,164-197)."""
 
-    def __init__(self, net, scene, batch, criterion=None):
-        """criterion (a spec of `Criterion`, default None = plain cross-entropy): what `ce_sum` evaluates."""
+    def __init__(self, net, scene, batch, criterion=None, tta=None):
+        """criterion (a spec of `Criterion`, default None = plain cross-entropy): what `ce_sum` evaluates.
+        tta (None, or ops as `Scene.atlas` takes them): test-time augmentation — `predict`, and with it the confusion matrix, the
+        label map, the collected logits, the calibration and the confidence maps, give the mean over the variants of the logits
+        (one forward per variant at the scene's mapped coordinates, then dmf_logits_mean).  The scene must be an `AtlasScene`
+        that holds those variants.  The validation pass (`ce_sum`, `valid_accum`) stays on the untouched scene."""
         self.net, self.scene, self.B = net, scene, int(batch)
+        self.tta_slots = None
+        if tta is not None:
+            from . import augment
+            ops = augment.ops_of(tta, 'tta')
+            if len(ops) > 1:
+                if not isinstance(scene, AtlasScene) or any(k not in scene.ops for k in ops):
+                    raise lib.DmfError('tta %s needs a scene atlas that holds these variants (Scene.atlas); this scene holds %s'
+                                       % (list(ops), list(getattr(scene, 'ops', (0,)))))
+                if (scene.patch, scene.scale) != (net.arch['P'], net.arch['S']):
+                    raise lib.DmfError('tta: the atlas was built for patch %d, scale %d, the net takes %d, %d'
+                                       % (scene.patch, scene.scale, net.arch['P'], net.arch['S']))
+                self.tta_slots = [scene.slot_of(k) for k in ops]
+                self.logits_v = torch.empty(len(ops) * self.B * net.arch['K'], device=scene.device)
         self.shape = net.shape
         lib.shape_supported(self.shape)
         dev = scene.device
@@ -1082,13 +1165,30 @@ class EvalEngine(_ShardedEval):
 
     def predict(self, xy):
         """xy [n,2] int32 device -> (logits [n,K], pred [n]) views valid until the next call."""
-        n = xy.shape[0]
+        if self.tta_slots is None:
+            return self._predict_plain(xy)
+        n, K = xy.shape[0], self.net.arch['K']
         self._check_batch(n)
+        V = len(self.tta_slots)
+        lv = self.logits_v[:V * n * K].view(V, n, K)
+        for v, s in enumerate(self.tta_slots):
+            self._forward(self.scene.map_xy(xy, s), lv[v], None)
+        if n:
+            lib.logits_mean(lv, self.logits[:n], self.pred)
+        return self.logits[:n], self.pred[:n]
+
+    def _forward(self, xy, logits, pred):
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, xy)
         if self.shape.attention:
-            lib.forward_attn(self.shape, inp, self._params(), self.net.pool_w, self.attn_ws, self.logits, self.pred)
+            lib.forward_attn(self.shape, inp, self._params(), self.net.pool_w, self.attn_ws, logits, pred)
         else:
-            lib.forward(self.shape, inp, self._params(), self.net.pool_w, self.logits, self.pred)
+            lib.forward(self.shape, inp, self._params(), self.net.pool_w, logits, pred)
+
+    def _predict_plain(self, xy):
+        """`predict` at the coordinates as they are: without test-time augmentation, and the validation pass with it."""
+        n = xy.shape[0]
+        self._check_batch(n)
+        self._forward(xy, self.logits, self.pred)
         return self.logits[:n], self.pred[:n]
 
     def _patch_losses(self, xy, labels):
@@ -1101,7 +1201,7 @@ class EvalEngine(_ShardedEval):
                                  library refuses the shape: asked once and remembered."""
         if self.criterion is not None:
             cr = self.criterion
-            lib.ce_loss(self.predict(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
+            lib.ce_loss(self._predict_plain(xy)[0], 1, 0, labels, cr.params, class_w=cr.class_w, loss=self.ce)
             return True
         if self.shape.attention or self._no_ce:
             return False
@@ -1131,10 +1231,18 @@ class EvalEngine(_ShardedEval):
         if self._patch_losses(xy, labels):
             lib.valid_accum(self.ce, n, acc)
         else:
-            acc += torch.nn.functional.cross_entropy(self.predict(xy)[0], labels.long()).double() * n
+            acc += torch.nn.functional.cross_entropy(self._predict_plain(xy)[0], labels.long()).double() * n
 
     def _check_bounds(self, xy_host):
-        lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)
+        """(with test-time augmentation: the mapped coordinates of every variant used, which are what the kernel reads)"""
+        if self.tta_slots is None or len(xy_host) == 0:
+            lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, xy_host)
+            return
+        Hp, Wp = self.scene.extent
+        if int(xy_host.min()) < 0 or int(xy_host[:, 0].max()) + self.shape.P > Hp or int(xy_host[:, 1].max()) + self.shape.P > Wp:
+            raise lib.DmfError('patch window outside the padded scene')            # (a mapped coordinate is only then inside its slot)
+        for s in self.tta_slots:
+            lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.map_xy(xy_host, s))
 
     def _chunk_pred(self, xy):
         return self.predict(xy)[1]

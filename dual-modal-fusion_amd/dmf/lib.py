@@ -133,6 +133,8 @@ def _load():
         'dmf_pan2ms': (i32, [vp, i32, i32, i32, vp, vp]),
         'dmf_scene_minmax': (i32, [vp, i32, i64, vp, vp]),
         'dmf_scene_prepare': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
+        'dmf_scene_atlas': (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, vp]),
+        'dmf_logits_mean': (i32, [vp, i32, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -822,3 +824,48 @@ def scene_prepare(raw, dtype_name, H, W, C, minmax, pad, out):
         raise DmfError('out must hold [%d, %d, %d] elements' % (H + pad, W + pad, C))
     check(_lib.dmf_scene_prepare(_ptr(raw), code, H, W, C, _ptr(minmax), pad, int(out.dtype == torch.float16), _ptr(out),
                                  _stream()))
+
+
+# return codes of the two entry points of csrc/dmf_augment.hip, which report by code (include/dmf.h)
+_ATLAS_ERRORS = {1: 'a NULL pointer', 2: 'rows, cols and C must be >= 1 and src_pitch >= cols', 3: 'elem_bytes must be 2 or 4',
+                 4: 'n_ops must be 1..8 and every op 0..7', 5: 'slot_rows / dst_pitch too small for a requested variant',
+                 6: 'src / dst not aligned to the element size', 7: 'dst overlaps src',
+                 8: 'a row or a grid beyond 32 bits', 9: 'the launch failed'}
+_MEAN_ERRORS = {1: 'a NULL pointer', 2: 'V must be >= 1 and B >= 0', 3: '1 <= K <= DMF_KMAX', 9: 'the launch failed'}
+
+
+def scene_atlas(src, rows, cols, ops, slot_rows, dst):
+    """dst [len(ops) * slot_rows, dst_pitch, C] <- the variants `ops` (0..7: transpose 4, reverse rows 2, reverse columns 1) of
+    the leading [rows, cols] pixels of src [>= rows, src_pitch, C], one per slot, zero-filled (dmf_scene_atlas).  src and dst
+    are contiguous device tensors of one 2- or 4-byte dtype; every byte of dst is written."""
+    for t, name in ((src, 'src'), (dst, 'dst')):
+        if not (t.is_cuda and t.is_contiguous() and t.dim() == 3 and t.element_size() in (2, 4)):
+            raise DmfError('scene_atlas: %s must be a contiguous [rows, pitch, C] GPU tensor of 2- or 4-byte elements' % name)
+    ops = [int(k) for k in ops]
+    if src.dtype != dst.dtype or src.device != dst.device or src.shape[2] != dst.shape[2]:
+        raise DmfError('scene_atlas: src and dst must share dtype, device and C')
+    if rows > src.shape[0] or dst.shape[0] != len(ops) * slot_rows:
+        raise DmfError('scene_atlas: src holds %d rows (%d asked for), dst %d (%d slots of %d)'
+                       % (src.shape[0], rows, dst.shape[0], len(ops), slot_rows))
+    rc = _lib.dmf_scene_atlas(_ptr(src), src.element_size(), rows, cols, src.shape[1], src.shape[2], (C.c_int32 * len(ops))(*ops),
+                              len(ops), slot_rows, dst.shape[1], _ptr(dst), _stream())
+    if rc != 0:
+        raise DmfError('dmf_scene_atlas: ' + _ATLAS_ERRORS.get(rc, 'error %d' % rc))
+
+
+def logits_mean(logits_v, logits, pred=None):
+    """logits [B, K] <- the mean over V of logits_v [V, B, K] (fp32, summed in variant order, then / V); pred [B] int32 <- the
+    first maximal index of each mean row (dmf_logits_mean)."""
+    _dev(logits_v, torch.float32, 'logits_v'); _dev(logits, torch.float32, 'logits')
+    if logits_v.dim() != 3 or logits_v.shape[0] < 1 or logits.dim() != 2 or tuple(logits.shape) != tuple(logits_v.shape[1:]):
+        raise DmfError('logits_mean wants logits_v [V >= 1, B, K] and logits [B, K]')
+    V, B, K = logits_v.shape
+    if pred is not None:
+        _dev(pred, torch.int32, 'pred')
+        if pred.numel() < B:
+            raise DmfError('pred must hold one element per row')
+    if B == 0:                                  # (an empty tensor has a null data pointer)
+        return
+    rc = _lib.dmf_logits_mean(_ptr(logits_v), V, B, K, _ptr(logits), _ptr(pred), _stream())
+    if rc != 0:
+        raise DmfError('dmf_logits_mean: ' + _MEAN_ERRORS.get(rc, 'error %d' % rc))

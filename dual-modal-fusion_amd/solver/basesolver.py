@@ -10,6 +10,8 @@ next passes as arrays, without the loader and with the same RNG stream (`train.e
 `scene_prep: device` (NEW; fast path only, the drop-in path ignores it): the resident scene is normalised, padded and converted
 on the GPU from the raw scenes (dmf.engine.Scene.from_raw), and the padded host arrays `self.MS` / `self.PAN` — and with them
 the arrays behind the materialising loaders — are computed only when something asks for them.
+`schedule.augment` / `test.tta` (NEW): on the fast path the resident scene becomes a scene atlas of the variants
+either key needs (`Scene.atlas`: V x the scene in HBM); with both `none` it stays the plain Scene.
 """
 import os
 import time
@@ -18,6 +20,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Subset
 
+from dmf import augment
 from function.function import data_padding, data_padding_aux, data_show, label_mat2np, read_tif, split_data, split_data_old
 from indicators.kappa import aa_oa, expo_result
 from train.dataset import collate_batched, dataset_dual
@@ -54,6 +57,7 @@ class BaseSolver:
         self.DEVICE = cfg['device']
         self.timestamp = int(time.time())
         self.num_workers = cfg['threads'] if cfg.get('gpu_mode') else 0
+        self.aug_ops, self.tta_ops = augment.augment_keys(cfg)      # schedule.augment, test.tta: (0,) = none
 
         self.ms = read_tif(cfg, 'ms')
         self.pan = read_tif(cfg, 'pan')
@@ -99,6 +103,11 @@ class BaseSolver:
                                             half=self.half)
             else:
                 self.scene = Scene(self.MS, self.PAN, self.DEVICE, half=self.half)
+            # schedule.augment / test.tta: the resident scene becomes an atlas of the variants either key needs;
+            # with both `none` it stays the plain Scene it was
+            ops = augment.union_ops(self.aug_ops, self.tta_ops)
+            if len(ops) > 1:
+                self.scene = self.scene.atlas(cfg['patch_size'], int(cfg.get('scale', 4)), ops)
 
     @property
     def MS(self):

@@ -57,6 +57,15 @@ and `<t>_conf_{1,2}.png` (8-bit grey, round(255 conf)), composed as the label ma
 dmf_calib_accum / dmf_temperature_step on the eval engine's logits, the label maps written by dmf_softmax_stats in
 dmf_labelmap_write's place; drop-in path: torch ops in float64; both through utils/calibration.py.  `indicator()` and its export
 are untouched; toStageSolver and data-parallel runs refuse the keys.  Neutral values change nothing.
+`schedule.augment: none | flips | d4` and `test.tta: none | flips | d4` (both optional): every train sample is seen as
+one of the 4 flips or 8 flips and quarter turns of its patch, the variant drawn per (cfg['seed'], epoch, pixel) by a stateless
+hash (`_augment_variants`: torch's RNG stream, and so batch order, splits and labels, stay those of an unaugmented run; every
+rank, route and path draws the same); `test()`, `_calibrate` and `color()` classify by the mean of the logits over the variants.
+Fast path: BaseSolver turns the resident scene into an atlas of the variants either key needs (`Scene.atlas`, dmf_scene_atlas), a
+variant is then a mapped coordinate (`_augment_xy`, before `load_plan`, `load_block` and `step` see it, so their bounds checks see
+what the kernel reads) and no train route changes; `EvalEngine(tta=)` runs one forward per variant and dmf_logits_mean.  Drop-in
+path: the materialised patches are transformed (`augment.tf_batch`), the mean is torch's (`_logits_dropin`).  The validation
+pass is never augmented.  With both keys `none` the scene is the plain Scene and nothing changes; toStageSolver refuses the keys.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -77,6 +86,7 @@ import torch
 from PIL import Image
 from tqdm import tqdm
 
+from dmf import augment
 from solver.basesolver import BaseSolver
 from utils import calibration as calib
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
@@ -97,7 +107,9 @@ class Solver(BaseSolver):
     epoch_blocks = True                                  # `train.epoch_block` > 1 has a block form for this stage
     weight_averaging = True                              # `schedule.weight_average` is in scope for this stage
     calibrated = True                                    # `test.calibration` / `test.temperature` / `color.confidence` are in scope
+    augmented = True                                     # `schedule.augment` / `test.tta` are in scope for this stage
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
+    aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
     def __init__(self, cfg):
@@ -113,6 +125,9 @@ class Solver(BaseSolver):
         if calib.keys_in_use(self.calib) and not self.calibrated:
             raise ValueError('%s is out of scope for %s (its prediction is the pair argmax of two streams): leave the key out'
                              % (calib.keys_in_use(self.calib)[0], type(self).__name__))
+        if augment.keys_in_use(cfg) and not self.augmented:
+            raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % (augment.keys_in_use(cfg)[0], type(self).__name__))
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
         self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken
         self.cfg, self.rank, self.world = cfg, 0, 1
@@ -381,6 +396,8 @@ class Solver(BaseSolver):
         self._set_epoch_hparams(self.epoch)
         # the epoch's shuffled coordinates, as the batches the engine steps on and the size of a full one
         batches, B = self._rank_batches([self._xy_labels(b) for b in self.train_index_loader])
+        if len(self.aug_ops) > 1:                          # schedule.augment: full batches and the short one alike, before any
+            batches = [(self._augment_xy(xy, self.epoch), lab) for xy, lab in batches]      # bounds check sees them
         full = [b for b in batches if b[0].shape[0] == B]
         losses = []
         if full:
@@ -390,6 +407,32 @@ class Solver(BaseSolver):
         losses += [self._step_short(xy, lab) for xy, lab in batches if xy.shape[0] != B]    # DataLoader keeps the short last batch
         self._check_exchange()
         return losses
+
+    # ------------------------------------------------------------------ schedule.augment / test.tta
+    def _augment_variants(self, xy, epoch):
+        """The variant (0..7) of every sample of epoch `epoch`, from the pixels' coordinates xy [n, 2] (numpy): the stateless
+        draw of dmf.augment.draw_slots on (cfg['seed'], epoch, x, y) — the same on every rank, route and path, and after a
+        resume; torch's RNG stream is not touched."""
+        ops = np.asarray(self.aug_ops, dtype=np.int64)
+        return ops[augment.draw_slots(int(self.cfg.get('seed') or 0), epoch, xy, len(ops))]
+
+    def _augment_xy(self, xy, epoch):
+        """Fast path: xy [n, 2] (host int32 tensor, pixel coordinates) -> the atlas coordinates of each sample's variant."""
+        xy = xy.numpy()
+        slot_of = np.zeros(8, dtype=np.int64)              # variant -> its slot in the atlas (every aug op is held: BaseSolver)
+        slot_of[list(self.scene.ops)] = np.arange(len(self.scene.ops))
+        return torch.from_numpy(self.scene.map_xy(xy, slot_of[self._augment_variants(xy, epoch)]))
+
+    def _logits_dropin(self, data1, data2):
+        """Drop-in path: the net's logits, or with `test.tta` the mean over the variants, (((l_0 + l_1) + l_2) + ...) / V."""
+        if len(self.tta_ops) == 1:
+            return self.cur_model(data1, data2)
+        total = None
+        for k in self.tta_ops:
+            ks = np.full(data1.shape[0], k)
+            logits = self.cur_model(augment.tf_batch(data1, ks), augment.tf_batch(data2, ks))
+            total = logits if total is None else total + logits
+        return total / float(len(self.tta_ops))
 
     # ------------------------------------------------------------------ blocks of epochs without the host (train.epoch_block)
     def _train_blocks(self, E):
@@ -431,6 +474,8 @@ class Solver(BaseSolver):
         eng, blk, B, save_best = self.engine, self._block, self.cfg['batchsize'], self.cfg['train']['save_best']
         # the RNG draws of these epochs in today's order: the train loader's two, then the validation loader's base seed
         xy, lab = self._epoch_streams(n_epochs, draws_after=1 if save_best else 0)
+        if len(self.aug_ops) > 1:                          # schedule.augment: every epoch's rows, the short batch's included
+            xy = torch.stack([self._augment_xy(xy[e], first_epoch + e) for e in range(n_epochs)])
         n_full, rest = divmod(xy.shape[1], B)
         short = (xy[:, n_full * B:], lab[:, n_full * B:]) if rest else (None, None)      # DataLoader keeps the short last batch
         eng.load_block(xy[:, :n_full * B].reshape(-1, 2), lab[:, :n_full * B].reshape(-1), *short,
@@ -529,6 +574,8 @@ class Solver(BaseSolver):
         from dmf.engine import EvalEngine
         big = 4096 if self.cur_model.arch['attention'] else 16384
         kw = {} if self.criterion is None else {'criterion': self.criterion}
+        if len(self.tta_ops) > 1:                          # test.tta: test(), _calibrate and color() see the mean logits
+            kw['tta'] = self.tta_ops
         return EvalEngine(self.cur_model, self.scene, max(self.cfg['test_batchsize'], self.cfg['color_batchsize'], big), **kw)
 
     def _rank_batches(self, batches):
@@ -552,7 +599,10 @@ class Solver(BaseSolver):
         losses = []
         max_norm = clip_grad_norm_of(self.cfg['schedule'])           # schedule.clip_grad_norm (None: the reference's loop)
         per_step = self.scheduler_unit == 'step' and self.scheduler is not None
-        for data1, data2, target, _, _ in loader:
+        for data1, data2, target, x, y in loader:
+            if len(self.aug_ops) > 1:                                # schedule.augment: the patches the fast path reads from the atlas
+                ks = self._augment_variants(np.stack([np.asarray(x), np.asarray(y)], 1), self.epoch)
+                data1, data2 = augment.tf_batch(data1, ks), augment.tf_batch(data2, ks)
             data1, data2, target = data1.to(self.DEVICE), data2.to(self.DEVICE), target.to(self.DEVICE)
             self.optimizer.zero_grad()
             output = self.cur_model(data1, data2)
@@ -585,7 +635,7 @@ class Solver(BaseSolver):
                     # the evaluation launch's own per-patch cross-entropy (dmf_forward_ce) where the shape has it ...
                     part = self.eval_engine.ce_sum(xy, lab)
                     if part is None:                         # ... else torch's on the logits (attention network)
-                        part = ce(self.eval_engine.predict(xy)[0], lab.long()).double() * lab.shape[0]
+                        part = ce(self._valid_logits(xy), lab.long()).double() * lab.shape[0]
                     tot += part
                 return float(tot.item())
             val_loss = 0.0
@@ -596,10 +646,14 @@ class Solver(BaseSolver):
                     break
         return val_loss
 
+    def _valid_logits(self, xy):
+        """The validation pass's logits where it takes torch's loss on them: without test-time augmentation."""
+        return self.eval_engine._predict_plain(xy)[0]
+
     def _predict_dropin(self, batch):
         """(pred [n] on the device, target [n], x, y) of a batch of the materialising loaders."""
         data1, data2, target, x, y = batch
-        return self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE)).data.max(1)[1], target, x, y
+        return self._logits_dropin(data1.to(self.DEVICE), data2.to(self.DEVICE)).data.max(1)[1], target, x, y
 
     def _test_whole_split(self):
         """The reference always stops after the first test batch (mainsolver.py:142); `test.full: 1` takes the whole split."""
@@ -673,7 +727,7 @@ class Solver(BaseSolver):
 
     def _dropin_logits(self, loader):
         """(logits [n, K] float64, labels [n]) as numpy over the batches of a materialising loader."""
-        out = [(self.cur_model(d1.to(self.DEVICE), d2.to(self.DEVICE)).detach().double().cpu().numpy(), np.asarray(t))
+        out = [(self._logits_dropin(d1.to(self.DEVICE), d2.to(self.DEVICE)).detach().double().cpu().numpy(), np.asarray(t))
                for d1, d2, t, _, _ in loader]
         return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out]).astype(np.int64)
 
@@ -794,7 +848,7 @@ class Solver(BaseSolver):
     def _confidence_map_dropin(self, loaders, H, W, beta):
         m, p = np.zeros([H, W], dtype=np.int32), np.zeros([3, H, W], dtype=np.float32)
         for data1, data2, _, x, y in loaders[1]:
-            logits = self.cur_model(data1.to(self.DEVICE), data2.to(self.DEVICE))
+            logits = self._logits_dropin(data1.to(self.DEVICE), data2.to(self.DEVICE))
             x, y = np.asarray(x), np.asarray(y)
             m[x, y] = logits.data.max(1)[1].cpu().numpy()                  # (the prediction of `_predict_dropin`)
             p[:, x, y] = calib.softmax_stats(logits, beta)[1].cpu().numpy().astype(np.float32)

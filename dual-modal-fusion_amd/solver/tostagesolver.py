@@ -57,6 +57,7 @@ class toStageSolver(Solver):
     epoch_blocks = False                                 # (its validation is a batch-coupled loss read back per batch)
     weight_averaging = False                             # (schedule.weight_average is out of scope here: refused by name)
     calibrated = False                                   # (test.calibration, test.temperature, color.confidence: refused by name)
+    augmented = False                                    # (schedule.augment, test.tta: refused by name)
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -511,6 +511,32 @@ int64_t dmf_temperature_workspace_bytes(int32_t N);
 int32_t dmf_temperature_step(const float* logits, const int32_t* labels, int32_t N, int32_t K, double* state, void* workspace,
                              int32_t update, void* stream);
 
+/* ---- flip / rotate augmentation and test-time augmentation from a scene atlas.  New symbols at an unchanged
+ * DMF_VERSION: detect them by name.
+ *
+ * Variant k in 0..7 of an array X [rows, cols, C]: Y = X transposed (axes 0 and 1) if k & 4; then the rows of Y reversed if
+ * k & 2; then its columns reversed if k & 1.  k = 0 is the identity; 0..3 are the flips, 0..7 the dihedral group.
+ * dmf_scene_atlas writes dst [n_ops * slot_rows, dst_pitch, C]: slot s (rows [s * slot_rows, (s + 1) * slot_rows)) holds variant
+ * ops[s] of src's leading [rows, cols] pixels at its top-left corner and zero elsewhere.  src is [>= rows, src_pitch, C],
+ * pixel-major; elements of elem_bytes (2 or 4) bytes are moved as bits, never converted.  EVERY byte of dst is written (the
+ * caller need not clear it), in one launch.  `ops` is a HOST array.  A flipped or transposed patch of the scene is then an
+ * ordinary patch of the atlas at a mirrored top-left coordinate: with the patch window n, the extent (Hp, Wp) of the region,
+ *   if k & 4: x, y, Hp, Wp = y, x, Wp, Hp;   if k & 2: x = Hp - n - x;   if k & 1: y = Wp - n - y;   x += s * slot_rows.
+ * Returns 0, or without a launch: 1 a NULL pointer; 2 rows, cols or C < 1, or src_pitch < cols; 3 elem_bytes not 2 or 4;
+ * 4 n_ops outside 1..8 or an op outside 0..7; 5 slot_rows or dst_pitch too small for a requested variant (a transposed one
+ * needs slot_rows >= cols and dst_pitch >= rows); 6 src or dst not aligned to elem_bytes; 7 dst overlaps src; 8 a row of more
+ * than 2^31 - 1 bytes or more workgroups than a grid holds; and 9 where the launch itself failed.  (These two entry points
+ * report by code: they do not set the text of dmf_last_error.) */
+int32_t dmf_scene_atlas(const void* src, int32_t elem_bytes, int32_t rows, int32_t cols, int32_t src_pitch, int32_t C,
+                        const int32_t* ops /* host */, int32_t n_ops, int32_t slot_rows, int32_t dst_pitch,
+                        void* dst, void* stream);
+/* The mean of V variants' logits: logits[b][c] = (((l_0 + l_1) + l_2) + ...) / (float)V in fp32, in variant order, from
+ * logits_v [V][B][K]; pred[b] (may be NULL) = the FIRST maximal index of that row of the mean (the rule of the forward entry
+ * points).  V = 1 copies; B == 0 is a no-op.  Returns 1 for NULL logits_v or logits, 2 for V < 1 or B < 0, 3 for K outside
+ * 1..DMF_KMAX, 9 where the launch failed. */
+int32_t dmf_logits_mean(const float* logits_v /* [V][B][K] */, int32_t V, int32_t B, int32_t K,
+                        float* logits /* [B][K] */, int32_t* pred /* nullable */, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

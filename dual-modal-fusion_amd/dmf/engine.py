@@ -146,6 +146,24 @@ class Scene:
         self.A = self.B = None
         return out
 
+    def affinity(self, H, W, radius=2, sigma_s=2.0, sigma_r=0.1):
+        """-> aff [H, W, n] float32 on the device, n = (2 radius + 1)^2: the bilateral affinities of the H x W scene that sits at
+        the top-left corner of the padded primary scene (dmf_spatial_affinity; fp32 and fp16 scenes alike; of a
+        scene atlas that corner is slot 0, the untouched scene).  4 n bytes per pixel; the last one is kept with its parameters
+        and handed out again for the same ones."""
+        key = (int(H), int(W), radius, float(sigma_s), float(sigma_r))
+        kept = getattr(self, '_affinity', None)
+        if kept is None or kept[0] != key:
+            Hp, Wp = getattr(self, 'extent', self.A.shape[:2])
+            if not (1 <= key[0] <= Hp and 1 <= key[1] <= Wp):
+                raise lib.DmfError('affinity: %d x %d pixels asked of a padded scene of %d x %d' % (key[0], key[1], Hp, Wp))
+            self._affinity = None                        # (the old one goes before the new one is allocated)
+            aff = torch.empty(key[0], key[1], lib._window(radius), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                lib.spatial_affinity(self.A, key[0], key[1], radius, sigma_s, sigma_r, aff)
+            self._affinity = kept = (key, aff)
+        return kept[1]
+
 
 class AtlasScene(Scene):
     """A `Scene` whose A and B are scene atlases: the variants `ops` of the padded scenes, stacked along the row
@@ -1274,6 +1292,39 @@ class EvalEngine(_ShardedEval):
             lib.softmax_stats(self.predict(xy)[0], pred=label_map, conf=planes[0], margin=planes[1], entropy=planes[2],
                               inv_temp=beta, xy=xy, W=W)
         return label_map, planes
+
+    # ------------------------------------------------------------------ spatial regularisation
+    def probability_map(self, xy_all, H, W, inv_temp=None):
+        """-> (prob [H, W, K] float32, mask [H, W] uint8): the softmax at beta = inv_temp of all given pixels and 1 where a
+        pixel was given, 0 elsewhere.  `label_map`'s chunks and bounds checks, with one dmf_prob_scatter per chunk on
+        `predict`'s logits: test-time augmentation and the attention net come with it."""
+        dev = self.scene.device
+        beta = self._beta(inv_temp)
+        host, xy_all = self._whole_set(None, xy_all)
+        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
+            raise lib.DmfError('pixel outside the %d x %d probability map' % (H, W))   # the kernel writes prob[(x * W + y) * K + c]
+        prob = torch.zeros(H, W, self.net.arch['K'], dtype=torch.float32, device=dev)
+        mask = torch.zeros(H, W, dtype=torch.uint8, device=dev)
+        for i in range(0, xy_all.shape[0], self.B):
+            xy = xy_all[i:i + self.B]
+            lib.prob_scatter(self.predict(xy)[0], xy, W, prob, mask, inv_temp=beta)
+        return prob, mask
+
+    def regularise(self, prob, mask, aff, iterations=1):
+        """-> (prob' [H, W, K], label map [H, W] int32): `iterations` >= 1 passes of dmf_spatial_filter over prob / mask (as
+        `probability_map` gives them) with the affinities aff [H, W, n] (`Scene.affinity`), ping-pong between two buffers; prob
+        itself is not written.  The label map is the argmax of prob' where mask is 1, and 0 elsewhere."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise lib.DmfError('regularise: iterations = %r is not a whole number >= 1' % (iterations,))
+        label_map = torch.zeros(prob.shape[0], prob.shape[1], dtype=torch.int32, device=prob.device)
+        src, bufs = prob, [torch.empty_like(prob)]
+        for it in range(iterations):
+            if it == 1:
+                bufs.append(torch.empty_like(prob))
+            dst = bufs[it % 2]
+            lib.spatial_filter(src, mask, aff, dst, label_map)
+            src = dst
+        return src, label_map
 
     def collect_logits(self, xy_all, labels_all=None):
         """-> the logits of all given pixels in ONE device tensor [N, K] (and their labels as device int32 [N])."""

@@ -135,6 +135,9 @@ def _load():
         'dmf_scene_prepare': (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
         'dmf_scene_atlas': (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(i32), i32, i32, i32, vp, vp]),
         'dmf_logits_mean': (i32, [vp, i32, i32, i32, vp, vp, vp]),
+        'dmf_prob_scatter': (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+        'dmf_spatial_affinity': (i32, [vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
+        'dmf_spatial_filter': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -869,3 +872,79 @@ def logits_mean(logits_v, logits, pred=None):
     rc = _lib.dmf_logits_mean(_ptr(logits_v), V, B, K, _ptr(logits), _ptr(pred), _stream())
     if rc != 0:
         raise DmfError('dmf_logits_mean: ' + _MEAN_ERRORS.get(rc, 'error %d' % rc))
+
+
+# return codes of the three entry points of csrc/dmf_spatial.hip, which report by code (include/dmf.h)
+_SPATIAL_ERRORS = {1: 'a NULL pointer', 2: 'H, W and C must be >= 1 (scatter: B >= 0 and W >= 1)', 3: '1 <= K <= DMF_KMAX',
+                   4: 'the radius must be 1, 2 or 3', 5: 'elem_bytes must be 2 or 4', 6: 'pitch < W', 7: 'prob_out overlaps prob_in',
+                   8: 'the scene is not aligned to its element size, or a grid beyond 32 bits', 9: 'the launch failed'}
+
+
+def _spatial_check(entry, rc):
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, _SPATIAL_ERRORS.get(rc, 'error %d' % rc)))
+
+
+def _window(radius):
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 3:
+        raise DmfError('the radius %r is not 1, 2 or 3' % (radius,))
+    return (2 * radius + 1) ** 2
+
+
+def prob_scatter(logits, xy, W, prob, mask, inv_temp=None):
+    """prob [H, W, K] float32 / mask [H, W] uint8 <- the softmax at beta = inv_temp[0] (device float32 [1]; None: 1) of every row
+    of logits [B, K], written at the row's pixel xy [B, 2] int32: prob[x, y, :] = e / Z as dmf_softmax_stats forms them,
+    mask[x, y] = 1 (dmf_prob_scatter).  Other cells stay as they are; the caller has checked the pixels against [H, W]."""
+    _dev(logits, torch.float32, 'logits'); _dev(xy, torch.int32, 'xy'); _dev(prob, torch.float32, 'prob'); _dev(mask, torch.uint8, 'mask')
+    if logits.dim() != 2 or tuple(xy.shape) != (logits.shape[0], 2):
+        raise DmfError('prob_scatter wants logits [B, K] and xy [B, 2]')
+    B, K = logits.shape
+    if inv_temp is not None:
+        _dev(inv_temp, torch.float32, 'inv_temp')
+        if inv_temp.numel() < 1:
+            raise DmfError('inv_temp holds one float')
+    if prob.dim() != 3 or prob.shape[1] != W or prob.shape[2] != K or tuple(mask.shape) != tuple(prob.shape[:2]):
+        raise DmfError('prob_scatter wants prob [H, %d, %d] and mask [H, %d]' % (W, K, W))
+    if B == 0:                                  # (an empty tensor has a null data pointer)
+        return
+    _spatial_check('dmf_prob_scatter', _lib.dmf_prob_scatter(_ptr(logits), B, K, _ptr(inv_temp), _ptr(xy), W, _ptr(prob), _ptr(mask),
+                                                             _stream()))
+
+
+def spatial_affinity(scene, H, W, radius, sigma_s, sigma_r, aff):
+    """aff [H, W, n] float32, n = (2 radius + 1)^2 <- the bilateral affinities of the leading [H, W] pixels of the resident
+    scene [>= H, pitch >= W, C] (fp32 or fp16, contiguous): exp(-(|d|^2 / (2 sigma_s^2) + mean_c (a_c(x) - a_c(y))^2 /
+    (2 sigma_r^2))), 0 for a neighbour outside [0, H) x [0, W), 1 at the centre (dmf_spatial_affinity)."""
+    n = _window(radius)
+    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
+        raise DmfError('spatial_affinity: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor')
+    _dev(aff, torch.float32, 'aff')
+    if H < 1 or W < 1 or H > scene.shape[0] or W > scene.shape[1]:
+        raise DmfError('spatial_affinity: %d x %d pixels asked of a scene of %d x %d' % (H, W, scene.shape[0], scene.shape[1]))
+    if tuple(aff.shape) != (H, W, n) or aff.device != scene.device:
+        raise DmfError('spatial_affinity: aff must be [%d, %d, %d] on the scene\'s device' % (H, W, n))
+    for name, s in (('sigma_s', sigma_s), ('sigma_r', sigma_r)):
+        if not (s > 0 and s < float('inf')):
+            raise DmfError('spatial_affinity: %s = %r is not a finite number > 0' % (name, s))
+    cs, cr = 1.0 / (2.0 * float(sigma_s) ** 2), 1.0 / (2.0 * float(sigma_r) ** 2)
+    _spatial_check('dmf_spatial_affinity', _lib.dmf_spatial_affinity(_ptr(scene), scene.element_size(), scene.shape[1], H, W, scene.shape[2],
+                                                                     radius, cs, cr, _ptr(aff), _stream()))
+
+
+def spatial_filter(prob_in, mask, aff, prob_out, label_map):
+    """One iteration of the filter (dmf_spatial_filter): prob_out [H, W, K] <- the aff-weighted mean of prob_in over the masked
+    neighbours of every masked pixel (an all-zero row elsewhere); label_map [H, W] int32 <- its first maximal index at the
+    masked pixels, the other cells untouched.  aff [H, W, n]; mask [H, W] uint8; prob_out must not overlap prob_in."""
+    _dev(prob_in, torch.float32, 'prob_in'); _dev(prob_out, torch.float32, 'prob_out'); _dev(mask, torch.uint8, 'mask')
+    _dev(aff, torch.float32, 'aff'); _dev(label_map, torch.int32, 'label_map')
+    if prob_in.dim() != 3 or aff.dim() != 3 or tuple(prob_out.shape) != tuple(prob_in.shape):
+        raise DmfError('spatial_filter wants prob_in and prob_out [H, W, K] and aff [H, W, n]')
+    H, W, K = prob_in.shape
+    radius = {9: 1, 25: 2, 49: 3}.get(aff.shape[2])
+    if radius is None or tuple(aff.shape[:2]) != (H, W) or tuple(mask.shape) != (H, W) or tuple(label_map.shape) != (H, W):
+        raise DmfError('spatial_filter: aff [%d, %d, 9 | 25 | 49], mask and label_map [%d, %d] go with prob [%d, %d, %d]'
+                       % (H, W, H, W, H, W, K))
+    if len({t.device for t in (prob_in, prob_out, mask, aff, label_map)}) != 1:
+        raise DmfError('spatial_filter: all tensors must live on one device')
+    _spatial_check('dmf_spatial_filter', _lib.dmf_spatial_filter(_ptr(prob_in), _ptr(mask), _ptr(aff), H, W, K, radius, _ptr(prob_out),
+                                                                 _ptr(label_map), _stream()))

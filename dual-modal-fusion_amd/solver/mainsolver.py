@@ -66,6 +66,16 @@ variant is then a mapped coordinate (`_augment_xy`, before `load_plan`, `load_bl
 what the kernel reads) and no train route changes; `EvalEngine(tta=)` runs one forward per variant and dmf_logits_mean.  Drop-in
 path: the materialised patches are transformed (`augment.tf_batch`), the mean is torch's (`_logits_dropin`).  The validation
 pass is never augmented.  With both keys `none` the scene is the plain Scene and nothing changes; toStageSolver refuses the keys.
+`test.spatial: none | bilateral` with `test.spatial_radius`, `test.spatial_sigma_s`, `test.spatial_sigma_r`, `test.spatial_iterations`,
+and `color.spatial: 1` (all optional): after the confusion matrix (and the calibration) `test()` classifies the pixels
+of both colour sets — the whole scene — at `test.temperature`'s beta, smooths the class probabilities over each pixel's window
+with scene-guided bilateral weights and forms a second confusion matrix over the same test pixels from the regularised map
+(`self.spatial`, `<t>_spatial.json`: parameters, matrix, OA / AA / kappa before and after, pixels whose class changed); `color()`
+also writes `<t>_pic_{1,2}_spatial.png`, composed as the plain maps are.  Fast path: EvalEngine.probability_map, Scene.affinity and
+EvalEngine.regularise (dmf_prob_scatter / dmf_spatial_affinity / dmf_spatial_filter); drop-in path: utils/spatial.py in numpy
+float64.  The pixels are taken from the index dataset's arrays, not from a loader, so torch's RNG stream and every artefact that
+was there stay as they are; `test_matrix`, `indicator()` and its export are untouched; toStageSolver and data-parallel runs refuse
+the keys.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -89,6 +99,7 @@ from tqdm import tqdm
 from dmf import augment
 from solver.basesolver import BaseSolver
 from utils import calibration as calib
+from utils import spatial
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
                          make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
@@ -108,6 +119,7 @@ class Solver(BaseSolver):
     weight_averaging = True                              # `schedule.weight_average` is in scope for this stage
     calibrated = True                                    # `test.calibration` / `test.temperature` / `color.confidence` are in scope
     augmented = True                                     # `schedule.augment` / `test.tta` are in scope for this stage
+    regularised = True                                   # `test.spatial` / `color.spatial` are in scope for this stage
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
     aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
@@ -128,6 +140,11 @@ class Solver(BaseSolver):
         if augment.keys_in_use(cfg) and not self.augmented:
             raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % (augment.keys_in_use(cfg)[0], type(self).__name__))
+        self.spat = spatial.spatial_keys(cfg)          # test.spatial / spatial_radius / _sigma_s / _sigma_r / _iterations, color.spatial
+        if spatial.keys_in_use(self.spat) and not self.regularised:
+            raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % (spatial.keys_in_use(self.spat)[0], type(self).__name__))
+        self.spatial, self._spatial_maps = None, None  # test()'s regularisation block; the whole-scene maps of the loaded weights
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
         self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken
         self.cfg, self.rank, self.world = cfg, 0, 1
@@ -174,6 +191,7 @@ class Solver(BaseSolver):
         super().dataloader()
         self._valid_dev = None
         self._temp = None
+        self._spatial_maps = None
         if criterion_keys(self.cfg):
             self.train_labels = self.index_dataset.label[np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)]
             self.criterion = criterion_spec(self.cfg, self.train_labels)
@@ -219,6 +237,7 @@ class Solver(BaseSolver):
         E = self._epoch_block()
         time1 = time.time()
         self._temp = None                              # (a fitted temperature belongs to the weights it was fitted on)
+        self._spatial_maps = None                      # (and so do the regularised maps)
         if not self.cfg['train']['pretrained']:
             self.init_model()
         self.cur_model = self.model.to(self.DEVICE)
@@ -677,6 +696,7 @@ class Solver(BaseSolver):
     def test(self):
         time1 = time.time()
         self._calibration_scope()
+        self._spatial_scope()
         self._ensure_model()
         self._load_weights(self.cfg['train']['save_best'])
         self.cur_model.eval()
@@ -688,6 +708,9 @@ class Solver(BaseSolver):
         if self.calib['calibration']:
             with torch.no_grad():
                 self._calibrate(whole)
+        if self.spat['kind'] is not None:
+            with torch.no_grad():
+                self._regularise(whole)
         if self.rank == 0:
             self.indicator()
         else:
@@ -787,9 +810,100 @@ class Solver(BaseSolver):
             with open(self.cfg['RESULT_output'] + str(self.time) + '_calibration.json', 'w') as f:
                 json.dump(block, f, indent=1)
 
+    # ------------------------------------------------------------------ spatial regularisation (test.spatial, color.spatial)
+    def _spatial_scope(self):
+        """Data-parallel runs refuse the keys (the probability map and the filter are not sharded), as `_calibration_scope` does."""
+        if spatial.keys_in_use(self.spat) and self.world > 1:
+            raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out'
+                             % (spatial.keys_in_use(self.spat)[0], self.world))
+
+    def _set_pixels(self, rows):
+        """xy [n, 2] int32 (numpy) of rows of the pixel table, from the index dataset's arrays: no loader, so torch's RNG stream
+        stays what it is without the keys."""
+        rows = np.asarray(rows, dtype=np.int64)
+        d = self.index_dataset
+        return np.stack([d.x[rows], d.y[rows]], 1).astype(np.int32).reshape(-1, 2)
+
+    def _scene_pixels(self):
+        """Both colour sets: every pixel of the scene (the labelled ones first)."""
+        return self._set_pixels(list(self.matrix_[1]) + list(self.matrix_[0]))
+
+    def _regularised_maps(self, best):
+        """-> (plain, regularised) label maps [H, W] int32 (numpy) of the WHOLE scene under the loaded weights (`best`: which file
+        they came from; the pair is kept per trained model and file; the fast path leaves the plain one None): all pixels of both colour sets are classified at
+        `test.temperature`'s beta, the probabilities go through `test.spatial_iterations` passes of the filter.  Fast path:
+        EvalEngine.probability_map, Scene.affinity and EvalEngine.regularise; drop-in path: utils.spatial in float64 on the
+        logits of `Net.forward` and the host's padded scene."""
+        if self._spatial_maps is not None and self._spatial_maps[0] == bool(best):
+            return self._spatial_maps[1]
+        k = self.spat
+        size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
+        H, W = int(size[0]), int(size[1])
+        beta = self._beta(self._temperature_used()[0])
+        xy = self._scene_pixels()
+        if self.fast:
+            eng = self.eval_engine
+            prob, mask = eng.probability_map(torch.from_numpy(xy), H, W, beta)
+            plain = None                                 # (the test pixels' own classes: `_regularise` asks the engine)
+            aff = self.scene.affinity(H, W, k['radius'], k['sigma_s'], k['sigma_r'])
+            smooth = eng.regularise(prob, mask, aff, k['iterations'])[1].cpu().numpy()
+        else:
+            from torch.utils.data import DataLoader, Subset
+            rows = list(self.matrix_[1]) + list(self.matrix_[0])
+            loader = DataLoader(Subset(self.dataset, indices=rows), batch_size=self.cfg['color_batchsize'], shuffle=False,
+                                num_workers=0, generator=torch.Generator())       # (a generator of its own: the global stream stays)
+            logits = self._dropin_logits(loader)[0]
+            prob, mask = np.zeros((H, W, logits.shape[1])), np.zeros((H, W), dtype=np.uint8)
+            prob[xy[:, 0], xy[:, 1]] = spatial.probabilities(logits, beta)
+            mask[xy[:, 0], xy[:, 1]] = 1
+            plain = np.zeros((H, W), dtype=np.int32)
+            plain[xy[:, 0], xy[:, 1]] = logits.argmax(1)
+            scene = self.MS.astype(np.float16) if self.half else self.MS
+            aff = spatial.affinity(scene, H, W, k['radius'], k['sigma_s'], k['sigma_r'])
+            smooth = spatial.regularise(prob, mask, aff, k['radius'], k['iterations'])[1]
+        self._spatial_maps = (bool(best), (plain, smooth))
+        return self._spatial_maps[1]
+
+    def _regularise(self, whole):
+        """`self.spatial` and `<t>_spatial.json`: a second confusion matrix over the pixels of the first, from the regularised
+        label map at their (x, y).  `self.test_matrix` and what `indicator()` makes of it stay as they are."""
+        plain, smooth = self._regularised_maps(self.cfg['train']['save_best'])
+        rows = np.asarray(self.test_index_loader.dataset.indices, dtype=np.int64)
+        if not whole:
+            rows = rows[:self.cfg['test_batchsize']]   # the first batch of the unshuffled loader
+        xy, lab = self._set_pixels(rows), self.index_dataset.label[rows].astype(np.int64)
+        if plain is None:
+            plain = self.eval_engine.label_map(torch.from_numpy(xy), *smooth.shape).cpu().numpy()
+        K = self.cfg['Categories_Number']
+        after = np.zeros([K, K], dtype=np.int64)
+        np.add.at(after, (smooth[xy[:, 0], xy[:, 1]], lab), 1)                    # matrix[pred][target] += 1
+        changed = int((smooth[xy[:, 0], xy[:, 1]] != plain[xy[:, 0], xy[:, 1]]).sum())
+        self.spatial = spatial.report(self.spat, self.test_matrix, after, changed)
+        if self.rank == 0:
+            with open(self.cfg['RESULT_output'] + str(self.time) + '_spatial.json', 'w') as f:
+                json.dump(self.spatial, f, indent=1)
+
+    def _color_spatial(self, H, W, lut):
+        """`<t>_pic_{1,2}_spatial.png`, composed as the plain maps are: map 1 the regularised classes on the labelled pixels,
+        map 2 with the other pixels too."""
+        smooth = self._regularised_maps(True)[1]
+        maps = []
+        for use, rows in ((self.cfg['color']['supervised'], self.matrix_[1]), (self.cfg['color']['unsupervised'], self.matrix_[0])):
+            m = np.zeros([H, W], dtype=np.int32)
+            if use:
+                xy = self._set_pixels(rows)
+                m[xy[:, 0], xy[:, 1]] = smooth[xy[:, 0], xy[:, 1]]
+            maps.append(m)
+        map2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
+        self.spatial_maps = (maps[0], map2)
+        if self.cfg['color']['supervised'] and self.rank == 0:
+            for n, m in enumerate(self.spatial_maps, 1):
+                Image.fromarray(lut[m]).save(self.cfg['RESULT_output'] + str(self.time) + '_pic_%d_spatial.png' % n)
+
     # ------------------------------------------------------------------ colour
     def color(self):
         self._calibration_scope()
+        self._spatial_scope()
         self._ensure_model()
         self._load_weights(True)
         self.cur_model.eval()
@@ -827,6 +941,9 @@ class Solver(BaseSolver):
                     np.save(self.cfg['RESULT_output'] + str(self.time) + '_confidence_%d.npy' % k, p)
                     grey = np.round(255.0 * p[0].astype(np.float64)).clip(0, 255).astype(np.uint8)
                     Image.fromarray(grey).save(self.cfg['RESULT_output'] + str(self.time) + '_conf_%d.png' % k)
+        if self.spat['color']:
+            with torch.no_grad():
+                self._color_spatial(H, W, lut)
 
     def _label_map_fast(self, loaders, H, W):
         """All pixels of the index-only loader, in evaluation chunks of the engine's own size."""

@@ -58,6 +58,7 @@ class toStageSolver(Solver):
     weight_averaging = False                             # (schedule.weight_average is out of scope here: refused by name)
     calibrated = False                                   # (test.calibration, test.temperature, color.confidence: refused by name)
     augmented = False                                    # (schedule.augment, test.tta: refused by name)
+    regularised = False                                  # (test.spatial, color.spatial: refused by name)
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -537,6 +537,38 @@ int32_t dmf_scene_atlas(const void* src, int32_t elem_bytes, int32_t rows, int32
 int32_t dmf_logits_mean(const float* logits_v /* [V][B][K] */, int32_t V, int32_t B, int32_t K,
                         float* logits /* [B][K] */, int32_t* pred /* nullable */, void* stream);
 
+/* ---- spatial regularisation of class maps: a scene-guided bilateral filter on the class probabilities.  New
+ * symbols at an unchanged DMF_VERSION: detect them by name.
+ *
+ * Pixel x = (i, j) of an H x W scene is element (i, j) of the resident padded primary scene [>= H, pitch_pixels >= W, C]
+ * (padded at the bottom and the right only; slot 0 of a scene atlas).  Radius r in 1..3, n = (2r + 1)^2, offset index
+ * k = (di + r)(2r + 1) + (dj + r) for di, dj in -r..r.  Everything is pixel-major.
+ *   affinity   aff [H W][n] fp32, once per scene.  For the neighbour y = x + (di, dj): 0 where y lies outside
+ *              [0, H) x [0, W); else d2 = (sum_c (a_c(x) - a_c(y))^2) / (float)C in fp32 (an fp16 scene widened exactly first;
+ *              the bands summed in ascending order, each term by one fmaf) and
+ *              aff = expf(-(((float)(di^2 + dj^2) * cs) + (d2 * cr))), the two products and the sum each rounded once;
+ *              cs = 1 / (2 sigma_s^2), cr = 1 / (2 sigma_r^2).  The centre (k = (n - 1) / 2) is exactly 1.
+ *   scatter    per row of logits [B, K], with beta = inv_temp[0] (device; NULL: 1): t_c, e_c and Z exactly as
+ *              dmf_softmax_stats forms them; prob[(x W + y) K + c] = e_c / Z for (x, y) = xy[row], and mask[x W + y] = 1.
+ *              prob[pred] is the bits of dmf_softmax_stats's conf.  Cells that no row names are left alone: the caller
+ *              clears prob and mask first.  Coordinates inside [0, H) x [0, W) are the caller's contract.
+ *   filter     one iteration.  For a pixel x with mask 1: w_k = aff[x][k] * mask(y_k) (mask(y) = 0 outside the scene),
+ *              N_c = sum_k w_k p_c(y_k) by fmaf in ascending k from 0, D = sum_k w_k in ascending k (D >= 1: the centre),
+ *              out_c = N_c / D; label_map[x] = the FIRST maximal index of out (the forward entry points' rule).  A pixel
+ *              with mask 0 gets an all-zero row of prob_out and its label-map cell is left alone; what its row of prob_in
+ *              holds is never read.  prob_out must not overlap prob_in.
+ * No float atomics and fixed orders: two runs give the same bits.  All three report by code, without a launch (and so with
+ * every output as it was): 1 a NULL pointer (inv_temp may be NULL); 2 H, W or C < 1 (scatter: B < 0 or W < 1); 3 K outside
+ * 1..DMF_KMAX; 4 r outside 1..3; 5 elem_bytes not 2 or 4; 6 pitch_pixels < W; 7 prob_out overlaps prob_in; 8 the scene not
+ * aligned to elem_bytes, or more workgroups than a grid holds; and 9 where the launch itself failed.  B == 0 is a no-op.
+ * (They do not set the text of dmf_last_error.) */
+int32_t dmf_prob_scatter(const float* logits, int32_t B, int32_t K, const float* inv_temp, const int32_t* xy, int32_t W,
+                         float* prob, uint8_t* mask, void* stream);
+int32_t dmf_spatial_affinity(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C,
+                             int32_t r, float cs, float cr, float* aff, void* stream);
+int32_t dmf_spatial_filter(const float* prob_in, const uint8_t* mask, const float* aff, int32_t H, int32_t W, int32_t K,
+                           int32_t r, float* prob_out, int32_t* label_map, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_rows.h"
 
 namespace dmf {
 
@@ -136,14 +137,13 @@ static hipError_t atlas_launch(const AtlasArgs& a, unsigned blocks, size_t lds, 
 }
 
 // ------------------------------------------------------------------------------ mean of the variants' logits
-// A group of L = next power of two >= K lanes holds one row, as softmax_stats_kernel does: lane c adds its column over the
-// variants in variant order, divides by (float)V, and the group's xor butterfly finds the row maximum with its FIRST index.
+// One row per group of L lanes (dmf_rows.h): lane c adds its column over the variants in variant order and divides by
+// (float)V; the group then finds the row maximum with its FIRST index.
 template <int L>
 __global__ __launch_bounds__(256) void logits_mean_kernel(const float* __restrict__ lv, int V, int B, int K,
                                                           float* __restrict__ logits, int32_t* __restrict__ pred) {
-  constexpr int ROWS = 256 / L;
-  const int c = threadIdx.x % L;
-  const int64_t r = (int64_t)blockIdx.x * ROWS + threadIdx.x / L;
+  const int c = row_column<L>();
+  const int64_t r = row_index<L>();
   const bool live = r < B && c < K;
   float m = -INFINITY;
   if (live) {
@@ -155,20 +155,8 @@ __global__ __launch_bounds__(256) void logits_mean_kernel(const float* __restric
   }
   if (pred == nullptr) return;
   int first = c;
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, 64);
-    const int oi = __shfl_xor(first, off, 64);
-    if (om > m || (om == m && oi < first)) { m = om; first = oi; }
-  }
+  row_argmax_first<L>(m, first);
   if (r < B && c == 0) pred[r] = first;
-}
-
-template <int L>
-static hipError_t mean_launch(const float* lv, int V, int B, int K, float* logits, int32_t* pred, hipStream_t st) {
-  const int rows = 256 / L;
-  hipLaunchKernelGGL(logits_mean_kernel<L>, dim3((unsigned)(((int64_t)B + rows - 1) / rows)), dim3(256), 0, st, lv, V, B, K, logits, pred);
-  return hipGetLastError();
 }
 
 }  // namespace dmf
@@ -238,14 +226,11 @@ int32_t dmf_logits_mean(const float* logits_v, int32_t V, int32_t B, int32_t K, 
   if (K < 1 || K > DMF_KMAX) return 3;
   if (B == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (K <= 1) e = mean_launch<1>(logits_v, V, B, K, logits, pred, st);
-  else if (K <= 2) e = mean_launch<2>(logits_v, V, B, K, logits, pred, st);
-  else if (K <= 4) e = mean_launch<4>(logits_v, V, B, K, logits, pred, st);
-  else if (K <= 8) e = mean_launch<8>(logits_v, V, B, K, logits, pred, st);
-  else if (K <= 16) e = mean_launch<16>(logits_v, V, B, K, logits, pred, st);
-  else if (K <= 32) e = mean_launch<32>(logits_v, V, B, K, logits, pred, st);
-  else e = mean_launch<64>(logits_v, V, B, K, logits, pred, st);
+  const hipError_t e = for_row_lanes(K, [&](auto L) {
+    hipLaunchKernelGGL(logits_mean_kernel<decltype(L)::value>, row_blocks<decltype(L)::value>(B), dim3(256), 0, st, logits_v, V, B, K,
+                       logits, pred);
+    return hipGetLastError();
+  });
   return e == hipSuccess ? 0 : 9;
 }
 

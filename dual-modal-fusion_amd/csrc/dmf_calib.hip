@@ -11,70 +11,45 @@
 #include <stdint.h>
 
 #include "dmf_kargs.h"
+#include "dmf_rows.h"
 
 namespace dmf {
 
 // ------------------------------------------------------------------------------ softmax statistics
-// A group of L = next power of two >= K lanes holds one row (rows are not 16-byte aligned when K % 4 != 0: one 4-byte load per
-// lane, and a wave of 64 / L consecutive rows still reads one contiguous span).  Lanes c >= K and the lanes of rows >= B hold
-// -inf; they take part in every shuffle and store nothing.  All cross-lane steps are xor butterflies inside the group: both
-// partners of a step form the same bits (a + b == b + a; the (value, index) order is total), so every lane of a group ends
-// with the group's result, in an order that depends on L alone.
+// One row per group of L lanes (dmf_rows.h).  Beyond the softmax terms: S = sum e t for the entropy ln Z - S / Z, and e2, the
+// largest e over c != pred, for the margin (1 - e2) / Z.
 template <int L>
 __global__ __launch_bounds__(256) void softmax_stats_kernel(const float* __restrict__ logits, int B, int K,
                                                             const float* __restrict__ inv_temp, const int32_t* __restrict__ xy, int W,
                                                             int32_t* __restrict__ pred, float* __restrict__ conf,
                                                             float* __restrict__ margin, float* __restrict__ entropy) {
-  constexpr int ROWS = 256 / L;
-  const int c = threadIdx.x % L;
-  const int64_t r = (int64_t)blockIdx.x * ROWS + threadIdx.x / L;
+  const int c = row_column<L>();
+  const int64_t r = row_index<L>();
   const bool row = r < B;
   const float beta = inv_temp != nullptr ? inv_temp[0] : 1.f;
-  const float l = row && c < K ? logits[(size_t)r * K + c] : -INFINITY;
-  // the row maximum with its FIRST index: the value decides, then the lower index (dmf_forward's rule)
-  float m = l;
-  int first = c;
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, 64);
-    const int oi = __shfl_xor(first, off, 64);
-    if (om > m || (om == m && oi < first)) { m = om; first = oi; }
-  }
-  const float t = (l - m) * beta;            // <= 0; -inf on the lanes past K
-  const float e = expf(t);
-  float Z = e;
-  float S = e == 0.f ? 0.f : e * t;          // (a term with e == 0 counts as 0: 0 * -inf is not a number)
-  float e2 = c == first ? 0.f : e;           // the largest e over c != pred; K == 1: 0
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) {
-    Z += __shfl_xor(Z, off, 64);
-    S += __shfl_xor(S, off, 64);
-    e2 = fmaxf(e2, __shfl_xor(e2, off, 64));
-  }
+  const RowSoftmax s = row_softmax<L>(row && c < K ? logits[(size_t)r * K + c] : -INFINITY, c, beta);
+  float Z = s.e;
+  float S = s.e == 0.f ? 0.f : s.e * s.t;                        // (a term with e == 0 counts as 0: 0 * -inf is not a number)
+  float e2 = c == s.first ? 0.f : s.e;                           // K == 1: 0
+  row_butterfly<L>([&](auto other) {
+    Z += other(Z);
+    S += other(S);
+    e2 = fmaxf(e2, other(e2));
+  });
   if (!row || c != 0) return;
   const size_t o = xy != nullptr ? (size_t)xy[2 * r] * W + xy[2 * r + 1] : (size_t)r;     // labelmap_kernel's addressing
-  if (pred != nullptr) pred[o] = first;
+  if (pred != nullptr) pred[o] = s.first;
   if (conf != nullptr) conf[o] = 1.f / Z;
   if (margin != nullptr) margin[o] = (1.f - e2) / Z;
   if (entropy != nullptr) entropy[o] = fmaxf(0.f, logf(Z) - S / Z);
 }
 
-template <int L>
-static hipError_t stats_launch(const SoftmaxStatsArgs& a, hipStream_t st) {
-  const int rows = 256 / L;
-  hipLaunchKernelGGL(softmax_stats_kernel<L>, dim3((unsigned)(((int64_t)a.B + rows - 1) / rows)), dim3(256), 0, st, a.logits, a.B, a.K,
-                     a.inv_temp, a.xy, a.W, a.pred, a.conf, a.margin, a.entropy);
-  return hipGetLastError();
-}
-
 hipError_t launch_softmax_stats(const SoftmaxStatsArgs& a, hipStream_t st) {
-  if (a.K <= 1) return stats_launch<1>(a, st);
-  if (a.K <= 2) return stats_launch<2>(a, st);
-  if (a.K <= 4) return stats_launch<4>(a, st);
-  if (a.K <= 8) return stats_launch<8>(a, st);
-  if (a.K <= 16) return stats_launch<16>(a, st);
-  if (a.K <= 32) return stats_launch<32>(a, st);
-  return stats_launch<64>(a, st);
+  return for_row_lanes(a.K, [&](auto L) {
+    hipLaunchKernelGGL(softmax_stats_kernel<decltype(L)::value>, row_blocks<decltype(L)::value>(a.B), dim3(256), 0, st, a.logits, a.B,
+                       a.K, a.inv_temp, a.xy, a.W, a.pred, a.conf, a.margin, a.entropy);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------ reliability histogram

@@ -30,48 +30,26 @@
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_rows.h"
 
 namespace dmf {
 
 // ------------------------------------------------------------------------------ probability scatter
-// softmax_stats_kernel's group of L lanes per row and its butterflies, so t_c, e_c and Z are the same bits as there and
-// p[pred] = 1 / Z is its conf.
+// softmax_stats_kernel's rows and softmax terms (dmf_rows.h): p[pred] = 1 / Z is its conf.
 template <int L>
 __global__ __launch_bounds__(256) void prob_scatter_kernel(const float* __restrict__ logits, int B, int K,
                                                            const float* __restrict__ inv_temp, const int32_t* __restrict__ xy, int W,
                                                            float* __restrict__ prob, uint8_t* __restrict__ mask) {
-  constexpr int ROWS = 256 / L;
-  const int c = threadIdx.x % L;
-  const int64_t r = (int64_t)blockIdx.x * ROWS + threadIdx.x / L;
+  const int c = row_column<L>();
+  const int64_t r = row_index<L>();
   const bool row = r < B;
   const float beta = inv_temp != nullptr ? inv_temp[0] : 1.f;
-  const float l = row && c < K ? logits[(size_t)r * K + c] : -INFINITY;
-  float m = l;
-  int first = c;
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, 64);
-    const int oi = __shfl_xor(first, off, 64);
-    if (om > m || (om == m && oi < first)) { m = om; first = oi; }
-  }
-  const float t = (l - m) * beta;
-  const float e = expf(t);
-  float Z = e;
-#pragma unroll
-  for (int off = L / 2; off > 0; off >>= 1) Z += __shfl_xor(Z, off, 64);
+  const RowSoftmax s = row_softmax<L>(row && c < K ? logits[(size_t)r * K + c] : -INFINITY, c, beta);
+  const float Z = row_sum<L>(s.e);
   if (!row || c >= K) return;
   const int64_t o = (int64_t)xy[2 * r] * W + xy[2 * r + 1];
-  prob[o * K + c] = e / Z;
+  prob[o * K + c] = s.e / Z;
   if (c == 0) mask[o] = 1;
-}
-
-template <int L>
-static hipError_t scatter_launch(const float* logits, int B, int K, const float* inv_temp, const int32_t* xy, int W, float* prob,
-                                 uint8_t* mask, hipStream_t st) {
-  const int rows = 256 / L;
-  hipLaunchKernelGGL(prob_scatter_kernel<L>, dim3((unsigned)(((int64_t)B + rows - 1) / rows)), dim3(256), 0, st, logits, B, K,
-                     inv_temp, xy, W, prob, mask);
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------ tiles
@@ -293,14 +271,11 @@ int32_t dmf_prob_scatter(const float* logits, int32_t B, int32_t K, const float*
   if (K < 1 || K > DMF_KMAX) return 3;
   if (B == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e;
-  if (K <= 1) e = scatter_launch<1>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else if (K <= 2) e = scatter_launch<2>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else if (K <= 4) e = scatter_launch<4>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else if (K <= 8) e = scatter_launch<8>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else if (K <= 16) e = scatter_launch<16>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else if (K <= 32) e = scatter_launch<32>(logits, B, K, inv_temp, xy, W, prob, mask, st);
-  else e = scatter_launch<64>(logits, B, K, inv_temp, xy, W, prob, mask, st);
+  const hipError_t e = for_row_lanes(K, [&](auto L) {
+    hipLaunchKernelGGL(prob_scatter_kernel<decltype(L)::value>, row_blocks<decltype(L)::value>(B), dim3(256), 0, st, logits, B, K,
+                       inv_temp, xy, W, prob, mask);
+    return hipGetLastError();
+  });
   return e == hipSuccess ? 0 : 9;
 }
 

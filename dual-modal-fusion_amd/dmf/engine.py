@@ -1062,10 +1062,11 @@ class TrainEngine(_PlanEngine):
 
 class _ShardedEval:
     """The whole-set passes of both evaluation engines: confusion matrix and label map over any number of pixels, in chunks
-    of the engine's size.  With a process group every rank takes its contiguous shard of the pixels and the per-rank results
-    are combined by an all-reduce.  An engine states two hooks:
+    of the engine's size (`_walk`, the one place that shards, checks, uploads and slices).  With a process group every rank
+    takes its contiguous shard of the pixels and the per-rank results are combined by an all-reduce.  An engine states two hooks:
       * `_check_bounds(xy_host)`: refuse pixels [n,2] (numpy) whose patches leave the resident scene;
-      * `_chunk_pred(xy)`: pixels [n <= B, 2] on the device, already checked -> `pred[:n]` (one forward with its argmax)."""
+      * `_chunk_forward(xy)`: pixels [n <= B, 2] on the device, already checked -> (logits or None, `pred[:n]`): one forward with
+        its argmax, views valid until the next call."""
 
     def _check_batch(self, n):
         if n > self.B:
@@ -1091,14 +1092,23 @@ class _ShardedEval:
         else:                                       # gloo (CPU tests, one-GPU rehearsal): reduce on the host
             x.copy_(allreduce_(x.cpu(), process_group))
 
-    def _whole_set(self, process_group, xy_all, *more):
-        """(this rank's pixels on the host as numpy, the same and the rows of `more` that go with them on the device as
-        int32); the pixels' bounds are checked here, once for the whole set."""
-        dev = self.scene.device
+    def _walk(self, process_group, xy_all, *more, extent=None):
+        """All given pixels in chunks of `self.B` -> (rows, chunks).  At once, before anything is launched: this rank's shard of
+        xy_all and of the per-pixel tensors `more` (labels) as int32; the pixels' patch bounds, checked on the host once for the
+        whole set; with extent = (H, W, what) also that every pixel lies inside the [H, W] map the caller writes at (x, y); the
+        upload, rows = (xy, *more) on the device.  `chunks` yields (xy, logits or None, pred, *its rows of more) per chunk."""
         rows = self._shard(process_group, *(torch.as_tensor(t).to(torch.int32) for t in (xy_all,) + more))
         host = rows[0].cpu().numpy()
         self._check_bounds(host)
-        return (host,) + tuple(t.to(dev).contiguous() for t in rows)
+        if extent is not None and len(host) and (int(host[:, 0].max()) >= extent[0] or int(host[:, 1].max()) >= extent[1]):
+            raise lib.DmfError('pixel outside the %d x %d %s' % extent)                # the kernels write map[x * W + y]
+        rows = tuple(t.to(self.scene.device).contiguous() for t in rows)
+
+        def chunks(xy_all=rows[0]):
+            for i in range(0, xy_all.shape[0], self.B):
+                xy, *rest = (t[i:i + self.B] for t in rows)
+                yield (xy, *self._chunk_forward(xy), *rest)
+        return rows, chunks()
 
     def confusion(self, xy_all, labels_all, matrix=None, process_group=None):
         """Confusion matrix [K,K] int64 (rows = prediction) over all given pixels (mainsolver.py:137-147, tostagesolver.py:
@@ -1106,12 +1116,11 @@ class _ShardedEval:
         pass zeros)."""
         from .parallel import allreduce_sum_
         K = self.net.arch['K']
-        _, xy_all, labels_all = self._whole_set(process_group, xy_all, labels_all)
+        _, chunks = self._walk(process_group, xy_all, labels_all)
         if matrix is None:
             matrix = torch.zeros(K, K, dtype=torch.int64, device=self.scene.device)
-        for i in range(0, xy_all.shape[0], self.B):
-            pred = self._chunk_pred(xy_all[i:i + self.B])
-            lib.confusion_accum(pred, labels_all[i:i + self.B], K, matrix)
+        for _, _, pred, labels in chunks:
+            lib.confusion_accum(pred, labels, K, matrix)
         self._all_reduce(matrix, process_group, allreduce_sum_)
         return matrix
 
@@ -1119,14 +1128,11 @@ class _ShardedEval:
         """Predicted class of every given pixel written at (x, y) of an [H, W] int32 map (mainsolver.py:171-183,
         tostagesolver.py:360-383).  With a process group the tiles are merged (every pixel is written by one rank)."""
         from .parallel import allreduce_max_
-        host, xy_all = self._whole_set(process_group, xy_all)
-        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
-            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))      # labelmap_kernel writes map[x * W + y]
+        _, chunks = self._walk(process_group, xy_all, extent=(H, W, 'label map'))
         if label_map is None:
             label_map = torch.zeros(H, W, dtype=torch.int32, device=self.scene.device)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            lib.labelmap_write(self._chunk_pred(xy), xy, W, label_map)
+        for xy, _, pred in chunks:
+            lib.labelmap_write(pred, xy, W, label_map)
         self._all_reduce(label_map, process_group, allreduce_max_)
         return label_map
 
@@ -1262,8 +1268,8 @@ class EvalEngine(_ShardedEval):
         for s in self.tta_slots:
             lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.map_xy(xy_host, s))
 
-    def _chunk_pred(self, xy):
-        return self.predict(xy)[1]
+    def _chunk_forward(self, xy):
+        return self.predict(xy)
 
     # ------------------------------------------------------------------ calibrated confidence
     # One device only: the solvers refuse the keys for data-parallel runs.  Everything works on `predict`'s logits, so the
@@ -1282,15 +1288,11 @@ class EvalEngine(_ShardedEval):
         place of dmf_labelmap_write: the label map is the one `label_map` gives."""
         dev = self.scene.device
         beta = self._beta(inv_temp)
-        host, xy_all = self._whole_set(None, xy_all)
-        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
-            raise lib.DmfError('pixel outside the %d x %d label map' % (H, W))      # the kernel writes map[x * W + y]
+        _, chunks = self._walk(None, xy_all, extent=(H, W, 'label map'))
         label_map = torch.zeros(H, W, dtype=torch.int32, device=dev)
         planes = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            lib.softmax_stats(self.predict(xy)[0], pred=label_map, conf=planes[0], margin=planes[1], entropy=planes[2],
-                              inv_temp=beta, xy=xy, W=W)
+        for xy, logits, _ in chunks:
+            lib.softmax_stats(logits, pred=label_map, conf=planes[0], margin=planes[1], entropy=planes[2], inv_temp=beta, xy=xy, W=W)
         return label_map, planes
 
     # ------------------------------------------------------------------ spatial regularisation (DESIGN.md §19)
@@ -1300,14 +1302,11 @@ class EvalEngine(_ShardedEval):
         `predict`'s logits: test-time augmentation and the attention net come with it."""
         dev = self.scene.device
         beta = self._beta(inv_temp)
-        host, xy_all = self._whole_set(None, xy_all)
-        if len(host) and (int(host[:, 0].max()) >= H or int(host[:, 1].max()) >= W):
-            raise lib.DmfError('pixel outside the %d x %d probability map' % (H, W))   # the kernel writes prob[(x * W + y) * K + c]
+        _, chunks = self._walk(None, xy_all, extent=(H, W, 'probability map'))
         prob = torch.zeros(H, W, self.net.arch['K'], dtype=torch.float32, device=dev)
         mask = torch.zeros(H, W, dtype=torch.uint8, device=dev)
-        for i in range(0, xy_all.shape[0], self.B):
-            xy = xy_all[i:i + self.B]
-            lib.prob_scatter(self.predict(xy)[0], xy, W, prob, mask, inv_temp=beta)
+        for xy, logits, _ in chunks:
+            lib.prob_scatter(logits, xy, W, prob, mask, inv_temp=beta)
         return prob, mask
 
     def regularise(self, prob, mask, aff, iterations=1):
@@ -1328,11 +1327,10 @@ class EvalEngine(_ShardedEval):
 
     def collect_logits(self, xy_all, labels_all=None):
         """-> the logits of all given pixels in ONE device tensor [N, K] (and their labels as device int32 [N])."""
-        _, *rows = self._whole_set(None, xy_all, *(() if labels_all is None else (labels_all,)))
-        xy_all = rows[0]
-        out = torch.empty(xy_all.shape[0], self.net.arch['K'], device=self.scene.device)
-        for i in range(0, xy_all.shape[0], self.B):
-            out[i:i + self.B].copy_(self.predict(xy_all[i:i + self.B])[0])
+        rows, chunks = self._walk(None, xy_all, *(() if labels_all is None else (labels_all,)))
+        out = torch.empty(rows[0].shape[0], self.net.arch['K'], device=self.scene.device)
+        for (_, logits, *_), dst in zip(chunks, out.split(self.B)):
+            dst.copy_(logits)
         return out if labels_all is None else (out, rows[1])
 
     def calibration_of(self, logits, labels, nbins, inv_temp=None, hist=None):
@@ -1351,10 +1349,10 @@ class EvalEngine(_ShardedEval):
         """Reliability histogram hist [nbins, 3] int64 over all given pixels (rows, hits, confidence sum in units of 2^-32 per
         confidence bin; dmf_softmax_stats + dmf_calib_accum per chunk).  Labels outside [0, K) are skipped."""
         beta = self._beta(inv_temp)
-        _, xy_all, labels_all = self._whole_set(None, xy_all, labels_all)
+        _, chunks = self._walk(None, xy_all, labels_all)
         hist = torch.zeros(nbins, 3, dtype=torch.int64, device=self.scene.device)
-        for i in range(0, xy_all.shape[0], self.B):
-            self.calibration_of(self.predict(xy_all[i:i + self.B])[0], labels_all[i:i + self.B], nbins, beta, hist)
+        for _, logits, _, labels in chunks:
+            self.calibration_of(logits, labels, nbins, beta, hist)
         return hist
 
     def _temp_ws(self, n):
@@ -1591,13 +1589,13 @@ class QuaEvalEngine(_ShardedEval):
     def _check_bounds(self, xy_host):            # (only the ms and pan streams are read)
         lib.check_xy_bounds(self.shape, self.scene.A, self.scene.B, self.scene.stack_xy(xy_host, 2).numpy())
 
-    def _chunk_pred(self, xy, checked=True):
+    def _chunk_forward(self, xy, checked=True):
         n = self._forward(xy, 2, checked)
         lib.pair_argmax(self.logits, n, self.pred)
-        return self.pred[:n]
+        return None, self.pred[:n]
 
     def predict(self, xy):
-        pred = self._chunk_pred(xy, checked=False)
+        pred = self._chunk_forward(xy, checked=False)[1]
         return self.logits[:2 * pred.shape[0]], pred
 
     def loss_value(self, xy, labels):

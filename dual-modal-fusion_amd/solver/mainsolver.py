@@ -6,8 +6,8 @@ its running loss exceeds the best one (:62-76), best weights -> `<time>_weights.
 epoch -> `<time>_curweights.pth` ({'state_dict','optimizer'}); `test()` fills `test_matrix[pred][target]` and calls
 `indicator()`; `color()` writes `<time>_pic_1.png` / `_pic_2.png`.
 
-Two execution paths, same arithmetic; `train()`, `test()` and `color()` choose between them once, by method
-(`_train_epoch_fast` / `_train_epoch_dropin`, `_test_matrix_*`, `_label_map_*`):
+Two execution paths, same arithmetic; `train()` chooses between them once, by method (`_train_epoch_fast` /
+`_train_epoch_dropin`), `test()` and `color()` by the class of `self.evaluation` (solver/evaluation.py):
   * fast (default on a GPU): resident scene + epoch plan + fused HIP step (dmf/engine.py) — no patch
     materialisation, no per-step host sync, confusion matrix and label maps built on the device;
   * drop-in (`fast_path: 0`): the reference's own loop body (mainsolver.py:49-55) over materialised batches through
@@ -48,15 +48,6 @@ copy of the weights, torch's `AveragedModel`, updated after every optimiser step
 the averaged weights (`_on_average`), `<t>_weights.pth` holds those of the best epoch (in an epoch block dmf_keep_best is handed
 them), so test() / color() classify with them; `<t>_curweights.pth` keeps the raw weights and the optimiser and gains the key
 `averaged`, which test() loads with `save_best: 0`.  toStageSolver refuses the keys.
-`test.calibration: 1`, `test.calibration_bins`, `test.temperature: none | fit | T` and `color.confidence: 1` (all optional, DESIGN
-§17): after the confusion matrix and over the same pixels `test()` fills the reliability histogram, ECE, MCE and the mean NLL
-(`self.calibration`, `<t>_calibration.json`), at the temperature T — a number, or with `fit` the temperature-scaling fit on
-the VALIDATION split (`_temperature_used`, once per trained model) —, and with T != 1 the same block `before` scaling;
-`color()` also writes `<t>_confidence_{1,2}.npy` (float32 [3, H, W]: confidence, margin, entropy; 0 where nothing is coloured)
-and `<t>_conf_{1,2}.png` (8-bit grey, round(255 conf)), composed as the label maps are.  Fast path: dmf_softmax_stats /
-dmf_calib_accum / dmf_temperature_step on the eval engine's logits, the label maps written by dmf_softmax_stats in
-dmf_labelmap_write's place; drop-in path: torch ops in float64; both through utils/calibration.py.  `indicator()` and its export
-are untouched; toStageSolver and data-parallel runs refuse the keys.  Neutral values change nothing.
 `schedule.augment: none | flips | d4` and `test.tta: none | flips | d4` (both optional): every train sample is seen as
 one of the 4 flips or 8 flips and quarter turns of its patch, the variant drawn per (cfg['seed'], epoch, pixel) by a stateless
 hash (`_augment_variants`: torch's RNG stream, and so batch order, splits and labels, stay those of an unaugmented run; every
@@ -66,16 +57,8 @@ variant is then a mapped coordinate (`_augment_xy`, before `load_plan`, `load_bl
 what the kernel reads) and no train route changes; `EvalEngine(tta=)` runs one forward per variant and dmf_logits_mean.  Drop-in
 path: the materialised patches are transformed (`augment.tf_batch`), the mean is torch's (`_logits_dropin`).  The validation
 pass is never augmented.  With both keys `none` the scene is the plain Scene and nothing changes; toStageSolver refuses the keys.
-`test.spatial: none | bilateral` with `test.spatial_radius`, `test.spatial_sigma_s`, `test.spatial_sigma_r`, `test.spatial_iterations`,
-and `color.spatial: 1` (all optional): after the confusion matrix (and the calibration) `test()` classifies the pixels
-of both colour sets — the whole scene — at `test.temperature`'s beta, smooths the class probabilities over each pixel's window
-with scene-guided bilateral weights and forms a second confusion matrix over the same test pixels from the regularised map
-(`self.spatial`, `<t>_spatial.json`: parameters, matrix, OA / AA / kappa before and after, pixels whose class changed); `color()`
-also writes `<t>_pic_{1,2}_spatial.png`, composed as the plain maps are.  Fast path: EvalEngine.probability_map, Scene.affinity and
-EvalEngine.regularise (dmf_prob_scatter / dmf_spatial_affinity / dmf_spatial_filter); drop-in path: utils/spatial.py in numpy
-float64.  The pixels are taken from the index dataset's arrays, not from a loader, so torch's RNG stream and every artefact that
-was there stay as they are; `test_matrix`, `indicator()` and its export are untouched; toStageSolver and data-parallel runs refuse
-the keys.
+`test.calibration`, `test.temperature`, `color.confidence` and `test.spatial`, `color.spatial`: see
+solver/evaluation.py, to whose class of this run's path (`self.evaluation`) `test()` and `color()` put their questions.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
 does not divide is trimmed to the largest multiple); the gradient exchange is the engine's; validation runs on every
@@ -98,6 +81,7 @@ from tqdm import tqdm
 
 from dmf import augment
 from solver.basesolver import BaseSolver
+from solver.evaluation import DropinEvaluation, EngineEvaluation, map2
 from utils import calibration as calib
 from utils import spatial
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
@@ -122,6 +106,8 @@ class Solver(BaseSolver):
     regularised = True                                   # `test.spatial` / `color.spatial` are in scope for this stage
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
     aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
+    calib, spat = calib.calibration_keys({}), spatial.spatial_keys({})     # (the constructor reads them from cfg; these: neutral)
+    evaluation = None                                    # solver.evaluation's class of this run's path (`_ensure_model`)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
     def __init__(self, cfg):
@@ -692,17 +678,26 @@ class Solver(BaseSolver):
             self.cur_model = self.model.to(self.DEVICE)
         if self.fast and self.eval_engine is None:
             self.eval_engine = self._eval_engine()
+        if self.evaluation is None:                      # the evaluation path, chosen once
+            self.evaluation = (EngineEvaluation if self.fast else DropinEvaluation)(self)
+
+    def _single_device_scope(self):
+        """Data-parallel runs refuse the calibration and regularisation keys (nothing of them is sharded), as `_epoch_block` does."""
+        keys = calib.keys_in_use(self.calib) + spatial.keys_in_use(self.spat)
+        if keys and self.world > 1:
+            raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out' % (keys[0], self.world))
+
+    _calibration_scope = _spatial_scope = _single_device_scope         # the names the two refusals had while they were two
 
     def test(self):
         time1 = time.time()
-        self._calibration_scope()
-        self._spatial_scope()
+        self._single_device_scope()
         self._ensure_model()
         self._load_weights(self.cfg['train']['save_best'])
         self.cur_model.eval()
         whole = self._test_whole_split()
         with torch.no_grad():
-            matrix = self._test_matrix_fast(whole) if self.fast else self._test_matrix_dropin(whole)
+            matrix = self.evaluation.confusion(whole)
         self.test_time = time.time() - time1
         self.test_matrix = matrix.astype(np.float64)
         if self.calib['calibration']:
@@ -717,89 +712,40 @@ class Solver(BaseSolver):
             from indicators.kappa import aa_oa_quiet
             self.result = list(aa_oa_quiet(self.test_matrix)) + [None]
 
-    def _test_matrix_fast(self, whole):
-        """The whole split in evaluation chunks of the engine's own size (data parallel: every rank classifies its part of
-        the pixels, the matrices are summed), or the first batch alone, which every rank classifies whole."""
-        xy, lab = self._test_pixels(whole)
-        return self.eval_engine.confusion(xy, lab, process_group=self.process_group if whole else None).cpu().numpy()
-
     def _test_pixels(self, whole):
         """(xy [n, 2], labels [n]) int32 on the host: the pixels test() classifies on the fast path."""
         parts = [self._xy_labels(b) for b in (self.test_index_loader if whole else itertools.islice(self.test_index_loader, 1))]
         return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
-    def _test_matrix_dropin(self, whole):
-        K = self.cfg['Categories_Number']
-        matrix = np.zeros([K, K])
-        for batch in (self.test_loader if whole else itertools.islice(self.test_loader, 1)):
-            pred, target, _, _ = self._predict_dropin(batch)
-            np.add.at(matrix, (pred.cpu().numpy(), target.long().numpy()), 1)            # test_matrix[pred][target] += 1
-        return matrix
-
     # ------------------------------------------------------------------ calibration (test.calibration, test.temperature; DESIGN §17)
-    def _calibration_scope(self):
-        """Data-parallel runs refuse the keys (the histogram and the fit are not sharded), as `_epoch_block` refuses its key."""
-        if calib.keys_in_use(self.calib) and self.world > 1:
-            raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out'
-                             % (calib.keys_in_use(self.calib)[0], self.world))
-
     @staticmethod
     def _beta(T):
         """beta = 1 / T as the float32 that the kernels read, on both paths."""
         return float(np.float32(1.0 / T))
 
-    def _dropin_logits(self, loader):
-        """(logits [n, K] float64, labels [n]) as numpy over the batches of a materialising loader."""
-        out = [(self._logits_dropin(d1.to(self.DEVICE), d2.to(self.DEVICE)).detach().double().cpu().numpy(), np.asarray(t))
-               for d1, d2, t, _, _ in loader]
-        return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out]).astype(np.int64)
-
     def _temperature_used(self):
         """(T, fit block or None) of `test.temperature`, decided once per trained model: a number as it stands, none -> 1, fit ->
-        temperature scaling on the VALIDATION split: 40 safeguarded Newton steps in beta = 1 / T, on the device without a host
-        round trip (EvalEngine.fit_temperature_of) or on the drop-in path the same rule on the host."""
+        temperature scaling on the VALIDATION split: 40 safeguarded Newton steps in beta = 1 / T."""
         if self._temp is None:
             t = self.calib['temperature']
             if t != 'fit':
                 self._temp = (1.0 if t is None else t, None)
             else:
                 with torch.no_grad():
-                    if self.fast:
-                        xy, lab = self._valid_split()
-                        at_one, state, at_fit = self.eval_engine.fit_temperature_of(*self.eval_engine.collect_logits(xy, lab),
-                                                                                    steps=calib.FIT_STEPS)
-                        n, beta, steps, nll1, nllT = int(lab.shape[0]), float(state[0]), int(state[6]), float(at_one[1]), float(at_fit[1])
-                    else:
-                        logits, lab = self._dropin_logits(self.valid_loader)
-                        f = calib.fit_temperature(logits, lab)
-                        n, beta, steps = len(lab), f['beta'], f['steps']
-                        nll1, nllT = calib.nll_terms(logits, lab, 1.0)[0], calib.nll_terms(logits, lab, beta)[0]
+                    n, beta, steps, nll1, nllT = self.evaluation.fit(*self.evaluation.split_logits('valid'))
                 if n < 1:
                     raise ValueError('test.temperature: fit needs a validation split')
                 self._temp = (1.0 / beta, dict(n=n, nll_at_1=nll1 / n, nll_at_T=nllT / n, beta=beta, steps=steps))
         return self._temp
 
     def _calibration_block(self, logits, labels, T):
-        """The block of utils.calibration.summary at temperature T, from the logits of the test pixels: device tensors on the
-        fast path, numpy on the drop-in path."""
-        bins, beta = self.calib['bins'], self._beta(T)
-        if self.fast:
-            hist = self.eval_engine.calibration_of(logits, labels, bins, beta).cpu().numpy()
-            nll = float(self.eval_engine.nll_of(logits, labels, beta)[1].item()) if logits.shape[0] else 0.0
-        else:
-            K = logits.shape[1]
-            pred, st = calib.softmax_stats(torch.from_numpy(logits), beta)
-            hist = calib.histogram(st[0].numpy(), pred.numpy(), labels, K, bins)
-            nll = calib.nll_terms(logits, labels, beta)[0]
-        return calib.summary(hist, nll, T)
+        """The block of utils.calibration.summary at temperature T, from the logits of the test pixels."""
+        return calib.summary(*self.evaluation.reliability(logits, labels, self.calib['bins'], self._beta(T)), T)
 
     def _calibrate(self, whole):
         """`self.calibration` and `<t>_calibration.json` over the pixels of the confusion matrix."""
         T, fit = self._temperature_used()
-        if self.fast:
-            logits, labels = self.eval_engine.collect_logits(*self._test_pixels(whole))
-        else:
-            logits, labels = self._dropin_logits(self.test_loader if whole else itertools.islice(self.test_loader, 1))
+        logits, labels = self.evaluation.split_logits('test', whole)
         block = self._calibration_block(logits, labels, T)
         if T != 1.0:
             block['before'] = self._calibration_block(logits, labels, 1.0)
@@ -811,12 +757,6 @@ class Solver(BaseSolver):
                 json.dump(block, f, indent=1)
 
     # ------------------------------------------------------------------ spatial regularisation (test.spatial, color.spatial)
-    def _spatial_scope(self):
-        """Data-parallel runs refuse the keys (the probability map and the filter are not sharded), as `_calibration_scope` does."""
-        if spatial.keys_in_use(self.spat) and self.world > 1:
-            raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out'
-                             % (spatial.keys_in_use(self.spat)[0], self.world))
-
     def _set_pixels(self, rows):
         """xy [n, 2] int32 (numpy) of rows of the pixel table, from the index dataset's arrays: no loader, so torch's RNG stream
         stays what it is without the keys."""
@@ -829,39 +769,13 @@ class Solver(BaseSolver):
         return self._set_pixels(list(self.matrix_[1]) + list(self.matrix_[0]))
 
     def _regularised_maps(self, best):
-        """-> (plain, regularised) label maps [H, W] int32 (numpy) of the WHOLE scene under the loaded weights (`best`: which file
-        they came from; the pair is kept per trained model and file; the fast path leaves the plain one None): all pixels of both colour sets are classified at
-        `test.temperature`'s beta, the probabilities go through `test.spatial_iterations` passes of the filter.  Fast path:
-        EvalEngine.probability_map, Scene.affinity and EvalEngine.regularise; drop-in path: utils.spatial in float64 on the
-        logits of `Net.forward` and the host's padded scene."""
-        if self._spatial_maps is not None and self._spatial_maps[0] == bool(best):
-            return self._spatial_maps[1]
-        k = self.spat
-        size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
-        H, W = int(size[0]), int(size[1])
-        beta = self._beta(self._temperature_used()[0])
-        xy = self._scene_pixels()
-        if self.fast:
-            eng = self.eval_engine
-            prob, mask = eng.probability_map(torch.from_numpy(xy), H, W, beta)
-            plain = None                                 # (the test pixels' own classes: `_regularise` asks the engine)
-            aff = self.scene.affinity(H, W, k['radius'], k['sigma_s'], k['sigma_r'])
-            smooth = eng.regularise(prob, mask, aff, k['iterations'])[1].cpu().numpy()
-        else:
-            from torch.utils.data import DataLoader, Subset
-            rows = list(self.matrix_[1]) + list(self.matrix_[0])
-            loader = DataLoader(Subset(self.dataset, indices=rows), batch_size=self.cfg['color_batchsize'], shuffle=False,
-                                num_workers=0, generator=torch.Generator())       # (a generator of its own: the global stream stays)
-            logits = self._dropin_logits(loader)[0]
-            prob, mask = np.zeros((H, W, logits.shape[1])), np.zeros((H, W), dtype=np.uint8)
-            prob[xy[:, 0], xy[:, 1]] = spatial.probabilities(logits, beta)
-            mask[xy[:, 0], xy[:, 1]] = 1
-            plain = np.zeros((H, W), dtype=np.int32)
-            plain[xy[:, 0], xy[:, 1]] = logits.argmax(1)
-            scene = self.MS.astype(np.float16) if self.half else self.MS
-            aff = spatial.affinity(scene, H, W, k['radius'], k['sigma_s'], k['sigma_r'])
-            smooth = spatial.regularise(prob, mask, aff, k['radius'], k['iterations'])[1]
-        self._spatial_maps = (bool(best), (plain, smooth))
+        """-> (plain or None, regularised) label maps [H, W] int32 (numpy) of the WHOLE scene under the loaded weights (`best`:
+        which file they came from; the pair is kept per trained model and file): all pixels of both colour sets are classified at
+        `test.temperature`'s beta, the probabilities go through `test.spatial_iterations` passes of the filter."""
+        if self._spatial_maps is None or self._spatial_maps[0] != bool(best):
+            size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
+            beta = self._beta(self._temperature_used()[0])
+            self._spatial_maps = (bool(best), self.evaluation.scene_maps(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.spat))
         return self._spatial_maps[1]
 
     def _regularise(self, whole):
@@ -872,12 +786,10 @@ class Solver(BaseSolver):
         if not whole:
             rows = rows[:self.cfg['test_batchsize']]   # the first batch of the unshuffled loader
         xy, lab = self._set_pixels(rows), self.index_dataset.label[rows].astype(np.int64)
-        if plain is None:
-            plain = self.eval_engine.label_map(torch.from_numpy(xy), *smooth.shape).cpu().numpy()
         K = self.cfg['Categories_Number']
         after = np.zeros([K, K], dtype=np.int64)
         np.add.at(after, (smooth[xy[:, 0], xy[:, 1]], lab), 1)                    # matrix[pred][target] += 1
-        changed = int((smooth[xy[:, 0], xy[:, 1]] != plain[xy[:, 0], xy[:, 1]]).sum())
+        changed = int((smooth[xy[:, 0], xy[:, 1]] != self.evaluation.plain_at(xy, plain, *smooth.shape)).sum())
         self.spatial = spatial.report(self.spat, self.test_matrix, after, changed)
         if self.rank == 0:
             with open(self.cfg['RESULT_output'] + str(self.time) + '_spatial.json', 'w') as f:
@@ -894,82 +806,48 @@ class Solver(BaseSolver):
                 xy = self._set_pixels(rows)
                 m[xy[:, 0], xy[:, 1]] = smooth[xy[:, 0], xy[:, 1]]
             maps.append(m)
-        map2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
-        self.spatial_maps = (maps[0], map2)
+        self.spatial_maps = (maps[0], map2(maps, self.cfg['color']['unsupervised']))
         if self.cfg['color']['supervised'] and self.rank == 0:
             for n, m in enumerate(self.spatial_maps, 1):
                 Image.fromarray(lut[m]).save(self.cfg['RESULT_output'] + str(self.time) + '_pic_%d_spatial.png' % n)
 
     # ------------------------------------------------------------------ colour
     def color(self):
-        self._calibration_scope()
-        self._spatial_scope()
+        self._single_device_scope()
         self._ensure_model()
         self._load_weights(True)
         self.cur_model.eval()
         size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
         H, W = int(size[0]), int(size[1])
         lut = np.asarray(self.cfg['DATA_DICT'][self.cfg['data_city']]['color'], dtype=np.uint8)
-        label_map = self._label_map_fast if self.fast else self._label_map_dropin
+        ev, col, out = self.evaluation, self.cfg['color'], self.cfg['RESULT_output'] + str(self.time)
         confident = self.calib['confidence']           # color.confidence: the label maps come with their confidence planes
         if confident:
             beta = self._beta(self._temperature_used()[0])
-            conf_map = self._confidence_map_fast if self.fast else self._confidence_map_dropin
         maps, planes = [], []
         with torch.no_grad():
-            for use, loaders in ((self.cfg['color']['supervised'], (self.color_index_loader1, self.color_loader1)),
-                                 (self.cfg['color']['unsupervised'], (self.color_index_loader2, self.color_loader2))):
+            for n, use in ((1, col['supervised']), (2, col['unsupervised'])):
                 if use and confident:
-                    m, p = conf_map(loaders, H, W, beta)
+                    m, p = ev.confidence_map(n, H, W, beta)
                     maps.append(m); planes.append(p)
                 else:
-                    maps.append(label_map(loaders, H, W) if use else np.zeros([H, W], dtype=np.int32))
+                    maps.append(ev.label_map(n, H, W) if use else np.zeros([H, W], dtype=np.int32))
                     if confident:
                         planes.append(np.zeros([3, H, W], dtype=np.float32))
-        label_np1 = maps[0]
-        label_np2 = np.where(maps[1] != 0, maps[1], maps[0]) if self.cfg['color']['unsupervised'] else maps[0]
-        self.label_maps = (label_np1, label_np2)
-        if self.cfg['color']['supervised'] and self.rank == 0:
-            Image.fromarray(lut[label_np1]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_1.png")
-            Image.fromarray(lut[label_np2]).save(self.cfg['RESULT_output'] + str(self.time) + "_pic_2.png")
+        self.label_maps = (maps[0], map2(maps, col['unsupervised']))
+        if col['supervised'] and self.rank == 0:
+            for k, m in enumerate(self.label_maps, 1):
+                Image.fromarray(lut[m]).save(out + '_pic_%d.png' % k)
         if confident:
-            # map 2 takes the unsupervised pixel where its label is not 0, as label_np2 does
-            conf2 = np.where(maps[1][None] != 0, planes[1], planes[0]) if self.cfg['color']['unsupervised'] else planes[0]
-            self.confidence_maps = (planes[0], conf2)
-            if self.cfg['color']['supervised'] and self.rank == 0:
+            self.confidence_maps = (planes[0], map2(maps, col['unsupervised'], planes))
+            if col['supervised'] and self.rank == 0:
                 for k, p in enumerate(self.confidence_maps, 1):
-                    np.save(self.cfg['RESULT_output'] + str(self.time) + '_confidence_%d.npy' % k, p)
+                    np.save(out + '_confidence_%d.npy' % k, p)
                     grey = np.round(255.0 * p[0].astype(np.float64)).clip(0, 255).astype(np.uint8)
-                    Image.fromarray(grey).save(self.cfg['RESULT_output'] + str(self.time) + '_conf_%d.png' % k)
+                    Image.fromarray(grey).save(out + '_conf_%d.png' % k)
         if self.spat['color']:
             with torch.no_grad():
                 self._color_spatial(H, W, lut)
-
-    def _label_map_fast(self, loaders, H, W):
-        """All pixels of the index-only loader, in evaluation chunks of the engine's own size."""
-        return self.eval_engine.label_map(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W,
-                                          process_group=self.process_group).cpu().numpy()
-
-    def _label_map_dropin(self, loaders, H, W):
-        m = np.zeros([H, W], dtype=np.int32)
-        for batch in loaders[1]:
-            pred, _, x, y = self._predict_dropin(batch)
-            m[np.asarray(x), np.asarray(y)] = pred.cpu().numpy()
-        return m
-
-    def _confidence_map_fast(self, loaders, H, W, beta):
-        """`_label_map_fast` with the confidence planes [3, H, W]: one dmf_softmax_stats per chunk writes all four maps."""
-        m, p = self.eval_engine.confidence_maps(torch.cat([self._xy_labels(b)[0] for b in loaders[0]]), H, W, beta)
-        return m.cpu().numpy(), p.cpu().numpy()
-
-    def _confidence_map_dropin(self, loaders, H, W, beta):
-        m, p = np.zeros([H, W], dtype=np.int32), np.zeros([3, H, W], dtype=np.float32)
-        for data1, data2, _, x, y in loaders[1]:
-            logits = self._logits_dropin(data1.to(self.DEVICE), data2.to(self.DEVICE))
-            x, y = np.asarray(x), np.asarray(y)
-            m[x, y] = logits.data.max(1)[1].cpu().numpy()                  # (the prediction of `_predict_dropin`)
-            p[:, x, y] = calib.softmax_stats(logits, beta)[1].cpu().numpy().astype(np.float32)
-        return m, p
 
     def run(self):
         while self.time < self.TIME:

@@ -5,8 +5,8 @@ are padded, sliced by `dataset_qua_dqtl`, concatenated on the batch axis and pus
 (`model.<model_name>.Net(args=cfg)` called as `net(data)`; this build's GMFNet takes the band mean of its input as the
 auxiliary modality, cfg['gmf']['single_input'] = 1), trained with `qua_loss` + ADAM, best epoch by the early-stopping
 validation loop, prediction = argmax softmax(out[:bs] + out[bs:2bs]).  `train()`, the fast epoch, `test()` and `color()`
-are solver.mainsolver's, with its two execution paths, its epoch loop (`_train_epochs`) and its epoch ledger (`_record_epoch`,
-`_save_current`); what stage 2 states differently is the hooks below, and nothing else:
+are solver.mainsolver's, with its two execution paths (evaluation: solver/evaluation.py, whose drop-in class calls `_predict_dropin`),
+its epoch loop (`_train_epochs`) and its epoch ledger (`_record_epoch`, `_save_current`); what stage 2 states differently is the hooks below:
 
   hook                  Solver                                        toStageSolver
   engine_loss             Criterion                                     qua_loss

@@ -3,6 +3,7 @@ new symbols; what the entry points refuse before any launch; utils/calibration.p
 the two refusals (stage 2, data-parallel runs); and the guards of the GPU cases of tests/test_gpu_calibration.py, checked on the
 float64 reference alone (tests/calib_ref.py)."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -218,3 +219,20 @@ def test_stats_cases_have_no_near_ties_but_the_deliberate_ones():
         top = np.sort(rows.astype(np.float64), 1)[:, ::-1]
         assert np.array_equal(top[:, 0] == top[:, 1], tied) and np.array_equal(rows.argmax(1), first)
         assert (rows[2] == rows[2, 0]).all() and (rows[1] == rows[1].max()).sum() == 3
+
+
+# ------------------------------------------------------------------------------------ the drop-in evaluation, end to end on the CPU
+def test_the_drop_in_test_and_color_leave_the_recorded_artefacts_and_rng_state(golden_dir, tmp_path):
+    """`test()` + `color()` with fast_path: 0 and every evaluation key on (tests/dropin_eval_case.py) against what the commit
+    named in tests/golden/g13_dropin_eval.npz left (tools/record_eval_fixtures.py dropin): the decoded artefacts, and torch's
+    RNG state afterwards — exactly: it moves with every loader that is iterated, and this path has no GPU test."""
+    import dropin_eval_case as D
+    got = D.outputs(golden_dir, str(tmp_path))
+    g = np.load(os.path.join(golden_dir, 'g13_dropin_eval.npz'), allow_pickle=False)
+    assert sorted(got) == sorted(k for k in g.files if k != 'recorded_from')
+    assert got['files'].tolist() == g['files'].tolist()
+    assert got['rng_state'].tobytes() == g['rng_state'].tobytes()
+    for name in D.TEXTS:
+        assert json.loads(str(got[name])) == json.loads(str(g[name])), name
+    for name in ('test_matrix',) + D.IMAGES + D.ARRAYS:
+        assert got[name].dtype == g[name].dtype and got[name].shape == g[name].shape and np.array_equal(got[name], g[name]), name

@@ -1612,7 +1612,8 @@ static hipError_t launch_v2_attn(int mode, const KArgs& a, hipStream_t st) {
   X(4, 1, 5, 1, 40, 1, 64)     /* the same on the small test scene */                                         \
   X(4, 1, 16, 4, 40, 1, 64)    /* the reference's own data: 4-band MS + PAN at 4x (config.yml:27,77-110) */         \
   X(8, 1, 5, 4, 40, 2, 64)     /* small test scene, aux at 4x */                                              \
-  DMF_V2_EXTRA_SHAPES(X)       /* rows added at build time: build.py --shapes FILE */
+  X(32, 1, 11, 1, 40, 2, 64)   /* band_reduce: pca at the default 32 components */             \
+  DMF_V2_EXTRA_SHAPES(X)      /* rows added at build time: build.py --shapes FILE */
 // ... the rows of the attention network (gmf.attention; attention block: F = 40, E = 96), which also get the two launches of
 // its train step / forward that are conv work: MODE_TOKENS and MODE_DENSE
 #define DMF_V2_ATTN_SHAPES(X)                                                                                 \
@@ -1623,7 +1624,8 @@ static hipError_t launch_v2_attn(int mode, const KArgs& a, hipStream_t st) {
   X(200, 1, 11, 1, 40, 10, 64)                                                                                \
   X(224, 3, 11, 1, 32, 8, 64)                                                                                 \
   X(8, 1, 5, 1, 40, 2, 64)                                                                                    \
-  X(4, 1, 16, 1, 40, 1, 64)
+  X(4, 1, 16, 1, 40, 1, 64)                                                                                   \
+  X(32, 1, 11, 1, 40, 2, 64)
 // One table row as a statement: the site's ROW with the row's shape as Sh
 #define SHAPE_ROW(C, C2, P, S, F, G, H) { using Sh = Shape<C, C2, P, S, F, G, H>; ROW }
 #define STR2(x) #x

@@ -93,6 +93,38 @@ def _host_fallback(why):
     print('dmf: scene preparation on the host (%s)' % why, flush=True)
 
 
+def band_reduce(raw, K, whiten, device):
+    """`band_reduce: pca` on the device -> (scores [H, W, K] float32 on the host, fit).  The raw primary scene
+    [H, W, C] is uploaded in its own dtype and normalised unpadded (dmf_scene_minmax / dmf_scene_prepare at pad 0, fp32) — on the
+    host, saying why, where prep_route sends it there; dmf_band_moments gives mean and covariance, which are read back once
+    (C + C^2 doubles) for utils.spectral.fit_basis; dmf_band_project writes the scores, which are copied back once.  `fit` is
+    fit_basis's dict plus `route`."""
+    from utils import spectral
+    raw = np.asarray(raw)
+    if raw.ndim != 3:
+        raise lib.DmfError('band_reduce wants a primary scene [H, W, C]')
+    H, W, C = raw.shape
+    K = int(K)
+    spectral.check_bands(K, C)
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        x = torch.empty(H, W, C, dtype=torch.float32, device=device)
+        why = prep_route(raw.dtype, H, W, 0)[1] or _prepare_on_device(raw, 0, x)
+        if why:
+            print('dmf: band_reduce normalises the scene on the host (%s)' % why, flush=True)
+            x = torch.from_numpy(spectral.normalise(raw)).to(device)
+        x = x.view(H * W, C)
+        mean = torch.empty(C, dtype=torch.float64, device=device)
+        cov = torch.empty(C, C, dtype=torch.float64, device=device)
+        lib.band_moments(x, mean, cov)
+        fit = spectral.fit_basis(mean.cpu().numpy(), cov.cpu().numpy(), K, whiten)
+        y = torch.empty(H * W, K, dtype=torch.float32, device=device)
+        lib.band_project(x, mean, torch.from_numpy(fit['basis']).to(device), y)
+        scores = y.cpu().numpy().reshape(H, W, K)
+    fit['route'] = 'device' if not why else 'device, normalised on the host (%s)' % why
+    return scores, fit
+
+
 class Scene:
     """Padded, normalised scenes resident in HBM: A [Hp, Wp, C], B [HpB, WpB, C2] (pixel-major, fp32).
     half: A is kept as IEEE fp16 (`gmf.half`; numpy's float32 -> float16 rounds to nearest even, as the oracle does)."""

@@ -138,6 +138,9 @@ def _load():
         'dmf_prob_scatter': (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
         'dmf_spatial_affinity': (i32, [vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp]),
         'dmf_spatial_filter': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        'dmf_band_moments_workspace_bytes': (i64, [i64, i32]),
+        'dmf_band_moments': (i32, [vp, i64, i32, i64, vp, vp, vp, vp]),
+        'dmf_band_project': (i32, [vp, i64, i32, i64, vp, vp, i32, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -948,3 +951,63 @@ def spatial_filter(prob_in, mask, aff, prob_out, label_map):
         raise DmfError('spatial_filter: all tensors must live on one device')
     _spatial_check('dmf_spatial_filter', _lib.dmf_spatial_filter(_ptr(prob_in), _ptr(mask), _ptr(aff), H, W, K, radius, _ptr(prob_out),
                                                                  _ptr(label_map), _stream()))
+
+
+# return codes of the two entry points of csrc/dmf_pca.hip, which report by code (include/dmf.h)
+PCA_RUN = 256                                   # DMF_PCA_RUN: pixels one fp32 accumulator of the covariance covers
+_PCA_ERRORS = {1: 'a NULL pointer', 2: 'N must be >= 2 (project: >= 0)', 3: '1 <= C <= 512', 4: '1 <= K <= min(C, 64)', 5: 'pitch < C',
+               6: 'a misaligned pointer', 8: 'N * pitch beyond 64-bit byte offsets, or a grid beyond 32 bits', 9: 'a launch failed'}
+
+
+def _pca_check(entry, rc):
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, _PCA_ERRORS.get(rc, 'error %d' % rc)))
+
+
+def _pixels(x, name):
+    """(N, C, pitch) of x: a [N, C] float32 GPU tensor whose rows are `pitch` >= C floats apart (a column slice of a
+    contiguous tensor passes as it is)."""
+    if not (x.is_cuda and x.dtype == torch.float32):
+        raise DmfError('%s must be a %s tensor on the GPU' % (name, torch.float32))
+    if x.dim() != 2 or x.shape[1] < 1 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise DmfError('%s must be [N, C] float32 with unit band stride and a row pitch >= C' % name)
+    return x.shape[0], x.shape[1], x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def band_moments_workspace_bytes(N, C):
+    n = _lib.dmf_band_moments_workspace_bytes(N, C)
+    if n < 0:
+        raise DmfError('dmf_band_moments: N >= 2 and 1 <= C <= 512, got N = %d, C = %d' % (N, C))
+    return n
+
+
+def band_moments(x, mean, cov, ws=None):
+    """mean [C] / cov [C, C] float64 <- the band means and the sample covariance of the pixels x [N, C] float32 (rows `pitch`
+    floats apart), the products in fp32 over runs of PCA_RUN pixels, the sums in double (dmf_band_moments).  ws: a uint8
+    tensor of band_moments_workspace_bytes(N, C) bytes, allocated here when None."""
+    N, C_, pitch = _pixels(x, 'x')
+    _dev(mean, torch.float64, 'mean'); _dev(cov, torch.float64, 'cov')
+    if tuple(mean.shape) != (C_,) or tuple(cov.shape) != (C_, C_) or mean.device != x.device or cov.device != x.device:
+        raise DmfError('band_moments wants mean [%d] and cov [%d, %d] float64 on x\'s device' % (C_, C_, C_))
+    need = band_moments_workspace_bytes(N, C_)
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+    elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need:
+        raise DmfError('band_moments: the workspace needs %d bytes on x\'s device' % need)
+    _pca_check('dmf_band_moments', _lib.dmf_band_moments(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(cov), _ptr(ws), _stream()))
+
+
+def band_project(x, mean, basis, y):
+    """y [N, K] float32 <- (x - float32(mean)) basis for the pixels x [N, C] float32 (rows `pitch` floats apart), mean [C]
+    float64 and basis [C, K] float32, K <= min(C, 64), accumulated in fp32 over the bands in ascending order
+    (dmf_band_project)."""
+    N, C_, pitch = _pixels(x, 'x')
+    _dev(mean, torch.float64, 'mean'); _dev(basis, torch.float32, 'basis'); _dev(y, torch.float32, 'y')
+    if tuple(mean.shape) != (C_,) or basis.dim() != 2 or basis.shape[0] != C_ or tuple(y.shape) != (N, basis.shape[1]):
+        raise DmfError('band_project wants mean [C], basis [C, K] and y [N, K] for x [N, C]')
+    if len({t.device for t in (x, mean, basis, y)}) != 1:
+        raise DmfError('band_project: all tensors must live on one device')
+    if N == 0:                                  # (an empty tensor has a null data pointer)
+        return
+    _pca_check('dmf_band_project', _lib.dmf_band_project(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(basis), basis.shape[1], _ptr(y),
+                                                         _stream()))

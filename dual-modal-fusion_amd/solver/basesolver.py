@@ -12,6 +12,8 @@ on the GPU from the raw scenes (dmf.engine.Scene.from_raw), and the padded host 
 the arrays behind the materialising loaders — are computed only when something asks for them.
 `schedule.augment` / `test.tta` (NEW): on the fast path the resident scene becomes a scene atlas of the variants
 either key needs (`Scene.atlas`: V x the scene in HBM); with both `none` it stays the plain Scene.
+`band_reduce: pca` (NEW): right after `read_tif`, `self.ms` is replaced by the first `band_reduce_bands` principal
+components of the normalised scene, a float32 [H, W, K] array; everything after that line takes it as the raw scene.
 """
 import os
 import time
@@ -24,6 +26,7 @@ from dmf import augment
 from function.function import data_padding, data_padding_aux, data_show, label_mat2np, read_tif, split_data, split_data_old
 from indicators.kappa import aa_oa, expo_result
 from train.dataset import collate_batched, dataset_dual
+from utils import spectral
 
 
 def epoch_orders(n, epochs, draws_after=0):
@@ -62,6 +65,10 @@ class BaseSolver:
         self.ms = read_tif(cfg, 'ms')
         self.pan = read_tif(cfg, 'pan')
         self.fast = bool(cfg.get('fast_path', 1)) and str(self.DEVICE).startswith('cuda')
+        self.band_fit = None                                        # band_reduce: pca — the fit (utils.spectral.fit_basis + route)
+        bands = spectral.band_keys(cfg)
+        if bands['kind'] is not None:                               # from here on the components ARE the raw primary scene
+            self.ms, self.band_fit = self._band_reduce(bands)
         prep = cfg.get('scene_prep') or 'host'
         if prep not in ('host', 'device'):
             raise ValueError('scene_prep: %s is not one of host, device' % prep)
@@ -108,6 +115,33 @@ class BaseSolver:
             ops = augment.union_ops(self.aug_ops, self.tta_ops)
             if len(ops) > 1:
                 self.scene = self.scene.atlas(cfg['patch_size'], int(cfg.get('scale', 4)), ops)
+
+    def _band_reduce(self, keys):
+        """`band_reduce: pca` -> (the scene's first `band_reduce_bands` principal components as a float32
+        [H, W, K] array, the fit).  Fast path: dmf.engine.band_reduce (the moments and the projection on the device, the fit on the
+        host); `fast_path: 0`: utils.spectral.reduce_host.  Writes `<t>_band_reduce.npz`."""
+        cfg, K = self.cfg, keys['bands']
+        if self.ms.ndim != 3:
+            raise ValueError('band_reduce wants a primary scene [H, W, C]')
+        spectral.check_bands(K, self.ms.shape[2])
+        if self.fast:
+            from dmf import lib
+            from dmf.arch import arch_from_cfg
+            from dmf.engine import band_reduce
+            a = arch_from_cfg(cfg)
+            try:
+                lib.shape_supported(lib.make_shape(a))
+            except lib.DmfError as e:
+                raise lib.DmfError('%s; band_reduce_bands: %d needs the line "%d %d %d %d %d %d" in that file'
+                                   % (e, K, a['C'], a['C2'], a['P'], a['S'], a['F'], a['G'])) from None
+            scores, fit = band_reduce(self.ms, K, keys['whiten'], self.DEVICE)
+        else:
+            scores, fit = spectral.reduce_host(self.ms, K, keys['whiten'])
+        print('band_reduce: %d of %d bands, %.4f of the variance, %s' % (K, self.ms.shape[2], float(fit['explained'].sum()), fit['route']))
+        if cfg.get('RESULT_output'):
+            os.makedirs(cfg['RESULT_output'], exist_ok=True)
+            spectral.save_fit(cfg['RESULT_output'] + str(self.time) + '_band_reduce.npz', fit)
+        return scores, fit
 
     @property
     def MS(self):

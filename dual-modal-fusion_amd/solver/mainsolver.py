@@ -83,7 +83,7 @@ from dmf import augment
 from solver.basesolver import BaseSolver
 from solver.evaluation import DropinEvaluation, EngineEvaluation, map2
 from utils import calibration as calib
-from utils import spatial
+from utils import spatial, spectral
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
                          make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
@@ -104,6 +104,7 @@ class Solver(BaseSolver):
     calibrated = True                                    # `test.calibration` / `test.temperature` / `color.confidence` are in scope
     augmented = True                                     # `schedule.augment` / `test.tta` are in scope for this stage
     regularised = True                                   # `test.spatial` / `color.spatial` are in scope for this stage
+    band_reduced = True                                  # `band_reduce` is in scope for this stage
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
     aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
     calib, spat = calib.calibration_keys({}), spatial.spatial_keys({})     # (the constructor reads them from cfg; these: neutral)
@@ -130,6 +131,9 @@ class Solver(BaseSolver):
         if spatial.keys_in_use(self.spat) and not self.regularised:
             raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % (spatial.keys_in_use(self.spat)[0], type(self).__name__))
+        if spectral.keys_in_use(spectral.band_keys(cfg)) and not self.band_reduced:
+            raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % type(self).__name__)
         self.spatial, self._spatial_maps = None, None  # test()'s regularisation block; the whole-scene maps of the loaded weights
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
         self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken

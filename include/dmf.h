@@ -569,6 +569,33 @@ int32_t dmf_spatial_affinity(const void* scene, int32_t elem_bytes, int32_t pitc
 int32_t dmf_spatial_filter(const float* prob_in, const uint8_t* mask, const float* aff, int32_t H, int32_t W, int32_t K,
                            int32_t r, float* prob_out, int32_t* label_map, void* stream);
 
+/* ---- band reduction: the device stages of a PCA of the primary scene in front of the network.  New symbols at
+ * an unchanged DMF_VERSION: detect them by name.  The eigen-decomposition between them is the caller's (utils/spectral.py).
+ *
+ * x is N pixels of C fp32 bands, `pitch` floats apart (pitch >= C); C in 1..512, any remainder mod 4.  Everything is device
+ * memory; x and y need 4-byte, mean, cov and workspace 8-byte alignment.
+ *   moments   mean[c] = (sum_n x[n][c]) / N, summed in double in a fixed tree (slices of the pixels, added as 16 interleaved chains;
+ *             inside a slice four row groups of four interleaved chains each).  cov[i][j] = (sum_n d[n][i] d[n][j]) / (N - 1) with
+ *             d[n][i] = x[n][i] - (float)mean[i] formed in fp32.  The products of a run of DMF_PCA_RUN consecutive pixels
+ *             (run q = pixels [q R, (q + 1) R)) are one fp32 fmaf chain in pixel order, on the fp32 matrix cores; the runs are
+ *             added in double, in ascending order inside a slice of runs and then over the slices in ascending order, and the
+ *             sum is divided by N - 1 in double.  Only the upper triangle is computed; cov[j][i] is written from the sum of
+ *             cov[i][j]: the same bits.  N >= 2.  `workspace` needs dmf_band_moments_workspace_bytes(N, C) bytes (-1 for an N
+ *             or C out of range); four launches, the last one the finishing launch.
+ *   project   y[n][k] = sum_c (x[n][c] - (float)mean[c]) * basis[c][k]: one fp32 fmaf chain over the bands in ascending order
+ *             from 0, on the fp32 matrix cores.  basis [C][K] fp32, K in 1..min(C, 64), y [N][K].  One pass over x; N == 0 is
+ *             a no-op.
+ * No float atomics and fixed orders that depend on (N, C) only: two runs give the same bits.  Both report by code, without a
+ * launch (and so with every output as it was): 1 a NULL pointer; 2 N < 2 (project: N < 0); 3 C outside 1..512; 4 K outside
+ * 1..min(C, 64); 5 pitch < C; 6 a misaligned pointer; 8 N * pitch beyond 64-bit byte offsets, or more workgroups than a grid
+ * holds; and 9 where a launch itself failed.  (They do not set the text of dmf_last_error.) */
+#define DMF_PCA_RUN 256   /* R: pixels one fp32 accumulator of the covariance covers */
+int64_t dmf_band_moments_workspace_bytes(int64_t N, int32_t C);
+int32_t dmf_band_moments(const float* x, int64_t N, int32_t C, int64_t pitch, double* mean /* [C] */, double* cov /* [C][C] */,
+                         void* workspace, void* stream);
+int32_t dmf_band_project(const float* x, int64_t N, int32_t C, int64_t pitch, const double* mean, const float* basis /* [C][K] */,
+                         int32_t K, float* y /* [N][K] */, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

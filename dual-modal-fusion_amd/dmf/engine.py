@@ -93,12 +93,31 @@ def _host_fallback(why):
     print('dmf: scene preparation on the host (%s)' % why, flush=True)
 
 
-def band_reduce(raw, K, whiten, device):
+def _noise_adjusted_fit(x, H, W, K, whiten, noise):
+    """The fit of `band_reduce_noise` for the normalised scene x [H W, C] on the device -> (mean on the device,
+    fit): dmf_band_moments, one dmf_band_noise_moments per direction, ONE read-back of C + C^2 (1 + directions) doubles, and
+    utils.spectral.fit_noise_adjusted on the host."""
+    from utils import spectral
+    C = x.shape[1]
+    dirs = spectral.noise_directions(noise)
+    buf = torch.empty(C + C * C * (1 + len(dirs)), dtype=torch.float64, device=x.device)
+    mean, mats = buf[:C], buf[C:].view(1 + len(dirs), C, C)
+    lib.band_moments(x, mean, mats[0])
+    ws = torch.empty(lib.band_noise_workspace_bytes(H, W, C) // 8, dtype=torch.float64, device=x.device)
+    for i, d in enumerate(dirs):
+        lib.band_noise_moments(x, H, W, mats[1 + i], d, ws)
+    host = buf.cpu().numpy()
+    hm = host[C:].reshape(1 + len(dirs), C, C)
+    return mean, spectral.fit_noise_adjusted(host[:C].copy(), hm[0], spectral.combine_noise(hm[1:]), K, whiten, noise=noise)
+
+
+def band_reduce(raw, K, whiten, device, noise=None):
     """`band_reduce: pca` on the device -> (scores [H, W, K] float32 on the host, fit).  The raw primary scene
     [H, W, C] is uploaded in its own dtype and normalised unpadded (dmf_scene_minmax / dmf_scene_prepare at pad 0, fp32) — on the
     host, saying why, where prep_route sends it there; dmf_band_moments gives mean and covariance, which are read back once
     (C + C^2 doubles) for utils.spectral.fit_basis; dmf_band_project writes the scores, which are copied back once.  `fit` is
-    fit_basis's dict plus `route`."""
+    fit_basis's dict plus `route`.  noise: None, or a direction of `band_reduce_noise`: the noise moments join
+    the read-back and the fit is fit_noise_adjusted's; everything else is as without it."""
     from utils import spectral
     raw = np.asarray(raw)
     if raw.ndim != 3:
@@ -106,6 +125,8 @@ def band_reduce(raw, K, whiten, device):
     H, W, C = raw.shape
     K = int(K)
     spectral.check_bands(K, C)
+    if noise is not None:
+        spectral.check_noise(noise, H, W)
     device = torch.device(device)
     with torch.cuda.device(device):
         x = torch.empty(H, W, C, dtype=torch.float32, device=device)
@@ -114,10 +135,13 @@ def band_reduce(raw, K, whiten, device):
             print('dmf: band_reduce normalises the scene on the host (%s)' % why, flush=True)
             x = torch.from_numpy(spectral.normalise(raw)).to(device)
         x = x.view(H * W, C)
-        mean = torch.empty(C, dtype=torch.float64, device=device)
-        cov = torch.empty(C, C, dtype=torch.float64, device=device)
-        lib.band_moments(x, mean, cov)
-        fit = spectral.fit_basis(mean.cpu().numpy(), cov.cpu().numpy(), K, whiten)
+        if noise is None:
+            mean = torch.empty(C, dtype=torch.float64, device=device)
+            cov = torch.empty(C, C, dtype=torch.float64, device=device)
+            lib.band_moments(x, mean, cov)
+            fit = spectral.fit_basis(mean.cpu().numpy(), cov.cpu().numpy(), K, whiten)
+        else:
+            mean, fit = _noise_adjusted_fit(x, H, W, K, whiten, noise)
         y = torch.empty(H * W, K, dtype=torch.float32, device=device)
         lib.band_project(x, mean, torch.from_numpy(fit['basis']).to(device), y)
         scores = y.cpu().numpy().reshape(H, W, K)

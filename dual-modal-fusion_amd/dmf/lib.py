@@ -141,6 +141,8 @@ def _load():
         'dmf_band_moments_workspace_bytes': (i64, [i64, i32]),
         'dmf_band_moments': (i32, [vp, i64, i32, i64, vp, vp, vp, vp]),
         'dmf_band_project': (i32, [vp, i64, i32, i64, vp, vp, i32, vp, vp]),
+        'dmf_band_noise_workspace_bytes': (i64, [i32, i32, i32]),
+        'dmf_band_noise_moments': (i32, [vp, i32, i32, i32, i64, i32, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -995,6 +997,44 @@ def band_moments(x, mean, cov, ws=None):
     elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need:
         raise DmfError('band_moments: the workspace needs %d bytes on x\'s device' % need)
     _pca_check('dmf_band_moments', _lib.dmf_band_moments(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(cov), _ptr(ws), _stream()))
+
+
+NOISE_DIRECTIONS = {'horizontal': 0, 'vertical': 1}
+_NOISE_ERRORS = {**_PCA_ERRORS, 2: 'no pixel has the neighbour (a one-column scene horizontally, a one-row scene vertically)',
+                 7: 'the direction must be 0 (horizontal) or 1 (vertical)'}
+
+
+def band_noise_workspace_bytes(H, W, C):
+    n = _lib.dmf_band_noise_workspace_bytes(H, W, C)
+    if n < 0:
+        raise DmfError('dmf_band_noise_moments: H, W >= 1, H W >= 2 and 1 <= C <= 512, got H = %d, W = %d, C = %d' % (H, W, C))
+    return n
+
+
+def band_noise_moments(x, H, W, ncov, direction, ws=None):
+    """ncov [C, C] float64 <- sum_p e_p e_p^T / (2 M) of the scene x, [H, W, C] or flat [H W, C] float32 (pixels `pitch` floats
+    apart, rows W pitch), with e_p = x[p] - x[p + s] in fp32 for the pixels that have the neighbour (direction 0 / 'horizontal':
+    s = 1, 1 / 'vertical': s = W) and 0 for the others, M of them (dmf_band_noise_moments: the covariance's arithmetic).  ws: a
+    tensor of band_noise_workspace_bytes(H, W, C) bytes, allocated here when None."""
+    direction = NOISE_DIRECTIONS.get(direction, direction)
+    if x.dim() == 3:
+        if tuple(x.shape[:2]) != (H, W) or (H > 1 and W > 1 and x.stride(0) != W * x.stride(1)):
+            raise DmfError('band_noise_moments wants x [H, W, C] with rows W pixels apart, or flat [H W, C]')
+        x = x.as_strided((H * W, x.shape[2]), (x.stride(1) if W > 1 else x.stride(0), x.stride(2)), x.storage_offset())
+    N, C_, pitch = _pixels(x, 'x')
+    if N != H * W:
+        raise DmfError('band_noise_moments: x has %d pixels, H W = %d' % (N, H * W))
+    _dev(ncov, torch.float64, 'ncov')
+    if tuple(ncov.shape) != (C_, C_) or ncov.device != x.device:
+        raise DmfError('band_noise_moments wants ncov [%d, %d] float64 on x\'s device' % (C_, C_))
+    need = band_noise_workspace_bytes(H, W, C_)
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+    elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need:
+        raise DmfError('band_noise_moments: the workspace needs %d bytes on x\'s device' % need)
+    rc = _lib.dmf_band_noise_moments(_ptr(x), H, W, C_, pitch, int(direction), _ptr(ncov), _ptr(ws), _stream())
+    if rc != 0:
+        raise DmfError('dmf_band_noise_moments: %s' % _NOISE_ERRORS.get(rc, 'error %d' % rc))
 
 
 def band_project(x, mean, basis, y):

@@ -14,6 +14,7 @@ the arrays behind the materialising loaders — are computed only when something
 either key needs (`Scene.atlas`: V x the scene in HBM); with both `none` it stays the plain Scene.
 `band_reduce: pca` (NEW): right after `read_tif`, `self.ms` is replaced by the first `band_reduce_bands` principal
 components of the normalised scene, a float32 [H, W, K] array; everything after that line takes it as the raw scene.
+`band_reduce_noise` (NEW) beside it: the components are the noise-adjusted ones (MNF), ordered by signal-to-noise ratio.
 """
 import os
 import time
@@ -67,7 +68,8 @@ class BaseSolver:
         self.fast = bool(cfg.get('fast_path', 1)) and str(self.DEVICE).startswith('cuda')
         self.band_fit = None                                        # band_reduce: pca — the fit (utils.spectral.fit_basis + route)
         bands = spectral.band_keys(cfg)
-        if bands['kind'] is not None:                               # from here on the components ARE the raw primary scene
+        spectral.noise_keys(cfg)                                    # band_reduce_noise without band_reduce: refused by name
+        if bands['kind'] is not None:                              # from here on the components ARE the raw primary scene
             self.ms, self.band_fit = self._band_reduce(bands)
         prep = cfg.get('scene_prep') or 'host'
         if prep not in ('host', 'device'):
@@ -119,11 +121,16 @@ class BaseSolver:
     def _band_reduce(self, keys):
         """`band_reduce: pca` -> (the scene's first `band_reduce_bands` principal components as a float32
         [H, W, K] array, the fit).  Fast path: dmf.engine.band_reduce (the moments and the projection on the device, the fit on the
-        host); `fast_path: 0`: utils.spectral.reduce_host.  Writes `<t>_band_reduce.npz`."""
+        host); `fast_path: 0`: utils.spectral.reduce_host.  Writes `<t>_band_reduce.npz`.  `band_reduce_noise`: the
+        components are the noise-adjusted ones, on either route; with the key at none no argument is added to either call."""
         cfg, K = self.cfg, keys['bands']
+        noise = spectral.noise_keys(cfg)
+        more = {} if noise is None else {'noise': noise}
         if self.ms.ndim != 3:
             raise ValueError('band_reduce wants a primary scene [H, W, C]')
         spectral.check_bands(K, self.ms.shape[2])
+        if noise is not None:
+            spectral.check_noise(noise, *self.ms.shape[:2])
         if self.fast:
             from dmf import lib
             from dmf.arch import arch_from_cfg
@@ -134,10 +141,14 @@ class BaseSolver:
             except lib.DmfError as e:
                 raise lib.DmfError('%s; band_reduce_bands: %d needs the line "%d %d %d %d %d %d" in that file'
                                    % (e, K, a['C'], a['C2'], a['P'], a['S'], a['F'], a['G'])) from None
-            scores, fit = band_reduce(self.ms, K, keys['whiten'], self.DEVICE)
+            scores, fit = band_reduce(self.ms, K, keys['whiten'], self.DEVICE, **more)
         else:
-            scores, fit = spectral.reduce_host(self.ms, K, keys['whiten'])
-        print('band_reduce: %d of %d bands, %.4f of the variance, %s' % (K, self.ms.shape[2], float(fit['explained'].sum()), fit['route']))
+            scores, fit = spectral.reduce_host(self.ms, K, keys['whiten'], **more)
+        if noise is None:
+            print('band_reduce: %d of %d bands, %.4f of the variance, %s' % (K, self.ms.shape[2], float(fit['explained'].sum()), fit['route']))
+        else:
+            print('band_reduce: %d of %d bands, noise-adjusted (%s), SNR %.4g (first) to %.4g (component %d), %s'
+                  % (K, self.ms.shape[2], noise, fit['snr'][0], fit['snr'][-1], K, fit['route']))
         if cfg.get('RESULT_output'):
             os.makedirs(cfg['RESULT_output'], exist_ok=True)
             spectral.save_fit(cfg['RESULT_output'] + str(self.time) + '_band_reduce.npz', fit)

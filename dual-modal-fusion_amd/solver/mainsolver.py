@@ -131,6 +131,9 @@ class Solver(BaseSolver):
         if spatial.keys_in_use(self.spat) and not self.regularised:
             raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % (spatial.keys_in_use(self.spat)[0], type(self).__name__))
+        if spectral.noise_keys(cfg) is not None and not self.band_reduced:
+            raise ValueError('band_reduce_noise is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % type(self).__name__)
         if spectral.keys_in_use(spectral.band_keys(cfg)) and not self.band_reduced:
             raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)

@@ -596,6 +596,31 @@ int32_t dmf_band_moments(const float* x, int64_t N, int32_t C, int64_t pitch, do
 int32_t dmf_band_project(const float* x, int64_t N, int32_t C, int64_t pitch, const double* mean, const float* basis /* [C][K] */,
                          int32_t K, float* y /* [N][K] */, void* stream);
 
+/* ---- noise moments for the noise-adjusted transform, `band_reduce_noise`.  New symbols at an unchanged
+ * DMF_VERSION: detect them by name.  The generalised eigen-fit is the caller's (utils/spectral.py, fit_noise_adjusted).
+ *
+ * x is the scene of H x W pixels, flat pixel p = row * W + column, C fp32 bands each, `pitch` floats apart: the contract of
+ * dmf_band_moments (device memory; pitch >= C; C in 1..512, any remainder mod 4; x 4-byte, ncov and workspace 8-byte aligned).
+ * For a direction with pixel step s — 0 horizontal, s = 1, the right neighbour in the row; 1 vertical, s = W, the pixel below —
+ *   e[p] = x[p] - x[p + s]      formed in fp32 (one rounding), for every pixel p that has that neighbour,
+ *   e[p] = 0                    for a pixel without it (last column; last row): by selection, not by multiplication — nothing
+ *                               behind the last pixel is read, and no value of the scene reaches a product through such a pixel,
+ *   M    = the number of pixels that have the neighbour: H (W - 1) horizontal, (H - 1) W vertical,
+ *   ncov[i][j] = (sum_p e[p][i] e[p][j]) / (2 M)      uncentred; the 2 is the shift-difference estimator's.
+ * The arithmetic is the covariance's: the products of run q = pixels [q R, (q + 1) R) of the flat scene, R = DMF_PCA_RUN, are one
+ * fp32 fmaf chain in pixel order on the fp32 matrix cores; the runs are added in double, ascending inside a slice of runs and
+ * then over the slices in ascending order by the finishing launch, which divides by 2 M in double.  Only the upper triangle is
+ * computed; ncov[j][i] is written from the sum of ncov[i][j].  Two launches; no allocation, no host synchronisation, no float
+ * atomics; the orders depend on (H, W, C, direction) only: two runs give the same bits.  `workspace` needs
+ * dmf_band_noise_workspace_bytes(H, W, C) bytes (-1 for H or W < 1, H W < 2 or C out of range).
+ * Reports by code as dmf_band_moments does, without a launch and with ncov as it was: 1 a NULL pointer; 2 M < 1 (a one-column
+ * scene horizontally, a one-row scene vertically; H or W < 1); 3 C outside 1..512; 5 pitch < C; 6 a misaligned pointer; 7 a
+ * direction outside 0..1; 8 H W pitch beyond 64-bit byte offsets; 9 where a launch itself failed. */
+int64_t dmf_band_noise_workspace_bytes(int32_t H, int32_t W, int32_t C);
+int32_t dmf_band_noise_moments(const float* x, int32_t H, int32_t W, int32_t C, int64_t pitch,
+                               int32_t direction /* 0 horizontal, 1 vertical */, double* ncov /* [C][C] */, void* workspace,
+                               void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

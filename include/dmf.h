@@ -85,7 +85,10 @@ int32_t dmf_patch_variant(const dmf_shape* shape, int32_t mode);
  * offsets[i] = start of tensor i, offsets[16] = total count. */
 int32_t dmf_param_layout(const dmf_shape* shape, int64_t offsets[17]);
 
-/* Bytes of scratch the train/backward entry points need for a batch of B patches. */
+/* Bytes of scratch the train/backward entry points need for a batch of B patches.  The workspace may hold anything at entry
+ * (no launch reads a word that no launch of the same step wrote) and serves any batch <= B, laid out for that batch; after a
+ * launch only the head vectors z, h, dh and dl[:, :K] of rows < B are defined, and no launch writes outside these bytes or
+ * outside the extents its other arguments state (which also lists the buffers the caller initialises). */
 int64_t dmf_workspace_bytes(const dmf_shape* shape, int32_t B);
 
 /* `pool_w` [P*P] is the network's fixed pooling profile (buffer `pool_w` of the Net).
@@ -103,7 +106,8 @@ int32_t dmf_forward_ce(const dmf_shape* shape, const dmf_input* in, const float*
 /* Forward of the network WITH the cross-modal attention block (shape->attention == 1; BASELINE configs[2]):
  * the conv stages emit bf16 token maps, then a matrix-core kernel (bf16 MFMA operands, fp32 accumulate) does the
  * projections, Q K^T, softmax, P V, the output projection, the pooling correction and the head.
- * `workspace` needs dmf_attn_workspace_bytes(shape, B) bytes.  Training: dmf_train_attn_fwd_bwd below. */
+ * `workspace` needs dmf_attn_workspace_bytes(shape, B) bytes; it may hold anything at entry, nothing in it is defined
+ * afterwards, and the launches write only inside it and logits [B, K] / pred [B].  Training: dmf_train_attn_fwd_bwd below. */
 int64_t dmf_attn_workspace_bytes(const dmf_shape* shape, int32_t B);
 int32_t dmf_forward_attn(const dmf_shape* shape, const dmf_input* in, const float* theta, const float* pool_w,
                          void* workspace, float* logits, int32_t* pred, void* stream);
@@ -123,7 +127,9 @@ int32_t dmf_train_fwd_bwd(const dmf_shape* shape, const dmf_input* in, const flo
  * from dense gradient maps).  Exactly one of labels (fused cross-entropy, as dmf_train_fwd_bwd) and dlogits
  * (caller-supplied dL/dlogits, as dmf_backward_dlogits; logits are still written) is non-NULL; loss may be NULL.
  * `workspace` as for dmf_train_fwd_bwd (dmf_workspace_bytes counts the attention slabs when shape->attention),
- * `attn_workspace` = dmf_attn_train_workspace_bytes(shape, B) bytes.  Gradients leave through dmf_grad_reduce*. */
+ * `attn_workspace` = dmf_attn_train_workspace_bytes(shape, B) bytes; like `workspace` it may hold anything at entry (token
+ * maps, gradient maps and weight copies are written before they are read), nothing in it is defined afterwards, and no launch
+ * of the step writes outside the two workspaces, logits [B, K] and loss [B].  Gradients leave through dmf_grad_reduce*. */
 int64_t dmf_attn_train_workspace_bytes(const dmf_shape* shape, int32_t B);
 int32_t dmf_train_attn_fwd_bwd(const dmf_shape* shape, const dmf_input* in, const float* theta, const float* pool_w,
                                const int32_t* labels, const float* dlogits, float loss_scale,

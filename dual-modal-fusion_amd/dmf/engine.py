@@ -413,14 +413,12 @@ class _PlanEngine:
         if bad.any():
             raise lib.DmfError('schedule table: beta1, beta2 and momentum must lie in [0, 1) (row %d)' % int(np.argwhere(bad)[0][0]))
         dev = self.scene.device
-        if not self._counts_on_device():             # from here on the device counts the steps: hand it the host's count
-            self.dev_step.fill_(self.step_count)
+        self._device_counts_from_here()
         self.hp_table = torch.from_numpy(t.copy()).to(dev)
         self.hp_row = torch.zeros(1, dtype=torch.int32, device=dev) if unit == 'epoch' else None
         self.hp_unit = unit
         self.sched = lib.hp_schedule(self.hp_table, self.hp_row)
         self.comm = None
-        self.graph = None
 
     # ------------------------------------------------------------------ an averaged copy of the weights, kept by the update
     def set_averaging(self, kind, decay=0.999, start_step=1):
@@ -439,11 +437,15 @@ class _PlanEngine:
             raise lib.DmfError('averaging decay %r is not in [0, 1)' % (decay,))
         if start_step < 1:
             raise lib.DmfError('averaging start_step %d: the first averaged step is at least 1' % start_step)
-        if not self._counts_on_device():             # from here on the device counts the steps: hand it the host's count
-            self.dev_step.fill_(self.step_count)
+        self._device_counts_from_here()
         self.avg = self.theta.clone()
         self.avg_spec = (kind, decay, start_step)
         self.wavg = lib.weight_avg(self.avg, kind, decay, start_step)
+
+    def _device_counts_from_here(self):
+        """set_schedule, set_averaging (their checks passed): from here on the device counts the steps, so it is handed the host's
+        count where it did not count yet; and the steps take other entry points, so a captured graph is dropped."""
+        self._seed_dev_step()
         self.graph = None
 
     def averaged_parameters(self):
@@ -459,13 +461,10 @@ class _PlanEngine:
     def _hparams(self):
         """What a captured graph bakes in as launch arguments.  With a schedule lr, the betas and momentum are not among them:
         the graph survives every change of them."""
-        avg = ()
-        if self.wavg is not None:                    # kind, the float32 weight and the first averaged step are launch arguments
-            avg = ('avg', self.wavg.kind, self.wavg.weight, self.wavg.start)
-        if self.sched is not None:
-            return ('sched', self.eps, self.alpha, self.weight_decay, self.clip_grad_norm) + (
-                self.scaler.hparams() if self.scaler is not None else ()) + avg
-        return (self.lr, self.b1, self.b2, self.eps, self.momentum, self.alpha, self.weight_decay, self.clip_grad_norm) + (
+        own = ('sched', self.eps) if self.sched is not None else (self.lr, self.b1, self.b2, self.eps, self.momentum)
+        # averaging: kind, the float32 weight and the first averaged step are launch arguments
+        avg = ('avg', self.wavg.kind, self.wavg.weight, self.wavg.start) if self.wavg is not None else ()
+        return own + (self.alpha, self.weight_decay, self.clip_grad_norm) + (
             self.scaler.hparams() if self.scaler is not None else ()) + avg
 
     def _regularised(self):
@@ -493,125 +492,95 @@ class _PlanEngine:
         self.step_count += 1
         return self.dev_step if dev_step is None and self._counts_on_device() else dev_step
 
+    def _fused_adam(self):
+        """ADAM, no scaler, nothing regularised: the step whose reduce launch applies ADAM itself (`_update`).  Only this step
+        runs from the library's launch loop (`_native_loop_ok`) and, over RCCL, from a captured graph (`_graphable`)."""
+        return self.scaler is None and self.optim == 'ADAM' and not self._regularised()
+
+    def _in_form(self, entry, args, hp, keys):
+        """THE choice between the plain, `_sched` and `_avg` form of lib's `entry` (grad_reduce_adam, optim_step,
+        train_plan_steps), called with the leading `args` and the keywords `keys`: set_averaging asks for `_avg`, which takes the
+        schedule too if there is one; set_schedule alone for `_sched`, which takes no `hp` (lr, b1, b2 and with optim_step momentum,
+        by name: its row of the table holds them)."""
+        if self.wavg is not None:
+            return getattr(lib, entry + '_avg')(*args, avg=self.wavg, sched=self.sched, **hp, **keys)
+        if self.sched is not None:
+            return getattr(lib, entry + '_sched')(*args, sched=self.sched, **keys)
+        return getattr(lib, entry)(*args, **hp, **keys)
+
     def _update(self, rows, dev_step, cursor, sum_scale, loss=None, loss_hist=None):
-        """The launches after the backward, from the slab rows of `rows` patches in self.ws:
-          ADAM, no scaler, one GPU      dmf_grad_reduce_adam (reduce + ADAM in one launch)
-          ADAM, no scaler, xGMI comm    dmf_grad_reduce_xgmi_adam (the ranks' rank-ordered sum inside that launch)
-          scaler, one GPU               dmf_grad_reduce_scaled (reduce, unscale, check) -> dmf_unscale_adam(unscaled = 1):
-                                        GradScaler's unscale_, step and update (tostagesolver.py:98,119)
-          everything else               dmf_grad_reduce -> all-reduce(sum) where the step has a collective -> the mean loss
-                                        into loss_hist[cursor] -> dmf_unscale_adam (the check sees the SUM, so every rank
-                                        takes the same skip decision) / dmf_sgd_step / dmf_rmsprop_step / dmf_adam_step
-          weight decay, ADAMW or        ALL of the cases above: dmf_grad_reduce -> all-reduce(sum) where the step has a
-          clip_grad_norm active         collective -> the mean loss into loss_hist[cursor] -> dmf_optim_step (unscale and
-                                        check with a scaler, the norm of the whole gradient and its clipping, weight decay,
-                                        the optimiser, the scaler's update: one launch; the pre-clip norm into
-                                        norm_hist[cursor], or into self.norm for an eager step)
-          a schedule (set_schedule)     the same reduce launch per case, and the `_sched` twin of the optimiser launch:
-                                        dmf_grad_reduce_adam_sched for the fused case, dmf_optim_step_sched for every other
-                                        (`_update_sched`; the xGMI case takes the collective route)
-          averaging (set_averaging)     the same reduce launch per case again, and the `_avg` form of the optimiser launch, with
-                                        the schedule if there is one: dmf_grad_reduce_adam_avg for the fused case,
-                                        dmf_optim_step_avg for every other (`_optim_step`); the xGMI case keeps its launch
-                                        and is followed by dmf_weight_average
+        """The launches after the backward, from the slab rows of `rows` patches in self.ws.  The reduce route, first match:
+          `_fused_adam()`, one GPU        dmf_grad_reduce_adam in the engine's form (`_in_form`): reduce + ADAM in one launch;
+                                          with a schedule lr and the betas go as 0.0
+          `_fused_adam()`, xGMI comm      dmf_grad_reduce_xgmi_adam (the ranks' rank-ordered sum inside that launch), followed
+                                          by dmf_weight_average with averaging (a schedule has let go of the communicator)
+          scaler, one GPU, nothing        dmf_grad_reduce_scaled (reduce, unscale, check) -> the optimiser launch with no
+          regularised                     cursor, grad_scale 1, unscaled = 1: GradScaler's unscale_, step and update
+                                          (tostagesolver.py:98,119)
+          everything else                 dmf_grad_reduce -> all-reduce(sum) where the step has a collective -> the mean loss
+                                          into loss_hist[cursor] -> the optimiser launch with cursor and sum_scale (a scaler's
+                                          check sees the SUM, so every rank takes the same skip decision); regularised, it
+                                          writes the pre-clip norm into norm_hist[cursor], or into self.norm for an eager step
+        The optimiser launch on self.grad (`_optimiser_launch`):
+          weight decay, ADAMW, clipping,  `_optim_step`: dmf_optim_step in the engine's form — unscale and check with a scaler,
+          a schedule or averaging         the norm of the whole gradient and its clipping, weight decay, the optimiser, the
+                                          scaler's update, the averaged copy: one launch
+          none of them                    dmf_unscale_adam (scaler) / dmf_sgd_step / dmf_rmsprop_step / dmf_adam_step
+        The reduce launch does not depend on the schedule or the averaging: gradients and recorded losses keep their bits.
         sum_scale scales the all-reduced gradient: 1/world where the loss is a per-rank mean, 1 where the loss kernel
         already divided by the global batch.  dev_step: the device step counter, or None for the host count.  loss /
         loss_hist: where the step's mean loss (this rank's) is recorded; None where the loss kernel records it itself.
         SGD and RMSprop keep their one state vector in m (momentum buffer / running mean of squares)."""
-        if self._regularised():
-            return self._update_regularised(rows, dev_step, cursor, sum_scale, loss, loss_hist)
-        sc, hp = self.scaler, (self.lr, self.b1, self.b2, self.eps)
-        fused = sc is None and self.optim == 'ADAM'
-        if self.sched is not None:
-            return self._update_sched(rows, dev_step, cursor, sum_scale, loss, loss_hist, fused)
+        sc, fused = self.scaler, self._fused_adam()
         if fused and self._single():
-            if self.wavg is not None:
-                lib.grad_reduce_adam_avg(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count, self.wavg,
-                                         adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
-            else:
-                lib.grad_reduce_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, None, *hp, self.step_count,
-                                     adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+            lr, b1, b2 = (0.0, 0.0, 0.0) if self.sched is not None else (self.lr, self.b1, self.b2)
+            self._in_form('grad_reduce_adam', (self.shape, rows, self.ws, self.theta, self.m, self.v, None), dict(lr=lr, b1=b1, b2=b2),
+                          dict(eps=self.eps, step=self.step_count, adam_step_dev=dev_step, cursor_dev=cursor, loss=loss,
+                               loss_hist=loss_hist))
         elif fused and self.comm is not None:
-            lib.grad_reduce_xgmi_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, self.comm.c, *hp, sum_scale,
-                                      dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
+            lib.grad_reduce_xgmi_adam(self.shape, rows, self.ws, self.theta, self.m, self.v, self.comm.c, self.lr, self.b1, self.b2,
+                                      self.eps, sum_scale, dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
             if self.wavg is not None:
                 lib.weight_average(self.wavg, self.theta, self.step_count, step_dev=dev_step)
-        elif sc is not None and self._single():
+        elif sc is not None and self._single() and not self._regularised():
             lib.grad_reduce_scaled(self.shape, rows, self.ws, self.grad, sc.state, cursor_dev=cursor, loss=loss,
                                    loss_hist=loss_hist)
-            if self.wavg is not None:
-                self._optim_step(dev_step, None, 1.0, unscaled=True)
-            else:
-                lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step, unscaled=True)
+            self._optimiser_launch(dev_step, None, 1.0, unscaled=True)
         else:
             lib.grad_reduce(self.shape, rows, self.ws, self.grad)
             if not self._single():
                 self._all_reduce_grad()
             if loss_hist is not None:
                 loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
-            if self.wavg is not None:
-                self._optim_step(dev_step, cursor, sum_scale)
-            elif sc is not None:
-                lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step,
-                                 grad_scale=sum_scale, cursor_dev=cursor)
-            elif self.optim == 'SGD':
-                lib.sgd_step(self.theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=sum_scale,
-                             step_dev=dev_step, cursor_dev=cursor)
-            elif self.optim == 'RMSprop':
-                lib.rmsprop_step(self.theta, self.grad, self.m, self.lr, self.alpha, grad_scale=sum_scale, cursor_dev=cursor)
-            else:
-                lib.adam_step(self.theta, self.grad, self.m, self.v, *hp, self.step_count, grad_scale=sum_scale,
-                              adam_step_dev=dev_step, cursor_dev=cursor)
+            norm_hist = None if not self._regularised() else self.norm_hist if cursor is not None else self.norm
+            self._optimiser_launch(dev_step, cursor, sum_scale, norm_hist=norm_hist)
 
-    def _update_regularised(self, rows, dev_step, cursor, sum_scale, loss, loss_hist):
-        """`_update` with weight decay, ADAMW or clip_grad_norm active (its docstring's last row)."""
-        lib.grad_reduce(self.shape, rows, self.ws, self.grad)
-        if not self._single():
-            self._all_reduce_grad()
-        if loss_hist is not None:
-            loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
-        self._optim_step(dev_step, cursor, sum_scale, norm_hist=self.norm_hist if cursor is not None else self.norm)
+    def _optimiser_launch(self, dev_step, cursor, sum_scale, unscaled=False, norm_hist=None):
+        """The optimiser launch on self.grad (`_update`: which one)."""
+        sc, hp = self.scaler, (self.lr, self.b1, self.b2, self.eps)
+        if self._regularised() or self.sched is not None or self.wavg is not None:
+            self._optim_step(dev_step, cursor, sum_scale, unscaled=unscaled, norm_hist=norm_hist)
+        elif sc is not None:
+            lib.unscale_adam(self.theta, self.grad, self.m, self.v, *hp, sc.state, *sc.hparams(), dev_step, grad_scale=sum_scale,
+                             cursor_dev=cursor, unscaled=unscaled)
+        elif self.optim == 'SGD':
+            lib.sgd_step(self.theta, self.grad, self.m, self.lr, self.momentum, self.step_count, grad_scale=sum_scale,
+                         step_dev=dev_step, cursor_dev=cursor)
+        elif self.optim == 'RMSprop':
+            lib.rmsprop_step(self.theta, self.grad, self.m, self.lr, self.alpha, grad_scale=sum_scale, cursor_dev=cursor)
+        else:
+            lib.adam_step(self.theta, self.grad, self.m, self.v, *hp, self.step_count, grad_scale=sum_scale,
+                          adam_step_dev=dev_step, cursor_dev=cursor)
 
     def _optim_step(self, dev_step, cursor, sum_scale, unscaled=False, norm_hist=None):
-        """dmf_optim_step on self.grad with the engine's optimiser, keys and scaler — dmf_optim_step_sched with a schedule,
-        dmf_optim_step_avg (which takes the schedule, if any) with averaging."""
+        """dmf_optim_step on self.grad with the engine's optimiser, keys and scaler, in the engine's form (`_in_form`)."""
         sc = self.scaler
         keys = dict(eps=1e-8 if self.optim == 'RMSprop' else self.eps, alpha=self.alpha, weight_decay=self.weight_decay,
                     max_norm=self.clip_grad_norm, step=self.step_count, grad_scale=sum_scale, step_dev=dev_step, cursor_dev=cursor,
                     scaler_state=sc.state if sc is not None else None, scaler_hparams=sc.hparams() if sc is not None else None,
                     unscaled=unscaled, norm_hist=norm_hist)
-        if self.wavg is not None:
-            lib.optim_step_avg(self.optim, self.theta, self.grad, self.m, self.v, self.wavg, sched=self.sched, lr=self.lr, b1=self.b1,
-                               b2=self.b2, momentum=self.momentum, **keys)
-        elif self.sched is not None:
-            lib.optim_step_sched(self.optim, self.theta, self.grad, self.m, self.v, self.sched, **keys)
-        else:
-            lib.optim_step(self.optim, self.theta, self.grad, self.m, self.v, self.lr, self.b1, self.b2, momentum=self.momentum, **keys)
-
-    def _update_sched(self, rows, dev_step, cursor, sum_scale, loss, loss_hist, fused):
-        """`_update` with a schedule and without weight decay, ADAMW or clipping: the same reduce launch per case, so the gradient
-        and the recorded loss keep their bits, and the optimiser's arithmetic from the step's row — fused ADAM on one GPU by
-        dmf_grad_reduce_adam_sched, everything else by dmf_optim_step_sched with neutral keys (the kernel behind
-        dmf_unscale_adam, dmf_sgd_step, dmf_rmsprop_step and dmf_adam_step)."""
-        sc = self.scaler
-        if fused and self._single() and self.wavg is not None:
-            lib.grad_reduce_adam_avg(self.shape, rows, self.ws, self.theta, self.m, self.v, None, 0.0, 0.0, 0.0, self.eps,
-                                     self.step_count, self.wavg, sched=self.sched, adam_step_dev=dev_step, cursor_dev=cursor,
-                                     loss=loss, loss_hist=loss_hist)
-        elif fused and self._single():
-            lib.grad_reduce_adam_sched(self.shape, rows, self.ws, self.theta, self.m, self.v, None, self.sched, self.eps,
-                                       self.step_count, adam_step_dev=dev_step, cursor_dev=cursor, loss=loss, loss_hist=loss_hist)
-        elif sc is not None and self._single():
-            lib.grad_reduce_scaled(self.shape, rows, self.ws, self.grad, sc.state, cursor_dev=cursor, loss=loss,
-                                   loss_hist=loss_hist)
-            self._optim_step(dev_step, None, 1.0, unscaled=True)
-        else:
-            lib.grad_reduce(self.shape, rows, self.ws, self.grad)
-            if not self._single():
-                self._all_reduce_grad()
-            if loss_hist is not None:
-                loss_hist.scatter_(0, cursor.long(), loss[:rows].mean().reshape(1))
-            self._optim_step(dev_step, cursor, sum_scale)
+        self._in_form('optim_step', (self.optim, self.theta, self.grad, self.m, self.v),
+                      dict(lr=self.lr, b1=self.b1, b2=self.b2, momentum=self.momentum), keys)
 
     # ------------------------------------------------------------------ the unit-gradient step on global batches
     def _unit_step(self, inp, rows, loss_launch, dev_step, cursor, loss=None, loss_hist=None):
@@ -1041,27 +1010,17 @@ class TrainEngine(_PlanEngine):
         k0 = self.host_cursor
         inp = lib.input_gather(self.shape, self.scene.A, self.scene.B, self.plan_xy[k0 * self.B:(k0 + steps) * self.B], B=self.B)
         labels = self.plan_labels[k0 * self.B:(k0 + steps) * self.B]
-        if self.wavg is not None:
-            lib.train_plan_steps_avg(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
-                                     self.ws, self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.dev_step, self.dev_cursor,
-                                     self.loss_hist, self.sched, self.wavg, steps)
-        elif self.sched is not None:
-            lib.train_plan_steps_sched(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
-                                       self.ws, self.m, self.v, self.sched, self.eps, self.dev_step, self.dev_cursor,
-                                       self.loss_hist, steps)
-        else:
-            lib.train_plan_steps(self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss, self.ws,
-                                 self.m, self.v, self.lr, self.b1, self.b2, self.eps, self.dev_step, self.dev_cursor,
-                                 self.loss_hist, steps)
+        self._in_form('train_plan_steps', (self.shape, inp, self.theta, self.net.pool_w, labels, 1.0 / self.B, self.logits, self.loss,
+                                           self.ws, self.m, self.v), dict(lr=self.lr, b1=self.b1, b2=self.b2),
+                      dict(eps=self.eps, adam_step_dev=self.dev_step, cursor_dev=self.dev_cursor, loss_hist=self.loss_hist, n_steps=steps))
         self.step_count += steps
         self.host_cursor += steps
         return steps
 
     def _native_loop_ok(self):
-        """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, ADAM, one GPU, no scaler,
-        the fused cross-entropy."""
-        return (self._single() and self.scaler is None and self.optim == 'ADAM' and not self.shape.attention and self.fused
-                and not self._regularised())
+        """run_plan(steps, steps_per_graph=-1): the C loop of dmf_train_plan_steps — late-fusion net, one GPU, the fused
+        cross-entropy, the fused ADAM step."""
+        return self._single() and self._fused_adam() and not self.shape.attention and self.fused
 
     def _graphable(self):
         """Can a step be captured in a hipGraph?  One GPU: yes.  The one-shot exchange: yes (it is part of the reduce launch).
@@ -1069,9 +1028,7 @@ class TrainEngine(_PlanEngine):
         all_reduce of 32 KB per ~16-us step would otherwise bound the step by the host (DMF_RCCL_GRAPH=0 switches this off)."""
         if self._single() or self.comm is not None:
             return True
-        if self.scaler is not None or self.optim != 'ADAM' or self._regularised():
-            return False
-        return self._rccl_capturable()
+        return self._fused_adam() and self._rccl_capturable()
 
     def _prepare_capture(self, n):
         if not self.fused:                         # the graph's steps read plan[cursor] like eager plan steps: no window

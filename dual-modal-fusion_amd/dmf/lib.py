@@ -350,16 +350,22 @@ def rmsprop_step(theta, grad, sq, lr, alpha, eps=1e-8, grad_scale=1.0, cursor_de
 OPTIM_KINDS = {'ADAM': 0, 'ADAMW': 1, 'SGD': 2, 'RMSprop': 3}          # DMF_OPT_* (include/dmf.h)
 
 
+def _optim_words(kind, scaler_state, scaler_hparams):
+    """What the optim_step wrappers share: -> (DMF_OPT_* of `kind`, growth_factor, backoff_factor, growth_interval), the
+    scaler's three neutral without a scaler."""
+    if kind not in OPTIM_KINDS:
+        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
+    return (OPTIM_KINDS[kind],) + (tuple(scaler_hparams) if scaler_state is not None else (0.0, 0.0, 0))
+
+
 def optim_step(kind, theta, grad, m, v, lr, b1=0.9, b2=0.999, eps=1e-8, momentum=0.0, alpha=0.99, weight_decay=0.0,
                max_norm=None, step=0, grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None, scaler_hparams=None,
                unscaled=False, norm_hist=None):
     """One optimiser step with weight decay, AdamW and gradient-norm clipping on the flat gradient (dmf_optim_step).  kind: a
     key of OPTIM_KINDS; max_norm None or 0: no clipping; scaler_hparams (growth_factor, backoff_factor, growth_interval) go with
     scaler_state; norm_hist[cursor] gets the pre-clip norm of a clipped step."""
-    if kind not in OPTIM_KINDS:
-        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
-    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
-    check(_lib.dmf_optim_step(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], lr, b1, b2, eps,
+    kind, growth, backoff, interval = _optim_words(kind, scaler_state, scaler_hparams)
+    check(_lib.dmf_optim_step(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), kind, lr, b1, b2, eps,
                               momentum, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
                               _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
                               _ptr(norm_hist), _stream()))
@@ -384,10 +390,8 @@ def optim_step_sched(kind, theta, grad, m, v, sched, eps=1e-8, alpha=0.99, weigh
                      grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None, scaler_hparams=None, unscaled=False,
                      norm_hist=None):
     """optim_step with lr, betas and momentum from the step's row of `sched` (an HpSchedule; dmf_optim_step_sched)."""
-    if kind not in OPTIM_KINDS:
-        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
-    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
-    check(_lib.dmf_optim_step_sched(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], _sched_ref(sched),
+    kind, growth, backoff, interval = _optim_words(kind, scaler_state, scaler_hparams)
+    check(_lib.dmf_optim_step_sched(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), kind, _sched_ref(sched),
                                     eps, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
                                     _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
                                     _ptr(norm_hist), _stream()))
@@ -433,10 +437,8 @@ def optim_step_avg(kind, theta, grad, m, v, avg, sched=None, lr=0.0, b1=0.9, b2=
                    weight_decay=0.0, max_norm=None, step=0, grad_scale=1.0, step_dev=None, cursor_dev=None, scaler_state=None,
                    scaler_hparams=None, unscaled=False, norm_hist=None):
     """optim_step (sched None) or optim_step_sched that also keeps the averaged copy `avg` (a WeightAvg; dmf_optim_step_avg)."""
-    if kind not in OPTIM_KINDS:
-        raise DmfError('optimizer %r is not one of %s' % (kind, sorted(OPTIM_KINDS)))
-    growth, backoff, interval = scaler_hparams if scaler_state is not None else (0.0, 0.0, 0)
-    check(_lib.dmf_optim_step_avg(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), OPTIM_KINDS[kind], lr, b1, b2, eps,
+    kind, growth, backoff, interval = _optim_words(kind, scaler_state, scaler_hparams)
+    check(_lib.dmf_optim_step_avg(_ptr(theta), _ptr(grad), _ptr(m), _ptr(v), theta.numel(), kind, lr, b1, b2, eps,
                                   momentum, alpha, weight_decay, float(max_norm or 0.0), step, grad_scale, _ptr(step_dev),
                                   _ptr(cursor_dev), _ptr(scaler_state), growth, backoff, interval, int(bool(unscaled)),
                                   _ptr(norm_hist), _sched_ref(sched), _avg_ref(avg), _stream()))

@@ -143,6 +143,11 @@ def _load():
         'dmf_band_project': (i32, [vp, i64, i32, i64, vp, vp, i32, vp, vp]),
         'dmf_band_noise_workspace_bytes': (i64, [i32, i32, i32]),
         'dmf_band_noise_moments': (i32, [vp, i32, i32, i32, i64, i32, vp, vp, vp]),
+        'dmf_slic_workspace_bytes': (i64, [i32, i32, i32, i32]),
+        'dmf_slic_init': (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        'dmf_slic_assign': (i32, [vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
+        'dmf_slic_update': (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        'dmf_segment_vote': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -955,6 +960,106 @@ def spatial_filter(prob_in, mask, aff, prob_out, label_map):
         raise DmfError('spatial_filter: all tensors must live on one device')
     _spatial_check('dmf_spatial_filter', _lib.dmf_spatial_filter(_ptr(prob_in), _ptr(mask), _ptr(aff), H, W, K, radius, _ptr(prob_out),
                                                                  _ptr(label_map), _stream()))
+
+
+# return codes of the entry points of csrc/dmf_segments.hip, which report by code (include/dmf.h)
+SEG_SMIN, SEG_SMAX = 4, 32                      # DMF_SEG_SMIN, DMF_SEG_SMAX
+VOTE_MODES = {'mean': 0, 'majority': 1}         # DMF_VOTE_MEAN, DMF_VOTE_MAJORITY
+_SEGMENT_ERRORS = {1: 'a NULL pointer', 2: 'H, W and C must be >= 1', 3: '1 <= K <= DMF_KMAX', 4: 'the segment size must be 4..32',
+                   5: 'elem_bytes must be 2 or 4', 6: 'pitch < W', 7: 'an output overlaps an input or another output',
+                   8: 'a misaligned scene or workspace, or a grid beyond 32 bits', 9: 'a launch failed',
+                   10: 'the compactness is not a finite number >= 0', 11: 'the vote mode is not mean or majority',
+                   12: 'the workspace is too small'}
+
+
+def _segment_check(entry, rc):
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, _SEGMENT_ERRORS.get(rc, 'error %d' % rc)))
+
+
+def segment_grid(H, W, size):
+    """-> (gh, gw): the cells of an H x W scene at segment size `size` (4..32); Kc = gh gw clusters."""
+    if isinstance(size, bool) or not isinstance(size, int) or not SEG_SMIN <= size <= SEG_SMAX:
+        raise DmfError('the segment size %r is not a whole number in %d..%d' % (size, SEG_SMIN, SEG_SMAX))
+    return (H + size - 1) // size, (W + size - 1) // size
+
+
+def _segment_scene(entry, scene, H, W, size):
+    """The scene arguments of the slic entry points -> (gh, gw, C, (ptr, elem_bytes, pitch, H, W, C, size))."""
+    gh, gw = segment_grid(H, W, size)
+    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
+        raise DmfError('%s: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor' % entry)
+    if H < 1 or W < 1 or H > scene.shape[0] or W > scene.shape[1]:
+        raise DmfError('%s: %d x %d pixels asked of a scene of %d x %d' % (entry, H, W, scene.shape[0], scene.shape[1]))
+    Cn = scene.shape[2]
+    return gh, gw, Cn, (_ptr(scene), scene.element_size(), scene.shape[1], H, W, Cn, size)
+
+
+def _segment_tensor(entry, t, dtype, shape, name, device):
+    _dev(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise DmfError('%s: %s must be %s on the scene\'s device' % (entry, name, list(shape)))
+
+
+def slic_workspace_bytes(H, W, Cn, size):
+    n = _lib.dmf_slic_workspace_bytes(H, W, Cn, size)
+    if n < 0:
+        raise DmfError('dmf_slic_workspace_bytes: H, W, C >= 1 and a segment size in 4..32')
+    return n
+
+
+def slic_init(scene, H, W, size, centres):
+    """centres [Kc, C + 2] float32 <- the spectrum and the position of the pixel in the middle of every cell of the leading
+    [H, W] pixels of the resident scene [>= H, pitch >= W, C] (dmf_slic_init)."""
+    gh, gw, Cn, args = _segment_scene('slic_init', scene, H, W, size)
+    _segment_tensor('slic_init', centres, torch.float32, (gh * gw, Cn + 2), 'centres', scene.device)
+    _segment_check('dmf_slic_init', _lib.dmf_slic_init(*args, _ptr(centres), _stream()))
+
+
+def slic_assign(scene, H, W, size, compactness, centres, seg):
+    """seg [H, W] int32 <- for every pixel the candidate cluster with the smallest D = d2 + (compactness / size)^2 |x - centre|^2,
+    the first slot on equality (dmf_slic_assign)."""
+    gh, gw, Cn, args = _segment_scene('slic_assign', scene, H, W, size)
+    _segment_tensor('slic_assign', centres, torch.float32, (gh * gw, Cn + 2), 'centres', scene.device)
+    _segment_tensor('slic_assign', seg, torch.int32, (H, W), 'seg', scene.device)
+    if not (compactness >= 0 and compactness < float('inf')):
+        raise DmfError('slic_assign: compactness = %r is not a finite number >= 0' % (compactness,))
+    _segment_check('dmf_slic_assign', _lib.dmf_slic_assign(*args, float(compactness), _ptr(centres), _ptr(seg), _stream()))
+
+
+def slic_update(scene, H, W, size, seg, centres, counts, workspace):
+    """centres [Kc, C + 2], counts [Kc] int32 <- the mean spectrum and position, and the number, of every cluster's members
+    (the pixels of its 3 x 3 cells with seg == k); a cluster without a member keeps its row (dmf_slic_update).  `workspace`:
+    a uint8 tensor of slic_workspace_bytes(H, W, C, size) bytes."""
+    gh, gw, Cn, args = _segment_scene('slic_update', scene, H, W, size)
+    _segment_tensor('slic_update', centres, torch.float32, (gh * gw, Cn + 2), 'centres', scene.device)
+    _segment_tensor('slic_update', seg, torch.int32, (H, W), 'seg', scene.device)
+    _segment_tensor('slic_update', counts, torch.int32, (gh * gw,), 'counts', scene.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    _segment_check('dmf_slic_update', _lib.dmf_slic_update(*args, _ptr(seg), _ptr(centres), _ptr(counts), _ptr(workspace),
+                                                           workspace.numel(), _stream()))
+
+
+def segment_vote(prob, mask, seg, size, mode, segprob, segcount, label_map, prob_out=None):
+    """segprob [Kc, K], segcount [Kc] <- the mean probabilities (mode 'mean') or the class counts ('majority') of every segment's
+    masked members; label_map [H, W] int32 <- at every masked pixel the first maximal class of its segment's row, the other cells
+    untouched; prob_out (optional) [H, W, K] <- that row, zeros where mask is 0 (dmf_segment_vote)."""
+    if mode not in VOTE_MODES:
+        raise DmfError('segment_vote: the mode %r is not mean or majority' % (mode,))
+    _dev(prob, torch.float32, 'prob'); _dev(mask, torch.uint8, 'mask'); _dev(seg, torch.int32, 'seg')
+    if prob.dim() != 3 or tuple(mask.shape) != tuple(prob.shape[:2]) or tuple(seg.shape) != tuple(prob.shape[:2]):
+        raise DmfError('segment_vote wants prob [H, W, K] with mask and seg [H, W]')
+    H, W, K = prob.shape
+    gh, gw = segment_grid(H, W, size)
+    _segment_tensor('segment_vote', segprob, torch.float32, (gh * gw, K), 'segprob', prob.device)
+    _segment_tensor('segment_vote', segcount, torch.int32, (gh * gw,), 'segcount', prob.device)
+    _segment_tensor('segment_vote', label_map, torch.int32, (H, W), 'label_map', prob.device)
+    if prob_out is not None:
+        _segment_tensor('segment_vote', prob_out, torch.float32, (H, W, K), 'prob_out', prob.device)
+    if mask.device != prob.device or seg.device != prob.device:
+        raise DmfError('segment_vote: all tensors must live on one device')
+    _segment_check('dmf_segment_vote', _lib.dmf_segment_vote(_ptr(prob), _ptr(mask), _ptr(seg), H, W, K, size, VOTE_MODES[mode],
+                                                             _ptr(segprob), _ptr(segcount), _ptr(label_map), _ptr(prob_out), _stream()))
 
 
 # return codes of the two entry points of csrc/dmf_pca.hip, which report by code (include/dmf.h)

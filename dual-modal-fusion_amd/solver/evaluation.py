@@ -23,6 +23,12 @@ with scene-guided bilateral weights and forms a second confusion matrix over the
 also writes `<t>_pic_{1,2}_spatial.png`, composed as the plain maps are.  Fast path: EvalEngine.probability_map, Scene.affinity and
 EvalEngine.regularise (dmf_prob_scatter / dmf_spatial_affinity / dmf_spatial_filter); drop-in path: utils/spatial.py in numpy
 float64.  `test_matrix`, `indicator()` and its export are untouched; toStageSolver and data-parallel runs refuse the keys.
+`test.segments: none | slic` with `test.segment_size`, `test.segment_compactness`, `test.segment_iterations`, `test.segment_vote` and
+`color.segments: 1` (all optional): the same flow with superpixels in the filter's place — the whole-scene probability
+map (the unfiltered one, whatever `test.spatial` says), SLIC segments of the primary scene, every pixel takes its segment's class;
+a second confusion matrix over the same test pixels (`self.segments`, `<t>_segments.json`, `<t>_segments.npy`: the int32 segment
+image); `color()` also writes `<t>_pic_{1,2}_segments.png`.  Fast path: EvalEngine.probability_map, Scene.segments and
+EvalEngine.segment_vote (dmf_slic_* / dmf_segment_vote); drop-in path: utils/segments.py in numpy float64.
 """
 import itertools
 
@@ -30,7 +36,7 @@ import numpy as np
 import torch
 
 from utils import calibration as calib
-from utils import spatial
+from utils import segments, spatial
 
 
 def map2(maps, unsupervised, values=None):
@@ -83,6 +89,13 @@ class EngineEvaluation(_Evaluation):
         prob, mask = eng.probability_map(torch.from_numpy(xy), H, W, beta)
         aff = self.s.scene.affinity(H, W, k['radius'], k['sigma_s'], k['sigma_r'])
         return None, eng.regularise(prob, mask, aff, k['iterations'])[1].cpu().numpy()
+
+    def scene_segments(self, xy, H, W, beta, k):
+        """-> (None, segment image, voted label map): EvalEngine.probability_map, Scene.segments, EvalEngine.segment_vote."""
+        eng = self.s.eval_engine
+        prob, mask = eng.probability_map(torch.from_numpy(xy), H, W, beta)
+        seg = self.s.scene.segments(H, W, k['size'], k['compactness'], k['iterations'])[0]
+        return None, seg.cpu().numpy(), eng.segment_vote(prob, mask, seg, k['size'], k['vote'])[2].cpu().numpy()
 
     def plain_at(self, xy, plain, H, W):
         return self.s.eval_engine.label_map(torch.from_numpy(xy), H, W).cpu().numpy()[xy[:, 0], xy[:, 1]]
@@ -138,8 +151,8 @@ class DropinEvaluation(_Evaluation):
             p[:, x, y] = calib.softmax_stats(logits, beta)[1].cpu().numpy().astype(np.float32)
         return m, p
 
-    def scene_maps(self, xy, H, W, beta, k):
-        """-> (plain, regularised) label maps: utils.spatial in float64 on the logits of `Net.forward` and the host's padded scene."""
+    def _scene_probabilities(self, xy, H, W, beta):
+        """-> (prob [H, W, K] float64, mask, plain label map, the host's padded scene) from the logits of `Net.forward`."""
         from torch.utils.data import DataLoader, Subset
         s = self.s
         rows = list(s.matrix_[1]) + list(s.matrix_[0])
@@ -151,9 +164,19 @@ class DropinEvaluation(_Evaluation):
         mask[xy[:, 0], xy[:, 1]] = 1
         plain = np.zeros((H, W), dtype=np.int32)
         plain[xy[:, 0], xy[:, 1]] = logits.argmax(1)
-        scene = s.MS.astype(np.float16) if s.half else s.MS
+        return prob, mask, plain, s.MS.astype(np.float16) if s.half else s.MS
+
+    def scene_maps(self, xy, H, W, beta, k):
+        """-> (plain, regularised) label maps: utils.spatial in float64 on the logits of `Net.forward` and the host's padded scene."""
+        prob, mask, plain, scene = self._scene_probabilities(xy, H, W, beta)
         aff = spatial.affinity(scene, H, W, k['radius'], k['sigma_s'], k['sigma_r'])
         return plain, spatial.regularise(prob, mask, aff, k['radius'], k['iterations'])[1]
+
+    def scene_segments(self, xy, H, W, beta, k):
+        """-> (plain, segment image, voted label map): utils.segments in float64 on the same logits and scene."""
+        prob, mask, plain, scene = self._scene_probabilities(xy, H, W, beta)
+        seg = segments.slic(scene, H, W, k['size'], k['compactness'], k['iterations'])[0]
+        return plain, seg, segments.vote(prob, mask, seg, k['size'], k['vote'])[2]
 
     def plain_at(self, xy, plain, H, W):
         return plain[xy[:, 0], xy[:, 1]]

@@ -57,7 +57,8 @@ variant is then a mapped coordinate (`_augment_xy`, before `load_plan`, `load_bl
 what the kernel reads) and no train route changes; `EvalEngine(tta=)` runs one forward per variant and dmf_logits_mean.  Drop-in
 path: the materialised patches are transformed (`augment.tf_batch`), the mean is torch's (`_logits_dropin`).  The validation
 pass is never augmented.  With both keys `none` the scene is the plain Scene and nothing changes; toStageSolver refuses the keys.
-`test.calibration`, `test.temperature`, `color.confidence` and `test.spatial`, `color.spatial`: see
+`test.calibration`, `test.temperature`, `color.confidence`, `test.spatial`, `color.spatial` and
+`test.segments`, `color.segments`: see
 solver/evaluation.py, to whose class of this run's path (`self.evaluation`) `test()` and `color()` put their questions.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
@@ -83,7 +84,7 @@ from dmf import augment
 from solver.basesolver import BaseSolver
 from solver.evaluation import DropinEvaluation, EngineEvaluation, map2
 from utils import calibration as calib
-from utils import spatial, spectral
+from utils import segments, spatial, spectral
 from utils.utils import (average_update_, averaging_keys, clip_grad_norm_of, criterion_keys, criterion_spec, epoch_hparams, export_optimizer, make_loss, optim_hparams,
                          make_optimizer, make_scheduler, save_checkpoint, schedule_groups, schedule_keys, schedule_table)
 
@@ -104,10 +105,12 @@ class Solver(BaseSolver):
     calibrated = True                                    # `test.calibration` / `test.temperature` / `color.confidence` are in scope
     augmented = True                                     # `schedule.augment` / `test.tta` are in scope for this stage
     regularised = True                                   # `test.spatial` / `color.spatial` are in scope for this stage
+    segmented = True                                     # `test.segments` / `color.segments` are in scope for this stage
     band_reduced = True                                  # `band_reduce` is in scope for this stage
     averaging = None                                     # (the constructor reads it from cfg['schedule'])
     aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
     calib, spat = calib.calibration_keys({}), spatial.spatial_keys({})     # (the constructor reads them from cfg; these: neutral)
+    segm = segments.segment_keys({})                     # (likewise)
     evaluation = None                                    # solver.evaluation's class of this run's path (`_ensure_model`)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
@@ -131,6 +134,10 @@ class Solver(BaseSolver):
         if spatial.keys_in_use(self.spat) and not self.regularised:
             raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % (spatial.keys_in_use(self.spat)[0], type(self).__name__))
+        self.segm = segments.segment_keys(cfg)         # test.segments / segment_size / _compactness / _iterations / _vote, color.segments
+        if segments.keys_in_use(self.segm) and not self.segmented:
+            raise ValueError('%s is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % (segments.keys_in_use(self.segm)[0], type(self).__name__))
         if spectral.noise_keys(cfg) is not None and not self.band_reduced:
             raise ValueError('band_reduce_noise is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)
@@ -138,6 +145,7 @@ class Solver(BaseSolver):
             raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)
         self.spatial, self._spatial_maps = None, None  # test()'s regularisation block; the whole-scene maps of the loaded weights
+        self.segments, self._segment_maps = None, None # test()'s superpixel block; the whole-scene maps of the loaded weights
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
         self._avg_flat, self._avg_steps = None, 0      # drop-in path: the averaged flat vector and the optimiser steps taken
         self.cfg, self.rank, self.world = cfg, 0, 1
@@ -185,6 +193,7 @@ class Solver(BaseSolver):
         self._valid_dev = None
         self._temp = None
         self._spatial_maps = None
+        self._segment_maps = None
         if criterion_keys(self.cfg):
             self.train_labels = self.index_dataset.label[np.asarray(self.train_index_loader.dataset.indices, dtype=np.int64)]
             self.criterion = criterion_spec(self.cfg, self.train_labels)
@@ -231,6 +240,7 @@ class Solver(BaseSolver):
         time1 = time.time()
         self._temp = None                              # (a fitted temperature belongs to the weights it was fitted on)
         self._spatial_maps = None                      # (and so do the regularised maps)
+        self._segment_maps = None                      # (and the voted ones)
         if not self.cfg['train']['pretrained']:
             self.init_model()
         self.cur_model = self.model.to(self.DEVICE)
@@ -690,7 +700,7 @@ class Solver(BaseSolver):
 
     def _single_device_scope(self):
         """Data-parallel runs refuse the calibration and regularisation keys (nothing of them is sharded), as `_epoch_block` does."""
-        keys = calib.keys_in_use(self.calib) + spatial.keys_in_use(self.spat)
+        keys = calib.keys_in_use(self.calib) + spatial.keys_in_use(self.spat) + segments.keys_in_use(self.segm)
         if keys and self.world > 1:
             raise ValueError('%s is out of scope for data-parallel runs (%d ranks): leave the key out' % (keys[0], self.world))
 
@@ -713,6 +723,9 @@ class Solver(BaseSolver):
         if self.spat['kind'] is not None:
             with torch.no_grad():
                 self._regularise(whole)
+        if self.segm['kind'] is not None:
+            with torch.no_grad():
+                self._segment(whole)
         if self.rank == 0:
             self.indicator()
         else:
@@ -789,34 +802,73 @@ class Solver(BaseSolver):
         """`self.spatial` and `<t>_spatial.json`: a second confusion matrix over the pixels of the first, from the regularised
         label map at their (x, y).  `self.test_matrix` and what `indicator()` makes of it stay as they are."""
         plain, smooth = self._regularised_maps(self.cfg['train']['save_best'])
+        self.spatial = spatial.report(self.spat, self.test_matrix, *self._second_matrix(whole, plain, smooth))
+        self._write_block(self.spatial, '_spatial.json')
+
+    def _second_matrix(self, whole, plain, remapped):
+        """-> (confusion matrix of the whole-scene label map `remapped` over the pixels of the first matrix, how many of them
+        changed class against the plain prediction)."""
         rows = np.asarray(self.test_index_loader.dataset.indices, dtype=np.int64)
         if not whole:
             rows = rows[:self.cfg['test_batchsize']]   # the first batch of the unshuffled loader
         xy, lab = self._set_pixels(rows), self.index_dataset.label[rows].astype(np.int64)
         K = self.cfg['Categories_Number']
         after = np.zeros([K, K], dtype=np.int64)
-        np.add.at(after, (smooth[xy[:, 0], xy[:, 1]], lab), 1)                    # matrix[pred][target] += 1
-        changed = int((smooth[xy[:, 0], xy[:, 1]] != self.evaluation.plain_at(xy, plain, *smooth.shape)).sum())
-        self.spatial = spatial.report(self.spat, self.test_matrix, after, changed)
-        if self.rank == 0:
-            with open(self.cfg['RESULT_output'] + str(self.time) + '_spatial.json', 'w') as f:
-                json.dump(self.spatial, f, indent=1)
+        np.add.at(after, (remapped[xy[:, 0], xy[:, 1]], lab), 1)                  # matrix[pred][target] += 1
+        return after, int((remapped[xy[:, 0], xy[:, 1]] != self.evaluation.plain_at(xy, plain, *remapped.shape)).sum())
 
-    def _color_spatial(self, H, W, lut):
-        """`<t>_pic_{1,2}_spatial.png`, composed as the plain maps are: map 1 the regularised classes on the labelled pixels,
-        map 2 with the other pixels too."""
-        smooth = self._regularised_maps(True)[1]
+    def _write_block(self, block, suffix):
+        if self.rank == 0:
+            with open(self.cfg['RESULT_output'] + str(self.time) + suffix, 'w') as f:
+                json.dump(block, f, indent=1)
+
+    def _color_remapped(self, H, W, lut, remapped, name):
+        """-> (map 1, map 2) of the whole-scene label map `remapped`, composed as the plain maps are — map 1 its classes on the
+        labelled pixels, map 2 with the other pixels too — and written as `<t>_pic_{1,2}_<name>.png`."""
         maps = []
         for use, rows in ((self.cfg['color']['supervised'], self.matrix_[1]), (self.cfg['color']['unsupervised'], self.matrix_[0])):
             m = np.zeros([H, W], dtype=np.int32)
             if use:
                 xy = self._set_pixels(rows)
-                m[xy[:, 0], xy[:, 1]] = smooth[xy[:, 0], xy[:, 1]]
+                m[xy[:, 0], xy[:, 1]] = remapped[xy[:, 0], xy[:, 1]]
             maps.append(m)
-        self.spatial_maps = (maps[0], map2(maps, self.cfg['color']['unsupervised']))
+        out = (maps[0], map2(maps, self.cfg['color']['unsupervised']))
         if self.cfg['color']['supervised'] and self.rank == 0:
-            for n, m in enumerate(self.spatial_maps, 1):
-                Image.fromarray(lut[m]).save(self.cfg['RESULT_output'] + str(self.time) + '_pic_%d_spatial.png' % n)
+            for n, m in enumerate(out, 1):
+                Image.fromarray(lut[m]).save(self.cfg['RESULT_output'] + str(self.time) + '_pic_%d_%s.png' % (n, name))
+        return out
+
+    def _color_spatial(self, H, W, lut):
+        """`<t>_pic_{1,2}_spatial.png`: the regularised classes."""
+        self.spatial_maps = self._color_remapped(H, W, lut, self._regularised_maps(True)[1], 'spatial')
+
+    # ------------------------------------------------------------------ superpixel voting (test.segments, color.segments; DESIGN §23)
+    def _segmented_maps(self, best):
+        """-> (plain or None, segment image [H, W] int32, voted label map [H, W] int32) (numpy) of the WHOLE scene under the loaded
+        weights (`best`: which file they came from; kept per trained model and file): all pixels of both colour sets are classified
+        at `test.temperature`'s beta, the scene is segmented, and every pixel takes its segment's class.  The probability map is
+        the unfiltered one, whatever `test.spatial` says."""
+        if self._segment_maps is None or self._segment_maps[0] != bool(best):
+            size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
+            beta = self._beta(self._temperature_used()[0])
+            self._segment_maps = (bool(best), self.evaluation.scene_segments(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.segm))
+        return self._segment_maps[1]
+
+    def _segment(self, whole):
+        """`self.segments`, `<t>_segments.json` and `<t>_segments.npy`: a second confusion matrix over the pixels of the first, from
+        the voted label map at their (x, y).  `self.test_matrix` and what `indicator()` makes of it stay as they are."""
+        plain, seg, voted = self._segmented_maps(self.cfg['train']['save_best'])
+        H, W = seg.shape
+        counts = np.bincount(seg.reshape(-1), minlength=int(np.prod(segments.grid(H, W, self.segm['size']))))
+        self.segments = segments.report(self.segm, H, W, counts, self.test_matrix, *self._second_matrix(whole, plain, voted))
+        self.segment_image = seg
+        self._write_block(self.segments, '_segments.json')
+        if self.rank == 0:
+            np.save(self.cfg['RESULT_output'] + str(self.time) + '_segments.npy', seg)
+
+    def _color_segments(self, H, W, lut):
+        """`<t>_pic_{1,2}_segments.png`: the voted classes."""
+        self.segment_maps = self._color_remapped(H, W, lut, self._segmented_maps(True)[2], 'segments')
 
     # ------------------------------------------------------------------ colour
     def color(self):
@@ -855,6 +907,9 @@ class Solver(BaseSolver):
         if self.spat['color']:
             with torch.no_grad():
                 self._color_spatial(H, W, lut)
+        if self.segm['color']:
+            with torch.no_grad():
+                self._color_segments(H, W, lut)
 
     def run(self):
         while self.time < self.TIME:

@@ -59,6 +59,7 @@ class toStageSolver(Solver):
     calibrated = False                                   # (test.calibration, test.temperature, color.confidence: refused by name)
     augmented = False                                    # (schedule.augment, test.tta: refused by name)
     regularised = False                                  # (test.spatial, color.spatial: refused by name)
+    segmented = False                                    # (test.segments, color.segments: refused by name)
     band_reduced = False                                 # (band_reduce: refused by name)
 
     def __init__(self, cfg):

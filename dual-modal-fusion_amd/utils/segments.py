@@ -1,0 +1,167 @@
+"""utils.segments — the host side of `test.segments` and `color.segments`: the config keys, the report block, and
+for `fast_path: 0` the arithmetic of dmf_slic_init / dmf_slic_assign / dmf_slic_update / dmf_segment_vote (include/dmf.h) in numpy
+float64.  Nothing here touches the GPU library.
+
+The scene is over-segmented into SLIC superpixels in the pixel-centric form: cells of S x S pixels, one cluster per cell for life,
+and every pixel chooses among the up to nine clusters of its own and the adjacent cells (slot s = 3 (u + 1) + (v + 1)) the one with
+the smallest D = mean_c (a_c - mu_c)^2 + (compactness / S)^2 |x - centre|^2, the first slot on equality.  Every classified pixel
+then takes the class of its segment: of the mean probability of the segment's classified pixels, or of their majority.
+Connectivity is not enforced."""
+import math
+
+import numpy as np
+
+KINDS = ('none', 'slic')
+VOTES = ('mean', 'majority')
+SIZE_MIN, SIZE_MAX = 4, 32
+
+
+def segment_keys(cfg):
+    """-> dict(kind, size, compactness, iterations, vote, color) from the optional keys
+         test.segments none / slic (default none)        test.segment_size 4..32 (default 8)
+         test.segment_compactness >= 0 (default 0.1)     test.segment_iterations >= 0 (default 10)
+         test.segment_vote mean / majority (default mean)  color.segments 0 / 1 (default 0)
+    `kind` is None or 'slic'.  Neutral values change nothing."""
+    test, color = cfg.get('test') or {}, cfg.get('color') or {}
+    kind = test.get('segments', 'none')
+    kind = 'none' if kind is None or kind is False or kind == 0 else str(kind).lower()
+    if kind not in KINDS:
+        raise ValueError('test.segments %r is not one of %s' % (test.get('segments'), ' / '.join(KINDS)))
+    col = color.get('segments', 0) or 0
+    if col not in (0, 1, True, False):
+        raise ValueError('color.segments is 0 or 1')
+    size, its = test.get('segment_size', 8), test.get('segment_iterations', 10)
+    if isinstance(size, bool) or not isinstance(size, int) or not SIZE_MIN <= size <= SIZE_MAX:
+        raise ValueError('test.segment_size %r is not a whole number in %d..%d' % (size, SIZE_MIN, SIZE_MAX))
+    if isinstance(its, bool) or not isinstance(its, int) or its < 0:
+        raise ValueError('test.segment_iterations %r is not a whole number >= 0' % (its,))
+    comp = test.get('segment_compactness', 0.1)
+    try:
+        f = float(comp)
+    except (TypeError, ValueError):
+        f = float('nan')
+    if isinstance(comp, bool) or not (math.isfinite(f) and f >= 0):
+        raise ValueError('test.segment_compactness %r is not a number >= 0' % (comp,))
+    vote = str(test.get('segment_vote', 'mean')).lower()
+    if vote not in VOTES:
+        raise ValueError('test.segment_vote %r is not one of %s' % (test.get('segment_vote'), ' / '.join(VOTES)))
+    if col and kind == 'none':
+        raise ValueError('color.segments: 1 draws the map that test.segments: slic votes on; test.segments is none')
+    return dict(kind=None if kind == 'none' else kind, size=size, compactness=f, iterations=its, vote=vote, color=bool(col))
+
+
+def keys_in_use(keys):
+    """The names of the keys that are not neutral, for a refusal."""
+    return [name for name, used in (('test.segments', keys['kind'] is not None), ('color.segments', keys['color'])) if used]
+
+
+def grid(H, W, size):
+    return (H + size - 1) // size, (W + size - 1) // size
+
+
+def _candidates(H, W, size):
+    """[(cluster index [H, W] (0 where invalid), valid [H, W])] for the nine slots in ascending order."""
+    gh, gw = grid(H, W, size)
+    gi, gj = np.arange(H)[:, None] // size, np.arange(W)[None, :] // size
+    out = []
+    for u in (-1, 0, 1):
+        for v in (-1, 0, 1):
+            ok = (gi + u >= 0) & (gi + u < gh) & (gj + v >= 0) & (gj + v < gw)
+            out.append((np.where(ok, (gi + u) * gw + gj + v, 0), ok))
+    return out
+
+
+def init_centres(scene, H, W, size):
+    """centres [Kc, C + 2] float64: the spectrum, row and column of the pixel in the middle of every cell."""
+    a = np.asarray(scene)[:H, :W].astype(np.float64)
+    gh, gw = grid(H, W, size)
+    k = np.arange(gh * gw)
+    i, j = np.minimum(H - 1, (k // gw) * size + size // 2), np.minimum(W - 1, (k % gw) * size + size // 2)
+    return np.concatenate([a[i, j], i[:, None].astype(np.float64), j[:, None].astype(np.float64)], 1)
+
+
+def assign(scene, H, W, size, compactness, centres):
+    """seg [H, W] int32; cw is rounded to fp32 as the kernel's is."""
+    a = np.asarray(scene)[:H, :W].astype(np.float64)
+    C = a.shape[2]
+    cw = float(np.float32((float(np.float32(compactness)) / size) ** 2))
+    i, j = np.arange(H)[:, None].astype(np.float64), np.arange(W)[None, :].astype(np.float64)
+    cands = _candidates(H, W, size)
+    best, seg = np.full((H, W), np.inf), cands[4][0]     # (the pixel's own cell is the fallback)
+    for k, ok in cands:
+        mu = centres[k]
+        D = np.square(a - mu[:, :, :C]).sum(2) / C + cw * (np.square(i - mu[:, :, C]) + np.square(j - mu[:, :, C + 1]))
+        take = ok & (D < best)                           # strict: the first slot on equality
+        seg = np.where(take, k, seg)
+        best = np.where(take, D, best)
+    return seg.astype(np.int32)
+
+
+def _members(seg, H, W, size):
+    m = np.zeros((H, W), dtype=bool)
+    for k, ok in _candidates(H, W, size):
+        m |= ok & (seg == k)
+    return m
+
+
+def update(scene, H, W, size, seg, centres):
+    """-> (centres', counts [Kc] int32): the mean spectrum and position of every cluster's members; without one the row stays."""
+    a = np.asarray(scene)[:H, :W].astype(np.float64)
+    gh, gw = grid(H, W, size)
+    m = _members(seg, H, W, size)
+    k = np.asarray(seg)[m].astype(np.int64)
+    counts = np.bincount(k, minlength=gh * gw)
+    ii, jj = np.nonzero(m)
+    sums = np.zeros_like(centres)
+    np.add.at(sums, k, np.concatenate([a[m], ii[:, None].astype(np.float64), jj[:, None].astype(np.float64)], 1))
+    out = centres.copy()
+    out[counts > 0] = sums[counts > 0] / counts[counts > 0][:, None]
+    return out, counts.astype(np.int32)
+
+
+def slic(scene, H, W, size, compactness, iterations):
+    """-> (seg [H, W] int32, centres, counts): init, `iterations` x (assign, update), a last assign."""
+    centres = init_centres(scene, H, W, size)
+    counts = np.zeros(centres.shape[0], dtype=np.int32)
+    for _ in range(iterations):
+        centres, counts = update(scene, H, W, size, assign(scene, H, W, size, compactness, centres), centres)
+    return assign(scene, H, W, size, compactness, centres), centres, counts
+
+
+def vote(prob, mask, seg, size, mode):
+    """-> (segprob [Kc, K] float64, segcount [Kc] int32, label map [H, W] int32: 0 where mask is 0).  A masked pixel whose seg is
+    none of its candidates stands for itself."""
+    live = np.asarray(mask) != 0
+    H, W = live.shape
+    p = np.where(live[:, :, None], np.asarray(prob, dtype=np.float64), 0.0)
+    gh, gw = grid(H, W, size)
+    m = _members(seg, H, W, size) & live
+    k = np.asarray(seg)[m].astype(np.int64)
+    segcount = np.bincount(k, minlength=gh * gw)
+    segprob = np.zeros((gh * gw, p.shape[2]))
+    own = p.argmax(2)
+    if mode == 'mean':
+        np.add.at(segprob, k, p[m])
+        segprob /= np.maximum(segcount, 1)[:, None]
+    else:
+        np.add.at(segprob, (k, own[m]), 1.0)
+    labels = own.copy()
+    labels[m] = segprob[k].argmax(1)
+    return segprob, segcount.astype(np.int32), np.where(live, labels, 0).astype(np.int32)
+
+
+def report(keys, H, W, counts, matrix_before, matrix_after, changed):
+    """The block of `<t>_segments.json`: the parameters, the grid, the sizes of the non-empty segments, the voted confusion matrix
+    (rows = prediction), OA / AA / kappa before and after (indicators.kappa) and the number of test pixels whose class changed."""
+    from indicators.kappa import aa_oa_quiet
+
+    def block(m):
+        aa, oa, k = aa_oa_quiet(np.asarray(m, dtype=np.float64))
+        return dict(OA=oa, AA=aa, kappa=k)
+    sizes = np.asarray(counts)[np.asarray(counts) > 0]
+    return dict(kind=keys['kind'], size=keys['size'], compactness=keys['compactness'], iterations=keys['iterations'], vote=keys['vote'],
+                Kc=int(np.prod(grid(H, W, keys['size']))), segments=int(sizes.size),
+                segment_pixels=dict(min=int(sizes.min()), mean=float(sizes.mean()), max=int(sizes.max())) if sizes.size else None,
+                connectivity='not enforced', n=int(np.asarray(matrix_after).sum()),
+                matrix=np.asarray(matrix_after, dtype=np.int64).tolist(), before=block(matrix_before), after=block(matrix_after),
+                changed=int(changed))

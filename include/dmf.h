@@ -627,6 +627,60 @@ int32_t dmf_band_noise_moments(const float* x, int32_t H, int32_t W, int32_t C, 
                                int32_t direction /* 0 horizontal, 1 vertical */, double* ncov /* [C][C] */, void* workspace,
                                void* stream);
 
+/* ---- superpixel voting of class maps: SLIC segments of the primary scene and a per-segment vote.  New symbols
+ * at an unchanged DMF_VERSION: detect them by name.
+ *
+ * The scene is the leading H x W pixels of the resident padded primary scene [>= H, pitch_pixels >= W, C], as
+ * dmf_spatial_affinity takes it (fp32, or fp16 widened exactly; slot 0 of a scene atlas).  Everything is device memory.
+ *   grid      segment size S in DMF_SEG_SMIN..DMF_SEG_SMAX; gh = ceil(H / S), gw = ceil(W / S), Kc = gh gw; cluster
+ *             k = gi gw + gj belongs to cell (gi, gj) and keeps that index for life.  The cell of pixel x = (i, j) is
+ *             (i div S, j div S); its candidates are the clusters of the cells (gi + u, gj + v), u, v in {-1, 0, 1}, that lie
+ *             inside the grid, visited in ascending slot s = 3 (u + 1) + (v + 1).
+ *   centres   [Kc][C + 2] fp32: C spectrum values, then row and column as floats.
+ *   init      cluster k sits at pixel (min(H - 1, gi S + S div 2), min(W - 1, gj S + S div 2)) and takes its spectrum.
+ *   assign    d2 = (sum_c (a_c(x) - mu_c)^2) / (float)C in fp32, the bands in ascending order, each term one fmaf of the rounded
+ *             difference; sp = fl(fl(di di) + fl(dj dj)) with di = fl((float)i - row_k), dj = fl((float)j - col_k);
+ *             D = fl(d2 + fl(cw sp)), cw = the double (compactness / S)^2 rounded to fp32.  seg[x] (int32) = the candidate with
+ *             the smallest D, the first slot on equality (a NaN D never wins; the pixel's own cell is the fallback).
+ *   update    the members of k are the pixels of its 3 x 3 cells with seg == k; counts[k] (int32) = their number.  Per cell and
+ *             candidate, the members' spectra are summed in fp32 from +0 over the cell's pixels in row order, and their rows and
+ *             columns as integers; cluster k adds its up to nine cell partials in double, in ascending slot of its own 3 x 3
+ *             cells, and divides once in double: the mean spectrum, the mean row and the mean column, each rounded to fp32.  A
+ *             cluster without a member keeps its row of centres.  A seg value that is none of a pixel's candidates is a
+ *             member of nothing.  Two launches; `workspace` needs dmf_slic_workspace_bytes(H, W, C, S) bytes, 16-byte aligned
+ *             (-1 for an argument out of range), and what it holds between calls does not matter.
+ *   vote      prob [H W][K] and mask [H W] as dmf_prob_scatter leaves them.  The masked members of k are the pixels of its 3 x 3
+ *             cells with seg == k and mask 1; segcount[k] = their number.  DMF_VOTE_MEAN: segprob[k][c] = (sum p_c) / (float)count
+ *             in fp32, the members in row order of the 3S x 3S window, an all-zero row for count 0.  DMF_VOTE_MAJORITY:
+ *             segprob[k][c] = the number of masked members whose FIRST maximal class is c, an exact integer in fp32 (at most
+ *             9 S^2 < 2^24).  label_map[x], for a pixel with mask 1, = the first maximal index of its segment's row; a pixel with
+ *             mask 0 keeps its cell and its row of prob is never read.  prob_out (may be NULL) [H W][K] = the segment's row, all
+ *             zeros where mask is 0.  A masked pixel whose seg value is none of its candidates counts for no segment and stands
+ *             for itself: its own first maximal class, and in prob_out its own row (mean) or 1 at that class (majority).  Labels
+ *             are compared with the candidates' indices and never used as an index, so this holds for any contents of seg.
+ * n iterations = init, n x (assign, update), a last assign; nothing synchronises with the host.  Connectivity is not enforced.
+ * No float atomics and fixed orders: two runs give the same bits.  All report by code, without a launch (and so with every
+ * output as it was): 1 a NULL pointer (prob_out may be NULL); 2 H, W or C < 1; 3 K outside 1..DMF_KMAX; 4 S outside
+ * DMF_SEG_SMIN..DMF_SEG_SMAX; 5 elem_bytes not 2 or 4; 6 pitch_pixels < W; 7 an output overlaps an input or another output;
+ * 8 the scene not aligned to elem_bytes, the workspace not to 16 bytes, or more workgroups than a grid holds; 9 a launch itself
+ * failed; 10 a compactness that is not finite and >= 0; 11 a mode other than the two; 12 workspace_bytes too small.
+ * (They do not set the text of dmf_last_error.) */
+#define DMF_SEG_SMIN 4
+#define DMF_SEG_SMAX 32
+#define DMF_VOTE_MEAN 0
+#define DMF_VOTE_MAJORITY 1
+int64_t dmf_slic_workspace_bytes(int32_t H, int32_t W, int32_t C, int32_t S);
+int32_t dmf_slic_init(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C, int32_t S,
+                      float* centres /* [Kc][C + 2] */, void* stream);
+int32_t dmf_slic_assign(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C, int32_t S,
+                        float compactness, const float* centres, int32_t* seg /* [H W] */, void* stream);
+int32_t dmf_slic_update(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C, int32_t S,
+                        const int32_t* seg, float* centres, int32_t* counts /* [Kc] */, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int32_t dmf_segment_vote(const float* prob, const uint8_t* mask, const int32_t* seg, int32_t H, int32_t W, int32_t K, int32_t S,
+                         int32_t mode, float* segprob /* [Kc][K] */, int32_t* segcount /* [Kc] */, int32_t* label_map /* [H W] */,
+                         float* prob_out /* nullable */, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

@@ -252,6 +252,27 @@ class Scene:
             self._segments = kept = (key, (seg, centres, counts))
         return kept[1]
 
+    def segment_regions(self, seg, H, W, n_labels=0, min_size=1):
+        """-> (region [H, W] int32 on the device, R, region sizes [R] int32 on the device, stats): the connected regions of the
+        label image seg [H, W] int32 (`segments`' image with n_labels = Kc, or any segmentation with n_labels = 0).
+        dmf_label_components, then dmf_region_merge: a component smaller than `min_size` that is not the main component of a
+        label in 0..n_labels - 1 joins the component before it.  stats = dict(regions, components, absorbed).  One host read (the
+        four statistics) at the end; the workspace of about 16 bytes per pixel is released on return."""
+        H, W = int(H), int(W)
+        if not (torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.int32 and tuple(seg.shape) == (H, W)):
+            raise lib.DmfError('segment_regions: seg must be an int32 GPU tensor [%d, %d]' % (H, W))
+        seg = seg.contiguous()
+        dev = seg.device
+        comp, region = torch.empty_like(seg), torch.empty_like(seg)
+        sizes = torch.empty(H * W, dtype=torch.int32, device=dev)
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ws = torch.empty(lib.region_workspace_bytes(H, W, n_labels), dtype=torch.uint8, device=dev)
+            lib.label_components(seg, comp, ws)
+            lib.region_merge(seg, comp, n_labels, min_size, region, sizes, stats, ws)
+            R, components, absorbed, _ = stats.tolist()
+        return region, R, sizes[:R].clone(), dict(regions=R, components=components, absorbed=absorbed)
+
 
 class AtlasScene(Scene):
     """A `Scene` whose A and B are scene atlases: the variants `ops` of the padded scenes, stacked along the row
@@ -1383,6 +1404,20 @@ class EvalEngine(_ShardedEval):
         with torch.cuda.device(prob.device):
             lib.segment_vote(prob, mask, seg, size, mode, segprob, segcount, label_map)
         return segprob, segcount, label_map
+
+    # ------------------------------------------------------------------ connected superpixels
+    def region_vote(self, prob, mask, region, R, mode='mean'):
+        """-> (regprob [R, K] float32, regcount [R] int32, label map [H, W] int32): one dmf_region_vote over prob / mask (as
+        `probability_map` gives them) and the regions 0..R - 1 of region [H, W] (`Scene.segment_regions`), which may have any shape.
+        mode `mean`: a region's row is the mean probability of its masked members in exact fixed point; `majority`: their class
+        counts.  The label map is the first maximal class of a masked pixel's region, and 0 where mask is 0; prob is not written."""
+        regprob = torch.empty(R, prob.shape[2], dtype=torch.float32, device=prob.device)
+        regcount = torch.empty(R, dtype=torch.int32, device=prob.device)
+        label_map = torch.zeros(prob.shape[0], prob.shape[1], dtype=torch.int32, device=prob.device)
+        with torch.cuda.device(prob.device):
+            ws = torch.empty(lib.region_vote_workspace_bytes(R, prob.shape[2]), dtype=torch.uint8, device=prob.device)
+            lib.region_vote(prob, mask, region, R, mode, regprob, regcount, label_map, ws)
+        return regprob, regcount, label_map
 
     def collect_logits(self, xy_all, labels_all=None):
         """-> the logits of all given pixels in ONE device tensor [N, K] (and their labels as device int32 [N])."""

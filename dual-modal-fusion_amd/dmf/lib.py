@@ -148,6 +148,11 @@ def _load():
         'dmf_slic_assign': (i32, [vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
         'dmf_slic_update': (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
         'dmf_segment_vote': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        'dmf_region_workspace_bytes': (i64, [i32, i32, i32]),
+        'dmf_region_vote_workspace_bytes': (i64, [i32, i32]),
+        'dmf_label_components': (i32, [vp, i32, i32, vp, vp, i64, vp]),
+        'dmf_region_merge': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        'dmf_region_vote': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -1060,6 +1065,96 @@ def segment_vote(prob, mask, seg, size, mode, segprob, segcount, label_map, prob
         raise DmfError('segment_vote: all tensors must live on one device')
     _segment_check('dmf_segment_vote', _lib.dmf_segment_vote(_ptr(prob), _ptr(mask), _ptr(seg), H, W, K, size, VOTE_MODES[mode],
                                                              _ptr(segprob), _ptr(segcount), _ptr(label_map), _ptr(prob_out), _stream()))
+
+
+# return codes of the entry points of csrc/dmf_regions.hip, which report by code (include/dmf.h)
+REGION_PIXELS_MAX, REGION_VOTE_PIXELS_MAX = 1 << 31, 1 << 27      # DMF_REGION_PIXELS_MAX, DMF_REGION_VOTE_PIXELS_MAX
+_REGION_ERRORS = {1: 'a NULL pointer', 2: 'H, W and R must be >= 1 and R <= H W', 3: '1 <= K <= DMF_KMAX',
+                  7: 'an output or the workspace overlaps an input or another output', 8: 'a misaligned pointer, or a grid beyond 32 bits',
+                  9: 'a launch failed', 11: 'the vote mode is not mean or majority', 12: 'the workspace is too small',
+                  13: 'too many pixels: H W < 2^31 for components and merge, < 2^27 for the vote', 14: 'min_size must be >= 1',
+                  15: 'n_labels must be >= 0'}
+
+
+def _region_check(entry, rc):
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, _REGION_ERRORS.get(rc, 'error %d' % rc)))
+
+
+def _whole(entry, name, v, least):
+    if isinstance(v, bool) or not isinstance(v, int) or v < least or v >= 1 << 31:
+        raise DmfError('%s: %s = %r is not a whole number >= %d' % (entry, name, v, least))
+    return v
+
+
+def region_workspace_bytes(H, W, n_labels=0):
+    n = _lib.dmf_region_workspace_bytes(H, W, n_labels)
+    if n < 0:
+        raise DmfError('dmf_region_workspace_bytes: H, W >= 1, n_labels >= 0 and H W < 2^31')
+    return n
+
+
+def region_vote_workspace_bytes(R, K):
+    n = _lib.dmf_region_vote_workspace_bytes(R, K)
+    if n < 0:
+        raise DmfError('dmf_region_vote_workspace_bytes: R >= 1 and 1 <= K <= DMF_KMAX')
+    return n
+
+
+def label_components(labels, comp, workspace):
+    """comp [H, W] int32 <- for every pixel the smallest raster index of its 4-connected component of equal values of
+    labels [H, W] int32 (dmf_label_components).  `workspace`: a uint8 tensor of region_workspace_bytes(H, W) bytes."""
+    _dev(labels, torch.int32, 'labels')
+    if labels.dim() != 2:
+        raise DmfError('label_components wants labels [H, W]')
+    H, W = labels.shape
+    _segment_tensor('label_components', comp, torch.int32, (H, W), 'comp', labels.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    _region_check('dmf_label_components', _lib.dmf_label_components(_ptr(labels), H, W, _ptr(comp), _ptr(workspace), workspace.numel(), _stream()))
+
+
+def region_merge(labels, comp, n_labels, min_size, region, region_size, stats, workspace):
+    """region [H, W] int32 <- the dense id of every pixel's region: its component, or for a fragment (smaller than min_size, not
+    the main component of a label in 0..n_labels - 1, not at pixel 0) the end of the chain of components before it; region_size
+    [H W] int32 <- the regions' pixel counts in the first R cells, 0 in the others; stats [4] int32 <- R, components, fragments
+    absorbed, 0 (dmf_region_merge).  `workspace`: a uint8 tensor of region_workspace_bytes(H, W, n_labels) bytes."""
+    _dev(labels, torch.int32, 'labels')
+    if labels.dim() != 2:
+        raise DmfError('region_merge wants labels [H, W]')
+    H, W = labels.shape
+    _whole('region_merge', 'n_labels', n_labels, 0); _whole('region_merge', 'min_size', min_size, 1)
+    _segment_tensor('region_merge', comp, torch.int32, (H, W), 'comp', labels.device)
+    _segment_tensor('region_merge', region, torch.int32, (H, W), 'region', labels.device)
+    _segment_tensor('region_merge', region_size, torch.int32, (H * W,), 'region_size', labels.device)
+    _segment_tensor('region_merge', stats, torch.int32, (4,), 'stats', labels.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    _region_check('dmf_region_merge', _lib.dmf_region_merge(_ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(region), _ptr(region_size),
+                                                           _ptr(stats), _ptr(workspace), workspace.numel(), _stream()))
+
+
+def region_vote(prob, mask, region, R, mode, regprob, regcount, label_map, workspace, prob_out=None):
+    """regprob [R, K], regcount [R] <- the mean probabilities in exact fixed point (mode 'mean') or the class counts ('majority') of
+    the masked members of every region 0..R - 1 of region [H, W] int32; label_map [H, W] int32 <- at every masked pixel the first
+    maximal class of its region's row, the other cells untouched; prob_out (optional) [H, W, K] <- that row, zeros where mask is 0
+    (dmf_region_vote).  `workspace`: a uint8 tensor of region_vote_workspace_bytes(R, K) bytes."""
+    if mode not in VOTE_MODES:
+        raise DmfError('region_vote: the mode %r is not mean or majority' % (mode,))
+    _dev(prob, torch.float32, 'prob'); _dev(mask, torch.uint8, 'mask'); _dev(region, torch.int32, 'region')
+    if prob.dim() != 3 or tuple(mask.shape) != tuple(prob.shape[:2]) or tuple(region.shape) != tuple(prob.shape[:2]):
+        raise DmfError('region_vote wants prob [H, W, K] with mask and region [H, W]')
+    H, W, K = prob.shape
+    _whole('region_vote', 'R', R, 1)
+    _segment_tensor('region_vote', regprob, torch.float32, (R, K), 'regprob', prob.device)
+    _segment_tensor('region_vote', regcount, torch.int32, (R,), 'regcount', prob.device)
+    _segment_tensor('region_vote', label_map, torch.int32, (H, W), 'label_map', prob.device)
+    if prob_out is not None:
+        _segment_tensor('region_vote', prob_out, torch.float32, (H, W, K), 'prob_out', prob.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    if mask.device != prob.device or region.device != prob.device or workspace.device != prob.device:
+        raise DmfError('region_vote: all tensors must live on one device')
+    _region_check('dmf_region_vote', _lib.dmf_region_vote(_ptr(prob), _ptr(mask), _ptr(region), H, W, K, R, VOTE_MODES[mode], _ptr(regprob),
+                                                         _ptr(regcount), _ptr(label_map), _ptr(prob_out), _ptr(workspace), workspace.numel(),
+                                                         _stream()))
 
 
 # return codes of the two entry points of csrc/dmf_pca.hip, which report by code (include/dmf.h)

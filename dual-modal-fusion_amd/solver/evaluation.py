@@ -29,6 +29,10 @@ map (the unfiltered one, whatever `test.spatial` says), SLIC segments of the pri
 a second confusion matrix over the same test pixels (`self.segments`, `<t>_segments.json`, `<t>_segments.npy`: the int32 segment
 image); `color()` also writes `<t>_pic_{1,2}_segments.png`.  Fast path: EvalEngine.probability_map, Scene.segments and
 EvalEngine.segment_vote (dmf_slic_* / dmf_segment_vote); drop-in path: utils/segments.py in numpy float64.
+`test.segment_connectivity: 1` with `test.segment_min_size`, and `test.segments: file` with `test.segment_file`: the
+segment image (SLIC's, or the file's) becomes connected regions, small fragments join the component before them, and the vote runs
+over the regions (Scene.segment_regions, EvalEngine.region_vote: dmf_label_components / dmf_region_merge / dmf_region_vote; drop-in
+path: utils.segments.regions / region_vote, the same integers); `<t>_segments.npy` then holds the region image.
 """
 import itertools
 
@@ -90,12 +94,22 @@ class EngineEvaluation(_Evaluation):
         aff = self.s.scene.affinity(H, W, k['radius'], k['sigma_s'], k['sigma_r'])
         return None, eng.regularise(prob, mask, aff, k['iterations'])[1].cpu().numpy()
 
-    def scene_segments(self, xy, H, W, beta, k):
-        """-> (None, segment image, voted label map): EvalEngine.probability_map, Scene.segments, EvalEngine.segment_vote."""
+    def scene_segments(self, xy, H, W, beta, k, rk=None):
+        """-> (None, segment image, voted label map): EvalEngine.probability_map, Scene.segments, EvalEngine.segment_vote.  With
+        the region keys `rk` on: (None, region image, voted label map, dict(regions, components, absorbed, sizes, raw))."""
         eng = self.s.eval_engine
         prob, mask = eng.probability_map(torch.from_numpy(xy), H, W, beta)
-        seg = self.s.scene.segments(H, W, k['size'], k['compactness'], k['iterations'])[0]
-        return None, seg.cpu().numpy(), eng.segment_vote(prob, mask, seg, k['size'], k['vote'])[2].cpu().numpy()
+        if rk is None or not rk['connectivity']:
+            seg = self.s.scene.segments(H, W, k['size'], k['compactness'], k['iterations'])[0]
+            return None, seg.cpu().numpy(), eng.segment_vote(prob, mask, seg, k['size'], k['vote'])[2].cpu().numpy()
+        # connected regions (DESIGN §24): Scene.segment_regions on SLIC's image or the file's, EvalEngine.region_vote
+        if k['kind'] == 'file':
+            seg, n_labels = torch.from_numpy(segments.load_segment_file(rk['file'], H, W)).to(prob.device), 0
+        else:
+            seg, n_labels = self.s.scene.segments(H, W, k['size'], k['compactness'], k['iterations'])[0], int(np.prod(segments.grid(H, W, k['size'])))
+        region, R, sizes, stats = self.s.scene.segment_regions(seg, H, W, n_labels, rk['min_size'])
+        voted = eng.region_vote(prob, mask, region, R, k['vote'])[2].cpu().numpy()
+        return None, region.cpu().numpy(), voted, dict(stats, sizes=sizes.cpu().numpy(), raw=seg.cpu().numpy())
 
     def plain_at(self, xy, plain, H, W):
         return self.s.eval_engine.label_map(torch.from_numpy(xy), H, W).cpu().numpy()[xy[:, 0], xy[:, 1]]
@@ -172,11 +186,21 @@ class DropinEvaluation(_Evaluation):
         aff = spatial.affinity(scene, H, W, k['radius'], k['sigma_s'], k['sigma_r'])
         return plain, spatial.regularise(prob, mask, aff, k['radius'], k['iterations'])[1]
 
-    def scene_segments(self, xy, H, W, beta, k):
-        """-> (plain, segment image, voted label map): utils.segments in float64 on the same logits and scene."""
+    def scene_segments(self, xy, H, W, beta, k, rk=None):
+        """-> (plain, segment image, voted label map): utils.segments in float64 on the same logits and scene.  With the region
+        keys `rk` on: the region image in the segment image's place and dict(regions, components, absorbed, sizes, raw) after them,
+        by utils.segments' integer arithmetic."""
         prob, mask, plain, scene = self._scene_probabilities(xy, H, W, beta)
-        seg = segments.slic(scene, H, W, k['size'], k['compactness'], k['iterations'])[0]
-        return plain, seg, segments.vote(prob, mask, seg, k['size'], k['vote'])[2]
+        if rk is None or not rk['connectivity']:
+            seg = segments.slic(scene, H, W, k['size'], k['compactness'], k['iterations'])[0]
+            return plain, seg, segments.vote(prob, mask, seg, k['size'], k['vote'])[2]
+        if k['kind'] == 'file':
+            seg, n_labels = segments.load_segment_file(rk['file'], H, W), 0
+        else:
+            seg, n_labels = segments.slic(scene, H, W, k['size'], k['compactness'], k['iterations'])[0], int(np.prod(segments.grid(H, W, k['size'])))
+        region, sizes, stats = segments.regions(seg, n_labels, rk['min_size'])
+        voted = segments.region_vote(prob, mask, region, stats['regions'], k['vote'])[2]
+        return plain, region, voted, dict(stats, sizes=sizes, raw=seg)
 
     def plain_at(self, xy, plain, H, W):
         return plain[xy[:, 0], xy[:, 1]]

@@ -58,7 +58,7 @@ what the kernel reads) and no train route changes; `EvalEngine(tta=)` runs one f
 path: the materialised patches are transformed (`augment.tf_batch`), the mean is torch's (`_logits_dropin`).  The validation
 pass is never augmented.  With both keys `none` the scene is the plain Scene and nothing changes; toStageSolver refuses the keys.
 `test.calibration`, `test.temperature`, `color.confidence`, `test.spatial`, `color.spatial` and
-`test.segments`, `color.segments` (DESIGN §23): see
+`test.segments`, `color.segments` (DESIGN §23, §24): see
 solver/evaluation.py, to whose class of this run's path (`self.evaluation`) `test()` and `color()` put their questions.
 Data parallel (`test.py` under `torch.distributed.run`, fast path only): every rank holds the scene, iterates the SAME
 shuffled index stream (same seed) and trains on its contiguous shard of each global batch (a batch that the world size
@@ -111,6 +111,7 @@ class Solver(BaseSolver):
     aug_ops, tta_ops = (0,), (0,)                        # (BaseSolver reads them from schedule.augment / test.tta; (0,) = none)
     calib, spat = calib.calibration_keys({}), spatial.spatial_keys({})     # (the constructor reads them from cfg; these: neutral)
     segm = segments.segment_keys({})                     # (likewise)
+    regn = segments.region_keys({}, segm)                # (likewise: test.segment_connectivity / _min_size / _file)
     evaluation = None                                    # solver.evaluation's class of this run's path (`_ensure_model`)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
@@ -144,6 +145,7 @@ class Solver(BaseSolver):
         if spectral.keys_in_use(spectral.band_keys(cfg)) and not self.band_reduced:
             raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)
+        self.regn = segments.region_keys(cfg, self.segm)   # test.segment_connectivity / segment_min_size / segment_file
         self.spatial, self._spatial_maps = None, None  # test()'s regularisation block; the whole-scene maps of the loaded weights
         self.segments, self._segment_maps = None, None # test()'s superpixel block; the whole-scene maps of the loaded weights
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
@@ -844,23 +846,29 @@ class Solver(BaseSolver):
 
     # ------------------------------------------------------------------ superpixel voting (test.segments, color.segments)
     def _segmented_maps(self, best):
-        """-> (plain or None, segment image [H, W] int32, voted label map [H, W] int32) (numpy) of the WHOLE scene under the loaded
+        """-> (plain or None, segment image [H, W] int32, voted label map [H, W] int32[, the regions' figures]) (numpy) of the WHOLE scene under the loaded
         weights (`best`: which file they came from; kept per trained model and file): all pixels of both colour sets are classified
         at `test.temperature`'s beta, the scene is segmented, and every pixel takes its segment's class.  The probability map is
         the unfiltered one, whatever `test.spatial` says."""
         if self._segment_maps is None or self._segment_maps[0] != bool(best):
             size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
             beta = self._beta(self._temperature_used()[0])
-            self._segment_maps = (bool(best), self.evaluation.scene_segments(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.segm))
+            self._segment_maps = (bool(best), self.evaluation.scene_segments(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.segm, self.regn))
         return self._segment_maps[1]
 
     def _segment(self, whole):
         """`self.segments`, `<t>_segments.json` and `<t>_segments.npy`: a second confusion matrix over the pixels of the first, from
         the voted label map at their (x, y).  `self.test_matrix` and what `indicator()` makes of it stay as they are."""
-        plain, seg, voted = self._segmented_maps(self.cfg['train']['save_best'])
+        plain, seg, voted, *extra = self._segmented_maps(self.cfg['train']['save_best'])
         H, W = seg.shape
-        counts = np.bincount(seg.reshape(-1), minlength=int(np.prod(segments.grid(H, W, self.segm['size']))))
+        raw = extra[0]['raw'] if extra else seg          # (connected regions, DESIGN §24: `seg` is then the region image)
+        if self.segm['kind'] == 'file':
+            counts = np.unique(raw, return_counts=True)[1]
+        else:
+            counts = np.bincount(raw.reshape(-1), minlength=int(np.prod(segments.grid(H, W, self.segm['size']))))
         self.segments = segments.report(self.segm, H, W, counts, self.test_matrix, *self._second_matrix(whole, plain, voted))
+        if extra:
+            self.segments = segments.region_report(self.segments, self.regn['min_size'], extra[0], extra[0]['sizes'])
         self.segment_image = seg
         self._write_block(self.segments, '_segments.json')
         if self.rank == 0:

@@ -6,22 +6,24 @@ The scene is over-segmented into SLIC superpixels in the pixel-centric form: cel
 and every pixel chooses among the up to nine clusters of its own and the adjacent cells (slot s = 3 (u + 1) + (v + 1)) the one with
 the smallest D = mean_c (a_c - mu_c)^2 + (compactness / S)^2 |x - centre|^2, the first slot on equality.  Every classified pixel
 then takes the class of its segment: of the mean probability of the segment's classified pixels, or of their majority.
-Connectivity is not enforced."""
+Connectivity is not enforced by SLIC itself; `test.segment_connectivity: 1` splits the segments into their
+4-connected components, joins small fragments to the component before them and votes over the regions: `components`, `regions` and
+`region_vote` below are that arithmetic in integers.  `test.segments: file` votes over the components of a user's label image."""
 import math
 
 import numpy as np
 
-KINDS = ('none', 'slic')
+KINDS = ('none', 'slic', 'file')
 VOTES = ('mean', 'majority')
 SIZE_MIN, SIZE_MAX = 4, 32
 
 
 def segment_keys(cfg):
     """-> dict(kind, size, compactness, iterations, vote, color) from the optional keys
-         test.segments none / slic (default none)        test.segment_size 4..32 (default 8)
+         test.segments none / slic / file (default none) test.segment_size 4..32 (default 8)
          test.segment_compactness >= 0 (default 0.1)     test.segment_iterations >= 0 (default 10)
          test.segment_vote mean / majority (default mean)  color.segments 0 / 1 (default 0)
-    `kind` is None or 'slic'.  Neutral values change nothing."""
+    `kind` is None, 'slic' or 'file' (a user's label image: `region_keys` reads its path).  Neutral values change nothing."""
     test, color = cfg.get('test') or {}, cfg.get('color') or {}
     kind = test.get('segments', 'none')
     kind = 'none' if kind is None or kind is False or kind == 0 else str(kind).lower()
@@ -48,6 +50,35 @@ def segment_keys(cfg):
     if col and kind == 'none':
         raise ValueError('color.segments: 1 draws the map that test.segments: slic votes on; test.segments is none')
     return dict(kind=None if kind == 'none' else kind, size=size, compactness=f, iterations=its, vote=vote, color=bool(col))
+
+
+def region_keys(cfg, keys):
+    """-> dict(connectivity, min_size, file) from the optional keys, given `segment_keys`' dict
+         test.segment_connectivity 0 / 1 (default 0)     test.segment_min_size auto / n >= 1 (default auto)
+         test.segment_file <path.npy>: the label image of test.segments: file, whose regions are its components
+    auto is max(1, S^2 div 4) for slic (Achanta et al. 2012) and 1 for file, which implies connectivity.  Neutral values change
+    nothing."""
+    test = cfg.get('test') or {}
+    con = test.get('segment_connectivity', 0) or 0
+    if con not in (0, 1, True, False):
+        raise ValueError('test.segment_connectivity is 0 or 1')
+    ms = test.get('segment_min_size', 'auto')
+    if ms is None or (isinstance(ms, str) and ms.lower() == 'auto'):
+        ms = None
+    elif isinstance(ms, bool) or not isinstance(ms, int) or not 1 <= ms < 1 << 31:
+        raise ValueError('test.segment_min_size %r is not auto or a whole number >= 1' % (ms,))
+    path = test.get('segment_file')
+    if keys['kind'] == 'file':
+        if not isinstance(path, str) or not path:
+            raise ValueError('test.segments: file reads the label image test.segment_file: <path.npy>, which is not given')
+        con = 1
+    elif path:
+        raise ValueError('test.segment_file is read by test.segments: file; test.segments is %s' % (keys['kind'] or 'none'))
+    if con and keys['kind'] is None:
+        raise ValueError('test.segment_connectivity: 1 connects the segments of test.segments: slic; test.segments is none')
+    if ms is None:
+        ms = max(1, keys['size'] ** 2 // 4) if keys['kind'] == 'slic' else 1
+    return dict(connectivity=bool(con), min_size=ms, file=path if keys['kind'] == 'file' else None)
 
 
 def keys_in_use(keys):
@@ -150,6 +181,125 @@ def vote(prob, mask, seg, size, mode):
     return segprob, segcount.astype(np.int32), np.where(live, labels, 0).astype(np.int32)
 
 
+# ------------------------------------------------------------------------------------------------ connected regions
+# The integer arithmetic of dmf_label_components / dmf_region_merge / dmf_region_vote (include/dmf.h): equal, not close.
+QBITS = 36                                   # the mean vote's fixed point: q = rint(clamp(p, 0, 1) 2^36)
+
+
+def components(labels):
+    """comp [H, W] int32: for every pixel the smallest raster index of its 4-connected component of equal values.  Hooking the
+    larger root of every joined pair to the smaller one and jumping pointers, in O(log n) rounds."""
+    lab = np.asarray(labels)
+    H, W = lab.shape
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    right, down = lab[:, 1:] == lab[:, :-1], lab[1:, :] == lab[:-1, :]
+    a = np.concatenate([idx[:, 1:][right], idx[1:, :][down]])
+    b = np.concatenate([idx[:, :-1][right], idx[:-1, :][down]])
+    p = idx.ravel().copy()
+    while True:
+        pa, pb = p[a], p[b]
+        differ = pa != pb
+        if not differ.any():
+            break
+        np.minimum.at(p, np.maximum(pa, pb)[differ], np.minimum(pa, pb)[differ])
+        while True:
+            pp = p[p]
+            if np.array_equal(pp, p):
+                break
+            p = pp
+    return p.reshape(H, W).astype(np.int32)
+
+
+def regions(labels, n_labels=0, min_size=1):
+    """-> (region [H, W] int32, region sizes [R] int32, dict(regions, components, absorbed)): the components of `labels`, with
+    every fragment (smaller than min_size, not the main component of a label in 0..n_labels - 1, not at pixel 0) joined to the end
+    of the chain of components before it: the one left of its root, above it for a root in column 0.  Regions are numbered in
+    ascending order of their roots."""
+    lab = np.asarray(labels)
+    H, W = lab.shape
+    if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 1 or int(n_labels) != n_labels or n_labels < 0:
+        raise ValueError('regions: min_size >= 1 and n_labels >= 0 are whole numbers')
+    comp = components(lab).ravel().astype(np.int64)
+    flat = lab.ravel()
+    roots = np.nonzero(comp == np.arange(H * W))[0]
+    size = np.bincount(comp, minlength=H * W)
+    kept = np.zeros(H * W, dtype=bool)
+    kept[roots] = size[roots] >= min_size
+    kept[0] = True
+    named = roots[(flat[roots] >= 0) & (flat[roots] < n_labels)]
+    if named.size:
+        order = np.lexsort((named, -size[named], flat[named]))            # by label, the largest first, then the smaller root
+        first = np.concatenate([[True], np.diff(flat[named][order]) != 0])
+        kept[named[order][first]] = True
+    target = np.arange(H * W)
+    frag = roots[~kept[roots]]
+    target[frag] = np.where(frag % W > 0, comp[np.maximum(frag - 1, 0)], comp[np.maximum(frag - W, 0)])
+    final = target.copy()
+    while True:                                          # pointer jumping: the chains end at kept roots
+        nxt = final[final]
+        if np.array_equal(nxt, final):
+            break
+        final = nxt
+    dense = np.cumsum(kept) - 1
+    region = dense[final[comp]]
+    R = int(kept.sum())
+    return (region.reshape(H, W).astype(np.int32), np.bincount(region, minlength=R).astype(np.int32),
+            dict(regions=R, components=int(roots.size), absorbed=int(frag.size)))
+
+
+def quantise(prob):
+    """int64: rint(clamp(p, 0, 1) 2^36), half to even, a NaN as 0."""
+    p = np.asarray(prob, dtype=np.float32).astype(np.float64)
+    return np.rint(np.where(p > 0, np.minimum(p, 1.0), 0.0) * float(1 << QBITS)).astype(np.int64)
+
+
+def region_vote(prob, mask, region, R, mode):
+    """-> (regprob [R, K] float32, regcount [R] int32, label map [H, W] int32: 0 where mask is 0).  mode mean: 64-bit integer sums
+    of the quantised probabilities, divided once in double and rounded to fp32; majority: the counts of the first maximal classes.
+    A masked pixel whose region is outside 0..R - 1 stands for itself."""
+    live = np.asarray(mask) != 0
+    reg = np.asarray(region)
+    K = np.asarray(prob).shape[2]
+    m = live & (reg >= 0) & (reg < R)
+    k = reg[m].astype(np.int64)
+    p = np.where(live[:, :, None], np.asarray(prob, dtype=np.float32), np.float32(0))
+    own = p.argmax(2)                                    # (numpy's argmax: the first maximal index)
+    regcount = np.bincount(k, minlength=R)
+    acc = np.zeros((R, K), dtype=np.int64)
+    if mode == 'mean':
+        np.add.at(acc, k, quantise(p[m]))
+        regprob = (acc.astype(np.float64) / (np.maximum(regcount, 1)[:, None].astype(np.float64) * float(1 << QBITS))).astype(np.float32)
+    elif mode == 'majority':
+        np.add.at(acc, (k, own[m]), 1)
+        regprob = acc.astype(np.float32)
+    else:
+        raise ValueError('region_vote: the mode %r is not mean or majority' % (mode,))
+    labels = own.copy()
+    labels[m] = regprob[k].argmax(1)
+    return regprob, regcount.astype(np.int32), np.where(live, labels, 0).astype(np.int32)
+
+
+def load_segment_file(path, H, W):
+    """The label image of `test.segment_file`: an integer [H, W] .npy array whose values fit int32 -> int32 [H, W]."""
+    a = np.load(path, allow_pickle=False)
+    if a.dtype.kind not in 'iu':
+        raise ValueError('test.segment_file %s holds %s, not integers' % (path, a.dtype))
+    if a.shape != (H, W):
+        raise ValueError('test.segment_file %s has shape %s, the scene is %s' % (path, list(a.shape), [H, W]))
+    if a.size and (int(a.min()) < -(1 << 31) or int(a.max()) >= 1 << 31):
+        raise ValueError('test.segment_file %s holds values that do not fit int32' % path)
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def region_report(block, min_size, stats, region_sizes):
+    """`report`'s block with connectivity enforced: min_size, components, absorbed, regions, region_pixels."""
+    sizes = np.asarray(region_sizes)
+    out = dict(block)
+    out.update(connectivity='enforced', min_size=int(min_size), components=int(stats['components']), absorbed=int(stats['absorbed']),
+               regions=int(stats['regions']), region_pixels=dict(min=int(sizes.min()), mean=float(sizes.mean()), max=int(sizes.max())))
+    return out
+
+
 def report(keys, H, W, counts, matrix_before, matrix_after, changed):
     """The block of `<t>_segments.json`: the parameters, the grid, the sizes of the non-empty segments, the voted confusion matrix
     (rows = prediction), OA / AA / kappa before and after (indicators.kappa) and the number of test pixels whose class changed."""
@@ -159,6 +309,12 @@ def report(keys, H, W, counts, matrix_before, matrix_after, changed):
         aa, oa, k = aa_oa_quiet(np.asarray(m, dtype=np.float64))
         return dict(OA=oa, AA=aa, kappa=k)
     sizes = np.asarray(counts)[np.asarray(counts) > 0]
+    if keys['kind'] == 'file':                           # no grid, no clusters: the file's values are the segments
+        return dict(kind='file', vote=keys['vote'], segments=int(sizes.size),
+                    segment_pixels=dict(min=int(sizes.min()), mean=float(sizes.mean()), max=int(sizes.max())) if sizes.size else None,
+                    connectivity='not enforced', n=int(np.asarray(matrix_after).sum()),
+                    matrix=np.asarray(matrix_after, dtype=np.int64).tolist(), before=block(matrix_before), after=block(matrix_after),
+                    changed=int(changed))
     return dict(kind=keys['kind'], size=keys['size'], compactness=keys['compactness'], iterations=keys['iterations'], vote=keys['vote'],
                 Kc=int(np.prod(grid(H, W, keys['size']))), segments=int(sizes.size),
                 segment_pixels=dict(min=int(sizes.min()), mean=float(sizes.mean()), max=int(sizes.max())) if sizes.size else None,

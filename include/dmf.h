@@ -658,7 +658,8 @@ int32_t dmf_band_noise_moments(const float* x, int32_t H, int32_t W, int32_t C, 
  *             zeros where mask is 0.  A masked pixel whose seg value is none of its candidates counts for no segment and stands
  *             for itself: its own first maximal class, and in prob_out its own row (mean) or 1 at that class (majority).  Labels
  *             are compared with the candidates' indices and never used as an index, so this holds for any contents of seg.
- * n iterations = init, n x (assign, update), a last assign; nothing synchronises with the host.  Connectivity is not enforced.
+ * n iterations = init, n x (assign, update), a last assign; nothing synchronises with the host.  Connectivity is the business of
+ * dmf_label_components and dmf_region_merge below, and dmf_region_vote votes over the regions they give.
  * No float atomics and fixed orders: two runs give the same bits.  All report by code, without a launch (and so with every
  * output as it was): 1 a NULL pointer (prob_out may be NULL); 2 H, W or C < 1; 3 K outside 1..DMF_KMAX; 4 S outside
  * DMF_SEG_SMIN..DMF_SEG_SMAX; 5 elem_bytes not 2 or 4; 6 pitch_pixels < W; 7 an output overlaps an input or another output;
@@ -680,6 +681,62 @@ int32_t dmf_slic_update(const void* scene, int32_t elem_bytes, int32_t pitch_pix
 int32_t dmf_segment_vote(const float* prob, const uint8_t* mask, const int32_t* seg, int32_t H, int32_t W, int32_t K, int32_t S,
                          int32_t mode, float* segprob /* [Kc][K] */, int32_t* segcount /* [Kc] */, int32_t* label_map /* [H W] */,
                          float* prob_out /* nullable */, void* stream);
+
+/* ---- connected superpixels: the 4-connected components of a label image, the merge of small fragments, and a vote over regions
+ * of any shape.  New symbols at an unchanged DMF_VERSION: detect them by name.  Everything is device memory and
+ * integer arithmetic: no order of execution can change a bit.
+ *   components  labels [H][W] int32 may hold any values: they are compared for equality and never used as an index.  Two pixels
+ *               are joined when they are 4-neighbours with equal labels.  comp[x] (int32) = the smallest raster index i W + j
+ *               among the pixels of x's component: its root.  Three launches whatever the image holds.  H W < 2^31.
+ *   kept        size[r] = the pixel count of the component with root r.  With n_labels > 0 every label k in 0..n_labels - 1 that
+ *               occurs has a main component: its largest, on equal size the one with the smaller root; other labels have none.  A
+ *               component is kept when size >= min_size, or it is a main component, or its root is pixel 0.  Every other
+ *               component is a fragment.
+ *   target      of a fragment: the component of the pixel to the left of its root, or, for a root in column 0, of the pixel
+ *               above it.  Both have a smaller raster index than the root, so they lie outside the component (the previously
+ *               visited adjacent label of scikit-image's enforce_connectivity), and the target's root is strictly smaller than
+ *               the fragment's: targets form a forest.  final[r] = r for a kept component and final[target] otherwise, chains
+ *               followed to the end.  Sizes do NOT accumulate along a chain: a target that is itself a fragment stays one however
+ *               many pixels it absorbs.  min_size = 1 keeps every component: it splits clusters and absorbs nothing.
+ *   regions     numbered 0..R - 1 in ascending order of their kept roots.  region [H][W] int32; region_size [H W] int32: the
+ *               first R cells the pixel counts with absorbed pixels included, the others 0; stats [4] int32 = R, the number of
+ *               components, the number of fragments absorbed, 0.  `comp` must be what dmf_label_components left for `labels`:
+ *               with other contents the regions are unspecified, but nothing is read or written out of range and every chain ends.
+ *   workspace   dmf_region_workspace_bytes(H, W, n_labels) bytes serve both calls (n_labels 0 for the labelling alone);
+ *               dmf_region_vote_workspace_bytes(R, K) the vote; -1 for an argument out of range; 16-byte aligned; what a
+ *               workspace holds between calls does not matter.
+ *   vote        prob [H W][K] and mask [H W] as dmf_prob_scatter leaves them.  The members of region r are the pixels with
+ *               region == r and mask 1; regcount[r] = their number.  A pixel's first maximal class is the smallest class index at
+ *               which its row of prob is largest.  DMF_VOTE_MAJORITY: regprob[r][c] = the number of members whose first maximal
+ *               class is c, counted as an integer and converted to fp32 (exact below 2^24).  DMF_VOTE_MEAN is exact fixed point, so
+ *               no summation order exists: each term is q = rint(clamp(p, 0, 1) 2^36), half to even, a NaN counted as 0 (the
+ *               product by 2^36 is exact in fp32); the terms are added as 64-bit integers (H W < 2^27 members of at most 2^36: below
+ *               2^63); regprob[r][c] = (float)((double)sum / ((double)count 2^36)), the int64 -> double conversion rounding to
+ *               nearest even, an all-zero row for count 0.  label_map[x], for a pixel with mask 1, = the first maximal index of its
+ *               region's row; a pixel with mask 0 keeps its cell and its row of prob is never read.  prob_out (may be NULL)
+ *               [H W][K] = the region's row, all zeros where mask is 0.  A masked pixel whose region value is outside 0..R - 1
+ *               counts for no region and stands for itself, as in dmf_segment_vote: its own first maximal class, and in prob_out
+ *               its own row (mean) or 1 at that class (majority).
+ *   bound       against the plain float64 mean m of clamp(p, 0, 1): |q 2^-36 - p| <= 2^-37 for every term, so the exact rational
+ *               sum / (count 2^36) is within 2^-37 of m; the conversion and the division in double add at most 2^-52 relative,
+ *               and the one rounding to fp32 of a value <= 1 at most 2^-25:  |regprob - m| <= 2^-37 + 2^-25 + 2^-50.
+ * Return codes, all before any launch (and so with every output as it was): 1 a NULL pointer (prob_out may be NULL); 2 H, W or R
+ * < 1, or R > H W; 3 K outside 1..DMF_KMAX; 7 an output or the workspace overlaps an input, or two of them each other; 8 a pointer
+ * not aligned to its type, the workspace not to 16 bytes, or more workgroups than a grid holds; 9 a launch itself failed; 11 a
+ * mode other than the two; 12 workspace_bytes too small; 13 H W >= DMF_REGION_PIXELS_MAX (components, merge) or >=
+ * DMF_REGION_VOTE_PIXELS_MAX (vote); 14 min_size < 1; 15 n_labels < 0.  (They do not set the text of dmf_last_error.) */
+#define DMF_REGION_PIXELS_MAX 2147483648LL      /* 2^31: a root is an int32 */
+#define DMF_REGION_VOTE_PIXELS_MAX 134217728LL  /* 2^27: 2^27 terms of at most 2^36 stay below 2^63 */
+int64_t dmf_region_workspace_bytes(int32_t H, int32_t W, int32_t n_labels);
+int64_t dmf_region_vote_workspace_bytes(int32_t R, int32_t K);
+int32_t dmf_label_components(const int32_t* labels, int32_t H, int32_t W, int32_t* comp /* [H W] */, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int32_t dmf_region_merge(const int32_t* labels, const int32_t* comp, int32_t H, int32_t W, int32_t n_labels, int32_t min_size,
+                         int32_t* region /* [H W] */, int32_t* region_size /* [H W] */, int32_t* stats /* [4] */, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int32_t dmf_region_vote(const float* prob, const uint8_t* mask, const int32_t* region, int32_t H, int32_t W, int32_t K, int32_t R,
+                        int32_t mode, float* regprob /* [R][K] */, int32_t* regcount /* [R] */, int32_t* label_map /* [H W] */,
+                        float* prob_out /* nullable */, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */

@@ -252,12 +252,18 @@ class Scene:
             self._segments = kept = (key, (seg, centres, counts))
         return kept[1]
 
-    def segment_regions(self, seg, H, W, n_labels=0, min_size=1):
+    def segment_regions(self, seg, H, W, n_labels=0, min_size=1, merge='position'):
         """-> (region [H, W] int32 on the device, R, region sizes [R] int32 on the device, stats): the connected regions of the
         label image seg [H, W] int32 (`segments`' image with n_labels = Kc, or any segmentation with n_labels = 0).
         dmf_label_components, then dmf_region_merge: a component smaller than `min_size` that is not the main component of a
         label in 0..n_labels - 1 joins the component before it.  stats = dict(regions, components, absorbed).  One host read (the
-        four statistics) at the end; the workspace of about 16 bytes per pixel is released on return."""
+        four statistics) at the end; the workspace of about 16 bytes per pixel is released on return.
+        merge = 'spectrum' (DESIGN.md §25): dmf_region_graph_count and dmf_region_graph_merge in dmf_region_merge's place.  A
+        fragment joins the adjacent group with the nearest mean spectrum of the H x W scene at the top-left corner of the padded
+        primary scene, groups of fragments grow, and one that reaches `min_size` becomes a region; stats gains `rounds`.  Two host
+        reads: the two counts that size the workspace (about 24 bytes per pixel and 32 + 16 C bytes per component) and the statistics."""
+        if merge not in ('position', 'spectrum'):
+            raise lib.DmfError('segment_regions: merge = %r is not position or spectrum' % (merge,))
         H, W = int(H), int(W)
         if not (torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.int32 and tuple(seg.shape) == (H, W)):
             raise lib.DmfError('segment_regions: seg must be an int32 GPU tensor [%d, %d]' % (H, W))
@@ -269,9 +275,24 @@ class Scene:
         with torch.cuda.device(dev):
             ws = torch.empty(lib.region_workspace_bytes(H, W, n_labels), dtype=torch.uint8, device=dev)
             lib.label_components(seg, comp, ws)
-            lib.region_merge(seg, comp, n_labels, min_size, region, sizes, stats, ws)
-            R, components, absorbed, _ = stats.tolist()
-        return region, R, sizes[:R].clone(), dict(regions=R, components=components, absorbed=absorbed)
+            if merge == 'spectrum':
+                Hp, Wp = getattr(self, 'extent', self.A.shape[:2])
+                if not (H <= Hp and W <= Wp) or self.A.device != dev:
+                    raise lib.DmfError('segment_regions: %d x %d pixels asked of a padded scene of %d x %d on %s' % (H, W, Hp, Wp, self.A.device))
+                counts = torch.empty(2, dtype=torch.int32, device=dev)
+                ws = torch.empty(lib.region_graph_workspace_bytes(H, W, 1, n_labels, 1), dtype=torch.uint8, device=dev)
+                lib.region_graph_count(seg, comp, n_labels, min_size, counts, ws)
+                components, fragments = counts.tolist()
+                ws = None                                # (the old one goes before the new one is allocated)
+                ws = torch.empty(lib.region_graph_workspace_bytes(H, W, self.A.shape[2], n_labels, components), dtype=torch.uint8, device=dev)
+                lib.region_graph_merge(seg, comp, self.A, n_labels, min_size, components, fragments, region, sizes, stats, ws)
+            else:
+                lib.region_merge(seg, comp, n_labels, min_size, region, sizes, stats, ws)
+            R, components, absorbed, rounds = stats.tolist()
+        out = dict(regions=R, components=components, absorbed=absorbed)
+        if merge == 'spectrum':
+            out['rounds'] = rounds
+        return region, R, sizes[:R].clone(), out
 
 
 class AtlasScene(Scene):

@@ -153,6 +153,9 @@ def _load():
         'dmf_label_components': (i32, [vp, i32, i32, vp, vp, i64, vp]),
         'dmf_region_merge': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
         'dmf_region_vote': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+        'dmf_region_graph_workspace_bytes': (i64, [i32, i32, i32, i32, i32]),
+        'dmf_region_graph_count': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
+        'dmf_region_graph_merge': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -1155,6 +1158,69 @@ def region_vote(prob, mask, region, R, mode, regprob, regcount, label_map, works
     _region_check('dmf_region_vote', _lib.dmf_region_vote(_ptr(prob), _ptr(mask), _ptr(region), H, W, K, R, VOTE_MODES[mode], _ptr(regprob),
                                                          _ptr(regcount), _ptr(label_map), _ptr(prob_out), _ptr(workspace), workspace.numel(),
                                                          _stream()))
+
+
+# the entry points of csrc/dmf_region_graph.hip, which report by code (include/dmf.h)
+_REGION_GRAPH_ERRORS = dict(_REGION_ERRORS)
+_REGION_GRAPH_ERRORS.update({2: 'H, W and C must be >= 1', 5: 'elem_bytes must be 2 or 4', 6: 'pitch_pixels < W', 13: 'too many pixels: H W < 2^27',
+                             16: 'components outside 1..H W, or fragments outside 0..components - 1'})
+
+
+def _region_graph_check(entry, rc):
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, _REGION_GRAPH_ERRORS.get(rc, 'error %d' % rc)))
+
+
+def region_graph_workspace_bytes(H, W, Cn=1, n_labels=0, components=1):
+    """The bytes dmf_region_graph_merge needs for `components` components of a C-band scene; with Cn = 1 and components = 1 the
+    bytes of region_graph_count."""
+    n = _lib.dmf_region_graph_workspace_bytes(H, W, Cn, n_labels, components)
+    if n < 0:
+        raise DmfError('dmf_region_graph_workspace_bytes: H, W, C >= 1, n_labels >= 0, H W < 2^27 and 1 <= components <= H W')
+    return n
+
+
+def region_graph_count(labels, comp, n_labels, min_size, counts, workspace):
+    """counts [2] int32 <- the number of components of comp [H, W] (as label_components leaves it) and the number of fragments
+    among them: smaller than min_size, not the main component of a label in 0..n_labels - 1, not at pixel 0
+    (dmf_region_graph_count).  `workspace`: a uint8 tensor of region_graph_workspace_bytes(H, W, 1, n_labels, 1) bytes."""
+    _dev(labels, torch.int32, 'labels')
+    if labels.dim() != 2:
+        raise DmfError('region_graph_count wants labels [H, W]')
+    H, W = labels.shape
+    _whole('region_graph_count', 'n_labels', n_labels, 0); _whole('region_graph_count', 'min_size', min_size, 1)
+    _segment_tensor('region_graph_count', comp, torch.int32, (H, W), 'comp', labels.device)
+    _segment_tensor('region_graph_count', counts, torch.int32, (2,), 'counts', labels.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    _region_graph_check('dmf_region_graph_count', _lib.dmf_region_graph_count(_ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(counts),
+                                                                              _ptr(workspace), workspace.numel(), _stream()))
+
+
+def region_graph_merge(labels, comp, scene, n_labels, min_size, components, fragments, region, region_size, stats, workspace):
+    """region [H, W] int32 <- the dense id of every pixel's region after the spectrum-aware merge: every fragment joins the adjacent
+    group with the nearest mean spectrum of the leading [H, W] pixels of scene [>= H, pitch >= W, C] (fp32 or fp16), groups of
+    fragments grow and one that reaches min_size becomes a region; region_size [H W] int32 <- the regions' pixel counts in the
+    first R cells, 0 in the others; stats [4] int32 <- R, components, components - R, rounds (dmf_region_graph_merge).
+    `components` and `fragments` are what region_graph_count left; `workspace`: a uint8 tensor of
+    region_graph_workspace_bytes(H, W, C, n_labels, components) bytes."""
+    _dev(labels, torch.int32, 'labels')
+    if labels.dim() != 2:
+        raise DmfError('region_graph_merge wants labels [H, W]')
+    H, W = labels.shape
+    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
+        raise DmfError('region_graph_merge: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor')
+    if H > scene.shape[0] or W > scene.shape[1] or scene.device != labels.device:
+        raise DmfError('region_graph_merge: %d x %d pixels asked of a scene of %d x %d on %s' % (H, W, scene.shape[0], scene.shape[1], scene.device))
+    _whole('region_graph_merge', 'n_labels', n_labels, 0); _whole('region_graph_merge', 'min_size', min_size, 1)
+    _whole('region_graph_merge', 'components', components, 1); _whole('region_graph_merge', 'fragments', fragments, 0)
+    _segment_tensor('region_graph_merge', comp, torch.int32, (H, W), 'comp', labels.device)
+    _segment_tensor('region_graph_merge', region, torch.int32, (H, W), 'region', labels.device)
+    _segment_tensor('region_graph_merge', region_size, torch.int32, (H * W,), 'region_size', labels.device)
+    _segment_tensor('region_graph_merge', stats, torch.int32, (4,), 'stats', labels.device)
+    _dev(workspace, torch.uint8, 'workspace')
+    _region_graph_check('dmf_region_graph_merge', _lib.dmf_region_graph_merge(
+        _ptr(labels), _ptr(comp), _ptr(scene), scene.element_size(), scene.shape[1], H, W, scene.shape[2], n_labels, min_size, components,
+        fragments, _ptr(region), _ptr(region_size), _ptr(stats), _ptr(workspace), workspace.numel(), _stream()))
 
 
 # return codes of the two entry points of csrc/dmf_pca.hip, which report by code (include/dmf.h)

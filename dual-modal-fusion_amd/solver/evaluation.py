@@ -33,6 +33,8 @@ EvalEngine.segment_vote (dmf_slic_* / dmf_segment_vote); drop-in path: utils/seg
 segment image (SLIC's, or the file's) becomes connected regions, small fragments join the component before them, and the vote runs
 over the regions (Scene.segment_regions, EvalEngine.region_vote: dmf_label_components / dmf_region_merge / dmf_region_vote; drop-in
 path: utils.segments.regions / region_vote, the same integers); `<t>_segments.npy` then holds the region image.
+`test.segment_merge: spectrum` sends every fragment to the adjacent group with the nearest mean spectrum and lets groups
+of fragments grow into regions (dmf_region_graph_count / dmf_region_graph_merge; drop-in path: utils.segments.region_graph).
 """
 import itertools
 
@@ -107,7 +109,7 @@ class EngineEvaluation(_Evaluation):
             seg, n_labels = torch.from_numpy(segments.load_segment_file(rk['file'], H, W)).to(prob.device), 0
         else:
             seg, n_labels = self.s.scene.segments(H, W, k['size'], k['compactness'], k['iterations'])[0], int(np.prod(segments.grid(H, W, k['size'])))
-        region, R, sizes, stats = self.s.scene.segment_regions(seg, H, W, n_labels, rk['min_size'])
+        region, R, sizes, stats = self.s.scene.segment_regions(seg, H, W, n_labels, rk['min_size'], merge=rk.get('merge', 'position'))
         voted = eng.region_vote(prob, mask, region, R, k['vote'])[2].cpu().numpy()
         return None, region.cpu().numpy(), voted, dict(stats, sizes=sizes.cpu().numpy(), raw=seg.cpu().numpy())
 
@@ -198,7 +200,10 @@ class DropinEvaluation(_Evaluation):
             seg, n_labels = segments.load_segment_file(rk['file'], H, W), 0
         else:
             seg, n_labels = segments.slic(scene, H, W, k['size'], k['compactness'], k['iterations'])[0], int(np.prod(segments.grid(H, W, k['size'])))
-        region, sizes, stats = segments.regions(seg, n_labels, rk['min_size'])
+        if rk.get('merge') == 'spectrum':                    # (the same integers and double operations as the device's)
+            region, sizes, stats = segments.region_graph(seg, scene, n_labels, rk['min_size'])
+        else:
+            region, sizes, stats = segments.regions(seg, n_labels, rk['min_size'])
         voted = segments.region_vote(prob, mask, region, stats['regions'], k['vote'])[2]
         return plain, region, voted, dict(stats, sizes=sizes, raw=seg)
 

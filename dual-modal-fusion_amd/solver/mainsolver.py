@@ -112,6 +112,7 @@ class Solver(BaseSolver):
     calib, spat = calib.calibration_keys({}), spatial.spatial_keys({})     # (the constructor reads them from cfg; these: neutral)
     segm = segments.segment_keys({})                     # (likewise)
     regn = segments.region_keys({}, segm)                # (likewise: test.segment_connectivity / _min_size / _file)
+    merge = 'position'                                   # (likewise: test.segment_merge)
     evaluation = None                                    # solver.evaluation's class of this run's path (`_ensure_model`)
     device_schedule, scheduler_unit, _step_groups = False, 'epoch', None      # (the constructor reads them from cfg['schedule'])
 
@@ -146,6 +147,7 @@ class Solver(BaseSolver):
             raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)
         self.regn = segments.region_keys(cfg, self.segm)   # test.segment_connectivity / segment_min_size / segment_file
+        self.merge = segments.merge_key(cfg, self.regn)    # test.segment_merge
         self.spatial, self._spatial_maps = None, None  # test()'s regularisation block; the whole-scene maps of the loaded weights
         self.segments, self._segment_maps = None, None # test()'s superpixel block; the whole-scene maps of the loaded weights
         self.calibration, self._temp = None, None      # test()'s calibration block; (T, fit block or None) once it is known
@@ -853,7 +855,8 @@ class Solver(BaseSolver):
         if self._segment_maps is None or self._segment_maps[0] != bool(best):
             size = self.cfg['DATA_DICT'][self.cfg['data_city']]['size']
             beta = self._beta(self._temperature_used()[0])
-            self._segment_maps = (bool(best), self.evaluation.scene_segments(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.segm, self.regn))
+            self._segment_maps = (bool(best), self.evaluation.scene_segments(self._scene_pixels(), int(size[0]), int(size[1]), beta, self.segm,
+                                                                             dict(self.regn, merge=self.merge)))
         return self._segment_maps[1]
 
     def _segment(self, whole):

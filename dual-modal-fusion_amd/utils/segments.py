@@ -8,13 +8,16 @@ the smallest D = mean_c (a_c - mu_c)^2 + (compactness / S)^2 |x - centre|^2, the
 then takes the class of its segment: of the mean probability of the segment's classified pixels, or of their majority.
 Connectivity is not enforced by SLIC itself; `test.segment_connectivity: 1` splits the segments into their
 4-connected components, joins small fragments to the component before them and votes over the regions: `components`, `regions` and
-`region_vote` below are that arithmetic in integers.  `test.segments: file` votes over the components of a user's label image."""
+`region_vote` below are that arithmetic in integers.  `test.segments: file` votes over the components of a user's label image.
+`test.segment_merge: spectrum` joins a fragment to the adjacent group with the nearest mean spectrum and lets groups
+of fragments grow into regions: `region_graph`, the integers and double operations of dmf_region_graph_merge."""
 import math
 
 import numpy as np
 
 KINDS = ('none', 'slic', 'file')
 VOTES = ('mean', 'majority')
+MERGES = ('position', 'spectrum')
 SIZE_MIN, SIZE_MAX = 4, 32
 
 
@@ -79,6 +82,20 @@ def region_keys(cfg, keys):
     if ms is None:
         ms = max(1, keys['size'] ** 2 // 4) if keys['kind'] == 'slic' else 1
     return dict(connectivity=bool(con), min_size=ms, file=path if keys['kind'] == 'file' else None)
+
+
+def merge_key(cfg, region):
+    """-> 'position' or 'spectrum' from the optional key, given `region_keys`' dict
+         test.segment_merge position / spectrum (default position): where a fragment goes
+    spectrum is valid only where regions are made: test.segment_connectivity: 1 or test.segments: file."""
+    given = (cfg.get('test') or {}).get('segment_merge', 'position')
+    merge = 'position' if given is None else str(given).lower()
+    if merge not in MERGES:
+        raise ValueError('test.segment_merge %r is not one of %s' % (given, ' / '.join(MERGES)))
+    if merge != 'position' and not region['connectivity']:
+        raise ValueError('test.segment_merge: %s merges the fragments of test.segment_connectivity: 1 or test.segments: file; '
+                         'neither is set' % merge)
+    return merge
 
 
 def keys_in_use(keys):
@@ -247,6 +264,81 @@ def regions(labels, n_labels=0, min_size=1):
             dict(regions=R, components=int(roots.size), absorbed=int(frag.size)))
 
 
+def region_graph(labels, scene, n_labels=0, min_size=1):
+    """-> (region [H, W] int32, region sizes [R] int32, dict(regions, components, absorbed, rounds)): the components of `labels`
+    with the spectrum-aware merge of dmf_region_graph_merge (include/dmf.h) on the leading [H, W] pixels of `scene`
+    [>= H, >= W, C] (fp32, or fp16 widened exactly).  A component's feature is the 64-bit integer sum of its pixels' quantised
+    values; every component starts as a group, kept by `regions`' rule.  In a round every group that is not kept chooses, among the
+    groups that share a 4-neighbour pixel pair with it, the smallest (squared distance of the mean spectra in double, id), on the
+    state at the start of the round; all pairs (group, choice) are united; sums and counts add, and the new group is kept when a
+    member was or its count reaches min_size.  Regions are numbered in ascending order of their smallest roots."""
+    lab = np.asarray(labels)
+    H, W = lab.shape
+    if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 1 or int(n_labels) != n_labels or n_labels < 0:
+        raise ValueError('region_graph: min_size >= 1 and n_labels >= 0 are whole numbers')
+    a = np.asarray(scene)[:H, :W]
+    if a.ndim != 3 or a.shape[:2] != (H, W) or a.shape[2] < 1:
+        raise ValueError('region_graph: the scene must hold [%d, %d] pixels of C >= 1 bands' % (H, W))
+    comp = components(lab).ravel().astype(np.int64)
+    flat = lab.ravel()
+    is_root = comp == np.arange(H * W)
+    roots = np.nonzero(is_root)[0]
+    n = roots.size
+    count = np.bincount(comp, minlength=H * W)[roots]
+    kept = count >= min_size
+    kept[0] = True                                       # (root 0 is component 0)
+    named = np.nonzero((flat[roots] >= 0) & (flat[roots] < n_labels))[0]
+    if named.size:
+        order = np.lexsort((named, -count[named], flat[roots][named]))      # by label, the largest first, then the smaller root
+        first = np.concatenate([[True], np.diff(flat[roots][named][order]) != 0])
+        kept[named[order][first]] = True
+    index = (np.cumsum(is_root) - 1)[comp].reshape(H, W)  # the dense component index of every pixel: ascending = ascending root
+    sums = np.zeros((n, a.shape[2]), dtype=np.int64)
+    np.add.at(sums, index.ravel(), quantise(a.astype(np.float32).reshape(H * W, -1)))
+    ea = np.concatenate([index[:, 1:].ravel(), index[1:, :].ravel()])
+    eb = np.concatenate([index[:, :-1].ravel(), index[:-1, :].ravel()])
+    edges = np.unique(np.stack([ea, eb], 1)[ea != eb], axis=0)
+    group, rounds = np.arange(n), 0
+    while not kept[np.unique(group)].all():
+        rounds += 1
+        f, g = group[edges[:, 0]], group[edges[:, 1]]
+        pairs = np.concatenate([np.stack([f, g], 1), np.stack([g, f], 1)])
+        pairs = np.unique(pairs[(pairs[:, 0] != pairs[:, 1]) & ~kept[pairs[:, 0]]], axis=0)
+        mean = sums.astype(np.float64) / (count.astype(np.float64) * float(1 << QBITS))[:, None]
+        d = np.zeros(len(pairs))
+        for b in range(sums.shape[1]):                   # one subtraction, one product, one addition at a time: nothing contracted
+            t = mean[pairs[:, 0], b] - mean[pairs[:, 1], b]
+            d = d + t * t
+        order = np.lexsort((pairs[:, 1], d, pairs[:, 0]))
+        first = np.concatenate([[True], np.diff(pairs[order, 0]) != 0])
+        cf, cg = pairs[order][first, 0], pairs[order][first, 1]
+        p = np.arange(n)
+        while True:                                      # hooking to the smaller index and pointer jumping, as `components`
+            pa, pb = p[cf], p[cg]
+            differ = pa != pb
+            if not differ.any():
+                break
+            np.minimum.at(p, np.maximum(pa, pb)[differ], np.minimum(pa, pb)[differ])
+            while True:
+                pp = p[p]
+                if np.array_equal(pp, p):
+                    break
+                p = pp
+        ids = np.unique(group)
+        gone = ids[p[ids] != ids]
+        np.add.at(sums, p[gone], sums[gone])
+        np.add.at(count, p[gone], count[gone])
+        np.logical_or.at(kept, p[gone], kept[gone])
+        group = p[group]
+        ids = np.unique(group)
+        kept[ids] |= count[ids] >= min_size
+    ids = np.unique(group)
+    region = np.searchsorted(ids, group)[index]
+    R = int(ids.size)
+    return (region.astype(np.int32), np.bincount(region.ravel(), minlength=R).astype(np.int32),
+            dict(regions=R, components=int(n), absorbed=int(n) - R, rounds=rounds))
+
+
 def quantise(prob):
     """int64: rint(clamp(p, 0, 1) 2^36), half to even, a NaN as 0."""
     p = np.asarray(prob, dtype=np.float32).astype(np.float64)
@@ -297,6 +389,8 @@ def region_report(block, min_size, stats, region_sizes):
     out = dict(block)
     out.update(connectivity='enforced', min_size=int(min_size), components=int(stats['components']), absorbed=int(stats['absorbed']),
                regions=int(stats['regions']), region_pixels=dict(min=int(sizes.min()), mean=float(sizes.mean()), max=int(sizes.max())))
+    if 'rounds' in stats:                                # test.segment_merge: spectrum
+        out.update(merge='spectrum', rounds=int(stats['rounds']))
     return out
 
 

@@ -738,6 +738,55 @@ int32_t dmf_region_vote(const float* prob, const uint8_t* mask, const int32_t* r
                         int32_t mode, float* regprob /* [R][K] */, int32_t* regcount /* [R] */, int32_t* label_map /* [H W] */,
                         float* prob_out /* nullable */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- connected superpixels, the spectrum-aware fragment merge: dmf_region_merge's positional target replaced by
+ * the adjacent group with the nearest mean spectrum, with groups of fragments that grow until they reach min_size (a Boruvka
+ * style merge over the region adjacency graph).  New symbols at an unchanged DMF_VERSION: detect them by name.  All sums are
+ * integers and every double operation is rounded on its own, so no order of execution can change a bit.
+ *   inputs      labels [H][W] int32 and comp as dmf_label_components leaves it; the scene as dmf_slic_* take it (the leading
+ *               H x W pixels of the resident padded primary scene, pitch_pixels, C bands, fp32, or fp16 widened exactly); n_labels
+ *               and min_size as in dmf_region_merge.  H W < DMF_REGION_VOTE_PIXELS_MAX, as for the vote.
+ *   features    every scene value a gives q = rint(clamp(a, 0, 1) 2^36), half to even, a NaN counted as 0: dmf_region_vote's
+ *               quantiser.  sum[r][b] = the 64-bit integer sum of q over the pixels of component r, n[r] its pixel count.
+ *   groups      every component starts as a group of its own, kept by the rule of dmf_region_merge unchanged (size >= min_size, or
+ *               the main component of a label in 0..n_labels - 1, or root 0).  A group's id is the smallest root among its
+ *               components; a group is active while it is not kept.
+ *   round       all choices use the state at the start of the round.  Every active group f looks at every group g != f that
+ *               shares a 4-neighbour pixel pair with it.  m_f[b] = (double)sum_f[b] / ((double)n_f 2^36) (the conversion rounding
+ *               to nearest even, the divisor exact); d(f, g) = sum_b (m_f[b] - m_g[b])^2 in double from 0, the bands in ascending
+ *               order, each subtraction, product and addition rounded on its own (nothing contracted).  f chooses the g with the
+ *               smallest (d, id of g), compared lexicographically; then every pair (f, choice(f)) is united.  Kept groups choose
+ *               nothing, so a united group holds at most one group that was kept at the start of the round: two kept regions never
+ *               merge.  Sums and counts add exactly; the new group is kept if a member was kept or its count >= min_size; its id
+ *               is the smallest root in it.
+ *   end         rounds repeat until no group is active.  Every active group is united with another, so the active groups at least
+ *               halve per round: at most 1 + floor(log2(fragments)) rounds, fragments = the initially active groups.  Root 0 is
+ *               kept and the image is connected, so the process ends.
+ *   result      regions numbered 0..R - 1 in ascending order of group id.  region [H][W] int32; region_size [H W] int32: the first R
+ *               cells the pixel counts, the others 0; stats [4] int32 = R, the number of components, components - R, the rounds
+ *               run.  With min_size = 1 nothing is active: region, region_size and the first three statistics equal
+ *               dmf_region_merge's at min_size = 1.
+ *   calls       dmf_region_graph_count leaves counts [2] int32 = the number of components and of fragments; the caller reads them
+ *               (the one host read), sizes the workspace with them and hands them to dmf_region_graph_merge, which enqueues
+ *               1 + floor(log2(fragments)) rounds (a round that finds no active group does nothing) and reads nothing itself.
+ *               `comp`, `components` and `fragments` must be what dmf_label_components and the count left: with other contents the
+ *               regions are unspecified, but nothing is read or written out of range and every loop ends.
+ *   workspace   dmf_region_graph_workspace_bytes(H, W, C, n_labels, components) bytes, 16-byte aligned; -1 for an argument out of
+ *               range; sums and means are indexed by component and cost 16 C bytes each.  The count needs the bytes of
+ *               (H, W, 1, n_labels, 1).  What a workspace holds between calls does not matter.
+ * Return codes, all before any launch (and so with every output as it was), numbered as above: 1 a NULL pointer; 2 H, W or C < 1;
+ * 5 elem_bytes not 2 or 4; 6 pitch_pixels < W; 7 an output or the workspace overlaps an input, or two of them each other; 8 a
+ * pointer not aligned to its type (the scene to elem_bytes) or the workspace not to 16 bytes (every grid fits: H W < 2^27);
+ * 9 a launch itself failed; 12 workspace_bytes too small; 13 H W >= DMF_REGION_VOTE_PIXELS_MAX; 14 min_size < 1; 15 n_labels < 0;
+ * 16 components outside 1..H W or fragments outside 0..components - 1.  (They do not set the text of dmf_last_error.) */
+#define DMF_REGION_GRAPH_ROUNDS_MAX 27          /* fragments < 2^27 */
+int64_t dmf_region_graph_workspace_bytes(int32_t H, int32_t W, int32_t C, int32_t n_labels, int32_t components);
+int32_t dmf_region_graph_count(const int32_t* labels, const int32_t* comp, int32_t H, int32_t W, int32_t n_labels, int32_t min_size,
+                               int32_t* counts /* [2] */, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t dmf_region_graph_merge(const int32_t* labels, const int32_t* comp, const void* scene, int32_t elem_bytes, int32_t pitch_pixels,
+                               int32_t H, int32_t W, int32_t C, int32_t n_labels, int32_t min_size, int32_t components,
+                               int32_t fragments, int32_t* region /* [H W] */, int32_t* region_size /* [H W] */,
+                               int32_t* stats /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

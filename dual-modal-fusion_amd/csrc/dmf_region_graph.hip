@@ -1,6 +1,8 @@
 // dmf_region_graph.hip — connected superpixels, the spectrum-aware fragment merge: fragments join the adjacent
 // group with the nearest mean spectrum, groups of fragments grow, and a group that reaches min_size becomes a region (a Boruvka
-// style merge over the region adjacency graph).  include/dmf.h states the arithmetic.
+// style merge over the region adjacency graph).  include/dmf.h states the arithmetic.  The union-find, the runs of a wave, the
+// scan, comp's range check, DESIGN.md 24's kept rule, the quantiser and the host helpers are dmf_region_prims.h's, shared with
+// dmf_regions.hip; gm_size_kernel, gm_main_kernel and the two scan kernels wrap its bodies.
 //   gm_zero_kernel         sizes, region sizes, per-label maxima, statistics, round counters and the feature sums start at 0
 //   gm_size_kernel         size[root] by integer atomics, one per run of equal roots in a wave
 //   gm_main_kernel         per label the 64-bit atomicMax of (size, complement of root): its main component
@@ -24,74 +26,21 @@
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_region_prims.h"
 
 namespace dmf {
 namespace gm {
 
-constexpr int SCAN = 4;                    // consecutive cells per thread of the scan
-constexpr int SCAN_BLOCK = 256 * SCAN;
-constexpr int QBITS = 36;                  // q = rint(clamp(a, 0, 1) 2^36): dmf_region_vote's fixed point
 constexpr int ROUNDS_MAX = DMF_REGION_GRAPH_ROUNDS_MAX;
 constexpr int NONE = 0x7fffffff;           // no choice yet
 
-using u64 = unsigned long long;
+// Pixel 0 is a root whatever comp holds (dmf_regions.hip lets comp decide there too).
+__device__ __forceinline__ bool gm_is_root(const int32_t* comp, int64_t x, int64_t pixels) { return x == 0 || comp_root(comp, x, pixels) == (int)x; }
 
-// ------------------------------------------------------------------------------ union-find (as dmf_regions.hip's)
-// A parent cell only ever decreases, and every value it held is a member of the same set.  A read that another XCD's L2 serves
-// late yields an earlier parent; the atomicMin on that node returns what the cell really holds, and the loop goes on from there.
-__device__ __forceinline__ int uf_load(const int* p, int64_t a) { return __hip_atomic_load(p + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(const int* p, int a) {
-  for (int up = uf_load(p, a); up != a; up = uf_load(p, a)) a = up;
-  return a;
-}
-
-__device__ __forceinline__ void uf_unite(int* p, int a, int b) {
-  a = uf_find(p, a);
-  b = uf_find(p, b);
-  while (a != b) {
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(p + a, b);
-    if (old == a) break;
-    a = old;
-  }
-}
-
-// ------------------------------------------------------------------------------ runs of equal keys in a wave
-__device__ __forceinline__ bool run_head(int key, int& last) {
-  const int lane = threadIdx.x & 63;
-  const int before = __shfl_up(key, 1);
-  const bool head = lane == 0 || before != key;
-  const u64 heads = __ballot(head);
-  const u64 above = lane == 63 ? 0ull : heads >> (lane + 1);
-  last = above ? lane + (__ffsll(above) - 1) : 63;
-  return head;
-}
-
-__device__ __forceinline__ long long run_sum(long long v, int last) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int lo = __shfl_down((int)(v & 0xffffffffll), d);
-    const int hi = __shfl_down((int)(v >> 32), d);
-    if (lane + d <= last) v += (long long)(((u64)(unsigned)hi << 32) | (unsigned)lo);
-  }
-  return v;
-}
-
-// comp as the merge reads it: a value outside the image stands for the pixel itself; pixel 0 is a root whatever comp holds.
-__device__ __forceinline__ int gm_root(const int32_t* comp, int64_t x, int64_t pixels) {
-  const int c = comp[x];
-  return (unsigned)c < (u64)pixels ? c : (int)x;
-}
-
-__device__ __forceinline__ bool gm_is_root(const int32_t* comp, int64_t x, int64_t pixels) { return x == 0 || gm_root(comp, x, pixels) == (int)x; }
-
-__device__ __forceinline__ u64 gm_key(int size, int root) { return ((u64)(unsigned)size << 32) | (unsigned)~root; }
-
-// The dense component index of pixel x: the scanned flag at its root, held inside 0..n - 1 (n >= 1) whatever comp holds.
+// The dense component index of pixel x: the scanned flag at its root, held inside 0..n - 1 (n >= 1) whatever comp holds
+// (dmf_regions.hip's rg_final_kernel reads the same cells without the clamp).
 __device__ __forceinline__ int gm_index(const int32_t* comp, const int32_t* prefix, const int32_t* sums, int64_t x, int64_t pixels, int n) {
-  const int r = gm_root(comp, x, pixels);
+  const int r = comp_root(comp, x, pixels);
   const int c = prefix[r] + sums[r / SCAN_BLOCK];
   return c < 0 ? 0 : (c < n ? c : n - 1);
 }
@@ -101,15 +50,8 @@ __device__ __forceinline__ int gm_ncomp(const int32_t* ncell, int cap) {
   return n < 1 ? 1 : (n < cap ? n : cap);
 }
 
-__device__ __forceinline__ long long gm_quantise(float a) {
-  const float in = a > 0.f ? (a < 1.f ? a : 1.f) : 0.f;              // a NaN counts as 0
-  return (long long)rintf(in * (float)(1ll << QBITS));              // (a power of two: the product is exact)
-}
-
-__device__ __forceinline__ float gm_widen(float a) { return a; }
-__device__ __forceinline__ float gm_widen(__half a) { return __half2float(a); }
-
 // ------------------------------------------------------------------------------ set-up
+// (a grid-stride loop: the grid is capped at 65,536 blocks; rg_zero_kernel has one cell per thread)
 __global__ __launch_bounds__(256) void gm_zero_kernel(int64_t pixels, int n_labels, int64_t cells, int32_t* __restrict__ size,
                                                       int32_t* __restrict__ region_size, u64* __restrict__ best_label,
                                                       int32_t* __restrict__ stats, int n_stats, int32_t* __restrict__ nactive,
@@ -128,25 +70,12 @@ __global__ __launch_bounds__(256) void gm_zero_kernel(int64_t pixels, int n_labe
 }
 
 __global__ __launch_bounds__(256) void gm_size_kernel(const int32_t* __restrict__ comp, int64_t pixels, int32_t* size) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int key = x < pixels ? gm_root(comp, x, pixels) : -1;
-  int last;
-  const bool head = run_head(key, last);
-  if (head && key >= 0) atomicAdd(size + key, last - (int)(threadIdx.x & 63) + 1);
+  size_per_root(comp, pixels, size);
 }
 
 __global__ __launch_bounds__(256) void gm_main_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ comp,
                                                       const int32_t* __restrict__ size, int64_t pixels, int n_labels, u64* best_label) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= pixels || gm_root(comp, x, pixels) != (int)x) return;
-  const int l = labels[x];
-  if ((unsigned)l < (unsigned)n_labels) atomicMax(best_label + l, gm_key(size[x], (int)x));
-}
-
-// DESIGN.md 24's rule, unchanged: size >= min_size, or the main component of a label in 0..n_labels - 1, or root 0.
-__device__ __forceinline__ bool gm_kept(const int32_t* labels, const int32_t* size, const u64* best_label, int64_t x, int n_labels, int min_size) {
-  const int l = labels[x], n = size[x];
-  return n >= min_size || x == 0 || ((unsigned)l < (unsigned)n_labels && best_label[l] == gm_key(n, (int)x));
+  main_per_label(labels, comp, size, pixels, n_labels, best_label);
 }
 
 __global__ __launch_bounds__(256) void gm_count_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ comp,
@@ -156,7 +85,7 @@ __global__ __launch_bounds__(256) void gm_count_kernel(const int32_t* __restrict
   bool root = false, kept = false;
   if (x < pixels) {
     root = gm_is_root(comp, x, pixels);
-    kept = root && gm_kept(labels, size, best_label, x, n_labels, min_size);
+    kept = root && kept_rule(labels, size, best_label, x, n_labels, min_size);
   }
   const u64 roots = __ballot(root), frags = __ballot(root && !kept);
   if ((threadIdx.x & 63) == 0) {
@@ -170,55 +99,12 @@ __global__ __launch_bounds__(256) void gm_flag_kernel(const int32_t* __restrict_
   if (x < pixels) flag[x] = gm_is_root(comp, x, pixels) ? 1 : 0;
 }
 
-__device__ __forceinline__ int block_scan(int v, int* cell, int& total) {
-  const int t = threadIdx.x;
-  cell[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int add = t >= d ? cell[t - d] : 0;
-    __syncthreads();
-    cell[t] += add;
-    __syncthreads();
-  }
-  const int incl = cell[t];
-  total = cell[255];
-  __syncthreads();
-  return incl - v;
-}
-
-// flag [cells] becomes its exclusive prefix inside every block of SCAN_BLOCK cells; sums[b] = the block's total.
 __global__ __launch_bounds__(256) void gm_scan_kernel(int32_t* flag, int64_t cells, int32_t* __restrict__ sums) {
-  __shared__ int cell[256];
-  const int64_t x0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * SCAN;
-  int f[SCAN], mine = 0;
-#pragma unroll
-  for (int e = 0; e < SCAN; ++e) {
-    f[e] = x0 + e < cells ? flag[x0 + e] : 0;
-    mine += f[e];
-  }
-  int total;
-  int run = block_scan(mine, cell, total);
-#pragma unroll
-  for (int e = 0; e < SCAN; ++e) {
-    if (x0 + e < cells) flag[x0 + e] = run;
-    run += f[e];
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+  DMF_SCAN_IN_BLOCKS(flag, cells, sums);
 }
 
-// One workgroup: sums [blocks] becomes its exclusive prefix; total[0] = the sum of all.
 __global__ __launch_bounds__(256) void gm_scan_blocks_kernel(int32_t* sums, int64_t blocks, int32_t* __restrict__ total_out) {
-  __shared__ int cell[256];
-  int carry = 0;
-  for (int64_t b0 = 0; b0 < blocks; b0 += 256) {
-    const int64_t b = b0 + threadIdx.x;
-    const int v = b < blocks ? sums[b] : 0;
-    int total;
-    const int before = block_scan(v, cell, total);
-    if (b < blocks) sums[b] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) total_out[0] = carry;
+  scan_block_totals(sums, blocks, total_out);
 }
 
 __global__ __launch_bounds__(256) void gm_init_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ comp,
@@ -234,7 +120,7 @@ __global__ __launch_bounds__(256) void gm_init_kernel(const int32_t* __restrict_
   const int c = prefix[x] + sums[x / SCAN_BLOCK];
   if ((unsigned)c >= (unsigned)gm_ncomp(ncell, cap)) return;
   gn[c] = size[x];
-  kept[c] = gm_kept(labels, size, best_label, x, n_labels, min_size) ? 1 : 0;
+  kept[c] = kept_rule(labels, size, best_label, x, n_labels, min_size) ? 1 : 0;
   gpa[c] = c;
 }
 
@@ -253,7 +139,7 @@ __global__ __launch_bounds__(256) void gm_sums_kernel(const T* __restrict__ scen
   const int i = (int)(px / W), j = (int)(px - (int64_t)i * W);
   const T* row = scene + ((int64_t)i * pitch + j) * C;
   for (int b = 0; b < C; ++b) {
-    const long long q = key >= 0 ? gm_quantise(gm_widen(row[b])) : 0;
+    const long long q = key >= 0 ? quantise(widen(row[b])) : 0;
     const long long n = run_sum(q, last);
     if (add && n) atomicAdd(gsum + (int64_t)key * C + b, (u64)n);
   }
@@ -400,25 +286,6 @@ __global__ __launch_bounds__(256) void gm_final_kernel(const int32_t* __restrict
 }
 
 // ------------------------------------------------------------------------------ host
-static bool overlap(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-static bool any_overlap(const void* const* outs, const uint64_t* out_bytes, int n_out, const void* const* ins, const uint64_t* in_bytes, int n_in) {
-  for (int o = 0; o < n_out; ++o) {
-    for (int p = 0; p < n_in; ++p)
-      if (overlap(outs[o], out_bytes[o], ins[p], in_bytes[p])) return true;
-    for (int p = o + 1; p < n_out; ++p)
-      if (overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return true;
-  }
-  return false;
-}
-
-static unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }      // (n < 2^31: the grid holds it)
-
-static int64_t up16(int64_t n) { return (n + 15) / 16 * 16; }
-
 struct Space {                                           // the workspace, every part 16-byte aligned
   int64_t best_label, size, prefix, sums, ncell, nactive, dright, ddown, gn, kept, gpa, gpb, choice, rid, rsums, best, gsum, mean, bytes;
 };
@@ -459,13 +326,8 @@ static int rounds_of(int64_t fragments) {                // 1 + floor(log2(fragm
 }  // namespace gm
 }  // namespace dmf
 
+using namespace dmf;
 using namespace dmf::gm;
-
-#define GM_LAUNCH(kernel, grid, block, ...)                                         \
-  do {                                                                              \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);        \
-    if (hipGetLastError() != hipSuccess) return 9;                                  \
-  } while (0)
 
 extern "C" {
 
@@ -501,11 +363,11 @@ int32_t dmf_region_graph_count(const int32_t* labels, const int32_t* comp, int32
   const unsigned grid = blocks_of(pixels, 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // (counts stands in for the statistics: its two cells start at 0; no region sizes, no round counters, no sums)
-  GM_LAUNCH(gm_zero_kernel, blocks_of(zero, 256), 256, pixels, n_labels, (int64_t)0, size, (int32_t*)nullptr, best_label, counts, 2,
+  DMF_LAUNCH(gm_zero_kernel, blocks_of(zero, 256), 256, pixels, n_labels, (int64_t)0, size, (int32_t*)nullptr, best_label, counts, 2,
             (int32_t*)nullptr, (u64*)nullptr);
-  GM_LAUNCH(gm_size_kernel, grid, 256, comp, pixels, size);
-  GM_LAUNCH(gm_main_kernel, grid, 256, labels, comp, size, pixels, n_labels, best_label);
-  GM_LAUNCH(gm_count_kernel, grid, 256, labels, comp, size, best_label, pixels, n_labels, min_size, counts);
+  DMF_LAUNCH(gm_size_kernel, grid, 256, comp, pixels, size);
+  DMF_LAUNCH(gm_main_kernel, grid, 256, labels, comp, size, pixels, n_labels, best_label);
+  DMF_LAUNCH(gm_count_kernel, grid, 256, labels, comp, size, best_label, pixels, n_labels, min_size, counts);
   return 0;
 }
 
@@ -534,7 +396,7 @@ int32_t dmf_region_graph_merge(const int32_t* labels, const int32_t* comp, const
   const void* outs[4] = {region, region_size, stats, workspace};
   const uint64_t out_bytes[4] = {plane, plane, 4 * sizeof(int32_t), (uint64_t)s.bytes};
   const void* ins[3] = {labels, comp, scene};
-  const uint64_t in_bytes[3] = {plane, plane, (((uint64_t)H - 1) * pitch_pixels + W) * C * elem_bytes};
+  const uint64_t in_bytes[3] = {plane, plane, scene_bytes(elem_bytes, pitch_pixels, H, W, C)};
   if (any_overlap(outs, out_bytes, 4, ins, in_bytes, 3)) return 7;
   char* base = static_cast<char*>(workspace);
   u64* best_label = reinterpret_cast<u64*>(base + s.best_label);
@@ -563,30 +425,30 @@ int32_t dmf_region_graph_merge(const int32_t* labels, const int32_t* comp, const
   const int64_t zero_blocks = (zero + 255) / 256;
   const unsigned grid = blocks_of(pixels, 256), grid_c = blocks_of(cap, 256), grid_w = blocks_of(cap, 4);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  GM_LAUNCH(gm_zero_kernel, (unsigned)(zero_blocks < 65536 ? zero_blocks : 65536), 256, pixels, n_labels, cells, size, region_size, best_label, stats,
+  DMF_LAUNCH(gm_zero_kernel, (unsigned)(zero_blocks < 65536 ? zero_blocks : 65536), 256, pixels, n_labels, cells, size, region_size, best_label, stats,
             4, nactive, gsum);
-  GM_LAUNCH(gm_size_kernel, grid, 256, comp, pixels, size);
-  GM_LAUNCH(gm_main_kernel, grid, 256, labels, comp, size, pixels, n_labels, best_label);
-  GM_LAUNCH(gm_flag_kernel, grid, 256, comp, pixels, prefix);
-  GM_LAUNCH(gm_scan_kernel, (unsigned)scan_blocks, 256, prefix, pixels, sums);
-  GM_LAUNCH(gm_scan_blocks_kernel, 1, 256, sums, scan_blocks, ncell);
-  GM_LAUNCH(gm_init_kernel, grid, 256, labels, comp, size, best_label, prefix, sums, ncell, cap, pixels, n_labels, min_size, gn, kept, gpa, stats);
+  DMF_LAUNCH(gm_size_kernel, grid, 256, comp, pixels, size);
+  DMF_LAUNCH(gm_main_kernel, grid, 256, labels, comp, size, pixels, n_labels, best_label);
+  DMF_LAUNCH(gm_flag_kernel, grid, 256, comp, pixels, prefix);
+  DMF_LAUNCH(gm_scan_kernel, (unsigned)scan_blocks, 256, prefix, pixels, sums);
+  DMF_LAUNCH(gm_scan_blocks_kernel, 1, 256, sums, scan_blocks, ncell);
+  DMF_LAUNCH(gm_init_kernel, grid, 256, labels, comp, size, best_label, prefix, sums, ncell, cap, pixels, n_labels, min_size, gn, kept, gpa, stats);
   if (elem_bytes == 4)
-    GM_LAUNCH(gm_sums_kernel<float>, grid, 256, static_cast<const float*>(scene), pitch_pixels, W, C, comp, prefix, sums, ncell, cap, pixels, gsum);
+    DMF_LAUNCH(gm_sums_kernel<float>, grid, 256, static_cast<const float*>(scene), pitch_pixels, W, C, comp, prefix, sums, ncell, cap, pixels, gsum);
   else
-    GM_LAUNCH(gm_sums_kernel<__half>, grid, 256, static_cast<const __half*>(scene), pitch_pixels, W, C, comp, prefix, sums, ncell, cap, pixels, gsum);
+    DMF_LAUNCH(gm_sums_kernel<__half>, grid, 256, static_cast<const __half*>(scene), pitch_pixels, W, C, comp, prefix, sums, ncell, cap, pixels, gsum);
   const int rounds = rounds_of(fragments);               // <= ROUNDS_MAX: fragments < 2^27
   for (int k = 0; k < rounds; ++k) {
-    GM_LAUNCH(gm_begin_kernel, grid_w, 256, ncell, cap, C, min_size, k, gpa, gpb, gn, kept, best, choice, gsum, mean, nactive, stats);
-    GM_LAUNCH(gm_pairs_kernel<0>, grid, 256, comp, prefix, sums, ncell, cap, W, pixels, C, k, nactive, gpa, kept, mean, dright, ddown, best, choice);
-    GM_LAUNCH(gm_pairs_kernel<1>, grid, 256, comp, prefix, sums, ncell, cap, W, pixels, C, k, nactive, gpa, kept, mean, dright, ddown, best, choice);
-    GM_LAUNCH(gm_unite_kernel, grid_c, 256, ncell, cap, k, nactive, gpa, kept, choice, gpb);
-    GM_LAUNCH(gm_end_kernel, grid_w, 256, ncell, cap, C, k, nactive, gpa, gpb, gn, kept, gsum);
+    DMF_LAUNCH(gm_begin_kernel, grid_w, 256, ncell, cap, C, min_size, k, gpa, gpb, gn, kept, best, choice, gsum, mean, nactive, stats);
+    DMF_LAUNCH(gm_pairs_kernel<0>, grid, 256, comp, prefix, sums, ncell, cap, W, pixels, C, k, nactive, gpa, kept, mean, dright, ddown, best, choice);
+    DMF_LAUNCH(gm_pairs_kernel<1>, grid, 256, comp, prefix, sums, ncell, cap, W, pixels, C, k, nactive, gpa, kept, mean, dright, ddown, best, choice);
+    DMF_LAUNCH(gm_unite_kernel, grid_c, 256, ncell, cap, k, nactive, gpa, kept, choice, gpb);
+    DMF_LAUNCH(gm_end_kernel, grid_w, 256, ncell, cap, C, k, nactive, gpa, gpb, gn, kept, gsum);
   }
-  GM_LAUNCH(gm_rflag_kernel, grid_c, 256, ncell, cap, gpa, rid);
-  GM_LAUNCH(gm_scan_kernel, (unsigned)rscan_blocks, 256, rid, (int64_t)cap, rsums);
-  GM_LAUNCH(gm_scan_blocks_kernel, 1, 256, rsums, rscan_blocks, stats);
-  GM_LAUNCH(gm_final_kernel, grid, 256, comp, prefix, sums, ncell, cap, pixels, gpa, rid, rsums, region, region_size, stats);
+  DMF_LAUNCH(gm_rflag_kernel, grid_c, 256, ncell, cap, gpa, rid);
+  DMF_LAUNCH(gm_scan_kernel, (unsigned)rscan_blocks, 256, rid, (int64_t)cap, rsums);
+  DMF_LAUNCH(gm_scan_blocks_kernel, 1, 256, rsums, rscan_blocks, stats);
+  DMF_LAUNCH(gm_final_kernel, grid, 256, comp, prefix, sums, ncell, cap, pixels, gpa, rid, rsums, region, region_size, stats);
   return 0;
 }
 

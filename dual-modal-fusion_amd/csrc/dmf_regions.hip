@@ -14,54 +14,26 @@
 // The entry points dmf_region_workspace_bytes, dmf_region_vote_workspace_bytes, dmf_label_components, dmf_region_merge and
 // dmf_region_vote live here too (host code at the end of the file) and report by return code, as dmf_segments.hip's do.
 // Plain HIP C++; integer atomics only, so no order of execution can change a bit.  include/dmf.h states the arithmetic.
+// The union-find, the runs of a wave, the scan, comp's range check, the kept rule, the quantiser and the host helpers are
+// dmf_region_prims.h's, shared with dmf_region_graph.hip; rg_size_kernel, rg_main_kernel and the two scan kernels wrap its bodies.
 //
-// The labelling is a union-find with links to the smaller index (Komura 2015; Playne and Hawick 2018): a parent is never larger
-// than its child, so the root of a set is its smallest raster index, which is the canonical answer whatever order the links
-// were made in.  Three launches whatever the image holds; a one-pixel spiral only makes the chains that `find` walks longer.
-// A pixel's local index inside a tile grows with its raster index, so the tile-local root is the tile's smallest raster index.
-// Lanes of a wave that hold the same key in a run of consecutive pixels combine before they touch memory (a region may be the
-// whole scene): the run's head adds the run's length, or the run's segmented sum.  All global offsets are 64-bit.  A label
-// is only compared; comp, which dmf_region_merge does index with, is range-checked on every use.
+// The labelling is the header's union-find on raster indices: the root of a component is its smallest raster index.  Three
+// launches whatever the image holds; a one-pixel spiral only makes the chains that `find` walks longer.  A pixel's local index
+// inside a tile grows with its raster index, so the tile-local root is the tile's smallest raster index.  All global offsets
+// are 64-bit.  A label is only compared; comp, which dmf_region_merge does index with, is range-checked on every use.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_region_prims.h"
 
 namespace dmf {
 
 constexpr int RG_T = 16;                   // tile edge of the local labelling; RG_T * RG_T threads
 constexpr int RG_THREADS = RG_T * RG_T;
-constexpr int RG_SCAN = 4;                 // consecutive pixels per thread of the scan
-constexpr int RG_SCAN_BLOCK = 256 * RG_SCAN;
-constexpr int RG_QBITS = 36;               // the mean vote's fixed point: q = rint(p 2^36)
 
-using u64 = unsigned long long;
-
-// ------------------------------------------------------------------------------ union-find
-// A parent cell only ever decreases, and every value it held is a pixel of the same component.  So a read that another XCD's L2
-// serves late yields an earlier parent: `find` then stops at a node that has been linked on since, the atomicMin on that node
-// returns what the cell really holds, and the loop goes on from there.  The atomics decide; the loads only shorten the way.
-__device__ __forceinline__ int uf_load(const int* p, int64_t a) { return __hip_atomic_load(p + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(const int* p, int a) {
-  for (int up = uf_load(p, a); up != a; up = uf_load(p, a)) a = up;
-  return a;
-}
-
-// a and b become one set.  The larger root is linked to the smaller by atomicMin; where another link got there first, what the
-// cell held before still has to meet b, and is smaller than a: the loop ends.
-__device__ __forceinline__ void uf_unite(int* p, int a, int b) {
-  a = uf_find(p, a);
-  b = uf_find(p, b);
-  while (a != b) {
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(p + a, b);
-    if (old == a) break;
-    a = old;
-  }
-}
-
+// ------------------------------------------------------------------------------ labelling
 __global__ __launch_bounds__(RG_THREADS) void cc_local_kernel(const int32_t* __restrict__ labels, int H, int W, int tiles_x,
                                                               int32_t* __restrict__ parent) {
   __shared__ int up[RG_THREADS];
@@ -105,39 +77,8 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(const int32_t* __restri
   comp[x] = a;
 }
 
-// ------------------------------------------------------------------------------ runs of equal keys in a wave
-// Consecutive lanes hold consecutive pixels.  -> true in the first lane of every run of equal keys; `last` = the run's last lane.
-__device__ __forceinline__ bool run_head(int key, int& last) {
-  const int lane = threadIdx.x & 63;
-  const int before = __shfl_up(key, 1);
-  const bool head = lane == 0 || before != key;
-  const u64 heads = __ballot(head);
-  const u64 above = lane == 63 ? 0ull : heads >> (lane + 1);          // the heads after this lane
-  last = above ? lane + (__ffsll(above) - 1) : 63;
-  return head;
-}
-
-// The sum of v over the lanes from this one to `last`: in a run's head, the run's sum.
-__device__ __forceinline__ long long run_sum(long long v, int last) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int lo = __shfl_down((int)(v & 0xffffffffll), d);
-    const int hi = __shfl_down((int)(v >> 32), d);
-    if (lane + d <= last) v += (long long)(((u64)(unsigned)hi << 32) | (unsigned)lo);
-  }
-  return v;
-}
-
-// comp as the merge reads it: a value outside the image stands for the pixel itself, so nothing is indexed out of range.
-__device__ __forceinline__ int rg_root(const int32_t* comp, int64_t x, int64_t pixels) {
-  const int c = comp[x];
-  return (unsigned)c < (u64)pixels ? c : (int)x;
-}
-
-__device__ __forceinline__ u64 rg_key(int size, int root) { return ((u64)(unsigned)size << 32) | (unsigned)~root; }
-
 // ------------------------------------------------------------------------------ merge
+// (one cell per thread: the grid covers them all; gm_zero_kernel strides instead)
 __global__ __launch_bounds__(256) void rg_zero_kernel(int64_t pixels, int n_labels, int32_t* __restrict__ size, int32_t* __restrict__ region_size,
                                                       u64* __restrict__ best, int32_t* __restrict__ stats) {
   const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -147,19 +88,12 @@ __global__ __launch_bounds__(256) void rg_zero_kernel(int64_t pixels, int n_labe
 }
 
 __global__ __launch_bounds__(256) void rg_size_kernel(const int32_t* __restrict__ comp, int64_t pixels, int32_t* size) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int key = x < pixels ? rg_root(comp, x, pixels) : -1;
-  int last;
-  const bool head = run_head(key, last);
-  if (head && key >= 0) atomicAdd(size + key, last - (int)(threadIdx.x & 63) + 1);
+  size_per_root(comp, pixels, size);
 }
 
 __global__ __launch_bounds__(256) void rg_main_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ comp,
                                                       const int32_t* __restrict__ size, int64_t pixels, int n_labels, u64* best) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= pixels || rg_root(comp, x, pixels) != (int)x) return;
-  const int l = labels[x];
-  if ((unsigned)l < (unsigned)n_labels) atomicMax(best + l, rg_key(size[x], (int)x));
+  main_per_label(labels, comp, size, pixels, n_labels, best);
 }
 
 __global__ __launch_bounds__(256) void rg_target_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ comp,
@@ -169,14 +103,13 @@ __global__ __launch_bounds__(256) void rg_target_kernel(const int32_t* __restric
   const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool root = false, kept = false;
   if (x < pixels) {
-    root = rg_root(comp, x, pixels) == (int)x;
+    root = comp_root(comp, x, pixels) == (int)x;         // (comp decides for pixel 0 too; gm_is_root makes it a root always)
     int to = (int)x;
     if (root) {
-      const int l = labels[x], n = size[x];
-      kept = n >= min_size || x == 0 || ((unsigned)l < (unsigned)n_labels && best[l] == rg_key(n, (int)x));
+      kept = kept_rule(labels, size, best, x, n_labels, min_size);
       if (!kept) {
         const int j = (int)(x % W);
-        to = j > 0 ? rg_root(comp, x - 1, pixels) : rg_root(comp, x - W, pixels);      // (x > 0 and column 0: a row above exists)
+        to = j > 0 ? comp_root(comp, x - 1, pixels) : comp_root(comp, x - W, pixels);      // (x > 0 and column 0: a row above exists)
       }
     }
     target[x] = to;
@@ -189,56 +122,12 @@ __global__ __launch_bounds__(256) void rg_target_kernel(const int32_t* __restric
   }
 }
 
-// -> the exclusive prefix of v over the workgroup's 256 threads; total = the sum.
-__device__ __forceinline__ int block_scan(int v, int* cell, int& total) {
-  const int t = threadIdx.x;
-  cell[t] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int add = t >= d ? cell[t - d] : 0;
-    __syncthreads();
-    cell[t] += add;
-    __syncthreads();
-  }
-  const int incl = cell[t];
-  total = cell[255];
-  __syncthreads();
-  return incl - v;
-}
-
-// flag [pixels] becomes its exclusive prefix inside every block of RG_SCAN_BLOCK pixels; sums[b] = the block's total.
 __global__ __launch_bounds__(256) void rg_scan_kernel(int32_t* flag, int64_t pixels, int32_t* __restrict__ sums) {
-  __shared__ int cell[256];
-  const int64_t x0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * RG_SCAN;
-  int f[RG_SCAN], mine = 0;
-#pragma unroll
-  for (int e = 0; e < RG_SCAN; ++e) {
-    f[e] = x0 + e < pixels ? flag[x0 + e] : 0;
-    mine += f[e];
-  }
-  int total;
-  int run = block_scan(mine, cell, total);
-#pragma unroll
-  for (int e = 0; e < RG_SCAN; ++e) {
-    if (x0 + e < pixels) flag[x0 + e] = run;
-    run += f[e];
-  }
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+  DMF_SCAN_IN_BLOCKS(flag, pixels, sums);
 }
 
-// One workgroup: sums [blocks] becomes its exclusive prefix; stats[0] = R.
 __global__ __launch_bounds__(256) void rg_scan_blocks_kernel(int32_t* sums, int64_t blocks, int32_t* __restrict__ stats) {
-  __shared__ int cell[256];
-  int carry = 0;
-  for (int64_t b0 = 0; b0 < blocks; b0 += 256) {
-    const int64_t b = b0 + threadIdx.x;
-    const int v = b < blocks ? sums[b] : 0;
-    int total;
-    const int before = block_scan(v, cell, total);
-    if (b < blocks) sums[b] = carry + before;
-    carry += total;
-  }
-  if (threadIdx.x == 0) stats[0] = carry;
+  scan_block_totals(sums, blocks, stats);                // stats[0] = R
 }
 
 __global__ __launch_bounds__(256) void rg_final_kernel(const int32_t* __restrict__ comp, const int32_t* __restrict__ target,
@@ -247,9 +136,9 @@ __global__ __launch_bounds__(256) void rg_final_kernel(const int32_t* __restrict
   const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
   int key = -1;
   if (x < pixels) {
-    int r = rg_root(comp, x, pixels);
+    int r = comp_root(comp, x, pixels);
     for (int to = target[r]; to < r; to = target[r]) r = to;           // targets are strictly smaller: the chain ends
-    key = prefix[r] + sums[r / RG_SCAN_BLOCK];
+    key = prefix[r] + sums[r / SCAN_BLOCK];              // (r is a root; gm_index clamps, this does not)
     region[x] = key;
   }
   int last;
@@ -262,16 +151,6 @@ __global__ __launch_bounds__(256) void rv_zero_kernel(int64_t cells, int R, long
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t < cells) acc[t] = 0;
   if (t < R) regcount[t] = 0;
-}
-
-__device__ __forceinline__ int first_max(const float* row, int K) {
-  float top = row[0];
-  int cls = 0;
-  for (int c = 1; c < K; ++c) {
-    const float v = row[c];
-    if (v > top) { top = v; cls = c; }                   // strict: the first maximal index
-  }
-  return cls;
 }
 
 template <int MODE>
@@ -299,13 +178,7 @@ __global__ __launch_bounds__(256) void rv_sum_kernel(const float* __restrict__ p
     }
   } else {
     for (int c = 0; c < K; ++c) {
-      long long q = 0;
-      if (key >= 0) {
-        const float p = row[c];
-        const float in = p > 0.f ? (p < 1.f ? p : 1.f) : 0.f;          // a NaN counts as 0
-        q = (long long)rintf(in * (float)(1ll << RG_QBITS));           // (a power of two: the product is exact)
-      }
-      const long long n = run_sum(q, last);
+      const long long n = run_sum(key >= 0 ? quantise(row[c]) : 0, last);
       if (add && n) atomicAdd(reinterpret_cast<u64*>(acc + (int64_t)key * K + c), (u64)n);
     }
   }
@@ -319,7 +192,7 @@ __global__ __launch_bounds__(256) void rv_finish_kernel(const long long* __restr
   const int n = regcount[t / K];
   float out;
   if (MODE == DMF_VOTE_MAJORITY) out = (float)acc[t];
-  else out = n > 0 ? (float)((double)acc[t] / ((double)n * (double)(1ll << RG_QBITS))) : 0.f;
+  else out = n > 0 ? (float)((double)acc[t] / ((double)n * (double)(1ll << QBITS))) : 0.f;
   regprob[t] = out;
 }
 
@@ -345,41 +218,19 @@ __global__ __launch_bounds__(256) void rv_label_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------ host
-static bool rg_overlap(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
-// outputs against inputs and against each other (a NULL output is absent) -> true where two of them meet
-static bool rg_any_overlap(const void* const* outs, const uint64_t* out_bytes, int n_out, const void* const* ins, const uint64_t* in_bytes,
-                           int n_in) {
-  for (int o = 0; o < n_out; ++o) {
-    if (outs[o] == nullptr) continue;
-    for (int p = 0; p < n_in; ++p)
-      if (rg_overlap(outs[o], out_bytes[o], ins[p], in_bytes[p])) return true;
-    for (int p = o + 1; p < n_out; ++p)
-      if (outs[p] != nullptr && rg_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return true;
-  }
-  return false;
-}
-
-static unsigned rg_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }      // (n < 2^31: the grid holds it)
-
-static int64_t rg_up16(int64_t n) { return (n + 15) / 16 * 16; }
-
 struct RegionSpace {                                     // the merge's workspace, every part 16-byte aligned
   int64_t best, size, target, prefix, sums, bytes;
 };
 
 static RegionSpace region_space(int64_t pixels, int n_labels) {
   RegionSpace s;
-  const int64_t plane = rg_up16(pixels * (int64_t)sizeof(int32_t));
+  const int64_t plane = up16(pixels * (int64_t)sizeof(int32_t));
   s.best = 0;
-  s.size = rg_up16((int64_t)n_labels * (int64_t)sizeof(u64));
+  s.size = up16((int64_t)n_labels * (int64_t)sizeof(u64));
   s.target = s.size + plane;
   s.prefix = s.target + plane;
   s.sums = s.prefix + plane;
-  s.bytes = s.sums + rg_up16((pixels + RG_SCAN_BLOCK - 1) / RG_SCAN_BLOCK * (int64_t)sizeof(int32_t));
+  s.bytes = s.sums + up16((pixels + SCAN_BLOCK - 1) / SCAN_BLOCK * (int64_t)sizeof(int32_t));
   return s;
 }
 
@@ -393,14 +244,14 @@ extern "C" {
 int64_t dmf_region_workspace_bytes(int32_t H, int32_t W, int32_t n_labels) {
   if (H < 1 || W < 1 || n_labels < 0 || (int64_t)H * W >= DMF_REGION_PIXELS_MAX) return -1;
   const int64_t pixels = (int64_t)H * W;
-  const int64_t label = rg_up16(pixels * (int64_t)sizeof(int32_t));           // dmf_label_components: parent
+  const int64_t label = up16(pixels * (int64_t)sizeof(int32_t));           // dmf_label_components: parent
   const int64_t merge = region_space(pixels, n_labels).bytes;
   return label > merge ? label : merge;
 }
 
 int64_t dmf_region_vote_workspace_bytes(int32_t R, int32_t K) {
   if (R < 1 || K < 1 || K > DMF_KMAX) return -1;
-  return rg_up16((int64_t)R * K * (int64_t)sizeof(long long));
+  return up16((int64_t)R * K * (int64_t)sizeof(long long));
 }
 
 int32_t dmf_label_components(const int32_t* labels, int32_t H, int32_t W, int32_t* comp, void* workspace, int64_t workspace_bytes,
@@ -409,7 +260,7 @@ int32_t dmf_label_components(const int32_t* labels, int32_t H, int32_t W, int32_
   if (H < 1 || W < 1) return 2;
   const int64_t pixels = (int64_t)H * W;
   if (pixels >= DMF_REGION_PIXELS_MAX) return 13;
-  const int64_t need = rg_up16(pixels * (int64_t)sizeof(int32_t));
+  const int64_t need = up16(pixels * (int64_t)sizeof(int32_t));
   if (workspace_bytes < need) return 12;
   if (reinterpret_cast<uintptr_t>(workspace) % 16 || reinterpret_cast<uintptr_t>(labels) % 4 || reinterpret_cast<uintptr_t>(comp) % 4) return 8;
   const uint64_t plane = (uint64_t)pixels * sizeof(int32_t);
@@ -417,17 +268,15 @@ int32_t dmf_label_components(const int32_t* labels, int32_t H, int32_t W, int32_
   const uint64_t out_bytes[2] = {plane, (uint64_t)need};
   const void* ins[1] = {labels};
   const uint64_t in_bytes[1] = {plane};
-  if (rg_any_overlap(outs, out_bytes, 2, ins, in_bytes, 1)) return 7;
+  if (any_overlap(outs, out_bytes, 2, ins, in_bytes, 1)) return 7;
   const int64_t tx = ((int64_t)W + RG_T - 1) / RG_T, ty = ((int64_t)H + RG_T - 1) / RG_T;
   if (tx * ty > INT32_MAX) return 8;
   int32_t* parent = static_cast<int32_t*>(workspace);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(cc_local_kernel, dim3((unsigned)(tx * ty)), dim3(RG_THREADS), 0, st, labels, H, W, (int)tx, parent);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(cc_border_kernel, dim3(rg_blocks(pixels, 256)), dim3(256), 0, st, labels, W, pixels, parent);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(rg_blocks(pixels, 256)), dim3(256), 0, st, parent, pixels, comp);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+  DMF_LAUNCH(cc_local_kernel, (unsigned)(tx * ty), RG_THREADS, labels, H, W, (int)tx, parent);
+  DMF_LAUNCH(cc_border_kernel, blocks_of(pixels, 256), 256, labels, W, pixels, parent);
+  DMF_LAUNCH(cc_flatten_kernel, blocks_of(pixels, 256), 256, parent, pixels, comp);
+  return 0;
 }
 
 int32_t dmf_region_merge(const int32_t* labels, const int32_t* comp, int32_t H, int32_t W, int32_t n_labels, int32_t min_size,
@@ -448,31 +297,25 @@ int32_t dmf_region_merge(const int32_t* labels, const int32_t* comp, int32_t H, 
   const uint64_t out_bytes[4] = {plane, plane, 4 * sizeof(int32_t), (uint64_t)s.bytes};
   const void* ins[2] = {labels, comp};
   const uint64_t in_bytes[2] = {plane, plane};
-  if (rg_any_overlap(outs, out_bytes, 4, ins, in_bytes, 2)) return 7;
+  if (any_overlap(outs, out_bytes, 4, ins, in_bytes, 2)) return 7;
   char* base = static_cast<char*>(workspace);
   u64* best = reinterpret_cast<u64*>(base + s.best);
   int32_t* size = reinterpret_cast<int32_t*>(base + s.size);
   int32_t* target = reinterpret_cast<int32_t*>(base + s.target);
   int32_t* prefix = reinterpret_cast<int32_t*>(base + s.prefix);
   int32_t* sums = reinterpret_cast<int32_t*>(base + s.sums);
-  const int64_t scan_blocks = (pixels + RG_SCAN_BLOCK - 1) / RG_SCAN_BLOCK;
+  const int64_t scan_blocks = (pixels + SCAN_BLOCK - 1) / SCAN_BLOCK;
   const int64_t zero = pixels > n_labels ? pixels : n_labels;
-  const unsigned grid = rg_blocks(pixels, 256);
+  const unsigned grid = blocks_of(pixels, 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rg_zero_kernel, dim3(rg_blocks(zero > 4 ? zero : 4, 256)), dim3(256), 0, st, pixels, n_labels, size, region_size, best, stats);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_size_kernel, dim3(grid), dim3(256), 0, st, comp, pixels, size);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_main_kernel, dim3(grid), dim3(256), 0, st, labels, comp, size, pixels, n_labels, best);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_target_kernel, dim3(grid), dim3(256), 0, st, labels, comp, size, best, W, pixels, n_labels, min_size, target, prefix, stats);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_scan_kernel, dim3((unsigned)scan_blocks), dim3(256), 0, st, prefix, pixels, sums);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_scan_blocks_kernel, dim3(1), dim3(256), 0, st, sums, scan_blocks, stats);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(rg_final_kernel, dim3(grid), dim3(256), 0, st, comp, target, prefix, sums, pixels, region, region_size);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+  DMF_LAUNCH(rg_zero_kernel, blocks_of(zero > 4 ? zero : 4, 256), 256, pixels, n_labels, size, region_size, best, stats);
+  DMF_LAUNCH(rg_size_kernel, grid, 256, comp, pixels, size);
+  DMF_LAUNCH(rg_main_kernel, grid, 256, labels, comp, size, pixels, n_labels, best);
+  DMF_LAUNCH(rg_target_kernel, grid, 256, labels, comp, size, best, W, pixels, n_labels, min_size, target, prefix, stats);
+  DMF_LAUNCH(rg_scan_kernel, (unsigned)scan_blocks, 256, prefix, pixels, sums);
+  DMF_LAUNCH(rg_scan_blocks_kernel, 1, 256, sums, scan_blocks, stats);
+  DMF_LAUNCH(rg_final_kernel, grid, 256, comp, target, prefix, sums, pixels, region, region_size);
+  return 0;
 }
 
 int32_t dmf_region_vote(const float* prob, const uint8_t* mask, const int32_t* region, int32_t H, int32_t W, int32_t K, int32_t R,
@@ -499,27 +342,22 @@ int32_t dmf_region_vote(const float* prob, const uint8_t* mask, const int32_t* r
   const void* outs[5] = {regprob, regcount, label_map, prob_out, workspace};
   const uint64_t out_bytes[5] = {(uint64_t)R * K * sizeof(float), (uint64_t)R * sizeof(int32_t), n * sizeof(int32_t), n * K * sizeof(float),
                                  (uint64_t)need};
-  if (rg_any_overlap(outs, out_bytes, 5, ins, in_bytes, 3)) return 7;
+  if (any_overlap(outs, out_bytes, 5, ins, in_bytes, 3)) return 7;
   const int64_t cells = (int64_t)R * K;                  // < 2^27 * 64
   long long* acc = static_cast<long long*>(workspace);
-  const unsigned grid = rg_blocks(pixels, 256), grid_c = rg_blocks(cells, 256);
+  const unsigned grid = blocks_of(pixels, 256), grid_c = blocks_of(cells, 256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rv_zero_kernel, dim3(grid_c), dim3(256), 0, st, cells, R, acc, regcount);
-  if (hipGetLastError() != hipSuccess) return 9;
+  DMF_LAUNCH(rv_zero_kernel, grid_c, 256, cells, R, acc, regcount);
   if (mode == DMF_VOTE_MEAN) {
-    hipLaunchKernelGGL(rv_sum_kernel<DMF_VOTE_MEAN>, dim3(grid), dim3(256), 0, st, prob, mask, region, pixels, K, R, acc, regcount);
-    if (hipGetLastError() != hipSuccess) return 9;
-    hipLaunchKernelGGL(rv_finish_kernel<DMF_VOTE_MEAN>, dim3(grid_c), dim3(256), 0, st, acc, regcount, K, cells, regprob);
-    if (hipGetLastError() != hipSuccess) return 9;
-    hipLaunchKernelGGL(rv_label_kernel<DMF_VOTE_MEAN>, dim3(grid), dim3(256), 0, st, prob, mask, region, K, R, pixels, regprob, label_map, prob_out);
+    DMF_LAUNCH(rv_sum_kernel<DMF_VOTE_MEAN>, grid, 256, prob, mask, region, pixels, K, R, acc, regcount);
+    DMF_LAUNCH(rv_finish_kernel<DMF_VOTE_MEAN>, grid_c, 256, acc, regcount, K, cells, regprob);
+    DMF_LAUNCH(rv_label_kernel<DMF_VOTE_MEAN>, grid, 256, prob, mask, region, K, R, pixels, regprob, label_map, prob_out);
   } else {
-    hipLaunchKernelGGL(rv_sum_kernel<DMF_VOTE_MAJORITY>, dim3(grid), dim3(256), 0, st, prob, mask, region, pixels, K, R, acc, regcount);
-    if (hipGetLastError() != hipSuccess) return 9;
-    hipLaunchKernelGGL(rv_finish_kernel<DMF_VOTE_MAJORITY>, dim3(grid_c), dim3(256), 0, st, acc, regcount, K, cells, regprob);
-    if (hipGetLastError() != hipSuccess) return 9;
-    hipLaunchKernelGGL(rv_label_kernel<DMF_VOTE_MAJORITY>, dim3(grid), dim3(256), 0, st, prob, mask, region, K, R, pixels, regprob, label_map, prob_out);
+    DMF_LAUNCH(rv_sum_kernel<DMF_VOTE_MAJORITY>, grid, 256, prob, mask, region, pixels, K, R, acc, regcount);
+    DMF_LAUNCH(rv_finish_kernel<DMF_VOTE_MAJORITY>, grid_c, 256, acc, regcount, K, cells, regprob);
+    DMF_LAUNCH(rv_label_kernel<DMF_VOTE_MAJORITY>, grid, 256, prob, mask, region, K, R, pixels, regprob, label_map, prob_out);
   }
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+  return 0;
 }
 
 }  // extern "C"

@@ -9,7 +9,8 @@
 //   vote_label_kernel     label_map, prob_out: every masked pixel takes the row of its segment
 // The entry points dmf_slic_workspace_bytes, dmf_slic_init, dmf_slic_assign, dmf_slic_update and dmf_segment_vote live here too
 // (host code at the end of the file) and report by return code, as dmf_spatial.hip's do.  Plain HIP C++; no float atomics, every
-// sum in a fixed order: the same bits on every run.  include/dmf.h states the arithmetic.
+// sum in a fixed order: the same bits on every run.  include/dmf.h states the arithmetic.  The fp16 widening, the first maximal
+// class of a row and the host helpers (overlap, scene bytes, launch and check) are dmf_region_prims.h's.
 //
 // Memory traffic.  The scene is band-innermost.
 //   * assign: a workgroup of 256 threads owns a 16 x 16 tile of pixels, one pixel per thread, whatever S is (S = 4: sixteen cells
@@ -32,6 +33,7 @@
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_region_prims.h"
 
 namespace dmf {
 
@@ -44,9 +46,6 @@ constexpr int SEG_BATCH = 8;               // pixels whose loads the update keep
 constexpr int SEG_WAVES = SEG_THREADS / 64;
 static_assert((SEG_T - 1 + DMF_SEG_SMIN - 1) / DMF_SEG_SMIN + 1 + 2 <= SEG_NL, "a tile's candidates fit the local grid");
 
-__device__ __forceinline__ float seg_widen(float v) { return v; }
-__device__ __forceinline__ float seg_widen(__half v) { return __half2float(v); }
-
 // ------------------------------------------------------------------------------ init
 template <typename T>
 __global__ __launch_bounds__(256) void slic_init_kernel(const T* __restrict__ scene, int pitch, int H, int W, int C, int S, int gw,
@@ -56,7 +55,7 @@ __global__ __launch_bounds__(256) void slic_init_kernel(const T* __restrict__ sc
   const int k = (int)(t / (C + 2)), c = (int)(t - (int64_t)k * (C + 2));
   const int gi = k / gw, gj = k - gi * gw;
   const int i = min(H - 1, gi * S + S / 2), j = min(W - 1, gj * S + S / 2);
-  centres[t] = c < C ? seg_widen(scene[((int64_t)i * pitch + j) * C + c]) : c == C ? (float)i : (float)j;
+  centres[t] = c < C ? widen(scene[((int64_t)i * pitch + j) * C + c]) : c == C ? (float)i : (float)j;
 }
 
 // ------------------------------------------------------------------------------ assign
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(SEG_THREADS) void slic_assign_kernel(const T* __res
       const int p = idx / SEG_CB, c = idx - p * SEG_CB;
       const int pi = i0 + p / SEG_T, pj = j0 + p % SEG_T;
       float v = 0.f;
-      if (pi < H && pj < W && c0 + c < C) v = seg_widen(scene[((int64_t)pi * pitch + pj) * C + c0 + c]);
+      if (pi < H && pj < W && c0 + c < C) v = widen(scene[((int64_t)pi * pitch + pj) * C + c0 + c]);
       pix[p * SEG_PS + c] = v;
     }
     for (int idx = threadIdx.x; idx < SEG_NL * SEG_NL * SEG_CB; idx += SEG_THREADS) {
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(SEG_THREADS) void slic_partial_kernel(const T* __re
       if (q < n) {
         const int pi = i0 + q / nw, pj = j0 + q % nw;
         slot[e] = seg_slot(seg[(int64_t)pi * W + pj], gi, gj, gh, gw);
-        if (live) v[e] = seg_widen(scene[((int64_t)pi * pitch + pj) * C + c]);
+        if (live) v[e] = widen(scene[((int64_t)pi * pitch + pj) * C + c]);
       }
     }
 #pragma unroll
@@ -260,12 +259,7 @@ __global__ __launch_bounds__(SEG_THREADS) void vote_sum_kernel(const float* __re
         }
       } else if (member) {
         const float* p = prob + ((int64_t)i * W + j) * K;
-        float top = p[0];
-        int cls = 0;
-        for (int c = 1; c < K; ++c) {
-          const float v = p[c];
-          if (v > top) { top = v; cls = c; }             // strict: the first maximal index
-        }
+        DMF_FIRST_MAX(p, K, cls)
         atomicAdd(&hist[wave][cls], 1);
       }
     }
@@ -303,12 +297,7 @@ __global__ __launch_bounds__(256) void vote_label_kernel(const float* __restrict
     if (ci >= 0 && ci < gh && cj >= 0 && cj < gw && l == ci * gw + cj) found = ci * gw + cj;
   }
   const float* row = found >= 0 ? segprob + (int64_t)found * K : prob + x * K;     // no segment: the pixel stands for itself
-  float top = row[0];
-  int cls = 0;
-  for (int c = 1; c < K; ++c) {
-    const float v = row[c];
-    if (v > top) { top = v; cls = c; }
-  }
+  DMF_FIRST_MAX(row, K, cls)
   label_map[x] = cls;
   if (prob_out != nullptr)
     for (int c = 0; c < K; ++c) prob_out[x * K + c] = (found >= 0 || MODE == 0) ? row[c] : (c == cls ? 1.f : 0.f);
@@ -328,11 +317,6 @@ static SegGrid seg_grid(int H, int W, int S) {
   return g;
 }
 
-static bool seg_overlap(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 // the checks every scene-reading entry point shares -> 0 or the code
 static int32_t seg_scene_check(const void* scene, int elem_bytes, int pitch, int H, int W, int C, int S) {
   if (H < 1 || W < 1 || C < 1) return 2;
@@ -343,10 +327,7 @@ static int32_t seg_scene_check(const void* scene, int elem_bytes, int pitch, int
   return 0;
 }
 
-static uint64_t seg_scene_bytes(int elem_bytes, int pitch, int H, int W, int C) {
-  return (((uint64_t)(H - 1) * pitch + W) * C) * elem_bytes;
-}
-
+// (refuses a grid beyond 32 bits, which the header's blocks_of leaves to its callers' limits)
 static bool seg_blocks(int64_t n, int per, unsigned& blocks) {
   const int64_t b = (n + per - 1) / per;
   if (b > INT32_MAX) return false;
@@ -373,17 +354,15 @@ int32_t dmf_slic_init(const void* scene, int32_t elem_bytes, int32_t pitch_pixel
   if (const int32_t rc = seg_scene_check(scene, elem_bytes, pitch_pixels, H, W, C, S)) return rc;
   const SegGrid g = seg_grid(H, W, S);
   const int64_t total = g.Kc * (C + 2);
-  if (seg_overlap(centres, (uint64_t)total * sizeof(float), scene, seg_scene_bytes(elem_bytes, pitch_pixels, H, W, C))) return 7;
+  if (overlap(centres, (uint64_t)total * sizeof(float), scene, scene_bytes(elem_bytes, pitch_pixels, H, W, C))) return 7;
   unsigned blocks;
   if (g.Kc > INT32_MAX || !seg_blocks(total, 256, blocks)) return 8;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (elem_bytes == 2)
-    hipLaunchKernelGGL(slic_init_kernel<__half>, dim3(blocks), dim3(256), 0, st, static_cast<const __half*>(scene), pitch_pixels, H, W, C, S,
-                       g.gw, total, centres);
+    DMF_LAUNCH(slic_init_kernel<__half>, blocks, 256, static_cast<const __half*>(scene), pitch_pixels, H, W, C, S, g.gw, total, centres);
   else
-    hipLaunchKernelGGL(slic_init_kernel<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(scene), pitch_pixels, H, W, C, S,
-                       g.gw, total, centres);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+    DMF_LAUNCH(slic_init_kernel<float>, blocks, 256, static_cast<const float*>(scene), pitch_pixels, H, W, C, S, g.gw, total, centres);
+  return 0;
 }
 
 int32_t dmf_slic_assign(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C, int32_t S,
@@ -393,8 +372,8 @@ int32_t dmf_slic_assign(const void* scene, int32_t elem_bytes, int32_t pitch_pix
   if (!(compactness >= 0.f) || isinf(compactness)) return 10;
   const SegGrid g = seg_grid(H, W, S);
   const uint64_t seg_bytes = (uint64_t)H * W * sizeof(int32_t);
-  if (seg_overlap(seg, seg_bytes, scene, seg_scene_bytes(elem_bytes, pitch_pixels, H, W, C)) ||
-      seg_overlap(seg, seg_bytes, centres, (uint64_t)g.Kc * (C + 2) * sizeof(float)))
+  if (overlap(seg, seg_bytes, scene, scene_bytes(elem_bytes, pitch_pixels, H, W, C)) ||
+      overlap(seg, seg_bytes, centres, (uint64_t)g.Kc * (C + 2) * sizeof(float)))
     return 7;
   const int64_t tx = ((int64_t)W + SEG_T - 1) / SEG_T, ty = ((int64_t)H + SEG_T - 1) / SEG_T;
   if (g.Kc > INT32_MAX || tx * ty > INT32_MAX) return 8;
@@ -402,12 +381,12 @@ int32_t dmf_slic_assign(const void* scene, int32_t elem_bytes, int32_t pitch_pix
   const float cw = (float)(ratio * ratio);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (elem_bytes == 2)
-    hipLaunchKernelGGL(slic_assign_kernel<__half>, dim3((unsigned)(tx * ty)), dim3(SEG_THREADS), 0, st, static_cast<const __half*>(scene),
-                       pitch_pixels, H, W, C, S, g.gh, g.gw, cw, centres, (int)tx, seg);
+    DMF_LAUNCH(slic_assign_kernel<__half>, (unsigned)(tx * ty), SEG_THREADS, static_cast<const __half*>(scene), pitch_pixels, H, W, C, S, g.gh,
+               g.gw, cw, centres, (int)tx, seg);
   else
-    hipLaunchKernelGGL(slic_assign_kernel<float>, dim3((unsigned)(tx * ty)), dim3(SEG_THREADS), 0, st, static_cast<const float*>(scene),
-                       pitch_pixels, H, W, C, S, g.gh, g.gw, cw, centres, (int)tx, seg);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+    DMF_LAUNCH(slic_assign_kernel<float>, (unsigned)(tx * ty), SEG_THREADS, static_cast<const float*>(scene), pitch_pixels, H, W, C, S, g.gh,
+               g.gw, cw, centres, (int)tx, seg);
+  return 0;
 }
 
 int32_t dmf_slic_update(const void* scene, int32_t elem_bytes, int32_t pitch_pixels, int32_t H, int32_t W, int32_t C, int32_t S,
@@ -418,15 +397,11 @@ int32_t dmf_slic_update(const void* scene, int32_t elem_bytes, int32_t pitch_pix
   if (workspace_bytes < need) return 12;
   if (reinterpret_cast<uintptr_t>(workspace) % 16) return 8;
   const SegGrid g = seg_grid(H, W, S);
-  const uint64_t scene_bytes = seg_scene_bytes(elem_bytes, pitch_pixels, H, W, C), seg_bytes = (uint64_t)H * W * sizeof(int32_t);
-  const uint64_t cen_bytes = (uint64_t)g.Kc * (C + 2) * sizeof(float), cnt_bytes = (uint64_t)g.Kc * sizeof(int32_t);
+  const void* ins[2] = {scene, seg};
+  const uint64_t in_bytes[2] = {scene_bytes(elem_bytes, pitch_pixels, H, W, C), (uint64_t)H * W * sizeof(int32_t)};
   const void* outs[3] = {centres, counts, workspace};
-  const uint64_t out_bytes[3] = {cen_bytes, cnt_bytes, (uint64_t)need};
-  for (int o = 0; o < 3; ++o) {
-    if (seg_overlap(outs[o], out_bytes[o], scene, scene_bytes) || seg_overlap(outs[o], out_bytes[o], seg, seg_bytes)) return 7;
-    for (int p = o + 1; p < 3; ++p)
-      if (seg_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return 7;
-  }
+  const uint64_t out_bytes[3] = {(uint64_t)g.Kc * (C + 2) * sizeof(float), (uint64_t)g.Kc * sizeof(int32_t), (uint64_t)need};
+  if (any_overlap(outs, out_bytes, 3, ins, in_bytes, 2)) return 7;
   const int nb = (C + 63) / 64;
   const int64_t items = g.Kc * nb, total = g.Kc * (C + 2);
   unsigned blocks_p, blocks_c;
@@ -435,14 +410,13 @@ int32_t dmf_slic_update(const void* scene, int32_t elem_bytes, int32_t pitch_pix
   int32_t* pcnt = reinterpret_cast<int32_t*>(psum + g.Kc * 9 * C);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (elem_bytes == 2)
-    hipLaunchKernelGGL(slic_partial_kernel<__half>, dim3(blocks_p), dim3(SEG_THREADS), 0, st, static_cast<const __half*>(scene), pitch_pixels,
-                       H, W, C, S, g.gh, g.gw, nb, items, seg, psum, pcnt);
+    DMF_LAUNCH(slic_partial_kernel<__half>, blocks_p, SEG_THREADS, static_cast<const __half*>(scene), pitch_pixels, H, W, C, S, g.gh, g.gw, nb,
+               items, seg, psum, pcnt);
   else
-    hipLaunchKernelGGL(slic_partial_kernel<float>, dim3(blocks_p), dim3(SEG_THREADS), 0, st, static_cast<const float*>(scene), pitch_pixels,
-                       H, W, C, S, g.gh, g.gw, nb, items, seg, psum, pcnt);
-  if (hipGetLastError() != hipSuccess) return 9;
-  hipLaunchKernelGGL(slic_combine_kernel, dim3(blocks_c), dim3(256), 0, st, psum, pcnt, C, S, g.gh, g.gw, total, centres, counts);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+    DMF_LAUNCH(slic_partial_kernel<float>, blocks_p, SEG_THREADS, static_cast<const float*>(scene), pitch_pixels, H, W, C, S, g.gh, g.gw, nb,
+               items, seg, psum, pcnt);
+  DMF_LAUNCH(slic_combine_kernel, blocks_c, 256, psum, pcnt, C, S, g.gh, g.gw, total, centres, counts);
+  return 0;
 }
 
 int32_t dmf_segment_vote(const float* prob, const uint8_t* mask, const int32_t* seg, int32_t H, int32_t W, int32_t K, int32_t S,
@@ -459,28 +433,18 @@ int32_t dmf_segment_vote(const float* prob, const uint8_t* mask, const int32_t* 
   const void* outs[4] = {segprob, segcount, label_map, prob_out};
   const uint64_t out_bytes[4] = {(uint64_t)g.Kc * K * sizeof(float), (uint64_t)g.Kc * sizeof(int32_t), pixels * sizeof(int32_t),
                                  pixels * K * sizeof(float)};
-  for (int o = 0; o < 4; ++o) {
-    if (outs[o] == nullptr) continue;
-    for (int p = 0; p < 3; ++p)
-      if (seg_overlap(outs[o], out_bytes[o], ins[p], in_bytes[p])) return 7;
-    for (int p = o + 1; p < 4; ++p)
-      if (outs[p] != nullptr && seg_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) return 7;
-  }
+  if (any_overlap(outs, out_bytes, 4, ins, in_bytes, 3)) return 7;
   unsigned blocks_s, blocks_l;
   if (g.Kc > INT32_MAX || !seg_blocks(g.Kc, SEG_WAVES, blocks_s) || !seg_blocks((int64_t)pixels, 256, blocks_l)) return 8;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (mode == DMF_VOTE_MEAN)
-    hipLaunchKernelGGL(vote_sum_kernel<0>, dim3(blocks_s), dim3(SEG_THREADS), 0, st, prob, mask, seg, H, W, K, S, g.gh, g.gw, segprob, segcount);
-  else
-    hipLaunchKernelGGL(vote_sum_kernel<1>, dim3(blocks_s), dim3(SEG_THREADS), 0, st, prob, mask, seg, H, W, K, S, g.gh, g.gw, segprob, segcount);
-  if (hipGetLastError() != hipSuccess) return 9;
-  if (mode == DMF_VOTE_MEAN)
-    hipLaunchKernelGGL(vote_label_kernel<0>, dim3(blocks_l), dim3(256), 0, st, prob, mask, seg, W, K, S, g.gh, g.gw, (int64_t)pixels, segprob,
-                       label_map, prob_out);
-  else
-    hipLaunchKernelGGL(vote_label_kernel<1>, dim3(blocks_l), dim3(256), 0, st, prob, mask, seg, W, K, S, g.gh, g.gw, (int64_t)pixels, segprob,
-                       label_map, prob_out);
-  return hipGetLastError() == hipSuccess ? 0 : 9;
+  if (mode == DMF_VOTE_MEAN) {
+    DMF_LAUNCH(vote_sum_kernel<0>, blocks_s, SEG_THREADS, prob, mask, seg, H, W, K, S, g.gh, g.gw, segprob, segcount);
+    DMF_LAUNCH(vote_label_kernel<0>, blocks_l, 256, prob, mask, seg, W, K, S, g.gh, g.gw, (int64_t)pixels, segprob, label_map, prob_out);
+  } else {
+    DMF_LAUNCH(vote_sum_kernel<1>, blocks_s, SEG_THREADS, prob, mask, seg, H, W, K, S, g.gh, g.gw, segprob, segcount);
+    DMF_LAUNCH(vote_label_kernel<1>, blocks_l, 256, prob, mask, seg, W, K, S, g.gh, g.gw, (int64_t)pixels, segprob, label_map, prob_out);
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -894,15 +894,21 @@ def logits_mean(logits_v, logits, pred=None):
         raise DmfError('dmf_logits_mean: ' + _MEAN_ERRORS.get(rc, 'error %d' % rc))
 
 
+def _code_check(errors, entry, rc):
+    """An entry point that reports by return code (include/dmf.h): `errors` is its table of texts."""
+    if rc != 0:
+        raise DmfError('%s: %s' % (entry, errors.get(rc, 'error %d' % rc)))
+
+
+def _resident_scene(entry, scene):
+    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
+        raise DmfError('%s: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor' % entry)
+
+
 # return codes of the three entry points of csrc/dmf_spatial.hip, which report by code (include/dmf.h)
 _SPATIAL_ERRORS = {1: 'a NULL pointer', 2: 'H, W and C must be >= 1 (scatter: B >= 0 and W >= 1)', 3: '1 <= K <= DMF_KMAX',
                    4: 'the radius must be 1, 2 or 3', 5: 'elem_bytes must be 2 or 4', 6: 'pitch < W', 7: 'prob_out overlaps prob_in',
                    8: 'the scene is not aligned to its element size, or a grid beyond 32 bits', 9: 'the launch failed'}
-
-
-def _spatial_check(entry, rc):
-    if rc != 0:
-        raise DmfError('%s: %s' % (entry, _SPATIAL_ERRORS.get(rc, 'error %d' % rc)))
 
 
 def _window(radius):
@@ -927,8 +933,8 @@ def prob_scatter(logits, xy, W, prob, mask, inv_temp=None):
         raise DmfError('prob_scatter wants prob [H, %d, %d] and mask [H, %d]' % (W, K, W))
     if B == 0:                                  # (an empty tensor has a null data pointer)
         return
-    _spatial_check('dmf_prob_scatter', _lib.dmf_prob_scatter(_ptr(logits), B, K, _ptr(inv_temp), _ptr(xy), W, _ptr(prob), _ptr(mask),
-                                                             _stream()))
+    _code_check(_SPATIAL_ERRORS, 'dmf_prob_scatter',
+                _lib.dmf_prob_scatter(_ptr(logits), B, K, _ptr(inv_temp), _ptr(xy), W, _ptr(prob), _ptr(mask), _stream()))
 
 
 def spatial_affinity(scene, H, W, radius, sigma_s, sigma_r, aff):
@@ -936,8 +942,7 @@ def spatial_affinity(scene, H, W, radius, sigma_s, sigma_r, aff):
     scene [>= H, pitch >= W, C] (fp32 or fp16, contiguous): exp(-(|d|^2 / (2 sigma_s^2) + mean_c (a_c(x) - a_c(y))^2 /
     (2 sigma_r^2))), 0 for a neighbour outside [0, H) x [0, W), 1 at the centre (dmf_spatial_affinity)."""
     n = _window(radius)
-    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
-        raise DmfError('spatial_affinity: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor')
+    _resident_scene('spatial_affinity', scene)
     _dev(aff, torch.float32, 'aff')
     if H < 1 or W < 1 or H > scene.shape[0] or W > scene.shape[1]:
         raise DmfError('spatial_affinity: %d x %d pixels asked of a scene of %d x %d' % (H, W, scene.shape[0], scene.shape[1]))
@@ -947,8 +952,8 @@ def spatial_affinity(scene, H, W, radius, sigma_s, sigma_r, aff):
         if not (s > 0 and s < float('inf')):
             raise DmfError('spatial_affinity: %s = %r is not a finite number > 0' % (name, s))
     cs, cr = 1.0 / (2.0 * float(sigma_s) ** 2), 1.0 / (2.0 * float(sigma_r) ** 2)
-    _spatial_check('dmf_spatial_affinity', _lib.dmf_spatial_affinity(_ptr(scene), scene.element_size(), scene.shape[1], H, W, scene.shape[2],
-                                                                     radius, cs, cr, _ptr(aff), _stream()))
+    _code_check(_SPATIAL_ERRORS, 'dmf_spatial_affinity', _lib.dmf_spatial_affinity(
+        _ptr(scene), scene.element_size(), scene.shape[1], H, W, scene.shape[2], radius, cs, cr, _ptr(aff), _stream()))
 
 
 def spatial_filter(prob_in, mask, aff, prob_out, label_map):
@@ -966,8 +971,8 @@ def spatial_filter(prob_in, mask, aff, prob_out, label_map):
                        % (H, W, H, W, H, W, K))
     if len({t.device for t in (prob_in, prob_out, mask, aff, label_map)}) != 1:
         raise DmfError('spatial_filter: all tensors must live on one device')
-    _spatial_check('dmf_spatial_filter', _lib.dmf_spatial_filter(_ptr(prob_in), _ptr(mask), _ptr(aff), H, W, K, radius, _ptr(prob_out),
-                                                                 _ptr(label_map), _stream()))
+    _code_check(_SPATIAL_ERRORS, 'dmf_spatial_filter', _lib.dmf_spatial_filter(
+        _ptr(prob_in), _ptr(mask), _ptr(aff), H, W, K, radius, _ptr(prob_out), _ptr(label_map), _stream()))
 
 
 # return codes of the entry points of csrc/dmf_segments.hip, which report by code (include/dmf.h)
@@ -980,11 +985,6 @@ _SEGMENT_ERRORS = {1: 'a NULL pointer', 2: 'H, W and C must be >= 1', 3: '1 <= K
                    12: 'the workspace is too small'}
 
 
-def _segment_check(entry, rc):
-    if rc != 0:
-        raise DmfError('%s: %s' % (entry, _SEGMENT_ERRORS.get(rc, 'error %d' % rc)))
-
-
 def segment_grid(H, W, size):
     """-> (gh, gw): the cells of an H x W scene at segment size `size` (4..32); Kc = gh gw clusters."""
     if isinstance(size, bool) or not isinstance(size, int) or not SEG_SMIN <= size <= SEG_SMAX:
@@ -995,8 +995,7 @@ def segment_grid(H, W, size):
 def _segment_scene(entry, scene, H, W, size):
     """The scene arguments of the slic entry points -> (gh, gw, C, (ptr, elem_bytes, pitch, H, W, C, size))."""
     gh, gw = segment_grid(H, W, size)
-    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
-        raise DmfError('%s: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor' % entry)
+    _resident_scene(entry, scene)
     if H < 1 or W < 1 or H > scene.shape[0] or W > scene.shape[1]:
         raise DmfError('%s: %d x %d pixels asked of a scene of %d x %d' % (entry, H, W, scene.shape[0], scene.shape[1]))
     Cn = scene.shape[2]
@@ -1021,7 +1020,7 @@ def slic_init(scene, H, W, size, centres):
     [H, W] pixels of the resident scene [>= H, pitch >= W, C] (dmf_slic_init)."""
     gh, gw, Cn, args = _segment_scene('slic_init', scene, H, W, size)
     _segment_tensor('slic_init', centres, torch.float32, (gh * gw, Cn + 2), 'centres', scene.device)
-    _segment_check('dmf_slic_init', _lib.dmf_slic_init(*args, _ptr(centres), _stream()))
+    _code_check(_SEGMENT_ERRORS, 'dmf_slic_init', _lib.dmf_slic_init(*args, _ptr(centres), _stream()))
 
 
 def slic_assign(scene, H, W, size, compactness, centres, seg):
@@ -1032,7 +1031,7 @@ def slic_assign(scene, H, W, size, compactness, centres, seg):
     _segment_tensor('slic_assign', seg, torch.int32, (H, W), 'seg', scene.device)
     if not (compactness >= 0 and compactness < float('inf')):
         raise DmfError('slic_assign: compactness = %r is not a finite number >= 0' % (compactness,))
-    _segment_check('dmf_slic_assign', _lib.dmf_slic_assign(*args, float(compactness), _ptr(centres), _ptr(seg), _stream()))
+    _code_check(_SEGMENT_ERRORS, 'dmf_slic_assign', _lib.dmf_slic_assign(*args, float(compactness), _ptr(centres), _ptr(seg), _stream()))
 
 
 def slic_update(scene, H, W, size, seg, centres, counts, workspace):
@@ -1044,8 +1043,8 @@ def slic_update(scene, H, W, size, seg, centres, counts, workspace):
     _segment_tensor('slic_update', seg, torch.int32, (H, W), 'seg', scene.device)
     _segment_tensor('slic_update', counts, torch.int32, (gh * gw,), 'counts', scene.device)
     _dev(workspace, torch.uint8, 'workspace')
-    _segment_check('dmf_slic_update', _lib.dmf_slic_update(*args, _ptr(seg), _ptr(centres), _ptr(counts), _ptr(workspace),
-                                                           workspace.numel(), _stream()))
+    _code_check(_SEGMENT_ERRORS, 'dmf_slic_update',
+                _lib.dmf_slic_update(*args, _ptr(seg), _ptr(centres), _ptr(counts), _ptr(workspace), workspace.numel(), _stream()))
 
 
 def segment_vote(prob, mask, seg, size, mode, segprob, segcount, label_map, prob_out=None):
@@ -1066,8 +1065,9 @@ def segment_vote(prob, mask, seg, size, mode, segprob, segcount, label_map, prob
         _segment_tensor('segment_vote', prob_out, torch.float32, (H, W, K), 'prob_out', prob.device)
     if mask.device != prob.device or seg.device != prob.device:
         raise DmfError('segment_vote: all tensors must live on one device')
-    _segment_check('dmf_segment_vote', _lib.dmf_segment_vote(_ptr(prob), _ptr(mask), _ptr(seg), H, W, K, size, VOTE_MODES[mode],
-                                                             _ptr(segprob), _ptr(segcount), _ptr(label_map), _ptr(prob_out), _stream()))
+    _code_check(_SEGMENT_ERRORS, 'dmf_segment_vote', _lib.dmf_segment_vote(
+        _ptr(prob), _ptr(mask), _ptr(seg), H, W, K, size, VOTE_MODES[mode], _ptr(segprob), _ptr(segcount), _ptr(label_map), _ptr(prob_out),
+        _stream()))
 
 
 # return codes of the entry points of csrc/dmf_regions.hip, which report by code (include/dmf.h)
@@ -1079,15 +1079,19 @@ _REGION_ERRORS = {1: 'a NULL pointer', 2: 'H, W and R must be >= 1 and R <= H W'
                   15: 'n_labels must be >= 0'}
 
 
-def _region_check(entry, rc):
-    if rc != 0:
-        raise DmfError('%s: %s' % (entry, _REGION_ERRORS.get(rc, 'error %d' % rc)))
-
-
 def _whole(entry, name, v, least):
     if isinstance(v, bool) or not isinstance(v, int) or v < least or v >= 1 << 31:
         raise DmfError('%s: %s = %r is not a whole number >= %d' % (entry, name, v, least))
     return v
+
+
+def _labels_preamble(entry, labels, n_labels, min_size):
+    """What the merges ask of labels, n_labels and min_size -> (H, W)."""
+    _dev(labels, torch.int32, 'labels')
+    if labels.dim() != 2:
+        raise DmfError('%s wants labels [H, W]' % entry)
+    _whole(entry, 'n_labels', n_labels, 0); _whole(entry, 'min_size', min_size, 1)
+    return labels.shape
 
 
 def region_workspace_bytes(H, W, n_labels=0):
@@ -1113,7 +1117,8 @@ def label_components(labels, comp, workspace):
     H, W = labels.shape
     _segment_tensor('label_components', comp, torch.int32, (H, W), 'comp', labels.device)
     _dev(workspace, torch.uint8, 'workspace')
-    _region_check('dmf_label_components', _lib.dmf_label_components(_ptr(labels), H, W, _ptr(comp), _ptr(workspace), workspace.numel(), _stream()))
+    _code_check(_REGION_ERRORS, 'dmf_label_components',
+                _lib.dmf_label_components(_ptr(labels), H, W, _ptr(comp), _ptr(workspace), workspace.numel(), _stream()))
 
 
 def region_merge(labels, comp, n_labels, min_size, region, region_size, stats, workspace):
@@ -1121,18 +1126,15 @@ def region_merge(labels, comp, n_labels, min_size, region, region_size, stats, w
     the main component of a label in 0..n_labels - 1, not at pixel 0) the end of the chain of components before it; region_size
     [H W] int32 <- the regions' pixel counts in the first R cells, 0 in the others; stats [4] int32 <- R, components, fragments
     absorbed, 0 (dmf_region_merge).  `workspace`: a uint8 tensor of region_workspace_bytes(H, W, n_labels) bytes."""
-    _dev(labels, torch.int32, 'labels')
-    if labels.dim() != 2:
-        raise DmfError('region_merge wants labels [H, W]')
-    H, W = labels.shape
-    _whole('region_merge', 'n_labels', n_labels, 0); _whole('region_merge', 'min_size', min_size, 1)
+    H, W = _labels_preamble('region_merge', labels, n_labels, min_size)
     _segment_tensor('region_merge', comp, torch.int32, (H, W), 'comp', labels.device)
     _segment_tensor('region_merge', region, torch.int32, (H, W), 'region', labels.device)
     _segment_tensor('region_merge', region_size, torch.int32, (H * W,), 'region_size', labels.device)
     _segment_tensor('region_merge', stats, torch.int32, (4,), 'stats', labels.device)
     _dev(workspace, torch.uint8, 'workspace')
-    _region_check('dmf_region_merge', _lib.dmf_region_merge(_ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(region), _ptr(region_size),
-                                                           _ptr(stats), _ptr(workspace), workspace.numel(), _stream()))
+    _code_check(_REGION_ERRORS, 'dmf_region_merge', _lib.dmf_region_merge(
+        _ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(region), _ptr(region_size), _ptr(stats), _ptr(workspace), workspace.numel(),
+        _stream()))
 
 
 def region_vote(prob, mask, region, R, mode, regprob, regcount, label_map, workspace, prob_out=None):
@@ -1155,20 +1157,15 @@ def region_vote(prob, mask, region, R, mode, regprob, regcount, label_map, works
     _dev(workspace, torch.uint8, 'workspace')
     if mask.device != prob.device or region.device != prob.device or workspace.device != prob.device:
         raise DmfError('region_vote: all tensors must live on one device')
-    _region_check('dmf_region_vote', _lib.dmf_region_vote(_ptr(prob), _ptr(mask), _ptr(region), H, W, K, R, VOTE_MODES[mode], _ptr(regprob),
-                                                         _ptr(regcount), _ptr(label_map), _ptr(prob_out), _ptr(workspace), workspace.numel(),
-                                                         _stream()))
+    _code_check(_REGION_ERRORS, 'dmf_region_vote', _lib.dmf_region_vote(
+        _ptr(prob), _ptr(mask), _ptr(region), H, W, K, R, VOTE_MODES[mode], _ptr(regprob), _ptr(regcount), _ptr(label_map), _ptr(prob_out),
+        _ptr(workspace), workspace.numel(), _stream()))
 
 
 # the entry points of csrc/dmf_region_graph.hip, which report by code (include/dmf.h)
 _REGION_GRAPH_ERRORS = dict(_REGION_ERRORS)
 _REGION_GRAPH_ERRORS.update({2: 'H, W and C must be >= 1', 5: 'elem_bytes must be 2 or 4', 6: 'pitch_pixels < W', 13: 'too many pixels: H W < 2^27',
                              16: 'components outside 1..H W, or fragments outside 0..components - 1'})
-
-
-def _region_graph_check(entry, rc):
-    if rc != 0:
-        raise DmfError('%s: %s' % (entry, _REGION_GRAPH_ERRORS.get(rc, 'error %d' % rc)))
 
 
 def region_graph_workspace_bytes(H, W, Cn=1, n_labels=0, components=1):
@@ -1184,16 +1181,12 @@ def region_graph_count(labels, comp, n_labels, min_size, counts, workspace):
     """counts [2] int32 <- the number of components of comp [H, W] (as label_components leaves it) and the number of fragments
     among them: smaller than min_size, not the main component of a label in 0..n_labels - 1, not at pixel 0
     (dmf_region_graph_count).  `workspace`: a uint8 tensor of region_graph_workspace_bytes(H, W, 1, n_labels, 1) bytes."""
-    _dev(labels, torch.int32, 'labels')
-    if labels.dim() != 2:
-        raise DmfError('region_graph_count wants labels [H, W]')
-    H, W = labels.shape
-    _whole('region_graph_count', 'n_labels', n_labels, 0); _whole('region_graph_count', 'min_size', min_size, 1)
+    H, W = _labels_preamble('region_graph_count', labels, n_labels, min_size)
     _segment_tensor('region_graph_count', comp, torch.int32, (H, W), 'comp', labels.device)
     _segment_tensor('region_graph_count', counts, torch.int32, (2,), 'counts', labels.device)
     _dev(workspace, torch.uint8, 'workspace')
-    _region_graph_check('dmf_region_graph_count', _lib.dmf_region_graph_count(_ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(counts),
-                                                                              _ptr(workspace), workspace.numel(), _stream()))
+    _code_check(_REGION_GRAPH_ERRORS, 'dmf_region_graph_count', _lib.dmf_region_graph_count(
+        _ptr(labels), _ptr(comp), H, W, n_labels, min_size, _ptr(counts), _ptr(workspace), workspace.numel(), _stream()))
 
 
 def region_graph_merge(labels, comp, scene, n_labels, min_size, components, fragments, region, region_size, stats, workspace):
@@ -1203,22 +1196,17 @@ def region_graph_merge(labels, comp, scene, n_labels, min_size, components, frag
     first R cells, 0 in the others; stats [4] int32 <- R, components, components - R, rounds (dmf_region_graph_merge).
     `components` and `fragments` are what region_graph_count left; `workspace`: a uint8 tensor of
     region_graph_workspace_bytes(H, W, C, n_labels, components) bytes."""
-    _dev(labels, torch.int32, 'labels')
-    if labels.dim() != 2:
-        raise DmfError('region_graph_merge wants labels [H, W]')
-    H, W = labels.shape
-    if not (scene.is_cuda and scene.is_contiguous() and scene.dim() == 3 and scene.dtype in (torch.float32, torch.float16)):
-        raise DmfError('region_graph_merge: the scene must be a contiguous [rows, pitch, C] fp32 or fp16 GPU tensor')
+    H, W = _labels_preamble('region_graph_merge', labels, n_labels, min_size)
+    _resident_scene('region_graph_merge', scene)
     if H > scene.shape[0] or W > scene.shape[1] or scene.device != labels.device:
         raise DmfError('region_graph_merge: %d x %d pixels asked of a scene of %d x %d on %s' % (H, W, scene.shape[0], scene.shape[1], scene.device))
-    _whole('region_graph_merge', 'n_labels', n_labels, 0); _whole('region_graph_merge', 'min_size', min_size, 1)
     _whole('region_graph_merge', 'components', components, 1); _whole('region_graph_merge', 'fragments', fragments, 0)
     _segment_tensor('region_graph_merge', comp, torch.int32, (H, W), 'comp', labels.device)
     _segment_tensor('region_graph_merge', region, torch.int32, (H, W), 'region', labels.device)
     _segment_tensor('region_graph_merge', region_size, torch.int32, (H * W,), 'region_size', labels.device)
     _segment_tensor('region_graph_merge', stats, torch.int32, (4,), 'stats', labels.device)
     _dev(workspace, torch.uint8, 'workspace')
-    _region_graph_check('dmf_region_graph_merge', _lib.dmf_region_graph_merge(
+    _code_check(_REGION_GRAPH_ERRORS, 'dmf_region_graph_merge', _lib.dmf_region_graph_merge(
         _ptr(labels), _ptr(comp), _ptr(scene), scene.element_size(), scene.shape[1], H, W, scene.shape[2], n_labels, min_size, components,
         fragments, _ptr(region), _ptr(region_size), _ptr(stats), _ptr(workspace), workspace.numel(), _stream()))
 
@@ -1227,11 +1215,6 @@ def region_graph_merge(labels, comp, scene, n_labels, min_size, components, frag
 PCA_RUN = 256                                   # DMF_PCA_RUN: pixels one fp32 accumulator of the covariance covers
 _PCA_ERRORS = {1: 'a NULL pointer', 2: 'N must be >= 2 (project: >= 0)', 3: '1 <= C <= 512', 4: '1 <= K <= min(C, 64)', 5: 'pitch < C',
                6: 'a misaligned pointer', 8: 'N * pitch beyond 64-bit byte offsets, or a grid beyond 32 bits', 9: 'a launch failed'}
-
-
-def _pca_check(entry, rc):
-    if rc != 0:
-        raise DmfError('%s: %s' % (entry, _PCA_ERRORS.get(rc, 'error %d' % rc)))
 
 
 def _pixels(x, name):
@@ -1264,7 +1247,7 @@ def band_moments(x, mean, cov, ws=None):
         ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
     elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need:
         raise DmfError('band_moments: the workspace needs %d bytes on x\'s device' % need)
-    _pca_check('dmf_band_moments', _lib.dmf_band_moments(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(cov), _ptr(ws), _stream()))
+    _code_check(_PCA_ERRORS, 'dmf_band_moments', _lib.dmf_band_moments(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(cov), _ptr(ws), _stream()))
 
 
 NOISE_DIRECTIONS = {'horizontal': 0, 'vertical': 1}
@@ -1300,9 +1283,8 @@ def band_noise_moments(x, H, W, ncov, direction, ws=None):
         ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
     elif not ws.is_cuda or ws.device != x.device or ws.numel() * ws.element_size() < need:
         raise DmfError('band_noise_moments: the workspace needs %d bytes on x\'s device' % need)
-    rc = _lib.dmf_band_noise_moments(_ptr(x), H, W, C_, pitch, int(direction), _ptr(ncov), _ptr(ws), _stream())
-    if rc != 0:
-        raise DmfError('dmf_band_noise_moments: %s' % _NOISE_ERRORS.get(rc, 'error %d' % rc))
+    _code_check(_NOISE_ERRORS, 'dmf_band_noise_moments',
+                _lib.dmf_band_noise_moments(_ptr(x), H, W, C_, pitch, int(direction), _ptr(ncov), _ptr(ws), _stream()))
 
 
 def band_project(x, mean, basis, y):
@@ -1317,5 +1299,5 @@ def band_project(x, mean, basis, y):
         raise DmfError('band_project: all tensors must live on one device')
     if N == 0:                                  # (an empty tensor has a null data pointer)
         return
-    _pca_check('dmf_band_project', _lib.dmf_band_project(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(basis), basis.shape[1], _ptr(y),
-                                                         _stream()))
+    _code_check(_PCA_ERRORS, 'dmf_band_project',
+                _lib.dmf_band_project(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(basis), basis.shape[1], _ptr(y), _stream()))

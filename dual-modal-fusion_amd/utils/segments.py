@@ -203,28 +203,45 @@ def vote(prob, mask, seg, size, mode):
 QBITS = 36                                   # the mean vote's fixed point: q = rint(clamp(p, 0, 1) 2^36)
 
 
-def components(labels):
-    """comp [H, W] int32: for every pixel the smallest raster index of its 4-connected component of equal values.  Hooking the
-    larger root of every joined pair to the smaller one and jumping pointers, in O(log n) rounds."""
-    lab = np.asarray(labels)
-    H, W = lab.shape
-    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
-    right, down = lab[:, 1:] == lab[:, :-1], lab[1:, :] == lab[:-1, :]
-    a = np.concatenate([idx[:, 1:][right], idx[1:, :][down]])
-    b = np.concatenate([idx[:, :-1][right], idx[:-1, :][down]])
-    p = idx.ravel().copy()
+def _hook(n, a, b):
+    """p [n] int64: for every index the smallest index of its set, the pairs (a[i], b[i]) joined.  Hooking the larger root of every
+    joined pair to the smaller one and jumping pointers, in O(log n) rounds."""
+    p = np.arange(n, dtype=np.int64)
     while True:
         pa, pb = p[a], p[b]
         differ = pa != pb
         if not differ.any():
-            break
+            return p
         np.minimum.at(p, np.maximum(pa, pb)[differ], np.minimum(pa, pb)[differ])
         while True:
             pp = p[p]
             if np.array_equal(pp, p):
                 break
             p = pp
-    return p.reshape(H, W).astype(np.int32)
+
+
+def _kept(flat, roots, size, n_labels, min_size):
+    """DESIGN.md §24's kept rule over the ascending `roots` (their pixel counts `size`) -> bool per root: at least min_size pixels,
+    or root 0, or the main component (the largest, then the smaller root) of a label in 0..n_labels - 1."""
+    kept = size >= min_size
+    kept[0] = True                                       # (pixel 0 is the first root)
+    named = np.nonzero((flat[roots] >= 0) & (flat[roots] < n_labels))[0]
+    if named.size:
+        order = np.lexsort((named, -size[named], flat[roots][named]))       # by label, the largest first, then the smaller root
+        first = np.concatenate([[True], np.diff(flat[roots][named][order]) != 0])
+        kept[named[order][first]] = True
+    return kept
+
+
+def components(labels):
+    """comp [H, W] int32: for every pixel the smallest raster index of its 4-connected component of equal values."""
+    lab = np.asarray(labels)
+    H, W = lab.shape
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    right, down = lab[:, 1:] == lab[:, :-1], lab[1:, :] == lab[:-1, :]
+    a = np.concatenate([idx[:, 1:][right], idx[1:, :][down]])
+    b = np.concatenate([idx[:, :-1][right], idx[:-1, :][down]])
+    return _hook(H * W, a, b).reshape(H, W).astype(np.int32)
 
 
 def regions(labels, n_labels=0, min_size=1):
@@ -241,13 +258,7 @@ def regions(labels, n_labels=0, min_size=1):
     roots = np.nonzero(comp == np.arange(H * W))[0]
     size = np.bincount(comp, minlength=H * W)
     kept = np.zeros(H * W, dtype=bool)
-    kept[roots] = size[roots] >= min_size
-    kept[0] = True
-    named = roots[(flat[roots] >= 0) & (flat[roots] < n_labels)]
-    if named.size:
-        order = np.lexsort((named, -size[named], flat[named]))            # by label, the largest first, then the smaller root
-        first = np.concatenate([[True], np.diff(flat[named][order]) != 0])
-        kept[named[order][first]] = True
+    kept[roots] = _kept(flat, roots, size[roots], n_labels, min_size)
     target = np.arange(H * W)
     frag = roots[~kept[roots]]
     target[frag] = np.where(frag % W > 0, comp[np.maximum(frag - 1, 0)], comp[np.maximum(frag - W, 0)])
@@ -285,13 +296,7 @@ def region_graph(labels, scene, n_labels=0, min_size=1):
     roots = np.nonzero(is_root)[0]
     n = roots.size
     count = np.bincount(comp, minlength=H * W)[roots]
-    kept = count >= min_size
-    kept[0] = True                                       # (root 0 is component 0)
-    named = np.nonzero((flat[roots] >= 0) & (flat[roots] < n_labels))[0]
-    if named.size:
-        order = np.lexsort((named, -count[named], flat[roots][named]))      # by label, the largest first, then the smaller root
-        first = np.concatenate([[True], np.diff(flat[roots][named][order]) != 0])
-        kept[named[order][first]] = True
+    kept = _kept(flat, roots, count, n_labels, min_size)
     index = (np.cumsum(is_root) - 1)[comp].reshape(H, W)  # the dense component index of every pixel: ascending = ascending root
     sums = np.zeros((n, a.shape[2]), dtype=np.int64)
     np.add.at(sums, index.ravel(), quantise(a.astype(np.float32).reshape(H * W, -1)))
@@ -312,18 +317,7 @@ def region_graph(labels, scene, n_labels=0, min_size=1):
         order = np.lexsort((pairs[:, 1], d, pairs[:, 0]))
         first = np.concatenate([[True], np.diff(pairs[order, 0]) != 0])
         cf, cg = pairs[order][first, 0], pairs[order][first, 1]
-        p = np.arange(n)
-        while True:                                      # hooking to the smaller index and pointer jumping, as `components`
-            pa, pb = p[cf], p[cg]
-            differ = pa != pb
-            if not differ.any():
-                break
-            np.minimum.at(p, np.maximum(pa, pb)[differ], np.minimum(pa, pb)[differ])
-            while True:
-                pp = p[p]
-                if np.array_equal(pp, p):
-                    break
-                p = pp
+        p = _hook(n, cf, cg)
         ids = np.unique(group)
         gone = ids[p[ids] != ids]
         np.add.at(sums, p[gone], sums[gone])

@@ -31,6 +31,11 @@ PATTERN_MERGES = ((0, 2), (2, 4), (0, 1))
 SCENES = (('f32', 1), ('f32', 3), ('f32', 8), ('f32', 200), ('f16', 8), ('f16', 200), ('const', 3), ('wild', 3))
 PITCH_EXTRA, ROWS_EXTRA = 3, 2                           # the device's scene is wider and taller than [H, W]
 CHAIN = RC.CHAIN                                         # 1 x 4,096 alternating labels at min_size 2 on the constant scene
+# The 513 x 512 checkerboard of regions_cases.CARRY on a constant one-band scene at min_size 1: no fragment, no round, and the
+# second scan, over 262,656 components = 257 blocks, carries past 256 blocks.  (min_size 2 would cost the reference minutes.)
+CARRY_CASE = RC.CARRY_CASES[0]
+CARRY_SCENE = ('const', 1)
+CARRY_STATS = (262656, 262656, 0, 0)
 
 # (name, H, W, n_labels, min_size): every label-image case
 LABEL_CASES = [(p, H, W, n, m) for H, W in SIZES for p in RC.PATTERNS for n, m in PATTERN_MERGES]

@@ -112,6 +112,13 @@ LABEL_CASES = [('%s' % p, H, W, n, m) for H, W in SIZES for p in PATTERNS for n,
 LABEL_CASES += [('slic%d' % S, H, W, kc(H, W, S), m) for H, W in SIZES for S in SLIC_S for m in (1, auto_min_size(S))]
 LABEL_CASES += [('alternate', CHAIN[0], CHAIN[1], 0, 2)]
 
+# The smallest checkerboard whose scans carry: 513 x 512 = 262,656 one-pixel components = 257 scan blocks of 1,024 cells, so the
+# one-workgroup scan of the block totals goes round its 256-block loop twice.  min_size 1: R = 262,656, the dense ids cross the
+# carry; min_size 2: one region, 262,655 absorbed, the deepest chain 1,023.  Not in SIZES: that would multiply every pattern.
+CARRY = (513, 512)
+CARRY_CASES = [('checker',) + CARRY + (0, 1), ('checker',) + CARRY + (0, 2)]
+CARRY_STATS = {1: ((262656, 262656, 0), 0), 2: ((1, 262656, 262655), 1023)}       # min_size -> (stats, depth) of the reference
+
 
 def labels_of(name, H, W):
     if name.startswith('slic'):

@@ -125,6 +125,16 @@ def test_the_alternating_row_on_the_constant_scene():
         assert counts == (4096, 4095) and tuple(stats) == want[2] and not region.any() and sizes[0] == 4096 and not sizes[1:].any()
 
 
+def test_the_scan_over_the_components_carries_past_256_blocks():
+    """262,656 one-pixel components on a constant scene at min_size 1: no fragment and no round, but both scans (over the pixels,
+    over the components) are 257 blocks, so the one-workgroup scan of the block totals goes round twice."""
+    kind, C = GC.CARRY_SCENE
+    name, H, W, n_labels, min_size = GC.CARRY_CASE
+    assert (H * W + 1023) // 1024 == 257 and (n_labels, min_size) == (0, 1)
+    stats, info = _check_case(GC.CARRY_CASE, kind, C, _dev(GC.padded(kind, C, H, W)))
+    assert stats == GC.CARRY_STATS and info['fragments'] == 0
+
+
 @pytest.mark.parametrize('size', GC.SIZES, ids=lambda s: '%dx%d' % s)
 def test_min_size_1_equals_the_positional_merge(size):
     from dmf import lib

@@ -98,6 +98,17 @@ def test_a_chain_of_4095_fragments_ends_at_pixel_0():
     assert stats == (1, 4096, 4095)
 
 
+def test_the_scan_of_the_block_totals_carries_past_256_blocks():
+    """513 x 512 one-pixel components are 257 scan blocks: the one-workgroup scan goes round twice, and at min_size 1 the dense
+    ids cross its carry; at min_size 2 all but pixel 0 are absorbed along chains of up to 1,023."""
+    H, W = RC.CARRY
+    assert (H * W + 1023) // 1024 == 257 and [c[3:] for c in RC.CARRY_CASES] == [(0, 1), (0, 2)]
+    for case in RC.CARRY_CASES:
+        want, depth = RC.CARRY_STATS[case[4]]
+        assert RC.reference(*case)[3:] == (want, depth), case
+        assert _check_case(case) == want
+
+
 # ------------------------------------------------------------------------------------------------ vote
 def _vote_gpu(prob, mask, region, Rn, mode, fill, with_out=True):
     from dmf import lib

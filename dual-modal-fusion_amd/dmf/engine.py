@@ -111,13 +111,14 @@ def _noise_adjusted_fit(x, H, W, K, whiten, noise):
     return mean, spectral.fit_noise_adjusted(host[:C].copy(), hm[0], spectral.combine_noise(hm[1:]), K, whiten, noise=noise)
 
 
-def band_reduce(raw, K, whiten, device, noise=None):
+def band_reduce(raw, K, whiten, device, noise=None, on_device=False):
     """`band_reduce: pca` on the device -> (scores [H, W, K] float32 on the host, fit).  The raw primary scene
     [H, W, C] is uploaded in its own dtype and normalised unpadded (dmf_scene_minmax / dmf_scene_prepare at pad 0, fp32) — on the
     host, saying why, where prep_route sends it there; dmf_band_moments gives mean and covariance, which are read back once
     (C + C^2 doubles) for utils.spectral.fit_basis; dmf_band_project writes the scores, which are copied back once.  `fit` is
     fit_basis's dict plus `route`.  noise: None, or a direction of `band_reduce_noise`: the noise moments join
-    the read-back and the fit is fit_noise_adjusted's; everything else is as without it."""
+    the read-back and the fit is fit_noise_adjusted's; everything else is as without it.  on_device: the scores are returned as
+    the float32 [H, W, K] tensor on the device and not copied back (what `band_profile` takes next)."""
     from utils import spectral
     raw = np.asarray(raw)
     if raw.ndim != 3:
@@ -144,9 +145,38 @@ def band_reduce(raw, K, whiten, device, noise=None):
             mean, fit = _noise_adjusted_fit(x, H, W, K, whiten, noise)
         y = torch.empty(H * W, K, dtype=torch.float32, device=device)
         lib.band_project(x, mean, torch.from_numpy(fit['basis']).to(device), y)
-        scores = y.cpu().numpy().reshape(H, W, K)
+        scores = y.view(H, W, K) if on_device else y.cpu().numpy().reshape(H, W, K)
     fit['route'] = 'device' if not why else 'device, normalised on the host (%s)' % why
     return scores, fit
+
+
+def band_profile(scores, P, radii, device):
+    """`band_profile: morph` on the device -> (profile [H, W, K + 2 n P] float32 on the host, info).  scores: the
+    float32 [H, W, K] scores of band_reduce, a numpy array or a tensor on the device (band_reduce(.., on_device=True): nothing
+    travels in between).  dmf_morph_markers, the reconstruction in batches of rounds with one read of the counters per batch,
+    dmf_morph_stack, and ONE copy back.  `info` is utils.morphology.make_info's dict: the band order, the route and the rounds of
+    each launch batch.  A score that is not finite is refused by name."""
+    from utils import morphology
+    radii = morphology.check_radii(radii)
+    device = torch.device(device)
+    if isinstance(scores, np.ndarray):
+        scores = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    if not (torch.is_tensor(scores) and scores.dim() == 3 and scores.dtype == torch.float32 and scores.device.type == 'cuda'):
+        raise lib.DmfError('band_profile wants the float32 scores [H, W, K] of band_reduce')
+    H, W, K = scores.shape
+    P, n = int(P), len(radii)
+    morphology.check_components(P, K)
+    with torch.cuda.device(scores.device):
+        if not bool(torch.isfinite(scores).all()):
+            raise ValueError('band_profile: the scores hold a value that is not finite')
+        ws = torch.empty(lib.morph_workspace_bytes(H, W, P, n), dtype=torch.uint8, device=scores.device)
+        mask, X, Y, state = lib.morph_carve(ws, H, W, P, n)
+        lib.morph_markers(scores, P, radii, mask, X, Y)
+        rounds = lib.morph_reconstruct_run(mask, X, Y, n, state)
+        out = torch.empty(H, W, morphology.band_count(K, P, n), dtype=torch.float32, device=scores.device)
+        lib.morph_stack(scores, P, n, mask, X, out)
+        profile = out.cpu().numpy()
+    return profile, morphology.make_info(K, P, radii, 'device', rounds)
 
 
 class Scene:

@@ -156,6 +156,11 @@ def _load():
         'dmf_region_graph_workspace_bytes': (i64, [i32, i32, i32, i32, i32]),
         'dmf_region_graph_count': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp]),
         'dmf_region_graph_merge': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        'dmf_morph_workspace_bytes': (i64, [i32, i32, i32, i32]),
+        'dmf_morph_state_bytes': (i64, [i32, i32, i32]),
+        'dmf_morph_markers': (i32, [vp, i32, i32, i32, i64, i32, C.POINTER(i32), i32, vp, vp, vp, vp]),
+        'dmf_morph_reconstruct': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        'dmf_morph_stack': (i32, [vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -1301,3 +1306,112 @@ def band_project(x, mean, basis, y):
         return
     _code_check(_PCA_ERRORS, 'dmf_band_project',
                 _lib.dmf_band_project(_ptr(x), N, C_, pitch, _ptr(mean), _ptr(basis), basis.shape[1], _ptr(y), _stream()))
+
+
+# the entry points of csrc/dmf_morph.hip, which report by code (include/dmf.h)
+MORPH_TILE, MORPH_BATCH = 32, 8                # DMF_MORPH_TILE, DMF_MORPH_BATCH
+_MORPH_ERRORS = {1: 'a NULL pointer', 2: 'H and W must be >= 1 and H W < 2^31', 3: '1 <= K <= 64 and 1 <= P <= K (reconstruct: the plane counts)',
+                 4: '1..8 strictly increasing radii in 1..32', 5: 'pitch < K', 6: 'a misaligned pointer', 7: 'two plane sets are the same memory',
+                 8: 'a grid beyond 32 bits, or H W pitch beyond 64-bit byte offsets', 9: 'a launch failed', 10: 'first_round or rounds out of range'}
+
+
+def morph_workspace_bytes(H, W, P, n):
+    nbytes = _lib.dmf_morph_workspace_bytes(H, W, P, n)
+    if nbytes < 0:
+        raise DmfError('dmf_morph_workspace_bytes: H, W >= 1, H W < 2^31, 1 <= P <= 64, 1 <= n <= 8, got %r' % ((H, W, P, n),))
+    return nbytes
+
+
+def morph_state_bytes(H, W, planes):
+    nbytes = _lib.dmf_morph_state_bytes(H, W, planes)
+    if nbytes < 0:
+        raise DmfError('dmf_morph_state_bytes: H, W >= 1, H W < 2^31, 1 <= planes <= 1024, got %r' % ((H, W, planes),))
+    return nbytes
+
+
+def morph_carve(ws, H, W, P, n):
+    """(mask [2 P, H, W], X [2 n P, H, W], Y [2 n P, H, W] float32, state uint8) as views of the uint8 workspace tensor `ws` of at
+    least morph_workspace_bytes(H, W, P, n) bytes, in the order include/dmf.h states."""
+    need = morph_workspace_bytes(H, W, P, n)
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous()) or ws.numel() < need or ws.data_ptr() % 4:
+        raise DmfError('morph_carve: the workspace must be a 4-byte aligned uint8 GPU tensor of at least %d bytes' % need)
+    L, plane = 2 * n * P, 4 * H * W
+    cuts = [0, 2 * P * plane, (2 * P + L) * plane, (2 * P + 2 * L) * plane, need]
+    mask, X, Y = (ws[a:b].view(torch.float32).view(-1, H, W) for a, b in zip(cuts[:3], cuts[1:4]))
+    return mask, X, Y, ws[cuts[3]:cuts[4]]
+
+
+def _morph_scores(entry, scores):
+    """(H, W, K, pitch) of scores: a [H, W, K] float32 GPU tensor, pixels `pitch` >= K floats apart, rows W pitch."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.numel() > 0 and scores.stride(2) == 1):
+        raise DmfError('%s: the scores must be a [H, W, K] float32 GPU tensor with unit band stride' % entry)
+    H, W, K = scores.shape
+    pitch = scores.stride(1) if W > 1 else (scores.stride(0) if H > 1 else K)
+    if pitch < K or (H > 1 and W > 1 and scores.stride(0) != W * pitch):
+        raise DmfError('%s: the pixels of the scores must be one pitch >= K apart, row after row' % entry)
+    return H, W, K, pitch
+
+
+def _morph_planes(entry, t, count, H, W, name, device):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (count, H, W) and t.device == device):
+        raise DmfError('%s: %s must be a contiguous [%d, %d, %d] float32 tensor on %s' % (entry, name, count, H, W, device))
+
+
+def morph_markers(scores, P, radii, mask, markers, scratch):
+    """mask [2 P, H, W] <- the first P components of scores [H, W, K] and their negatives, canonicalised; markers [2 n P, H, W] <-
+    the erosion of its mask plane at each radius (dmf_morph_markers; `scratch`, as large as markers, holds the row pass)."""
+    H, W, K, pitch = _morph_scores('morph_markers', scores)
+    radii = [int(r) for r in radii]
+    n = len(radii)
+    _morph_planes('morph_markers', mask, 2 * P, H, W, 'mask', scores.device)
+    _morph_planes('morph_markers', markers, 2 * n * P, H, W, 'markers', scores.device)
+    _morph_planes('morph_markers', scratch, 2 * n * P, H, W, 'scratch', scores.device)
+    _code_check(_MORPH_ERRORS, 'dmf_morph_markers', _lib.dmf_morph_markers(
+        _ptr(scores), H, W, K, pitch, P, (C.c_int32 * max(n, 1))(*radii), n, _ptr(mask), _ptr(markers), _ptr(scratch), _stream()))
+
+
+def morph_reconstruct(mask, X, Y, per_mask, first_round, rounds, state):
+    """Enqueues the rounds first_round .. first_round + rounds - 1 of the reconstruction by dilation of the planes X [L, H, W]
+    under mask [L / per_mask, H, W] (dmf_morph_reconstruct); reads nothing.  state: a uint8 tensor of morph_state_bytes(H, W, L)."""
+    if not (X.is_cuda and X.dim() == 3):
+        raise DmfError('morph_reconstruct: X must be a [L, H, W] float32 GPU tensor')
+    L, H, W = X.shape
+    _morph_planes('morph_reconstruct', X, L, H, W, 'X', X.device)
+    _morph_planes('morph_reconstruct', Y, L, H, W, 'Y', X.device)
+    _morph_planes('morph_reconstruct', mask, L // max(per_mask, 1), H, W, 'mask', X.device)
+    if not (state.is_cuda and state.dtype == torch.uint8 and state.is_contiguous() and state.device == X.device
+            and state.numel() >= morph_state_bytes(H, W, L)):
+        raise DmfError('morph_reconstruct: the state needs %d bytes on X\'s device' % morph_state_bytes(H, W, L))
+    _code_check(_MORPH_ERRORS, 'dmf_morph_reconstruct', _lib.dmf_morph_reconstruct(
+        _ptr(mask), _ptr(X), _ptr(Y), H, W, L, per_mask, first_round, rounds, _ptr(state), _stream()))
+
+
+def morph_reconstruct_run(mask, X, Y, per_mask, state):
+    """The whole reconstruction: batches of MORPH_BATCH rounds, the batch's counters read once after each, until a round changed
+    no tile -> the rounds that ran in each batch (the last entry ends with the round that found nothing to do).  X and Y are equal
+    afterwards.  More than H W rounds is an internal error: a value moves at least one pixel per round."""
+    L, H, W = X.shape
+    batches, k = [], 0
+    while True:
+        morph_reconstruct(mask, X, Y, per_mask, k, MORPH_BATCH, state)
+        counts = state[:8 * MORPH_BATCH].view(torch.int32)[(k % (2 * MORPH_BATCH)):(k % (2 * MORPH_BATCH)) + MORPH_BATCH].tolist()
+        if 0 in counts:
+            batches.append(counts.index(0) + 1)
+            return batches
+        batches.append(MORPH_BATCH)
+        k += MORPH_BATCH
+        if k > H * W:
+            raise DmfError('morph_reconstruct_run: no fixed point after %d rounds of a %d x %d image (internal error)' % (k, H, W))
+
+
+def morph_stack(scores, P, n, mask, planes, out):
+    """out [H, W, K + 2 n P] float32 <- the profile in the order include/dmf.h states, from the reconstructed planes
+    (dmf_morph_stack)."""
+    H, W, K, pitch = _morph_scores('morph_stack', scores)
+    _morph_planes('morph_stack', mask, 2 * P, H, W, 'mask', scores.device)
+    _morph_planes('morph_stack', planes, 2 * n * P, H, W, 'planes', scores.device)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (H, W, K + 2 * n * P)
+            and out.device == scores.device):
+        raise DmfError('morph_stack: out must be a contiguous [%d, %d, %d] float32 tensor on the scores\' device' % (H, W, K + 2 * n * P))
+    _code_check(_MORPH_ERRORS, 'dmf_morph_stack', _lib.dmf_morph_stack(
+        _ptr(scores), H, W, K, pitch, P, n, _ptr(mask), _ptr(planes), _ptr(out), _stream()))

@@ -15,6 +15,8 @@ either key needs (`Scene.atlas`: V x the scene in HBM); with both `none` it stay
 `band_reduce: pca` (NEW): right after `read_tif`, `self.ms` is replaced by the first `band_reduce_bands` principal
 components of the normalised scene, a float32 [H, W, K] array; everything after that line takes it as the raw scene.
 `band_reduce_noise` (NEW) beside it: the components are the noise-adjusted ones (MNF), ordered by signal-to-noise ratio.
+`band_profile: morph` (NEW) after it: `self.ms` becomes the components and the openings / closings by reconstruction of
+the first `band_profile_components` of them, a float32 [H, W, K + 2 n P] array.
 """
 import os
 import time
@@ -27,7 +29,7 @@ from dmf import augment
 from function.function import data_padding, data_padding_aux, data_show, label_mat2np, read_tif, split_data, split_data_old
 from indicators.kappa import aa_oa, expo_result
 from train.dataset import collate_batched, dataset_dual
-from utils import spectral
+from utils import morphology, spectral
 
 
 def epoch_orders(n, epochs, draws_after=0):
@@ -69,8 +71,12 @@ class BaseSolver:
         self.band_fit = None                                        # band_reduce: pca — the fit (utils.spectral.fit_basis + route)
         bands = spectral.band_keys(cfg)
         spectral.noise_keys(cfg)                                    # band_reduce_noise without band_reduce: refused by name
+        profile = morphology.profile_keys(cfg)                      # band_profile without band_reduce: refused by name
+        self.band_profile_info = None                               # band_profile: morph — utils.morphology.make_info's dict
         if bands['kind'] is not None:                              # from here on the components ARE the raw primary scene
-            self.ms, self.band_fit = self._band_reduce(bands)
+            self.ms, self.band_fit = self._band_reduce(bands, **({} if profile is None else {'profile': profile}))
+        if profile is not None:                                    # .. and here their morphological profile is
+            self.ms, self.band_profile_info = self._band_profile(profile)
         prep = cfg.get('scene_prep') or 'host'
         if prep not in ('host', 'device'):
             raise ValueError('scene_prep: %s is not one of host, device' % prep)
@@ -118,11 +124,12 @@ class BaseSolver:
             if len(ops) > 1:
                 self.scene = self.scene.atlas(cfg['patch_size'], int(cfg.get('scale', 4)), ops)
 
-    def _band_reduce(self, keys):
+    def _band_reduce(self, keys, profile=None):
         """`band_reduce: pca` -> (the scene's first `band_reduce_bands` principal components as a float32
         [H, W, K] array, the fit).  Fast path: dmf.engine.band_reduce (the moments and the projection on the device, the fit on the
         host); `fast_path: 0`: utils.spectral.reduce_host.  Writes `<t>_band_reduce.npz`.  `band_reduce_noise`: the
-        components are the noise-adjusted ones, on either route; with the key at none no argument is added to either call."""
+        components are the noise-adjusted ones, on either route; with the key at none no argument is added to either call.
+        profile: `band_profile`'s keys when that follows — the fast path then leaves the scores on the device."""
         cfg, K = self.cfg, keys['bands']
         noise = spectral.noise_keys(cfg)
         more = {} if noise is None else {'noise': noise}
@@ -139,8 +146,11 @@ class BaseSolver:
             try:
                 lib.shape_supported(lib.make_shape(a))
             except lib.DmfError as e:
-                raise lib.DmfError('%s; band_reduce_bands: %d needs the line "%d %d %d %d %d %d" in that file'
-                                   % (e, K, a['C'], a['C2'], a['P'], a['S'], a['F'], a['G'])) from None
+                raise lib.DmfError('%s; band_reduce_bands: %d%s needs the line "%d %d %d %d %d %d" in that file'
+                                   % (e, K, '' if profile is None else ' with band_profile: morph', a['C'], a['C2'], a['P'], a['S'], a['F'],
+                                      a['G'])) from None
+            if profile is not None:
+                more['on_device'] = True
             scores, fit = band_reduce(self.ms, K, keys['whiten'], self.DEVICE, **more)
         else:
             scores, fit = spectral.reduce_host(self.ms, K, keys['whiten'], **more)
@@ -153,6 +163,23 @@ class BaseSolver:
             os.makedirs(cfg['RESULT_output'], exist_ok=True)
             spectral.save_fit(cfg['RESULT_output'] + str(self.time) + '_band_reduce.npz', fit)
         return scores, fit
+
+    def _band_profile(self, keys):
+        """`band_profile: morph` -> (the float32 [H, W, K + 2 n P] profile of the scores in `self.ms`, its info).  Fast
+        path: dmf.engine.band_profile on the scores `_band_reduce` left on the device; `fast_path: 0`:
+        utils.morphology.profile_host.  Writes `<t>_band_profile.json`."""
+        cfg = self.cfg
+        if self.fast:
+            from dmf.engine import band_profile
+            ms, info = band_profile(self.ms, keys['components'], keys['radii'], self.DEVICE)
+        else:
+            ms, info = morphology.profile_host(self.ms, keys['components'], keys['radii'])
+        print('band_profile: %d components at radii %s, %d bands, %d reconstruction rounds, %s'
+              % (info['components'], info['radii'], info['bands'], sum(info['rounds']), info['route']))
+        if cfg.get('RESULT_output'):
+            os.makedirs(cfg['RESULT_output'], exist_ok=True)
+            morphology.save_info(cfg['RESULT_output'] + str(self.time) + '_band_profile.json', info)
+        return ms, info
 
     @property
     def MS(self):

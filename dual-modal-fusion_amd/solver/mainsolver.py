@@ -143,6 +143,9 @@ class Solver(BaseSolver):
         if spectral.noise_keys(cfg) is not None and not self.band_reduced:
             raise ValueError('band_reduce_noise is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)
+        if cfg.get('band_profile', 'none') not in (None, False, 0, 'none') and not self.band_reduced:
+            raise ValueError('band_profile is out of scope for %s (its four streams live in one tall scene): leave the key out'
+                             % type(self).__name__)
         if spectral.keys_in_use(spectral.band_keys(cfg)) and not self.band_reduced:
             raise ValueError('band_reduce is out of scope for %s (its four streams live in one tall scene): leave the key out'
                              % type(self).__name__)

@@ -787,6 +787,61 @@ int32_t dmf_region_graph_merge(const int32_t* labels, const int32_t* comp, const
                                int32_t fragments, int32_t* region /* [H W] */, int32_t* region_size /* [H W] */,
                                int32_t* stats /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- morphological profiles of the reduced bands, `band_profile: morph`: openings and closings by reconstruction
+ * of the first P components of the scores that dmf_band_project leaves, at a ladder of n radii.  New symbols at an unchanged
+ * DMF_VERSION: detect them by name.  All arithmetic is min / max of fp32 values, so no order of execution can change a bit.
+ *   input       scores [H][W] pixels of K fp32 components, `pitch` floats apart (pitch >= K), finite (the caller refuses
+ *               anything else).  Every value read is canonicalised once as x + 0.0f: -0 becomes +0.
+ *   operators   on one plane f [H][W]; B_r the (2 r + 1) x (2 r + 1) square, the window clipped to the image (the same as padding
+ *               with +inf for the erosion and -inf for the dilation):
+ *                 eps_r(f) = min over B_r                          delta_r(f) = max over B_r
+ *                 R^delta(m | f), m <= f: the limit of j <- min(delta_1(j), f) from j = m (connectivity 8); R^eps(m | f), m >= f,
+ *                 its dual: the limit of j <- max(eps_1(j), f)
+ *                 gamma_r(f) = R^delta(eps_r(f) | f)   the opening,   phi_r(f) = R^eps(delta_r(f) | f)   the closing by reconstruction
+ *   planes      the closing side is computed on g = -f (negation is exact; -0 is canonicalised again): phi_r(f) =
+ *               -R^delta(eps_r(g) | g).  Side s (0 opening, 1 closing), component p < P and radius index i < n give mask plane
+ *               s P + p (f or -f) and plane q = (s P + p) n + i; planes are [H][W] fp32, planar, H W floats apart.
+ *   markers     mask [2 P] planes and markers [2 n P] planes = eps_{r_i}(mask plane q / n), by separable row and column passes with
+ *               a running minimum over LDS-staged lines; `scratch` [2 n P] planes holds the row pass.  radii: HOST memory, n
+ *               strictly increasing values in 1..DMF_MORPH_RMAX.  Two launches.
+ *   reconstruct X holds the markers on entry.  Round k reads X for even k and Y for odd k and writes the other; a workgroup owns a
+ *               tile of DMF_MORPH_TILE x DMF_MORPH_TILE pixels, iterates it with a halo in LDS to its own stability and writes it
+ *               back, so the result and the number of rounds depend on (H, W, data) only.  A tile is skipped in a round when
+ *               neither it nor one of its 8 neighbours changed in the round before (both buffers then hold its value); a launch
+ *               whose predecessor changed no tile returns at once.  One call enqueues the rounds first_round .. first_round +
+ *               rounds - 1 (first_round a multiple of DMF_MORPH_BATCH, 1 <= rounds <= DMF_MORPH_BATCH; the first call has
+ *               first_round 0) and reads nothing.  `state` (device, dmf_morph_state_bytes(H, W, planes) bytes, 4-byte aligned, any
+ *               contents before round 0) starts with 2 DMF_MORPH_BATCH int32 counters: counter k mod (2 DMF_MORPH_BATCH) = the
+ *               tiles that round k changed.  The caller reads a batch's counters after enqueuing it; at the first zero the
+ *               reconstruction is complete and X and Y are equal.  `planes_per_mask`: plane q has mask plane q / planes_per_mask.
+ *               With a marker above its mask, or NaN, the result is unspecified; nothing is read or written out of range and
+ *               every loop ends.
+ *   stack       out [H][W][C] fp32, C = K + 2 n P: for each p < P the bands phi_{r_n}, .., phi_{r_1}, f, gamma_{r_1}, .., gamma_{r_n}
+ *               (f canonicalised), then the components P .. K - 1 of the scores bit for bit.  `planes` = X or Y after the end.
+ *   workspace   dmf_morph_workspace_bytes(H, W, P, n) = the bytes of mask, X, Y (each plane H W floats, in that order) and the
+ *               state of 2 n P planes; -1 for an argument out of range.  Nothing allocates.
+ * No float atomics (the counters are int32 atomic adds).  All report by code, without a launch (and so with every output as it
+ * was): 1 a NULL pointer; 2 H or W < 1, or H W >= DMF_MORPH_PIXELS_MAX; 3 K outside 1..64 or P outside 1..K (reconstruct: planes
+ * outside 1..DMF_MORPH_PLANES_MAX, or not a multiple of planes_per_mask >= 1); 4 n outside 1..DMF_MORPH_NMAX, or radii that are not
+ * strictly increasing in 1..DMF_MORPH_RMAX; 5 pitch < K; 6 a pointer not 4-byte aligned; 7 two of the plane sets (or out and an
+ * input) are the same memory; 8 more workgroups than a grid holds, or H W pitch beyond 64-bit byte offsets; 9 a launch itself
+ * failed; 10 first_round or rounds out of range.  (They do not set the text of dmf_last_error.) */
+#define DMF_MORPH_RMAX 32
+#define DMF_MORPH_NMAX 8
+#define DMF_MORPH_TILE 32
+#define DMF_MORPH_BATCH 8
+#define DMF_MORPH_PLANES_MAX 1024               /* 2 DMF_MORPH_NMAX 64 */
+#define DMF_MORPH_PIXELS_MAX 2147483648LL       /* 2^31 */
+int64_t dmf_morph_workspace_bytes(int32_t H, int32_t W, int32_t P, int32_t n);
+int64_t dmf_morph_state_bytes(int32_t H, int32_t W, int32_t planes);
+int32_t dmf_morph_markers(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P,
+                          const int32_t* radii /* host [n] */, int32_t n, float* mask /* [2 P][H][W] */,
+                          float* markers /* [2 n P][H][W] */, float* scratch /* [2 n P][H][W] */, void* stream);
+int32_t dmf_morph_reconstruct(const float* mask, float* X, float* Y, int32_t H, int32_t W, int32_t planes, int32_t planes_per_mask,
+                              int32_t first_round, int32_t rounds, void* state, void* stream);
+int32_t dmf_morph_stack(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t n, const float* mask,
+                        const float* planes /* [2 n P][H][W] */, float* out /* [H][W][K + 2 n P] */, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

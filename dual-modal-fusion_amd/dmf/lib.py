@@ -161,6 +161,10 @@ def _load():
         'dmf_morph_markers': (i32, [vp, i32, i32, i32, i64, i32, C.POINTER(i32), i32, vp, vp, vp, vp]),
         'dmf_morph_reconstruct': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         'dmf_morph_stack': (i32, [vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp]),
+        'dmf_attr_workspace_bytes': (i64, [i32, i32, i32, i32, i32]),
+        'dmf_attr_quantise': (i32, [vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, i64, vp]),
+        'dmf_attr_area_levels': (i32, [vp, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+        'dmf_attr_stack': (i32, [vp, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -1415,3 +1419,95 @@ def morph_stack(scores, P, n, mask, planes, out):
         raise DmfError('morph_stack: out must be a contiguous [%d, %d, %d] float32 tensor on the scores\' device' % (H, W, K + 2 * n * P))
     _code_check(_MORPH_ERRORS, 'dmf_morph_stack', _lib.dmf_morph_stack(
         _ptr(scores), H, W, K, pitch, P, n, _ptr(mask), _ptr(planes), _ptr(out), _stream()))
+
+
+# the entry points of csrc/dmf_attr.hip, which report by code (include/dmf.h)
+ATTR_BATCH_MAX, ATTR_LEVELS_MAX, ATTR_AREAS_MAX = 16, 256, 8     # DMF_ATTR_BATCH_MAX, DMF_ATTR_LEVELS_MAX, DMF_ATTR_NMAX
+_ATTR_ERRORS = {1: 'a NULL pointer', 2: 'H and W must be >= 1 and H W < 2^31', 3: '1 <= K <= 64 and 1 <= P <= K (area_levels: 1 <= P <= 64)',
+                4: '1..8 strictly increasing areas >= 1', 5: 'pitch < K', 6: 'a misaligned pointer', 7: 'an output overlaps an input or another output',
+                8: 'a grid beyond 32 bits, or H W pitch beyond 64-bit byte offsets', 9: 'a launch failed',
+                10: 'first_level, levels or T out of range', 11: 'L outside 2..256', 12: 'the workspace is too small'}
+
+
+def attr_workspace_bytes(H, W, P, n, T):
+    nbytes = _lib.dmf_attr_workspace_bytes(H, W, P, n, T)
+    if nbytes < 0:
+        raise DmfError('dmf_attr_workspace_bytes: H, W >= 1, H W < 2^31, 1 <= P <= 64, 1 <= n <= 8, 1 <= T <= 16, got %r' % ((H, W, P, n, T),))
+    return nbytes
+
+
+def attr_carve(ws, H, W, P, n, T):
+    """(keys uint8 view of the 2 P uint32 min / max keys, parent [2 P, T, H W] int32, size [2 P, T, H W] int32) as views of the
+    uint8 workspace tensor `ws` of at least attr_workspace_bytes(H, W, P, n, T) bytes, in the order include/dmf.h states."""
+    need = attr_workspace_bytes(H, W, P, n, T)
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous()) or ws.numel() < need or ws.data_ptr() % 16:
+        raise DmfError('attr_carve: the workspace must be a 16-byte aligned uint8 GPU tensor of at least %d bytes' % need)
+    keys = (8 * P + 15) // 16 * 16
+    planes = (2 * P * T * H * W * 4 + 15) // 16 * 16
+    cells = 2 * P * T * H * W * 4
+    parent, size = (ws[a:a + cells].view(torch.int32).view(2 * P, T, H * W) for a in (keys, keys + planes))
+    return ws[:keys], parent, size
+
+
+def _attr_workspace(entry, ws, need, device):
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous() and ws.device == device and ws.numel() >= need):
+        raise DmfError('%s: the workspace must be a uint8 tensor of at least %d bytes on %s' % (entry, need, device))
+
+
+def _attr_bytes(entry, t, shape, name, device):
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == device):
+        raise DmfError('%s: %s must be a contiguous %s uint8 tensor on %s' % (entry, name, list(shape), device))
+
+
+def attr_quantise(scores, P, L, q, rng, ws):
+    """rng [P, 2] float32 <- the exact (min, max) of the first P components of scores [H, W, K]; q [2 P, H, W] uint8 <- their
+    quantised planes at L levels and the complements L - 1 - q (dmf_attr_quantise).  ws: a uint8 tensor that holds at least the
+    2 P keys at the head of the workspace (16-byte aligned)."""
+    H, W, K, pitch = _morph_scores('attr_quantise', scores)
+    _attr_bytes('attr_quantise', q, (2 * P, H, W), 'q', scores.device)
+    if not (rng.is_cuda and rng.dtype == torch.float32 and rng.is_contiguous() and tuple(rng.shape) == (P, 2) and rng.device == scores.device):
+        raise DmfError('attr_quantise: range must be a contiguous [%d, 2] float32 tensor on the scores\' device' % P)
+    _attr_workspace('attr_quantise', ws, (8 * max(P, 1) + 15) // 16 * 16, scores.device)
+    _code_check(_ATTR_ERRORS, 'dmf_attr_quantise', _lib.dmf_attr_quantise(
+        _ptr(scores), H, W, K, pitch, P, L, _ptr(q), _ptr(rng), _ptr(ws), ws.numel(), _stream()))
+
+
+def attr_area_levels(q, areas, L, first_level, levels, count, ws, T):
+    """Enqueues the levels first_level .. first_level + levels - 1 of every plane of q [2 P, H, W] (dmf_attr_area_levels): count
+    [2 P, n, H, W] uint8 is stored by the call with first_level 1 and added to by the later ones.  Reads nothing back."""
+    if not (q.is_cuda and q.dim() == 3 and q.shape[0] % 2 == 0 and q.numel() > 0):
+        raise DmfError('attr_area_levels: q must be a [2 P, H, W] uint8 GPU tensor')
+    P2, H, W = q.shape
+    areas = [int(a) for a in areas]
+    n = len(areas)
+    _attr_bytes('attr_area_levels', q, (P2, H, W), 'q', q.device)
+    _attr_bytes('attr_area_levels', count, (P2, n, H, W), 'count', q.device)
+    if not 1 <= T <= ATTR_BATCH_MAX:
+        raise DmfError('attr_area_levels: %s' % _ATTR_ERRORS[10])
+    if not 1 <= n <= ATTR_AREAS_MAX or not all(1 <= a < 2 ** 31 for a in areas):          # (what an int32 cannot carry to the check)
+        raise DmfError('attr_area_levels: %s' % _ATTR_ERRORS[4])
+    _attr_workspace('attr_area_levels', ws, attr_workspace_bytes(H, W, P2 // 2, n, T), q.device)
+    _code_check(_ATTR_ERRORS, 'dmf_attr_area_levels', _lib.dmf_attr_area_levels(
+        _ptr(q), H, W, P2 // 2, (C.c_int32 * n)(*areas), n, L, first_level, levels, T, _ptr(count), _ptr(ws), ws.numel(), _stream()))
+
+
+def attr_area_run(q, areas, L, count, ws, T):
+    """Every level 1 .. L - 1 in ascending batches of T: ceil((L - 1) / T) calls, nothing read back -> the number of calls."""
+    calls = 0
+    for first in range(1, L, T):
+        attr_area_levels(q, areas, L, first, min(T, L - first), count, ws, T)
+        calls += 1
+    return calls
+
+
+def attr_stack(scores, P, n, L, count, rng, out):
+    """out [H, W, K + 2 n P] float32 <- the profile in the order include/dmf.h states, from count and range (dmf_attr_stack)."""
+    H, W, K, pitch = _morph_scores('attr_stack', scores)
+    _attr_bytes('attr_stack', count, (2 * P, n, H, W), 'count', scores.device)
+    if not (rng.is_cuda and rng.dtype == torch.float32 and rng.is_contiguous() and tuple(rng.shape) == (P, 2) and rng.device == scores.device):
+        raise DmfError('attr_stack: range must be a contiguous [%d, 2] float32 tensor on the scores\' device' % P)
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (H, W, K + 2 * n * P)
+            and out.device == scores.device):
+        raise DmfError('attr_stack: out must be a contiguous [%d, %d, %d] float32 tensor on the scores\' device' % (H, W, K + 2 * n * P))
+    _code_check(_ATTR_ERRORS, 'dmf_attr_stack', _lib.dmf_attr_stack(
+        _ptr(scores), H, W, K, pitch, P, n, L, _ptr(count), _ptr(rng), _ptr(out), _stream()))

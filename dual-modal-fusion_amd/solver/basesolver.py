@@ -17,6 +17,7 @@ components of the normalised scene, a float32 [H, W, K] array; everything after 
 `band_reduce_noise` (NEW) beside it: the components are the noise-adjusted ones (MNF), ordered by signal-to-noise ratio.
 `band_profile: morph` (NEW) after it: `self.ms` becomes the components and the openings / closings by reconstruction of
 the first `band_profile_components` of them, a float32 [H, W, K + 2 n P] array.
+`band_profile: area` (NEW) in its place: the area openings / closings at `band_profile_areas`, the same band count.
 """
 import os
 import time
@@ -29,7 +30,7 @@ from dmf import augment
 from function.function import data_padding, data_padding_aux, data_show, label_mat2np, read_tif, split_data, split_data_old
 from indicators.kappa import aa_oa, expo_result
 from train.dataset import collate_batched, dataset_dual
-from utils import morphology, spectral
+from utils import attribute, morphology, spectral
 
 
 def epoch_orders(n, epochs, draws_after=0):
@@ -72,7 +73,9 @@ class BaseSolver:
         bands = spectral.band_keys(cfg)
         spectral.noise_keys(cfg)                                    # band_reduce_noise without band_reduce: refused by name
         profile = morphology.profile_keys(cfg)                      # band_profile without band_reduce: refused by name
-        self.band_profile_info = None                               # band_profile: morph — utils.morphology.make_info's dict
+        if profile is None:
+            profile = attribute.profile_keys(cfg)                   # band_profile: area, its keys carry kind='area'
+        self.band_profile_info = None                               # band_profile: morph / area — the kind's make_info dict
         if bands['kind'] is not None:                              # from here on the components ARE the raw primary scene
             self.ms, self.band_fit = self._band_reduce(bands, **({} if profile is None else {'profile': profile}))
         if profile is not None:                                    # .. and here their morphological profile is
@@ -147,7 +150,7 @@ class BaseSolver:
                 lib.shape_supported(lib.make_shape(a))
             except lib.DmfError as e:
                 raise lib.DmfError('%s; band_reduce_bands: %d%s needs the line "%d %d %d %d %d %d" in that file'
-                                   % (e, K, '' if profile is None else ' with band_profile: morph', a['C'], a['C2'], a['P'], a['S'], a['F'],
+                                   % (e, K, '' if profile is None else ' with band_profile: %s' % profile.get('kind', 'morph'), a['C'], a['C2'], a['P'], a['S'], a['F'],
                                       a['G'])) from None
             if profile is not None:
                 more['on_device'] = True
@@ -169,6 +172,8 @@ class BaseSolver:
         path: dmf.engine.band_profile on the scores `_band_reduce` left on the device; `fast_path: 0`:
         utils.morphology.profile_host.  Writes `<t>_band_profile.json`."""
         cfg = self.cfg
+        if keys.get('kind') == 'area':
+            return self._area_profile(keys)
         if self.fast:
             from dmf.engine import band_profile
             ms, info = band_profile(self.ms, keys['components'], keys['radii'], self.DEVICE)
@@ -179,6 +184,23 @@ class BaseSolver:
         if cfg.get('RESULT_output'):
             os.makedirs(cfg['RESULT_output'], exist_ok=True)
             morphology.save_info(cfg['RESULT_output'] + str(self.time) + '_band_profile.json', info)
+        return ms, info
+
+    def _area_profile(self, keys):
+        """`band_profile: area` -> (the float32 [H, W, K + 2 n P] attribute profile of the scores in `self.ms`, its
+        info).  Fast path: dmf.engine.band_profile(kind='area'); `fast_path: 0`: utils.attribute.profile_host.  Writes
+        `<t>_band_profile.json`."""
+        cfg = self.cfg
+        if self.fast:
+            from dmf.engine import band_profile
+            ms, info = band_profile(self.ms, keys['components'], None, self.DEVICE, kind='area', areas=keys['areas'], levels=keys['levels'])
+        else:
+            ms, info = attribute.profile_host(self.ms, keys['components'], keys['areas'], keys['levels'])
+        print('band_profile: area, %d components at areas %s, %d levels, %d bands, %s'
+              % (info['components'], info['areas'], info['levels'], info['bands'], info['route']))
+        if cfg.get('RESULT_output'):
+            os.makedirs(cfg['RESULT_output'], exist_ok=True)
+            attribute.save_info(cfg['RESULT_output'] + str(self.time) + '_band_profile.json', info)
         return ms, info
 
     @property

@@ -12,7 +12,7 @@ import json
 
 import numpy as np
 
-KINDS = ('none', 'morph')
+KINDS = ('none', 'morph', 'area')             # area: utils/attribute.py
 RADIUS_MAX, RADII_MAX = 32, 8                # DMF_MORPH_RMAX, DMF_MORPH_NMAX (include/dmf.h)
 DEFAULT_COMPONENTS, DEFAULT_RADII = 4, (2, 4, 6)
 
@@ -40,15 +40,15 @@ def check_components(P, K):
 
 
 def profile_keys(cfg):
-    """-> None, or dict(components, radii) from the optional top-level keys
-         band_profile none / morph (default none)    band_profile_components 1..band_reduce_bands (default 4)
+    """-> None (the kind is none, or area: DESIGN.md §27), or dict(components, radii) from the optional top-level keys
+         band_profile none / morph / area (default none)    band_profile_components 1..band_reduce_bands (default 4)
          band_profile_radii 1..8 strictly increasing whole numbers in 1..32 (default [2, 4, 6])
     which stand beside `band_reduce: pca`; with `band_reduce: none` anything but none is refused."""
     kind = cfg.get('band_profile', 'none')
     kind = 'none' if kind is None or kind is False or kind == 0 else str(kind).lower()
     if kind not in KINDS:
         raise ValueError('band_profile %r is not one of %s' % (cfg.get('band_profile'), ' / '.join(KINDS)))
-    if kind == 'none':
+    if kind != 'morph':                          # none; area: utils.attribute.profile_keys holds its keys (DESIGN.md §27)
         return None
     if cfg.get('band_reduce', 'none') in (None, False, 0, 'none'):
         raise ValueError('band_profile: morph profiles the components of band_reduce: pca, and band_reduce is none')

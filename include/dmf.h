@@ -842,6 +842,59 @@ int32_t dmf_morph_reconstruct(const float* mask, float* X, float* Y, int32_t H, 
 int32_t dmf_morph_stack(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t n, const float* mask,
                         const float* planes /* [2 n P][H][W] */, float* out /* [H][W][K + 2 n P] */, void* stream);
 
+/* ---- attribute profiles of the reduced bands, `band_profile: area`: area openings and closings of the first P
+ * components of the scores that dmf_band_project leaves, at a ladder of n area thresholds.  New symbols at an unchanged
+ * DMF_VERSION: detect them by name.  From the quantiser on everything is integer, so no order of execution can change a bit.
+ *   input       scores [H][W] pixels of K fp32 components, `pitch` floats apart (pitch >= K), finite (the caller refuses
+ *               anything else).  Every value read is canonicalised once as x + 0.0f: -0 becomes +0.
+ *   range       per component f: lo = min f, hi = max f over the plane, exact (integer atomics on the order-preserving unsigned
+ *               image of the float; no float atomics).  range [P][2] = {lo, hi}.
+ *   quantise    in double, the operations in this order (no multiply is followed by an add: nothing contracts):
+ *                 d = (double)f - (double)lo;  m = d (double)L;  v = m / ((double)hi - (double)lo);  q = min(L - 1, (int)floor(v))
+ *               and q = 0 everywhere where hi == lo.  L = the number of levels, 2..DMF_ATTR_LEVELS_MAX.
+ *   opening     on the integer plane q, 4-connectivity, threshold a >= 1:
+ *                 gamma_a(q)(x) = the largest t in 0..q(x) such that the 4-connected component of {q >= t} that holds x has at
+ *                 least a pixels (level 0 always counts) = the number of levels t in 1..q(x) whose component qualifies: the sets
+ *                 {q >= t} are nested, so the component's size falls as t rises.
+ *   closing     phi_a(q) = (L - 1) - gamma_a((L - 1) - q)
+ *   value       value(c) = (float)((double)lo + ((double)c ((double)hi - (double)lo)) / (double)L): multiply, divide, add.
+ *   planes      q [2 P][H][W] uint8: plane p < P holds q of component p, plane P + p holds L - 1 - q.
+ *               count [2 P][n][H][W] uint8: count[s][i] = gamma_{a_i} of plane s.
+ *   levels      dmf_attr_area_levels takes the levels first_level .. first_level + levels - 1 of all 2 P planes (1 <= levels <= T,
+ *               1 <= first_level, the last level <= L - 1; T = the level planes the workspace was sized for, 1..DMF_ATTR_BATCH_MAX):
+ *               four launches, nothing is read back, there is no convergence loop.  Per (plane, level): the components of {q >= t}
+ *               (a 16 x 16 tile's union-find in LDS, the tile's q staged once per call; atomicMin links across tile borders; every
+ *               pixel's root), the size of every root (integer atomicAdd, one per run of equal roots in a wave), and the pixel's
+ *               owner adds to count the levels at which size >= a_i.  The call with first_level 1 STORES count, every later call
+ *               adds: enqueue the levels 1 .. L - 1 in ascending batches on one stream.  areas: HOST memory, n strictly increasing
+ *               values >= 1 (int32: < 2^31).
+ *   stack       out [H][W][C] fp32, C = K + 2 n P: for each p < P the bands value(phi_{a_n}), .., value(phi_{a_1}), f
+ *               (canonicalised, not quantised), value(gamma_{a_1}), .., value(gamma_{a_n}), then the components P .. K - 1 of the
+ *               scores bit for bit.
+ *   workspace   dmf_attr_workspace_bytes(H, W, P, n, T) = up16(2 P uint32: the min / max keys of dmf_attr_quantise) + parent
+ *               [2 P][T][H W] int32 + size [2 P][T][H W] int32, each of the two rounded up to 16 bytes, in that order; -1 for an
+ *               argument out of range.  16-byte aligned, any contents.  dmf_attr_quantise uses (and asks for) the keys alone.
+ *               Nothing allocates.
+ * Limits: H W < DMF_ATTR_PIXELS_MAX (raster indices are int32; offsets are 64-bit).  All report by code, without a launch (and so
+ * with every output as it was): 1 a NULL pointer; 2 H or W < 1, or H W >= DMF_ATTR_PIXELS_MAX; 3 K outside 1..64 or P outside 1..K
+ * (area_levels: P outside 1..64); 4 n outside 1..DMF_ATTR_NMAX, or areas that are not strictly increasing and >= 1; 5 pitch < K;
+ * 6 a misaligned pointer (fp32: 4 bytes, the workspace: 16); 7 an output overlaps an input or another output; 8 more workgroups
+ * than a grid holds, or H W pitch beyond 64-bit byte offsets; 9 a launch itself failed; 10 first_level, levels or T out of range;
+ * 11 L outside 2..DMF_ATTR_LEVELS_MAX; 12 the workspace is too small.  (They do not set the text of dmf_last_error.) */
+#define DMF_ATTR_NMAX 8
+#define DMF_ATTR_BATCH_MAX 16
+#define DMF_ATTR_LEVELS_MAX 256
+#define DMF_ATTR_PIXELS_MAX 2147483648LL        /* 2^31 */
+int64_t dmf_attr_workspace_bytes(int32_t H, int32_t W, int32_t P, int32_t n, int32_t T);
+int32_t dmf_attr_quantise(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t L,
+                          uint8_t* q /* [2 P][H][W] */, float* range /* [P][2] */, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int32_t dmf_attr_area_levels(const uint8_t* q, int32_t H, int32_t W, int32_t P, const int32_t* areas /* host [n] */, int32_t n,
+                             int32_t L, int32_t first_level, int32_t levels, int32_t T, uint8_t* count /* [2 P][n][H][W] */,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int32_t dmf_attr_stack(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t n, int32_t L,
+                       const uint8_t* count, const float* range /* [P][2] */, float* out /* [H][W][K + 2 n P] */, void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);

@@ -21,7 +21,7 @@ NAMES = ('dmf_patch_v2.hip', 'dmf_attention.hip', 'dmf_qua.hip', 'dmf_loss.hip',
          'dmf_spatial.hip', 'dmf_pca.hip', 'dmf_noise.hip', 'dmf_segments.hip', 'dmf_regions.hip', 'dmf_region_graph.hip',
          'dmf_morph.hip', 'dmf_attr.hip', 'dmf_capi.hip')
 SRC = [os.path.join(HERE, 'csrc', n) for n in NAMES]
-HDR = [os.path.join(HERE, 'csrc', n) for n in ('dmf_shapes.h', 'dmf_kargs.h', 'dmf_lanes.h', 'dmf_xgmi.h', 'dmf_ce_math.h', 'dmf_rows.h', 'dmf_pca_tiles.h', 'dmf_region_prims.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'dmf.h')]
+HDR = [os.path.join(HERE, 'csrc', n) for n in ('dmf_shapes.h', 'dmf_kargs.h', 'dmf_lanes.h', 'dmf_xgmi.h', 'dmf_ce_math.h', 'dmf_rows.h', 'dmf_pca_tiles.h', 'dmf_region_prims.h', 'dmf_attr_criteria.h')] + [os.path.join(os.path.dirname(HERE), 'include', 'dmf.h')]
 OUT = os.path.join(HERE, 'dmf', 'libdmf_hip.so')
 OBJ = os.path.join(HERE, 'build')
 # (-Wno-pass-failed: `#pragma unroll` on the run-time class loops of qua_loss_kernel<0> is a request, not a requirement)

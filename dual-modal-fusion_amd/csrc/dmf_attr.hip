@@ -31,11 +31,33 @@
 // count [2 P][n][H W] uint8: the thread that owns pixel x is the only writer of its cells; calls on one stream are ordered; the
 // call with first_level 1 stores, later calls add.  No atomics touch count.  No float atomics, no allocation, no host
 // synchronisation.  Raster indices are int32 (H W < 2^31), offsets 64-bit.
+//
+// SEVERAL ATTRIBUTES (dmf_attr_multi_levels).  The same components, measured three ways: pixel count, bounding box,
+// sum and sum of squares of q.  The thresholds are areas ++ diagonals ++ stds and count keeps its shape, so the quantiser and the
+// stack serve unchanged.  at_local_kernel and at_border_kernel are shared as they are; three kernels are new:
+//   at_multi_init_kernel<BOX, STD>    per (plane, level): the identities of the accumulators, at the root cells alone
+//   at_multi_root_kernel<BOX, STD>    at_root_kernel, and per run of equal roots in a wave one atomic per accumulator
+//   at_multi_count_kernel<BOX, STD>   at_count_kernel with the n criteria of dmf_attr_criteria.h at the root's cell
+// BOX / STD say which plane sets exist: one that was not asked for is neither allocated nor touched.
+// INITIALISATION.  at_multi_init_kernel runs after the border launch and before the root launch.  By then the forest is final (the
+// root launch joins no sets), so the roots are exactly the pixels >= t with parent == self, and the kernel stores INT32_MAX / -1
+// (min / max of column and row) and 0 (the sums) there and nowhere else.  The root launch's atomics go to the cell of a root
+// that some pixel >= t found, and the count launch reads the cell of such a root: both touch initialised cells only, whatever the
+// workspace held before.  size is zeroed by at_local_kernel, as above.  So the workspace still needs no clearing.
+// THE RUN OF A WAVE is a stretch of consecutive raster indices x0 .. x1, so its box is known from its two ends: rows row(x0) ..
+// row(x1); columns col(x0) .. col(x1) when both ends lie in one row, and 0 .. W - 1 otherwise (the run then holds the last pixel
+// of one row and the first of the next).  Rows shorter than a wave are thereby covered, and the box costs no shuffle.  The two
+// sums are reduced over the run with run_sum's segmented shuffles, packed into one 64-bit word (sum q <= 64 255 in the low half,
+// sum q^2 <= 64 255^2 in the high half: no carry crosses).  The head issues atomicAdd int32 (size), atomicMin / atomicMax int32
+// (box), atomicAdd uint64 (sums): one 64-bit atomic per sum and run, not partial sums staged per tile — the roots of a tile's
+// pixels are not known to be few, so a tile has no table to stage into, and an atomic that returns nothing costs its issuer a
+// few cycles; after the wave's reduction there are as many of them as there are size atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/dmf.h"
+#include "dmf_attr_criteria.h"
 #include "dmf_region_prims.h"
 
 namespace dmf {
@@ -225,6 +247,109 @@ __global__ __launch_bounds__(256) void at_count_kernel(const uint8_t* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------ several attributes
+struct AttrThresholds { int32_t t[DMF_ATTR_NMAX]; };     // areas ++ diagonals ++ stds
+
+struct AttrPlanes {                                      // [2 P][T][H W] each; a set that was not asked for is NULL and not read
+  int32_t *xmin, *xmax, *ymin, *ymax;
+  u64 *sum_q, *sum_q2;
+};
+
+// blockIdx.z = plane * levels + l.  After the border launch the roots are the pixels >= t with parent == self.
+template <bool BOX, bool STD>
+__global__ __launch_bounds__(256) void at_multi_init_kernel(const uint8_t* __restrict__ q, int64_t pixels, int first, int levels, int T,
+                                                            const int32_t* __restrict__ parent, AttrPlanes pl) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= pixels) return;
+  const int plane = (int)(blockIdx.z / (unsigned)levels), l = (int)blockIdx.z - plane * levels, th = first + l;
+  if ((int)q[(int64_t)plane * pixels + x] < th) return;
+  const int64_t cell = ((int64_t)plane * T + l) * pixels + x;
+  if (parent[cell] != (int32_t)x) return;
+  if (BOX) {
+    pl.xmin[cell] = INT32_MAX; pl.xmax[cell] = -1;
+    pl.ymin[cell] = INT32_MAX; pl.ymax[cell] = -1;
+  }
+  if (STD) { pl.sum_q[cell] = 0; pl.sum_q2[cell] = 0; }
+}
+
+// at_root_kernel, and the run's head adds the run to every accumulator of its root (the file head says how the run is reduced).
+template <bool BOX, bool STD>
+__global__ __launch_bounds__(256) void at_multi_root_kernel(const uint8_t* __restrict__ q, int W, int64_t pixels, int first, int levels, int T,
+                                                            int32_t* parent, int32_t* size, AttrPlanes pl) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int plane = (int)(blockIdx.z / (unsigned)levels), l = (int)blockIdx.z - plane * levels, th = first + l;
+  const int64_t base = ((int64_t)plane * T + l) * pixels;
+  int32_t* par = parent + base;
+  int key = -1, qv = 0;
+  if (x < pixels) {
+    qv = (int)q[(int64_t)plane * pixels + x];
+    if (qv >= th) {
+      key = uf_find(par, (int)x);
+      if (uf_load(par, x) != key) atomicMin(par + x, key);
+    }
+  }
+  int last;                                              // (every lane of the wave is here: the run is formed by shuffles)
+  const bool head = run_head(key, last);
+  const int lane = (int)(threadIdx.x & 63);
+  long long sums = 0;
+  if (STD) sums = run_sum(key >= 0 ? ((long long)(qv * qv) << 32) | (long long)qv : 0ll, last);
+  if (head && key >= 0) {
+    const int64_t cell = base + key;
+    atomicAdd(size + cell, last - lane + 1);
+    if (BOX) {
+      const int x0 = (int)x, x1 = x0 + (last - lane);    // (the lanes of a run with key >= 0 hold pixels of the image)
+      const int i0 = x0 / W, i1 = x1 / W;
+      const bool rows = i1 > i0;                         // the run holds the end of a row and the start of the next
+      atomicMin(pl.xmin + cell, rows ? 0 : x0 - i0 * W);
+      atomicMax(pl.xmax + cell, rows ? W - 1 : x1 - i1 * W);
+      atomicMin(pl.ymin + cell, i0);
+      atomicMax(pl.ymax + cell, i1);
+    }
+    if (STD) {
+      atomicAdd(pl.sum_q + cell, (u64)(unsigned)(sums & 0xffffffffll));
+      atomicAdd(pl.sum_q2 + cell, (u64)sums >> 32);
+    }
+  }
+}
+
+// at_count_kernel with the criteria of dmf_attr_criteria.h: thresholds 0 .. na - 1 are areas, na .. nd - 1 diagonals, nd .. n - 1 stds.
+template <bool BOX, bool STD>
+__global__ __launch_bounds__(256) void at_multi_count_kernel(const uint8_t* __restrict__ q, int64_t pixels, int first, int levels, int T, int na,
+                                                             int nd, int n, AttrThresholds tau, const int32_t* __restrict__ parent,
+                                                             const int32_t* __restrict__ size, AttrPlanes pl,
+                                                             uint8_t* __restrict__ count /* [2 P][n][H W] */) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= pixels) return;
+  const int plane = (int)blockIdx.z;
+  const int qx = (int)q[(int64_t)plane * pixels + x];
+  int add[DMF_ATTR_NMAX];
+#pragma unroll
+  for (int a = 0; a < DMF_ATTR_NMAX; ++a) add[a] = 0;
+  for (int l = 0; l < levels && first + l <= qx; ++l) {
+    const int64_t cell = ((int64_t)plane * T + l) * pixels + uf_find(parent + ((int64_t)plane * T + l) * pixels, (int)x);
+    const uint32_t s = (uint32_t)size[cell];
+    int32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+    u64 sq = 0, sq2 = 0;
+    if (BOX) { x0 = pl.xmin[cell]; x1 = pl.xmax[cell]; y0 = pl.ymin[cell]; y1 = pl.ymax[cell]; }
+    if (STD) { sq = pl.sum_q[cell]; sq2 = pl.sum_q2[cell]; }
+#pragma unroll
+    for (int a = 0; a < DMF_ATTR_NMAX; ++a) {
+      const uint32_t t = (uint32_t)tau.t[a];
+      bool ok = false;
+      if (a < na) ok = attr_crit_area(s, t);
+      else if (BOX && a < nd) ok = attr_crit_diagonal(x0, x1, y0, y1, t);
+      else if (STD && a < n) ok = attr_crit_std(s, sq, sq2, t);
+      add[a] += ok ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < DMF_ATTR_NMAX; ++a)
+    if (a < n) {
+      uint8_t* cell = count + ((int64_t)plane * n + a) * pixels + x;
+      *cell = (uint8_t)((first == 1 ? 0 : (int)*cell) + add[a]);       // (at most L - 1 <= 255 levels in all)
+    }
+}
+
 // ------------------------------------------------------------------------------ stack
 // out[pixel][c], c fastest: per profiled component the closings from the largest area down, the component, the openings from the
 // smallest up; then the components P .. K - 1 as the scores hold them.
@@ -267,6 +392,21 @@ static AttrSpace attr_space(int64_t pixels, int P, int T) {
   return s;
 }
 
+struct AttrMultiSpace {                                  // attr_space, then the four box planes, then the two sums: as asked for
+  AttrSpace area;
+  int64_t box, sums, bytes;
+};
+
+static AttrMultiSpace attr_multi_space(int64_t pixels, int P, int T, bool box, bool std_) {
+  AttrMultiSpace s;
+  s.area = attr_space(pixels, P, T);
+  const int64_t cells = (int64_t)2 * P * T * pixels;
+  s.box = s.area.bytes;
+  s.sums = s.box + (box ? 4 * up16(cells * (int64_t)sizeof(int32_t)) : 0);
+  s.bytes = s.sums + (std_ ? 2 * up16(cells * (int64_t)sizeof(uint64_t)) : 0);
+  return s;
+}
+
 static inline bool attr_extent_ok(int32_t H, int32_t W) { return H >= 1 && W >= 1 && (int64_t)H * W < DMF_ATTR_PIXELS_MAX; }
 
 static inline bool attr_areas_ok(const int32_t* areas, int32_t n) {
@@ -277,6 +417,22 @@ static inline bool attr_areas_ok(const int32_t* areas, int32_t n) {
 }
 
 static inline bool attr_aligned(const void* p, int to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
+
+// the three launches of a batch that depend on which plane sets exist
+template <bool BOX, bool STD>
+static int32_t attr_multi_launch(const uint8_t* q, int W, int64_t pixels, int P, int first, int levels, int T, int na, int nd, int n,
+                                 const AttrThresholds& tau, int32_t* parent, int32_t* size, const AttrPlanes& pl, uint8_t* count, hipStream_t st) {
+  const unsigned per = blocks_of(pixels, 256);
+  const auto root = at_multi_root_kernel<BOX, STD>;      // (a name with a comma does not pass through DMF_LAUNCH)
+  const auto tally = at_multi_count_kernel<BOX, STD>;
+  if constexpr (BOX || STD) {                            // (areas alone: size is the only accumulator, and at_local_kernel zeroes it)
+    const auto init = at_multi_init_kernel<BOX, STD>;
+    DMF_LAUNCH(init, dim3(per, 1, 2 * P * levels), 256, q, pixels, first, levels, T, (const int32_t*)parent, pl);
+  }
+  DMF_LAUNCH(root, dim3(per, 1, 2 * P * levels), 256, q, W, pixels, first, levels, T, parent, size, pl);
+  DMF_LAUNCH(tally, dim3(per, 1, 2 * P), 256, q, pixels, first, levels, T, na, nd, n, tau, (const int32_t*)parent, (const int32_t*)size, pl, count);
+  return 0;
+}
 
 }  // namespace dmf
 
@@ -345,6 +501,72 @@ int32_t dmf_attr_area_levels(const uint8_t* q, int32_t H, int32_t W, int32_t P, 
   DMF_LAUNCH(at_root_kernel, dim3(per, 1, 2 * P * levels), 256, q, pixels, first_level, levels, T, parent, size);
   DMF_LAUNCH(at_count_kernel, dim3(per, 1, 2 * P), 256, q, pixels, first_level, levels, T, n, aa, parent, size, count);
   return 0;
+}
+
+int64_t dmf_attr_multi_workspace_bytes(int32_t H, int32_t W, int32_t P, int32_t n_diag, int32_t n_std, int32_t T) {
+  if (!attr_extent_ok(H, W) || P < 1 || P > 64 || n_diag < 0 || n_diag >= DMF_ATTR_NMAX || n_std < 0 || n_std >= DMF_ATTR_NMAX ||
+      n_diag + n_std >= DMF_ATTR_NMAX || T < 1 || T > DMF_ATTR_BATCH_MAX)
+    return -1;
+  if (n_std > 0 && (int64_t)H * W > DMF_ATTR_STD_PIXELS_MAX) return -1;
+  return attr_multi_space((int64_t)H * W, P, T, n_diag > 0, n_std > 0).bytes;
+}
+
+int32_t dmf_attr_multi_levels(const uint8_t* q, int32_t H, int32_t W, int32_t P, const int32_t* thresholds, int32_t n_area, int32_t n_diag,
+                              int32_t n_std, int32_t L, int32_t first_level, int32_t levels, int32_t T, uint8_t* count, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  if (q == nullptr || thresholds == nullptr || count == nullptr || workspace == nullptr) return 1;
+  if (!attr_extent_ok(H, W)) return 2;
+  if (P < 1 || P > 64) return 3;
+  if (!attr_areas_ok(thresholds, n_area)) return 4;
+  if (L < 2 || L > DMF_ATTR_LEVELS_MAX) return 11;
+  if (n_diag < 0 || n_std < 0 || (int64_t)n_area + n_diag + n_std > DMF_ATTR_NMAX) return 14;
+  const int32_t n = n_area + n_diag + n_std;
+  for (int i = n_area; i < n; ++i) {
+    const bool first_of_its_kind = i == n_area || i == n_area + n_diag;
+    if (thresholds[i] < 1 || (!first_of_its_kind && thresholds[i] <= thresholds[i - 1])) return 14;
+    if (i >= n_area + n_diag && thresholds[i] > L - 1) return 14;
+  }
+  const int64_t pixels = (int64_t)H * W;
+  if (n_std > 0 && pixels > DMF_ATTR_STD_PIXELS_MAX) return 13;
+  if (T < 1 || T > DMF_ATTR_BATCH_MAX || levels < 1 || levels > T || first_level < 1 || first_level + levels - 1 > L - 1) return 10;
+  const bool box = n_diag > 0, std_ = n_std > 0;
+  const AttrMultiSpace sp = attr_multi_space(pixels, P, T, box, std_);
+  if (workspace_bytes < sp.bytes) return 12;
+  if (!attr_aligned(workspace, 16)) return 6;
+  const void* outs[2] = {count, workspace};
+  const uint64_t out_bytes[2] = {(uint64_t)2 * P * n * pixels, (uint64_t)sp.bytes};
+  const void* ins[1] = {q};
+  const uint64_t in_bytes[1] = {(uint64_t)2 * P * pixels};
+  if (any_overlap(outs, out_bytes, 2, ins, in_bytes, 1)) return 7;
+  const int64_t tx = ((int64_t)W + AT_T - 1) / AT_T, ty = ((int64_t)H + AT_T - 1) / AT_T;
+  if (tx * ty > INT32_MAX) return 8;
+  AttrThresholds tau = {};
+  for (int i = 0; i < n; ++i) tau.t[i] = thresholds[i];
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(workspace);
+  int32_t* parent = reinterpret_cast<int32_t*>(w + sp.area.parent);
+  int32_t* size = reinterpret_cast<int32_t*>(w + sp.area.size);
+  const int64_t cells = (int64_t)2 * P * T * pixels;
+  const int64_t box_plane = up16(cells * (int64_t)sizeof(int32_t)), sum_plane = up16(cells * (int64_t)sizeof(uint64_t));
+  AttrPlanes pl = {};
+  if (box) {
+    pl.xmin = reinterpret_cast<int32_t*>(w + sp.box);
+    pl.xmax = reinterpret_cast<int32_t*>(w + sp.box + box_plane);
+    pl.ymin = reinterpret_cast<int32_t*>(w + sp.box + 2 * box_plane);
+    pl.ymax = reinterpret_cast<int32_t*>(w + sp.box + 3 * box_plane);
+  }
+  if (std_) {
+    pl.sum_q = reinterpret_cast<u64*>(w + sp.sums);
+    pl.sum_q2 = reinterpret_cast<u64*>(w + sp.sums + sum_plane);
+  }
+  const unsigned per = blocks_of(pixels, 256);
+  DMF_LAUNCH(at_local_kernel, dim3((unsigned)(tx * ty), 1, 2 * P), AT_THREADS, q, H, W, (int)tx, first_level, levels, T, parent, size);
+  DMF_LAUNCH(at_border_kernel, dim3(per, 1, 2 * P * levels), 256, q, W, pixels, first_level, levels, T, parent);
+  const int na = n_area, nd = n_area + n_diag;
+  if (box && std_) return attr_multi_launch<true, true>(q, W, pixels, P, first_level, levels, T, na, nd, n, tau, parent, size, pl, count, st);
+  if (box) return attr_multi_launch<true, false>(q, W, pixels, P, first_level, levels, T, na, nd, n, tau, parent, size, pl, count, st);
+  if (std_) return attr_multi_launch<false, true>(q, W, pixels, P, first_level, levels, T, na, nd, n, tau, parent, size, pl, count, st);
+  return attr_multi_launch<false, false>(q, W, pixels, P, first_level, levels, T, na, nd, n, tau, parent, size, pl, count, st);
 }
 
 int32_t dmf_attr_stack(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t n, int32_t L, const uint8_t* count,

@@ -6,7 +6,7 @@ reference).  Keys this build adds: `scale` (aux/primary resolution ratio; the re
 train/dataset.py:166), `aux_bands`, `gmf.{width,groups,hidden,pool_sigma,attention,single_input,half}`, and `band_reduce` /
 `band_reduce_bands`: with `band_reduce: pca` the primary band count C is the number of components; `band_profile: morph` beside it
 adds 2 n P bands, n = len(`band_profile_radii`), P = `band_profile_components`; `band_profile: area` does the same
-with n = len(`band_profile_areas`).
+with n = len(`band_profile_areas`) + len(`band_profile_diagonals`) + len(`band_profile_stds`).
 """
 import math
 
@@ -30,7 +30,9 @@ def arch_from_cfg(cfg):
     if cfg.get('band_reduce') not in (None, False, 0, 'none'):     # band_reduce: pca: the net sees the components
         C = int(cfg.get('band_reduce_bands', 32))
         if str(cfg.get('band_profile')).lower() == 'area':             # band_profile: area: n = the areas
-            C += 2 * len(cfg.get('band_profile_areas', (25, 100, 400))) * int(cfg.get('band_profile_components', 4))
+            n = len(cfg.get('band_profile_areas', (25, 100, 400)))
+            n += sum(len(cfg.get(k) or ()) for k in ('band_profile_diagonals', 'band_profile_stds'))      # 
+            C += 2 * n * int(cfg.get('band_profile_components', 4))
         elif cfg.get('band_profile') not in (None, False, 0, 'none'):  # band_profile: morph: C = K + 2 n P
             C += 2 * len(cfg.get('band_profile_radii', (2, 4, 6))) * int(cfg.get('band_profile_components', 4))
     width = int(gmf.get('width', 40))

@@ -184,16 +184,55 @@ def _area_profile(scores, P, areas, levels, device, batch=ATTR_BATCH):
     return profile, attribute.make_info(K, P, areas, L, ranges, 'device')
 
 
-def band_profile(scores, P, radii, device, kind='morph', areas=None, levels=None):
+def _multi_profile(scores, P, areas, diagonals, stds, levels, device, batch=ATTR_BATCH):
+    """`band_profile: area` with diagonals and / or stds on the device: _area_profile with dmf_attr_multi_levels in
+    the place of dmf_attr_area_levels and the threshold list areas ++ diagonals ++ stds in the place of the areas; ONE copy back."""
+    from utils import attribute, morphology
+    L = attribute.check_levels(levels)
+    areas, diagonals, stds = attribute.check_thresholds(areas, diagonals, stds, L)
+    device = torch.device(device)
+    if isinstance(scores, np.ndarray):
+        scores = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    if not (torch.is_tensor(scores) and scores.dim() == 3 and scores.dtype == torch.float32 and scores.device.type == 'cuda'):
+        raise lib.DmfError('band_profile wants the float32 scores [H, W, K] of band_reduce')
+    H, W, K = scores.shape
+    P = int(P)
+    morphology.check_components(P, K)
+    attribute.check_std_extent(H, W, stds)
+    thresholds, counts = areas + diagonals + stds, (len(areas), len(diagonals), len(stds))
+    n = len(thresholds)
+    T = max(1, min(int(batch), L - 1))
+    with torch.cuda.device(scores.device):
+        if not bool(torch.isfinite(scores).all()):
+            raise ValueError('band_profile: the scores hold a value that is not finite')
+        ws = torch.empty(lib.attr_multi_workspace_bytes(H, W, P, counts[1], counts[2], T), dtype=torch.uint8, device=scores.device)
+        q = torch.empty(2 * P, H, W, dtype=torch.uint8, device=scores.device)
+        count = torch.empty(2 * P, n, H, W, dtype=torch.uint8, device=scores.device)
+        cells = H * W * attribute.band_count(K, P, n)
+        both = torch.empty(cells + 2 * P, dtype=torch.float32, device=scores.device)      # the profile, then the P ranges: one copy
+        out, rng = both[:cells].view(H, W, -1), both[cells:].view(P, 2)
+        lib.attr_quantise(scores, P, L, q, rng, ws)
+        lib.attr_multi_run(q, thresholds, counts, L, count, ws, T)
+        lib.attr_stack(scores, P, n, L, count, rng, out)
+        host = both.cpu().numpy()
+        profile, ranges = host[:cells].reshape(H, W, -1), host[cells:].reshape(P, 2)
+    return profile, attribute.make_info(K, P, areas, L, ranges, 'device', diagonals, stds)
+
+
+def band_profile(scores, P, radii, device, kind='morph', areas=None, levels=None, diagonals=(), stds=()):
     """`band_profile: morph` on the device -> (profile [H, W, K + 2 n P] float32 on the host, info).  scores: the
     float32 [H, W, K] scores of band_reduce, a numpy array or a tensor on the device (band_reduce(.., on_device=True): nothing
     travels in between).  dmf_morph_markers, the reconstruction in batches of rounds with one read of the counters per batch,
     dmf_morph_stack, and ONE copy back.  `info` is utils.morphology.make_info's dict: the band order, the route and the rounds of
     each launch batch.  A score that is not finite is refused by name.
     kind='area' (DESIGN.md §27): `areas` and `levels` in the place of `radii` (which is not read); `info` is
-    utils.attribute.make_info's dict."""
+    utils.attribute.make_info's dict.  diagonals / stds: further thresholds over the same components; with both
+    empty the calls are the ones of §27."""
     if kind == 'area':
         from utils import attribute
+        if len(diagonals or ()) or len(stds or ()):
+            return _multi_profile(scores, P, attribute.DEFAULT_AREAS if areas is None else areas, diagonals or (), stds or (),
+                                  attribute.DEFAULT_LEVELS if levels is None else levels, device)
         return _area_profile(scores, P, attribute.DEFAULT_AREAS if areas is None else areas,
                              attribute.DEFAULT_LEVELS if levels is None else levels, device)
     if kind != 'morph':

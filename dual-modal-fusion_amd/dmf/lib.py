@@ -165,6 +165,8 @@ def _load():
         'dmf_attr_quantise': (i32, [vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, i64, vp]),
         'dmf_attr_area_levels': (i32, [vp, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp, i64, vp]),
         'dmf_attr_stack': (i32, [vp, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp]),
+        'dmf_attr_multi_workspace_bytes': (i64, [i32, i32, i32, i32, i32, i32]),
+        'dmf_attr_multi_levels': (i32, [vp, i32, i32, i32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -1426,7 +1428,9 @@ ATTR_BATCH_MAX, ATTR_LEVELS_MAX, ATTR_AREAS_MAX = 16, 256, 8     # DMF_ATTR_BATC
 _ATTR_ERRORS = {1: 'a NULL pointer', 2: 'H and W must be >= 1 and H W < 2^31', 3: '1 <= K <= 64 and 1 <= P <= K (area_levels: 1 <= P <= 64)',
                 4: '1..8 strictly increasing areas >= 1', 5: 'pitch < K', 6: 'a misaligned pointer', 7: 'an output overlaps an input or another output',
                 8: 'a grid beyond 32 bits, or H W pitch beyond 64-bit byte offsets', 9: 'a launch failed',
-                10: 'first_level, levels or T out of range', 11: 'L outside 2..256', 12: 'the workspace is too small'}
+                10: 'first_level, levels or T out of range', 11: 'L outside 2..256', 12: 'the workspace is too small',
+                13: 'stds with H W > 2^22', 14: '0..7 strictly increasing diagonals >= 1 and stds in 1..L - 1, at most 8 thresholds in all'}
+ATTR_STD_PIXELS_MAX = 1 << 22                                   # DMF_ATTR_STD_PIXELS_MAX
 
 
 def attr_workspace_bytes(H, W, P, n, T):
@@ -1511,3 +1515,69 @@ def attr_stack(scores, P, n, L, count, rng, out):
         raise DmfError('attr_stack: out must be a contiguous [%d, %d, %d] float32 tensor on the scores\' device' % (H, W, K + 2 * n * P))
     _code_check(_ATTR_ERRORS, 'dmf_attr_stack', _lib.dmf_attr_stack(
         _ptr(scores), H, W, K, pitch, P, n, L, _ptr(count), _ptr(rng), _ptr(out), _stream()))
+
+
+# several attributes over the same components: dmf_attr_multi_workspace_bytes / dmf_attr_multi_levels
+def attr_multi_workspace_bytes(H, W, P, n_diag, n_std, T):
+    nbytes = _lib.dmf_attr_multi_workspace_bytes(H, W, P, n_diag, n_std, T)
+    if nbytes < 0:
+        raise DmfError('dmf_attr_multi_workspace_bytes: H, W >= 1, H W < 2^31 (with stds: <= 2^22), 1 <= P <= 64, 0 <= n_diag, n_std and '
+                       'n_diag + n_std <= 7, 1 <= T <= 16, got %r' % ((H, W, P, n_diag, n_std, T),))
+    return nbytes
+
+
+def attr_multi_carve(ws, H, W, P, n_diag, n_std, T):
+    """dict of views of the uint8 workspace tensor `ws` of at least attr_multi_workspace_bytes(..) bytes, in the order include/dmf.h
+    states: keys, parent, size as attr_carve gives them; xmin, xmax, ymin, ymax [2 P, T, H W] int32 where n_diag > 0; sum_q, sum_q2
+    [2 P, T, H W] int64 (the bits of the uint64 cells) where n_std > 0.  A plane set that was not asked for has no entry."""
+    need = attr_multi_workspace_bytes(H, W, P, n_diag, n_std, T)
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous()) or ws.numel() < need or ws.data_ptr() % 16:
+        raise DmfError('attr_multi_carve: the workspace must be a 16-byte aligned uint8 GPU tensor of at least %d bytes' % need)
+    keys, parent, size = attr_carve(ws, H, W, P, 1, T)
+    views = dict(keys=keys, parent=parent, size=size)
+    cells = 2 * P * T * H * W
+    at = attr_workspace_bytes(H, W, P, 1, T)
+    for names, dtype, width in ((('xmin', 'xmax', 'ymin', 'ymax') if n_diag else (), torch.int32, 4),
+                                (('sum_q', 'sum_q2') if n_std else (), torch.int64, 8)):
+        for name in names:
+            views[name] = ws[at:at + cells * width].view(dtype).view(2 * P, T, H * W)
+            at += (cells * width + 15) // 16 * 16
+    assert at == need
+    return views
+
+
+def attr_multi_levels(q, thresholds, counts, L, first_level, levels, count, ws, T):
+    """Enqueues the levels first_level .. first_level + levels - 1 of every plane of q [2 P, H, W] (dmf_attr_multi_levels).
+    thresholds: areas ++ diagonals ++ stds; counts = (n_area, n_diag, n_std).  count [2 P, n, H, W] uint8 is stored by the call with
+    first_level 1 and added to by the later ones.  Reads nothing back."""
+    if not (q.is_cuda and q.dim() == 3 and q.shape[0] % 2 == 0 and q.numel() > 0):
+        raise DmfError('attr_multi_levels: q must be a [2 P, H, W] uint8 GPU tensor')
+    P2, H, W = q.shape
+    thresholds = [int(t) for t in thresholds]
+    na, nd, ns = (int(c) for c in counts)
+    n = len(thresholds)
+    if min(na, nd, ns) < 0 or na + nd + ns != n:
+        raise DmfError('attr_multi_levels: the counts %r do not add up to the %d thresholds' % ((na, nd, ns), n))
+    if not 1 <= na <= ATTR_AREAS_MAX or not all(1 <= a < 2 ** 31 for a in thresholds[:na]):
+        raise DmfError('attr_multi_levels: %s' % _ATTR_ERRORS[4])
+    if n > ATTR_AREAS_MAX or not all(1 <= t < 2 ** 31 for t in thresholds[na:]):          # (what an int32 cannot carry to the check)
+        raise DmfError('attr_multi_levels: %s' % _ATTR_ERRORS[14])
+    if ns and H * W > ATTR_STD_PIXELS_MAX:
+        raise DmfError('attr_multi_levels: %s' % _ATTR_ERRORS[13])
+    _attr_bytes('attr_multi_levels', q, (P2, H, W), 'q', q.device)
+    _attr_bytes('attr_multi_levels', count, (P2, n, H, W), 'count', q.device)
+    if not 1 <= T <= ATTR_BATCH_MAX:
+        raise DmfError('attr_multi_levels: %s' % _ATTR_ERRORS[10])
+    _attr_workspace('attr_multi_levels', ws, attr_multi_workspace_bytes(H, W, P2 // 2, nd, ns, T), q.device)
+    _code_check(_ATTR_ERRORS, 'dmf_attr_multi_levels', _lib.dmf_attr_multi_levels(
+        _ptr(q), H, W, P2 // 2, (C.c_int32 * n)(*thresholds), na, nd, ns, L, first_level, levels, T, _ptr(count), _ptr(ws), ws.numel(),
+        _stream()))
+
+
+def attr_multi_run(q, thresholds, counts, L, count, ws, T):
+    """Every level 1 .. L - 1 in ascending batches of T: ceil((L - 1) / T) calls, nothing read back -> the number of calls."""
+    calls = 0
+    for first in range(1, L, T):
+        attr_multi_levels(q, thresholds, counts, L, first, min(T, L - first), count, ws, T)
+        calls += 1
+    return calls

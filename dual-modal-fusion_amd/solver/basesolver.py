@@ -17,7 +17,8 @@ components of the normalised scene, a float32 [H, W, K] array; everything after 
 `band_reduce_noise` (NEW) beside it: the components are the noise-adjusted ones (MNF), ordered by signal-to-noise ratio.
 `band_profile: morph` (NEW) after it: `self.ms` becomes the components and the openings / closings by reconstruction of
 the first `band_profile_components` of them, a float32 [H, W, K + 2 n P] array.
-`band_profile: area` (NEW) in its place: the area openings / closings at `band_profile_areas`, the same band count.
+`band_profile: area` (NEW; DESIGN §27) in its place: the area openings / closings at `band_profile_areas`, the same band count;
+`band_profile_diagonals` / `band_profile_stds` (NEW) add thresholds on the same components' box diagonal and std.
 """
 import os
 import time
@@ -73,8 +74,9 @@ class BaseSolver:
         bands = spectral.band_keys(cfg)
         spectral.noise_keys(cfg)                                    # band_reduce_noise without band_reduce: refused by name
         profile = morphology.profile_keys(cfg)                      # band_profile without band_reduce: refused by name
-        if profile is None:
-            profile = attribute.profile_keys(cfg)                   # band_profile: area, its keys carry kind='area'
+        area = attribute.profile_keys(cfg)                          # (always read: band_profile_diagonals / _stds without the kind
+        if profile is None:                                         #  area are refused by name)
+            profile = area                                          # band_profile: area, its keys carry kind='area'
         self.band_profile_info = None                               # band_profile: morph / area — the kind's make_info dict
         if bands['kind'] is not None:                              # from here on the components ARE the raw primary scene
             self.ms, self.band_fit = self._band_reduce(bands, **({} if profile is None else {'profile': profile}))
@@ -191,13 +193,16 @@ class BaseSolver:
         info).  Fast path: dmf.engine.band_profile(kind='area'); `fast_path: 0`: utils.attribute.profile_host.  Writes
         `<t>_band_profile.json`."""
         cfg = self.cfg
+        more = {k: keys[k] for k in ('diagonals', 'stds') if k in keys}       # (DESIGN §28; absent: the calls of §27 as they were)
         if self.fast:
             from dmf.engine import band_profile
-            ms, info = band_profile(self.ms, keys['components'], None, self.DEVICE, kind='area', areas=keys['areas'], levels=keys['levels'])
+            ms, info = band_profile(self.ms, keys['components'], None, self.DEVICE, kind='area', areas=keys['areas'], levels=keys['levels'],
+                                    **more)
         else:
-            ms, info = attribute.profile_host(self.ms, keys['components'], keys['areas'], keys['levels'])
-        print('band_profile: area, %d components at areas %s, %d levels, %d bands, %s'
-              % (info['components'], info['areas'], info['levels'], info['bands'], info['route']))
+            ms, info = attribute.profile_host(self.ms, keys['components'], keys['areas'], keys['levels'], **more)
+        print('band_profile: area, %d components at areas %s%s, %d levels, %d bands, %s'
+              % (info['components'], info['areas'], ', diagonals %s, stds %s' % (info['diagonals'], info['stds']) if more else '',
+                 info['levels'], info['bands'], info['route']))
         if cfg.get('RESULT_output'):
             os.makedirs(cfg['RESULT_output'], exist_ok=True)
             attribute.save_info(cfg['RESULT_output'] + str(self.time) + '_band_profile.json', info)

@@ -895,6 +895,44 @@ int32_t dmf_attr_area_levels(const uint8_t* q, int32_t H, int32_t W, int32_t P, 
 int32_t dmf_attr_stack(const float* scores, int32_t H, int32_t W, int32_t K, int64_t pitch, int32_t P, int32_t n, int32_t L,
                        const uint8_t* count, const float* range /* [P][2] */, float* out /* [H][W][K + 2 n P] */, void* stream);
 
+/* ---- several attributes over the same components: `band_profile: area` with `band_profile_diagonals` and / or
+ * `band_profile_stds`.  New symbols at an unchanged DMF_VERSION: detect them by name.  Range, quantiser, closing and value() are
+ * those above; dmf_attr_quantise and dmf_attr_stack serve unchanged with n = the length of the threshold list.
+ *   thresholds  T = areas ++ diagonals ++ stds, n = n_area + n_diag + n_std <= DMF_ATTR_NMAX, HOST memory.  n_area >= 1; each of
+ *               the three parts strictly increasing and >= 1 (int32: < 2^31); stds <= L - 1, in quantisation-level units.
+ *   opening     for a threshold tau of attribute A, gamma_{A,tau}(q)(x) = the number of levels t in 1..q(x) at which the
+ *               4-connected component S of {q >= t} that holds x satisfies crit_A(S, tau):
+ *                 area       |S| >= tau                                                        (the criterion above)
+ *                 diagonal   w^2 + h^2 >= tau^2, w and h the side lengths in pixels of S's bounding box
+ *                 std        |S| sum q^2 - (sum q)^2 >= tau^2 |S|^2, the sums over the pixels of S of THAT PLANE's q (the closing
+ *                            planes hold L - 1 - q: the closing side is the dual); the population variance is >= tau^2
+ *               all in unsigned 64-bit without a division (csrc/dmf_attr_criteria.h states the functions and why nothing
+ *               overflows).  Area and diagonal grow with S, the qualifying levels are 1 .. some t, and the count is the largest
+ *               of them (the max rule).  The standard deviation does not grow with S: the count is the subtractive rule of
+ *               attribute profiles and in general differs from the largest qualifying level.
+ *   count       [2 P][n][H][W] uint8: count[s][i] = gamma_{T_i} of plane s.  The stack's band order per profiled component is
+ *               therefore the closings at T_n .. T_1, f, the openings at T_1 .. T_n.
+ *   levels      dmf_attr_multi_levels follows dmf_attr_area_levels' batch protocol (first_level 1 STORES count, later calls add;
+ *               ascending batches on one stream) with five launches per call (four with n_diag = n_std = 0: there is no identity to
+ *               write), nothing read back: the local labelling and the
+ *               border links of dmf_attr_area_levels, the identities of the accumulators at the root cells, the root pass
+ *               (per run of equal roots in a wave one integer atomic per accumulator: atomicAdd int32, atomicMin / atomicMax
+ *               int32, atomicAdd uint64), and the count pass, which evaluates the n criteria at the root's cell.
+ *   workspace   dmf_attr_multi_workspace_bytes(H, W, P, n_diag, n_std, T) = dmf_attr_workspace_bytes' layout (keys, parent, size);
+ *               then, if n_diag > 0, four int32 planes [2 P][T][H W] (column min, column max, row min, row max); then, if
+ *               n_std > 0, two uint64 planes [2 P][T][H W] (sum q, sum q^2); each plane rounded up to 16 bytes.  -1 for an
+ *               argument out of range.  With n_diag = n_std = 0 it equals dmf_attr_workspace_bytes.  16-byte aligned, any
+ *               contents; a plane set that was not asked for is neither part of it nor touched.
+ * Limits and codes as above, and: 4 n_area outside 1..DMF_ATTR_NMAX or areas not strictly increasing and >= 1; 13 n_std > 0 with
+ * H W > DMF_ATTR_STD_PIXELS_MAX (the 64-bit products of the std criterion); 14 n_diag or n_std < 0, n > DMF_ATTR_NMAX, diagonals or
+ * stds that are not strictly increasing and >= 1, or a std > L - 1.  Every code leaves every output as it was. */
+#define DMF_ATTR_STD_PIXELS_MAX 4194304LL       /* 2^22 */
+int64_t dmf_attr_multi_workspace_bytes(int32_t H, int32_t W, int32_t P, int32_t n_diag, int32_t n_std, int32_t T);
+int32_t dmf_attr_multi_levels(const uint8_t* q, int32_t H, int32_t W, int32_t P, const int32_t* thresholds /* host [n] */,
+                              int32_t n_area, int32_t n_diag, int32_t n_std, int32_t L, int32_t first_level, int32_t levels,
+                              int32_t T, uint8_t* count /* [2 P][n][H][W] */, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+
 /* Replaces image_convert/IHS.py:14-19 `pan2ms` (2x2 mean pool + 2x2 polyphase split) for out [H, W, 4]
  * from pan [>=4H, >=4W] with row pitch `pitch` floats; computed in fp64 like the reference. */
 int32_t dmf_pan2ms(const double* pan, int32_t pitch, int32_t H, int32_t W, double* out, void* stream);
